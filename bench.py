@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: input MB/s to bit-exact .bwt (+ sampled SA files) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|huge|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|huge|...] [--dump-outputs DIR] [--full]
 
 A "step" is one complete pass of the hot path (window scan -> phrase dedup -> dictionary suffix sort
 -> BWT of the parse -> merge -> run sampling / 5-byte packing) over one synthetic input that is already
@@ -14,10 +14,15 @@ One process per GPU.  For N > 1 the ranks build ONE BWT of a collection of N suc
 variant r of the same base sequences - a pangenome slice per GPU, weak scaling) through
 big-bwt_amd/dist.py; `--multi independent` lets every rank build the BWT of its own text instead.
 
-Rank 0 prints ONE JSON line.  `roofline` = the kernel with the largest share of the step, timed live
-with HIP events on the library's own stream; `roofline_passes` = SURVEY.md 8(d)'s per-pass algorithmic
-bytes over the measured pass times; `cpu_baseline` = the real reference (oracle/_ref: pscan.x -t N ->
-bwtparse -t N -> pfbwt[NT].x, N = host cores) timed on this host on a bounded prefix of the same text.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline
+(`value`, `ms_per_step`, `config`); `--dump-outputs DIR` first writes what the last timed step produced
+as DIR/<name>.npy (a fixed, seeded sample where an output is larger than the size budget).  `--full`
+adds everything else after the timed steps: `roofline` = the kernel with the largest share of the step,
+timed live with HIP events on the library's own stream; `roofline_passes` = SURVEY.md 8(d)'s per-pass
+algorithmic bytes over the measured pass times; digest and permutation checks of the outputs; the
+host-buffer and C-driver legs; `cpu_baseline` = the real reference (oracle/_ref: pscan.x -t N ->
+bwtparse -t N -> pfbwt[NT].x, N = host cores) timed on this host on a bounded prefix of the same text;
+and, on the default workload, the north-star leg.
 """
 import argparse
 import hashlib
@@ -35,6 +40,39 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy peak ~6.3 TB/s
+DUMP_BYTES = 60_000_000        # --dump-outputs: .npy data of all outputs together (the limit is 64 MB)
+ROW_BYTES = {"bwt": 1, "sa": 5, "ssa": 10, "esa": 10}          # one byte / one 5-byte value / a pair of 5-byte values
+
+
+def sample_rows(m, cap, seed):
+    """`cap` sorted row indices out of `m`, one drawn at random from each of `cap` equal strata (all rows if m <= cap)"""
+    if m <= cap:
+        return np.arange(m, dtype=np.int64)
+    edges = np.arange(cap + 1, dtype=np.int64) * m // cap
+    return edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(d, outs, pkg, budget=DUMP_BYTES, prefix="", seed=20240601):
+    """--dump-outputs: every output in `outs` (name -> its reference-format bytes, a device tensor or a host array) as
+    d/<prefix><name>.npy - .bwt bytes as float32, the 5-byte values of .sa / .ssa / .esa as float64 (exact below 2^53;
+    .ssa / .esa as (runs, 2) pairs).  An output with more rows than its equal share of `budget` is sampled (sample_rows)."""
+    os.makedirs(d, exist_ok=True)
+    for name, buf in outs.items():
+        width = ROW_BYTES[name]
+        per_row = 4 if width == 1 else 8 * (width // 5)
+        m = (buf.numel() if torch.is_tensor(buf) else len(buf)) // width
+        idx = sample_rows(m, budget // len(outs) // per_row, seed)
+        if torch.is_tensor(buf):
+            rows = buf[: m * width].view(m, width)[torch.from_numpy(idx).to(buf.device)].cpu().numpy()
+        else:
+            rows = buf[: m * width].reshape(m, width)[idx]
+        if width == 1:
+            arr = rows.reshape(-1).astype(np.float32)
+        else:
+            arr = pkg.unpack5(rows).astype(np.float64)
+            if width == 10:
+                arr = arr.reshape(-1, 2)
+        np.save(os.path.join(d, prefix + name + ".npy"), arr)
 
 
 def sha_dev(t):
@@ -293,7 +331,12 @@ def main():
     ap.add_argument("--multi", default="collection", choices=["collection", "independent"],
                     help="N>1: one BWT of a sharded collection (RCCL exchanges) or one independent text per GPU")
     ap.add_argument("--north-star", dest="north_star", default="auto", choices=["auto", "on", "off"],
-                    help="N=1, default workload: also time 2 steps of the >= 10 GB north-star workload (huge_s) with its digest check")
+                    help="--full, N=1, default workload: also time 2 steps of the >= 10 GB north-star workload (huge_s) with its digest check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, sampled to 60 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything besides the headline: kernel trace, profiled "
+                         "phases, roofline, digests, host-buffer and C-driver legs, CPU reference baseline, north-star leg")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -323,7 +366,7 @@ def main():
     wl_name = args.workload or "c3"
     wl = synth.WORKLOADS[wl_name]
     w, p, flags = wl["w"], wl["p"], wl["flags"]
-    O = entry.load_oracle() if (rank == 0 and not args.no_cpu_baseline and world == 1) else None
+    O = entry.load_oracle() if (args.full and rank == 0 and not args.no_cpu_baseline and world == 1) else None
 
     # rank r holds variant r of the same base sequences (collection) or its own text (independent: other seed)
     variant = rank if world > 1 else 0
@@ -383,6 +426,47 @@ def main():
         total_bytes = float(n)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_bytes * args.steps / elapsed / 1e6
+
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: the .bwt bytes and the .sa / .ssa / .esa bytes the flags ask for
+        if collection:
+            r = last["r"]
+            outs = {"bwt": r["bwt"], "sa": r.get("sa5"), "ssa": r.get("ssa"), "esa": r.get("esa")}
+        else:
+            outs = dict(bwt=bwt[: last["n_used"] + 1], **{k: ctx.fetch_dev(*outbuf[k]) for k in outbuf})
+        dump_outputs(args.dump_outputs, {k: v for k, v in outs.items() if v is not None}, pkg,
+                     budget=DUMP_BYTES // world, prefix=f"rank{rank}_" if world > 1 else "")
+
+    def headline(st):
+        """the fields of the result line a plain run prints (the counts in `config` are those of the last step run)"""
+        return {
+            "metric": "input MB/s to .bwt (bit-exact vs ref)", "value": round(value, 2), "unit": "MB/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic",
+            "config": {"workload": wl["desc"], "name": wl_name, "bytes_per_gpu": n, "w": w, "p": p, "flags": flags,
+                       "phrases": last["r"]["stats"]["phrases_total"] if collection else st["n_phrases"], "words": st["n_words"], "dict_bytes": st["dict_size"],
+                       "parse_density": st.get("parse_density"),          # the fused chain cut with probability parse_density / p (pfpgpu.h: pfp_set_parse_density)
+                       "outputs_in_timed_step": ["bwt"] + [k for k in ("sa", "ssa", "esa") if k in outbuf or (collection and ("sa5" if k == "sa" else k) in last.get("r", {}))],
+                       "parallelism": ("1 GPU" if world == 1 else
+                                       (f"{world} shards of one collection over RCCL: halo allgather, hash-partitioned all-to-all phrase dedup, "
+                                        f"allgatherv of the distinct words and of the parse, suffix array of the global dictionary sharded "
+                                        f"by key range, every rank emits (and samples / packs) the BWT range its share of SA(D) produces") if collection else
+                                       f"{world} independent texts (one per GPU), no collective")},
+        }
+
+    def finish(out):
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+
+    if not args.full:
+        finish(headline(ctx.stats()) if rank == 0 else None)
+        return
+
     # per-kernel device times: HIP events around every kernel on the library's own stream, over TRACE_STEPS further steps
     # of the same input right after the timed ones (two events per launch inside the timed region cost ~1 ms per step)
     TRACE_STEPS = 2
@@ -531,19 +615,7 @@ def main():
             got = ctx.bigbwt(host, w, p, flags)           # the same sample through the HIP path: bit-exact?
             parity_sample = {k: bool(np.array_equal(got[k], ref[k])) for k in ref if k in got}
         out = {
-            "metric": "input MB/s to .bwt (bit-exact vs ref)", "value": round(value, 2), "unit": "MB/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": wl["desc"], "name": wl_name, "bytes_per_gpu": n, "w": w, "p": p, "flags": flags,
-                       "phrases": dstats["phrases_total"] if collection else st["n_phrases"], "words": st["n_words"], "dict_bytes": st["dict_size"],
-                       "parse_density": st.get("parse_density"),          # the fused chain cut with probability parse_density / p (pfpgpu.h: pfp_set_parse_density)
-                       "outputs_in_timed_step": ["bwt"] + [k for k in ("sa", "ssa", "esa") if k in outbuf or (collection and ("sa5" if k == "sa" else k) in last.get("r", {}))],
-                       "parallelism": ("1 GPU" if world == 1 else
-                                       (f"{world} shards of one collection over RCCL: halo allgather, hash-partitioned all-to-all phrase dedup, "
-                                        f"allgatherv of the distinct words and of the parse, suffix array of the global dictionary sharded "
-                                        f"by key range, every rank emits (and samples / packs) the BWT range its share of SA(D) produces") if collection else
-                                       f"{world} independent texts (one per GPU), no collective")},
+            **headline(st),
             "roofline": roofline,
             "roofline_passes": passes,
             "kernels": rows[:24],
@@ -576,12 +648,7 @@ def main():
                 out["north_star"] = {"error": f"{type(ex).__name__}: {ex}"}
         else:
             out["north_star"] = {"skipped": "needs ~200 GB of device memory"}
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    ctx.close()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+    finish(out)
 
 
 if __name__ == "__main__":

@@ -652,7 +652,7 @@ def test_bench_two_ranks_rehearsal():
     import subprocess
     env = dict(os.environ, PFP_BENCH_BACKEND="gloo", PFP_BENCH_ONE_GPU="1")
     env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "small"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "small", "--full"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

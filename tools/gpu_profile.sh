@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 D=$PWD/gpurun_out/${tag}_prof_$wl
 rm -rf $D; mkdir -p $D
-B="python3 $GRAFT_REPO_ROOT/bench.py --workload $wl --no-cpu-baseline --no-host-boundary --north-star off $*"
+B="python3 $PWD/bench.py --full --workload $wl --no-cpu-baseline --no-host-boundary --north-star off $*"
 ( cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $D/k -o k -- $B --steps 5 --warmup 2 > $D/k.log 2>&1 ); rc=$?; echo "stats rc=$rc"
 if [ $rc -ge 124 ]; then exit $rc; fi
 tail -1 $D/k.log > gpurun_out/${tag}_${wl}_bench_under_rocprof.json
