@@ -273,6 +273,19 @@ struct RunSampler {
 };
 
 
+// ---------------------------------------------------------------- inverting / checking a BWT (unbwt.hip)
+// Device pointers.  out != NULL: write the text (n = n1 - 1 bytes) there; else text != NULL: compare with text_len bytes.
+// sa5 / ssa10 / esa10 (each may be NULL): the files to check.  Not a BWT -> Error(PFP_EFORMAT).
+struct BwtCheckArgs {
+  const uint8_t *bwt = nullptr; uint64_t n1 = 0;
+  uint8_t *out = nullptr;
+  const uint8_t *text = nullptr; uint64_t text_len = 0;
+  const uint8_t *sa5 = nullptr; uint64_t sa_bytes = 0;
+  const uint8_t *ssa10 = nullptr; uint64_t ssa_bytes = 0;
+  const uint8_t *esa10 = nullptr; uint64_t esa_bytes = 0;
+};
+void invert_bwt(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res);
+
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);
 void validate_dictionary(pfp_ctx *c, const Dictionary &D, int w);

@@ -1365,6 +1365,102 @@ int pfp_bigbwt_fd(pfp_ctx *c, int fd, uint64_t file_offset, uint64_t n, int w, u
   return bigbwt_to_files(c, n, w, p, flags, base, out_bytes, [&](StagedText &tx) { tx.stage_fd(c, fd, file_offset, n, w); });
 }
 
+// ---------------------------------------------------------------- inverting / checking a BWT (unbwt.hip)
+int pfp_unbwt_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, void *d_text) {
+  if (!c || !d_bwt || (!d_text && n_plus_1 > 1)) return PFP_EINVAL;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  BwtCheckArgs a;
+  a.bwt = (const uint8_t *)d_bwt; a.n1 = n_plus_1; a.out = (uint8_t *)d_text;
+  pfp_check_result r;
+  invert_bwt(c, a, &r);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_unbwt(pfp_ctx *c, const uint8_t *bwt, uint64_t n_plus_1, uint8_t *text) {
+  if (!c || (!bwt && n_plus_1) || (!text && n_plus_1 > 1)) return PFP_EINVAL;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  PFP_REQUIRE(n_plus_1 <= (1ull << 40), PFP_ELIMIT, "a BWT of more than 2^40 bytes (the limit of the 5-byte .sa format)");
+  DBuf<uint8_t> d_bwt(c, n_plus_1), d_text(c, n_plus_1);
+  stream_h2d(c, d_bwt.p, n_plus_1, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_memcpy(pin, bwt + off, len); });
+  BwtCheckArgs a;
+  a.bwt = d_bwt.p; a.n1 = n_plus_1; a.out = d_text.p;
+  pfp_check_result r;
+  invert_bwt(c, a, &r);
+  if (n_plus_1 > 1)
+    stream_d2h(c, d_text.p, n_plus_1 - 1, [&](const uint8_t *pin, uint64_t off, uint64_t len) { par_memcpy(text + off, pin, len); });
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_check_bwt_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_text, const void *d_sa5, const void *d_ssa10,
+                      uint64_t ssa_bytes, const void *d_esa10, uint64_t esa_bytes, pfp_check_result *out) {
+  if (!c || !d_bwt || !out) return PFP_EINVAL;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  BwtCheckArgs a;
+  const uint64_t n = n_plus_1 ? n_plus_1 - 1 : 0;
+  a.bwt = (const uint8_t *)d_bwt; a.n1 = n_plus_1;
+  a.text = (const uint8_t *)d_text; a.text_len = n;
+  a.sa5 = (const uint8_t *)d_sa5; a.sa_bytes = 5 * n;
+  a.ssa10 = (const uint8_t *)d_ssa10; a.ssa_bytes = ssa_bytes;
+  a.esa10 = (const uint8_t *)d_esa10; a.esa_bytes = esa_bytes;
+  invert_bwt(c, a, out);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// a whole file into a device buffer of the pool, through the pinned staging buffers
+static uint64_t file_to_dev(pfp_ctx *c, const std::string &path, DBuf<uint8_t> &d) {
+  const int fd = open(path.c_str(), O_RDONLY);
+  struct stat sb;
+  if (fd < 0 || fstat(fd, &sb) != 0) {
+    if (fd >= 0) close(fd);
+    throw Error(PFP_EINVAL, "cannot read " + path + ": " + strerror(errno));
+  }
+  const uint64_t bytes = (uint64_t)sb.st_size;
+  try {
+    d.alloc(c, bytes + 16);
+    stream_h2d(c, d.p, bytes, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_pread(fd, off, pin, len); });
+    sync(c);
+  } catch (...) {
+    close(fd);
+    throw;
+  }
+  close(fd);
+  return bytes;
+}
+
+int pfp_check_bwt_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, int flags,
+                        pfp_check_result *out) {
+  if (!c || !base || !out || (!text && text_fd < 0 && n)) return PFP_EINVAL;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string b(base);
+  DBuf<uint8_t> d_bwt, d_text, d_sa, d_ssa, d_esa;
+  BwtCheckArgs a;
+  a.n1 = file_to_dev(c, b + ".bwt", d_bwt);
+  a.bwt = d_bwt.p;
+  PFP_REQUIRE(a.n1 <= (1ull << 40), PFP_ELIMIT, "a BWT of more than 2^40 bytes (the limit of the 5-byte .sa format)");
+  d_text.alloc(c, n + 16);
+  if (text) stream_h2d(c, d_text.p, n, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_memcpy(pin, text + off, len); });
+  else stream_h2d(c, d_text.p, n, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_pread(text_fd, text_offset + off, pin, len); });
+  sync(c);      // (the next stream_h2d fills the same pinned buffers)
+  a.text = d_text.p; a.text_len = n;
+  if (flags & PFP_FLAG_SA) { a.sa_bytes = file_to_dev(c, b + ".sa", d_sa); a.sa5 = d_sa.p; }
+  if (flags & PFP_FLAG_SSA) { a.ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa); a.ssa10 = d_ssa.p; }
+  if (flags & PFP_FLAG_ESA) { a.esa_bytes = file_to_dev(c, b + ".esa", d_esa); a.esa10 = d_esa.p; }
+  sync(c);
+  invert_bwt(c, a, out);
+  out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------- multi-GPU chain (one rank's share)

@@ -19,6 +19,8 @@
  * per GPU inside the library, RCCL collectives between them, every rank reads its byte range of the text and pwrites its
  * ranges of the output files (the reference's -t N threads do the same on the CPU); --sum and -c then run as for one GPU.
  * PFP_MULTI_PYTHON=1 starts N processes of ../dist_main.py under torch.distributed instead (the driver the bench uses).
+ * --verify checks the files just written by inverting the BWT on the GPU (pfp_check_bwt_files: O(n), no suffix sort), the
+ * way the reference's readme suggests for inputs too large for -c; exit status 1 on any difference.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -38,6 +40,7 @@
 #include <unistd.h>
 #include "pfpgpu.h"
 #include "fasta.h"
+#include "verify.h"
 
 static double now_s(void) {
   struct timespec ts;
@@ -129,7 +132,7 @@ static int run_ranks(int gpus, const char *textfile, const char *base, int w, un
 
 static void usage(const char *argv0) {
   printf("usage: %s [-h] [-w WSIZE] [-p MOD] [-t T] [-s] [-e] [-S] [-k] [-v] [-c] [-f] [--sum]\n"
-         "              [--parsing] [--compress] [--probing] [-G N] input\n\n"
+         "              [--parsing] [--compress] [--probing] [-G N] [--verify] input\n\n"
          "MI355X build of the prefix-free-parsing BWT tool (drop-in for alshai/Big-BWT's bigbwt).\n\n"
          "  input            input file name\n"
          "  -w, --wsize W    sliding window size (def. 10)\n"
@@ -143,6 +146,7 @@ static void usage(const char *argv0) {
          "  -c               check BWT against the whole-text suffix array (reference: SACA-K)\n"
          "  -f               read fasta/fastq, plain or gzip (headers and newlines dropped, upper-cased)\n"
          "  --sum            compute output files sha256sum\n"
+         "      --verify     check the outputs by inverting the BWT on the GPU (exit 1 on any difference; not with --parsing / --compress)\n"
          "  --parsing        stop after the parsing phase (debug only)\n"
          "  --compress       compress output of the parsing phase (.parse.txz of .parse and .dicz)\n"
          "  -P, --probing    accepted for compatibility (deduplication here is exact)\n"
@@ -156,7 +160,7 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
   const double t_main = now_s();
   int w = 10, th = 0, s = 0, e = 0, S = 0, keep = 0, verbose = 0, check = 0, fasta = 0, sum = 0, parsing = 0,
-      compress = 0, device = 0, gpus = 1;
+      compress = 0, device = 0, gpus = 1, verify = 0;
   unsigned long long p = 100, halo = 1ull << 20;
   double density = 0;
   static struct option lo[] = {{"wsize", required_argument, 0, 'w'}, {"mod", required_argument, 0, 'p'},
@@ -164,7 +168,7 @@ int main(int argc, char **argv) {
                                {"compress", no_argument, 0, 1002},   {"probing", no_argument, 0, 'P'},
                                {"device", required_argument, 0, 1003}, {"help", no_argument, 0, 'h'},
                                {"gpus", required_argument, 0, 'G'},  {"halo", required_argument, 0, 1004},
-                               {"density", required_argument, 0, 1005},
+                               {"density", required_argument, 0, 1005}, {"verify", no_argument, 0, 1006},
                                {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "w:p:t:seSkvcfPhG:", lo, NULL)) != -1) {
@@ -186,6 +190,7 @@ int main(int argc, char **argv) {
       case 1003: device = atoi(optarg); break;
       case 1004: halo = strtoull(optarg, NULL, 10); break;
       case 1005: density = atof(optarg); break;
+      case 1006: verify = 1; break;
       case 'G': gpus = atoi(optarg); break;
       case 'h': usage(argv[0]); return 0;
       default: usage(argv[0]); return 2;
@@ -197,6 +202,10 @@ int main(int argc, char **argv) {
   if (S && (s || e)) {   /* bigbwt:59-61 */
     printf("You can either compute the full SA or a sample of it, not both. Exiting...\n");
     return 0;
+  }
+  if (verify && (parsing || compress)) {
+    printf("--verify checks the BWT, which --parsing / --compress do not build. Exiting...\n");
+    return 2;
   }
   if (gpus == 0) {   /* -G 0: every GPU this process can see */
     /* (the Python ranks are started by fork + exec: this process must not have touched HIP before that - pfp_device_count
@@ -242,6 +251,7 @@ int main(int argc, char **argv) {
   }
 
   int flags = (S ? PFP_FLAG_SA : 0) | (s ? PFP_FLAG_SSA : 0) | (e ? PFP_FLAG_ESA : 0);
+  uint64_t n_seen = n;      /* the text the chain saw: it stops at the first byte <= 2 (newscan.cpp:364) */
   double start0 = now_s(), start = start0;
   int status = 0;
   fprintf(logf, "==== %s\n==== input %s (%llu bytes) -w %d -p %llu%s%s%s\n", pfp_version(), input,
@@ -311,6 +321,7 @@ int main(int argc, char **argv) {
     printf("==== Parsing. Command: pfp_parse(%s, -w %d -p %llu%s)\n", input, w, p, flags ? " -s" : "");
     rc = pfp_parse(ctx, text, n, w, p, flags != 0, &pr);
     if (rc) goto fail;
+    n_seen = pr.n_used;
     fprintf(logf, "Found %llu distinct words\nTotal number of words: %llu\n", (unsigned long long)pr.n_words,
             (unsigned long long)pr.n_phrases);
     status |= write_file(input, "parse", pr.parse, pr.n_phrases * 4);
@@ -393,6 +404,7 @@ int main(int argc, char **argv) {
       printf("  GPU ms: scan %.2f phrases %.2f dictSA %.2f parseSA %.2f merge %.2f total %.2f\n", st.ms_scan,
              st.ms_phrases, st.ms_sa_dict, st.ms_sa_parse, st.ms_merge, st.ms_total);
     if (st.n != n) fprintf(stderr, "Invalid char found in input file: no additional chars will be read\n");
+    n_seen = st.n;
     fprintf(logf, "Index width: %llu bits\n", (unsigned long long)st.index_bits);      /* the reference's 32- / 64-bit executables (bigbwt:109-151) */
     printf("Elapsed time: %.4f\n", now_s() - start);
   }
@@ -404,6 +416,11 @@ int main(int argc, char **argv) {
     if (e) print_digest("ESA", input, "esa");
   }
   if (!keep) printf("==== Deleting temporary files.\n");   /* nothing was written: intermediates lived in HBM */
+  if (verify) {   /* the files just written, against the text the chain saw (with -f: the filtered text) */
+    start = now_s();
+    status |= pfp_verify_files(ctx, input, input, fd_in >= 0 ? NULL : text, fd_in, n_seen, flags);
+    printf("Elapsed time: %.4f\n", now_s() - start);
+  }
   if (check) {   /* bigbwt:177-194: whole-text suffix array -> .Bwt, then compare */
     start = now_s();
     printf("==== Computing BWT using the whole-text suffix array. Command: pfp_sacak(%s)\n", input);

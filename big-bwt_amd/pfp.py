@@ -32,13 +32,26 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_bwtparse", "pfp_merge", "pfp_bwt_result_free", "pfp_bigbwt", "pfp_bigbwt_files", "pfp_bigbwt_dev", "pfp_bigbwt_formats_dev", "pfp_dev_free", "pfp_memcpy_d2h", "pfp_pack5_dev", "pfp_sample_runs_dev", "pfp_pwrite_dev", "pfp_get_stats",
            "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
            "pfp_dist_propose_triggers", "pfp_dist_local_parse", "pfp_dist_export_local", "pfp_dist_global", "pfp_dist_global_sort", "pfp_dist_global_finish", "pfp_dist_partition_words", "pfp_dist_export_partition",
-           "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa"]
+           "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
+           "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files"]
 
 
 class PfpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERRORS.get(code, code)}: {msg}")
         self.code = code
+
+
+class CheckResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("text_mismatch", C.c_uint64), ("sa_mismatch", C.c_uint64), ("ssa_runs", C.c_uint64),
+                ("esa_runs", C.c_uint64), ("ssa_mismatch", C.c_uint64), ("esa_mismatch", C.c_uint64), ("ms", C.c_double)]
+
+    def as_dict(self):
+        """mismatch fields are None where the output is correct or was not checked (UINT64_MAX in the C struct)"""
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("text_mismatch", "sa_mismatch", "ssa_mismatch", "esa_mismatch"):
+            d[k] = None if d[k] == 2**64 - 1 else int(d[k])
+        return d
 
 
 class _ParseResult(C.Structure):
@@ -416,6 +429,35 @@ class Context:
         """device bytes -> file at an offset (pfthreads.hpp:369-376 pattern), through pinned staging buffers"""
         self._check(self.lib.pfp_pwrite_dev(self._h, C.c_char_p(os.fsencode(path)), C.c_uint64(file_offset), C.c_void_p(d_src_ptr),
                                             C.c_uint64(nbytes)))
+
+    # -- inverting / checking a BWT (the reference's readme: "check the correctness of the BWT by ... inverting it")
+    def unbwt(self, bwt):
+        """host .bwt bytes (n+1, one 0) -> the text (numpy uint8, n bytes); PfpError(PFP_EFORMAT) if they are not a BWT"""
+        b = _arr(bwt, np.uint8)
+        out = np.empty(max(len(b) - 1, 0), dtype=np.uint8)
+        self._check(self.lib.pfp_unbwt(self._h, _ptr(b, C.c_uint8) if len(b) else None, C.c_uint64(len(b)),
+                                       _ptr(out, C.c_uint8) if len(out) else None))
+        return out
+
+    def unbwt_dev(self, d_bwt_ptr, n_plus_1, d_text_ptr):
+        """device .bwt (n_plus_1 bytes) -> device text (n_plus_1 - 1 bytes)"""
+        self._check(self.lib.pfp_unbwt_dev(self._h, C.c_void_p(d_bwt_ptr), C.c_uint64(n_plus_1), C.c_void_p(d_text_ptr) if d_text_ptr else None))
+
+    def check_bwt_dev(self, d_bwt_ptr, n_plus_1, d_text_ptr=None, d_sa5_ptr=None, d_ssa10_ptr=None, ssa_bytes=0, d_esa10_ptr=None, esa_bytes=0):
+        """invert a device .bwt and compare with whatever is given (device pointers): -> dict of pfp_check_result"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        r = CheckResult()
+        self._check(self.lib.pfp_check_bwt_dev(self._h, C.c_void_p(d_bwt_ptr), C.c_uint64(n_plus_1), vp(d_text_ptr), vp(d_sa5_ptr),
+                                               vp(d_ssa10_ptr), C.c_uint64(ssa_bytes), vp(d_esa10_ptr), C.c_uint64(esa_bytes), C.byref(r)))
+        return r.as_dict()
+
+    def check_bwt_files(self, base, text, flags=0):
+        """<base>.bwt (and .sa / .ssa / .esa as flags ask) against a host text: -> dict of pfp_check_result"""
+        t = _arr(text, np.uint8)
+        r = CheckResult()
+        self._check(self.lib.pfp_check_bwt_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(t, C.c_uint8) if len(t) else None, C.c_int(-1),
+                                                 C.c_uint64(0), C.c_uint64(len(t)), C.c_int(flags), C.byref(r)))
+        return r.as_dict()
 
     # -- multi-GPU chain, one rank's share (device pointers; collectives are the caller's: dist.py)
     def dist_propose_triggers(self, d_text_ptr, n, w, p):

@@ -416,6 +416,42 @@ int pfp_multi_rccl_selftest(int device, char *errbuf, uint64_t errbuf_len);
  * it failed as intended and came back */
 int pfp_multi_rccl_selftest2(int device, int inject_failure, char *errbuf, uint64_t errbuf_len);
 
+/* ------------------------------------------------------------------------------------
+ * Inverting and checking a BWT (csrc/unbwt.hip).  The reference has no inverter; its readme asks users of large inputs to
+ * "check the correctness of the BWT by some other means (for example inverting it)" (readme.md, and the Description of the
+ * bigbwt script), and its only whole-output check is `bigbwt -c` (bigbwt:177-194: a whole-text suffix array).  These take
+ * O(n) work and about 4 (below 2^32 rows) or 8 bytes of device memory per BWT byte, plus 0.14 per .ssa / .esa checked.
+ * Conventions for a text T of n bytes: the .bwt holds n+1 bytes with exactly one 0; row j has SA[j] and BWT[j] = T[SA[j]-1]
+ * (0 where SA[j] = 0), SA[0] = n.  .sa holds SA[1..n] as 5-byte little-endian ints; .ssa the pairs <j, SA[j]> of the run
+ * starts (j = 0 or BWT[j] != BWT[j-1]), .esa those of the run ends (j = n or BWT[j] != BWT[j+1]), 5 + 5 bytes each.
+ * Validity: n+1 bytes are a BWT iff they hold exactly one 0 and LF(j) = C[BWT[j]] + #{i < j : BWT[i] = BWT[j]} is ONE cycle
+ * through all n+1 rows; anything else returns PFP_EFORMAT (pfp_last_error names the rule).  A mismatch against the text or
+ * the SA files is not an error: the call returns PFP_OK with the fields below set.  n+1 > 2^40 -> PFP_ELIMIT (the .sa
+ * format's limit).  PFP_FORCE_IDX64=1 / pfp_set_index_bits(ctx, 64) selects the 8-byte layout at any size.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t n;                           /* text length the BWT encodes (n_plus_1 - 1) */
+  uint64_t text_mismatch;               /* smallest text position where the inverse differs from the given text (a text of another
+                                           length: at most the shorter length); UINT64_MAX = equal or not checked */
+  uint64_t sa_mismatch;                 /* smallest j in 1..n whose .sa entry != SA[j], or the first index past a short / long file */
+  uint64_t ssa_runs, esa_runs;          /* run starts / ends of the BWT = the pairs a correct .ssa / .esa holds (0 if not checked) */
+  uint64_t ssa_mismatch, esa_mismatch;  /* smallest pair index that is wrong, missing or extra; UINT64_MAX = correct or not checked */
+  double ms;                            /* host wall time of the call */
+} pfp_check_result;
+/* d_bwt: n_plus_1 device bytes -> d_text: n device bytes (may be NULL when n = 0) */
+int pfp_unbwt_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, void *d_text);
+/* the same with host buffers (text: n_plus_1 - 1 bytes) */
+int pfp_unbwt(pfp_ctx *ctx, const uint8_t *bwt, uint64_t n_plus_1, uint8_t *text);
+/* device pointers; every input but d_bwt may be NULL (not checked): d_text n bytes, d_sa5 5n bytes, d_ssa10 / d_esa10 of
+ * ssa_bytes / esa_bytes.  out is filled on PFP_OK. */
+int pfp_check_bwt_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, const void *d_text, const void *d_sa5, const void *d_ssa10,
+                      uint64_t ssa_bytes, const void *d_esa10, uint64_t esa_bytes, pfp_check_result *out);
+/* what `bigbwt --verify` and `unbwt --check` call: reads <base>.bwt and, as flags ask (PFP_FLAG_SA / SSA / ESA), <base>.sa /
+ * .ssa / .esa through the pinned staging buffers; the text (n bytes) comes from host memory, or (text == NULL) from bytes
+ * [text_offset, text_offset + n) of the open file text_fd.  A requested file that cannot be read -> PFP_EINVAL. */
+int pfp_check_bwt_files(pfp_ctx *ctx, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, int flags,
+                        pfp_check_result *out);
+
 /* ---- micro entry points used by bench.py's roofline leg and by the parity tests ---- */
 /* copy a device-resident text into the ctx's padded staging buffer (T' = Dollar.T.Dollar^w) */
 int pfp_stage_text_dev(pfp_ctx *ctx, const void *d_text, uint64_t n, int w);
