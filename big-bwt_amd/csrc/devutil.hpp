@@ -75,4 +75,19 @@ __device__ __forceinline__ void load_flags16(const uint8_t *__restrict__ flags, 
     for (int k = 0; k < 16; k++) if (base + k < n && flags[base + k]) w[k >> 2] |= 1u << (8 * (k & 3));
   }
 }
+// rank in a bitmap with a popcount directory of 512-bit superblocks: set bits of bits[] before bit r (bits[r >> 6] must exist)
+__device__ __forceinline__ uint64_t bit_rank(const uint64_t *__restrict__ bits, const uint64_t *__restrict__ dir, uint64_t r) {
+  const uint64_t wi = r >> 6;
+  uint64_t k = dir[r >> 9];
+  for (uint64_t w = (r >> 9) << 3; w < wi; w++) k += __popcll(bits[w]);
+  return k + __popcll(bits[wi] & ((1ull << (r & 63)) - 1));
+}
+
+// the 5-byte little-endian integer at byte off of a buffer of `bytes` bytes (the .sa / .ssa / .esa format)
+__device__ __forceinline__ uint64_t ld5(const uint8_t *p, uint64_t off, uint64_t bytes) {
+  if (off + 8 <= bytes) return ld8u(p + off) & 0xFFFFFFFFFFull;
+  uint64_t v = 0;
+  for (int i = 4; i >= 0; i--) v = (v << 8) | p[off + i];
+  return v;
+}
 }  // namespace pfp

@@ -1,0 +1,532 @@
+// fmsearch.hip -- counting and locating patterns over a .bwt and its run samples (.ssa / .esa): the r-index of Gagie, Navarro
+// and Prezza, "Optimal-time text indexing in BWT-runs bounded space" (SODA 2018), with the plain BWT bytes for rank.  The
+// reference has no counterpart; the paper is the source.  Conventions: include/pfpgpu.h (rows j = 0..n, SA[0] = n).
+//
+//   Rank.  The symbols present (bytes other than 0) get dense codes.  The BWT is cut into 256-row blocks and 65536-row
+//   superblocks; sbc[superblock][k] = C[c] + occurrences of c before the superblock (u64), blk[block][k] = occurrences before
+//   the block inside its superblock (u16).  LF(i, c) = C[c] + rank_c(i) = sbc + blk + the c's among the first i & 255 bytes of
+//   i's block, which a group of 16 lanes counts from one contiguous 256-byte read (16 bytes per lane, a SWAR compare, a masked
+//   popcount and a group sum): "lanes per item matched to the item".
+//   Count.  One group of 16 lanes per pattern runs backward search from [0, n+1): sp' = LF(sp, c), ep' = LF(ep, c), at most m
+//   steps.  With samples it keeps the toehold SA[sp]: toehold - 1 if BWT[sp] = c, else SA[j] - 1 for the first c in [sp, ep),
+//   a run start j (BWT[j-1] != c) found by a select (binary search over the block directory, then the 16 lanes of one block),
+//   whose SA value is the run-start sample of rank j in the run-start bitmap.
+//   Locate.  The run starts inside [sp, sp + cap) cut the range into segments whose first SA value is known (the toehold, or a
+//   run-start sample); inside a segment SA[j+1] = phi^-1(SA[j]) = SA[s_{i+1}] + (SA[j] - SA[e_i]) with SA[e_i] the largest
+//   run-end sample <= SA[j].  Plan (segments and positions per pattern) -> library scans -> expand (one lane per segment:
+//   pattern by binary search, start row and value, output slot out_off[p] + row - sp) -> chains, one lane per segment, at
+//   most kChainSteps steps per launch; the predecessor search reads a bucket directory over text positions, then at most
+//   log2 of the bucket's keys.
+// Bounds: every loop is bounded by the pattern length, a directory's size or kChainSteps; values read from the samples only
+// ever become output values or are clamped before they index anything.
+#include "kernels.hpp"
+#include "prims.hpp"
+#include "devutil.hpp"
+
+namespace pfp {
+
+namespace {
+
+constexpr int kTB = 256;
+constexpr int kBlkLog = 8;                  // 256 rows per rank block
+constexpr int kSbLog = 16;                  // 65536 rows per superblock: in-superblock counts fit u16
+constexpr int kBlkPerSb = 1 << (kSbLog - kBlkLog);
+constexpr int kHistBlocks = 16;             // rank blocks per wave of the directory build
+constexpr uint64_t kChainSteps = 16384;     // phi^-1 steps per chain and launch
+constexpr uint8_t kAbsent = 0xFF;
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void atomic_min_u64(uint64_t *p, uint64_t v) { atomicMin((unsigned long long *)p, (unsigned long long)v); }
+__device__ __forceinline__ void atomic_max_u64(uint64_t *p, uint64_t v) { atomicMax((unsigned long long *)p, (unsigned long long)v); }
+
+// ---------------------------------------------------------------- directory build
+// hist[c] += occurrences of byte c (per-wave LDS histograms)
+__global__ void __launch_bounds__(kTB) fm_bytehist(const uint8_t *__restrict__ bwt, uint64_t n1, unsigned long long *__restrict__ hist) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t lo = BID * 16384, hi = lo + 16384 < n1 ? lo + 16384 : n1;
+  for (uint64_t x = lo + 16 * (uint64_t)threadIdx.x; x < hi; x += 16 * kTB) {
+    const uint4 v = ld16u(bwt + x);      // (the copy is padded: whole 16-byte words are in bounds)
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 16; q++)
+      if (x + q < hi) atomicAdd(&h[(w[q >> 2] >> (8 * (q & 3))) & 255], 1u);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// cnt[b * sigma + k] = occurrences of code k in rank block b; one wave per kHistBlocks blocks, 4 bytes per lane
+__global__ void __launch_bounds__(kTB) fm_blockhist(const uint8_t *__restrict__ bwt, uint64_t n1, uint64_t nb, const uint8_t *__restrict__ codes,
+                                                    int sigma, uint16_t *__restrict__ cnt) {
+  __shared__ uint32_t h[kTB / 64][256];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t b0 = (BID * (kTB / 64) + wv) * kHistBlocks;
+  if (b0 >= nb) return;                                 // (no block-wide barrier below: every wave works alone)
+  const uint64_t b1 = b0 + kHistBlocks < nb ? b0 + kHistBlocks : nb;
+  for (uint64_t b = b0; b < b1; b++) {
+    for (int i = lane; i < 256; i += 64) h[wv][i] = 0;
+    wave_sync();
+    const uint64_t r = (b << kBlkLog) + 4 * (uint64_t)lane;
+    const uint32_t w = *reinterpret_cast<const uint32_t *>(bwt + r);
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if (r + q < n1) atomicAdd(&h[wv][(w >> (8 * q)) & 255], 1u);
+    wave_sync();
+    for (int k = lane; k < sigma; k += 64) cnt[b * sigma + k] = (uint16_t)h[wv][codes[256 + k]];
+    wave_sync();
+  }
+}
+
+// in place: cnt[b * sigma + k] -> occurrences of code k in the blocks of b's superblock before b; tot[k * ns + s] = the superblock's
+__global__ void __launch_bounds__(kTB) fm_blockscan(uint16_t *__restrict__ cnt, uint64_t nb, uint64_t ns, int sigma, uint64_t *__restrict__ tot) {
+  const uint64_t t = BID * kTB + threadIdx.x;
+  if (t >= ns * sigma) return;
+  const uint64_t s = t / sigma, k = t % sigma;
+  const uint64_t b0 = s * kBlkPerSb, b1 = b0 + kBlkPerSb < nb ? b0 + kBlkPerSb : nb;
+  uint32_t run = 0;
+  for (uint64_t b = b0; b < b1; b++) {
+    const uint32_t x = cnt[b * sigma + k];
+    cnt[b * sigma + k] = (uint16_t)run;
+    run += x;
+  }
+  tot[k * ns + s] = run;
+}
+
+// sbc[s * sigma + k] = base[k * ns + s] + 1: the symbol-major exclusive sum counts the bytes of smaller codes, + 1 for the 0
+__global__ void __launch_bounds__(kTB) fm_sbc(const uint64_t *__restrict__ base, uint64_t ns, int sigma, uint64_t *__restrict__ sbc) {
+  const uint64_t t = BID * kTB + threadIdx.x;
+  if (t >= ns * sigma) return;
+  const uint64_t s = t / sigma, k = t % sigma;
+  sbc[t] = base[k * ns + s] + 1;
+}
+
+// ---------------------------------------------------------------- samples
+// pair i of .ssa / .esa: its row must be the i-th run start / end (bit set, rank i); the smallest bad pair index meets in
+// bad[0] / bad[1].  rs_row / rs_sa: the run starts; key / val: the phi^-1 table SA[e_i] -> SA[s_{i+1}], i < runs - 1
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_pairs(const uint8_t *__restrict__ ssa, const uint8_t *__restrict__ esa, uint64_t runs, uint64_t n1,
+                                                const uint64_t *__restrict__ sbits, const uint64_t *__restrict__ sdir, const uint64_t *__restrict__ ebits,
+                                                const uint64_t *__restrict__ edir, I *__restrict__ rs_row, I *__restrict__ rs_sa, I *__restrict__ key,
+                                                I *__restrict__ val, uint64_t *__restrict__ bad) {
+  const uint64_t i = BID * kTB + threadIdx.x;
+  if (i >= runs) return;
+  const uint64_t bytes = 10 * runs;
+  const uint64_t js = ld5(ssa, 10 * i, bytes), vs = ld5(ssa, 10 * i + 5, bytes);
+  const uint64_t je = ld5(esa, 10 * i, bytes), ve = ld5(esa, 10 * i + 5, bytes);
+  if (js >= n1 || !((sbits[js >> 6] >> (js & 63)) & 1) || bit_rank(sbits, sdir, js) != i) atomic_min_u64(&bad[0], i);
+  if (je >= n1 || !((ebits[je >> 6] >> (je & 63)) & 1) || bit_rank(ebits, edir, je) != i) atomic_min_u64(&bad[1], i);
+  rs_row[i] = (I)js;
+  rs_sa[i] = (I)vs;
+  if (i + 1 < runs) {
+    key[i] = (I)ve;
+    val[i] = (I)ld5(ssa, 10 * (i + 1) + 5, bytes);
+  }
+}
+
+// dir[b] = first index of a key >= b << shift (b = 0..nbk; the keys are sorted)
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_phidir(const I *__restrict__ key, uint64_t nkeys, uint64_t nbk, int shift, I *__restrict__ dir) {
+  const uint64_t b = BID * kTB + threadIdx.x;
+  if (b > nbk) return;
+  const uint64_t x = b << shift;
+  uint64_t lo = 0, hi = nkeys;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)key[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  dir[b] = (I)lo;
+}
+
+// ---------------------------------------------------------------- searches
+template <class I>
+struct FmArgs {
+  const uint8_t *bwt; uint64_t n1;
+  const uint8_t *codes;
+  const uint16_t *blk; const uint64_t *sbc; int sigma;
+  const uint64_t *rbits, *rdir; uint64_t runs;
+  const I *rs_row, *rs_sa;
+  const I *key, *val, *dir; uint64_t nphi, nbk; int shift;
+};
+
+__device__ __forceinline__ uint64_t gsum16(uint64_t v) {
+  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+  return v;
+}
+__device__ __forceinline__ uint64_t gmin16(uint64_t v) {
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1) { const uint64_t o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
+  return v;
+}
+// bit 7 of each byte of w set where that byte equals the byte replicated in c4
+__device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c4) {
+  const uint32_t x = w ^ c4;
+  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+}
+
+// C[c] + rank_c(i) for 0 <= i <= n1; gl = this lane's place in its group of 16 (all 16 call it with the same arguments)
+template <class I>
+__device__ __forceinline__ uint64_t lf_at(const FmArgs<I> &a, uint64_t i, uint32_t c4, uint32_t k, int gl) {
+  const uint64_t blk = i >> kBlkLog;
+  const uint64_t base = a.sbc[(i >> kSbLog) * a.sigma + k] + a.blk[blk * a.sigma + k];
+  const uint4 v = ld16u(a.bwt + (blk << kBlkLog) + 16 * gl);
+  const int keep = (int)(i & 255) - 16 * gl;           // bytes of this lane's 16 that lie before row i
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int kq = keep - 4 * q;
+    const uint32_t m = kq >= 4 ? 0x80808080u : kq <= 0 ? 0u : (0x80808080u & ((1u << (8 * kq)) - 1u));
+    cnt += __popc(eq_bytes(w[q], c4) & m);
+  }
+  return base + gsum16(cnt);
+}
+
+// the row j in [sp, ep) of the c with C[c] + rank_c(j) = target (the first c there); ~0 if there is none
+template <class I>
+__device__ __forceinline__ uint64_t select_first(const FmArgs<I> &a, uint64_t sp, uint64_t ep, uint64_t target, uint32_t c4, uint32_t k, int gl) {
+  uint64_t lo = sp >> kBlkLog, hi = (ep - 1) >> kBlkLog;        // the last block whose start has lf <= target
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) >> 1;
+    const uint64_t r = a.sbc[(mid >> (kSbLog - kBlkLog)) * a.sigma + k] + a.blk[mid * a.sigma + k];
+    if (r <= target) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint64_t want = target - (a.sbc[(lo >> (kSbLog - kBlkLog)) * a.sigma + k] + a.blk[lo * a.sigma + k]);
+  const uint4 v = ld16u(a.bwt + (lo << kBlkLog) + 16 * gl);
+  const uint32_t e[4] = {eq_bytes(v.x, c4), eq_bytes(v.y, c4), eq_bytes(v.z, c4), eq_bytes(v.w, c4)};
+  const uint32_t mine = __popc(e[0]) + __popc(e[1]) + __popc(e[2]) + __popc(e[3]);
+  uint32_t incl = mine;                                            // inclusive sum over the group's lanes
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1) {
+    const uint32_t o = __shfl_up(incl, d, 16);
+    if (gl >= d) incl += o;
+  }
+  uint64_t j = ~0ull;
+  const uint64_t excl = incl - mine;
+  if (want >= excl && want < incl) {
+    uint32_t left = (uint32_t)(want - excl);
+    for (int q = 0; q < 4; q++) {
+      uint32_t m = e[q];
+      const uint32_t pc = __popc(m);
+      if (left < pc) {
+        for (uint32_t t = 0; t < left; t++) m &= m - 1;
+        j = (lo << kBlkLog) + 16 * gl + 4 * q + (__ffs(m) - 1) / 8;
+        break;
+      }
+      left -= pc;
+    }
+  }
+  j = gmin16(j);
+  return j >= sp && j < ep ? j : ~0ull;
+}
+
+// one group of 16 lanes per pattern
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_count_k(FmArgs<I> a, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
+                                                  uint64_t *__restrict__ sp_out, uint64_t *__restrict__ ep_out, uint64_t *__restrict__ first_out) {
+  __shared__ uint8_t code[256];
+  code[threadIdx.x] = a.codes[threadIdx.x];
+  __syncthreads();
+  const int gl = threadIdx.x & 15;
+  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
+  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
+  const uint64_t o0 = off[p], o1 = off[p + 1];
+  uint64_t sp = 0, ep = o1 < o0 ? 0 : a.n1, first = a.n1 - 1;      // (decreasing offsets: no pattern, no occurrence)
+  for (uint64_t t = o1; t > o0 && sp < ep;) {           // at most m = o1 - o0 steps
+    t--;
+    const uint32_t c = pat[t], k = code[c];
+    if (k == kAbsent) { ep = sp; break; }               // (byte 0 has no code: a pattern holding it has no occurrence)
+    const uint32_t c4 = c * 0x01010101u;
+    const uint64_t nsp = lf_at(a, sp, c4, k, gl), nep = lf_at(a, ep, c4, k, gl);
+    if (first_out && nep > nsp) {
+      if (a.bwt[sp] == c) {
+        first -= 1;
+      } else {
+        const uint64_t j = select_first(a, sp, ep, nsp, c4, k, gl);
+        const uint64_t q = j < a.n1 ? bit_rank(a.rbits, a.rdir, j) : a.runs;
+        first = q < a.runs ? (uint64_t)a.rs_sa[q] - 1 : ~0ull;
+      }
+    }
+    sp = nsp; ep = nep;
+  }
+  if (ep <= sp) { sp = ep = 0; first = ~0ull; }
+  if (gl == 0) {
+    sp_out[p] = sp; ep_out[p] = ep;
+    if (first_out) first_out[p] = first;
+  }
+}
+
+// run starts in rows [0, x), 0 <= x <= n1
+template <class I>
+__device__ __forceinline__ uint64_t starts_before(const FmArgs<I> &a, uint64_t x) { return x >= a.n1 ? a.runs : bit_rank(a.rbits, a.rdir, x); }
+
+// per pattern: positions cap = min(ep - sp, max_occ), segments 1 + run starts in (sp, sp + cap), q0 = rank of the first of them
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_plan(FmArgs<I> a, uint64_t npat, const uint64_t *__restrict__ sp, const uint64_t *__restrict__ ep,
+                                               uint64_t max_occ, uint64_t *__restrict__ npos, uint64_t *__restrict__ nseg, uint64_t *__restrict__ q0) {
+  const uint64_t p = BID * kTB + threadIdx.x;
+  if (p > npat) return;
+  uint64_t cap = 0, segs = 0, q = 0;
+  if (p < npat) {
+    const uint64_t s = sp[p], e = ep[p];
+    cap = e <= a.n1 && s < e ? e - s : 0;
+    if (max_occ && cap > max_occ) cap = max_occ;
+    if (cap && nseg) {
+      q = starts_before(a, s + 1);
+      segs = 1 + starts_before(a, s + cap) - q;
+    }
+  }
+  npos[p] = cap;                                       // (entry npat = 0: the exclusive sums end with the totals)
+  if (nseg) { nseg[p] = segs; q0[p] = q; }
+}
+
+struct Seg { uint64_t x, slot, rem; };
+
+// one lane per segment: its pattern (binary search over seg_off), start row and SA value, output slot and length
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_expand(FmArgs<I> a, uint64_t npat, uint64_t S, const uint64_t *__restrict__ seg_off,
+                                                 const uint64_t *__restrict__ nseg, const uint64_t *__restrict__ q0, const uint64_t *__restrict__ npos,
+                                                 const uint64_t *__restrict__ out_off, const uint64_t *__restrict__ sp, const uint64_t *__restrict__ first,
+                                                 Seg *__restrict__ seg, uint64_t *__restrict__ maxlen) {
+  const uint64_t g = BID * kTB + threadIdx.x;
+  if (g >= S) return;
+  uint64_t lo = 0, hi = npat - 1;                      // the last pattern p with seg_off[p] <= g
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) >> 1;
+    if (seg_off[mid] <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint64_t p = lo, k = g - seg_off[p], s = sp[p];
+  uint64_t row = s, x = first[p];
+  if (k) { row = a.rs_row[q0[p] + k - 1]; x = a.rs_sa[q0[p] + k - 1]; }
+  const uint64_t end = k + 1 < nseg[p] ? (uint64_t)a.rs_row[q0[p] + k] : s + npos[p];
+  const uint64_t len = end > row ? end - row : 0;
+  seg[g] = Seg{x, out_off[p] + (row - s), len};
+  atomic_max_u64(maxlen, len);
+}
+
+// SA[j + 1] from x = SA[j] (j not the last row of a run): the largest key <= x, searched in x's bucket
+template <class I>
+__device__ __forceinline__ uint64_t phi_inv(const FmArgs<I> &a, uint64_t x) {
+  uint64_t b = x >> a.shift;
+  if (b >= a.nbk) b = a.nbk - 1;
+  uint64_t lo = a.dir[b], hi = a.dir[b + 1];           // keys [lo, hi) are in the bucket; the answer is in [lo - 1, hi - 1]
+  while (lo < hi) {                                    // first index in [lo, hi) with key > x
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)a.key[mid] <= x) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint64_t i = lo ? lo - 1 : 0;                  // (lo = 0: no key <= x, only for samples that are not this BWT's)
+  return (uint64_t)a.val[i] + (x - (uint64_t)a.key[i]);
+}
+
+// one lane per segment, at most kChainSteps positions per launch; the state goes back for the next launch
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_chain(FmArgs<I> a, uint64_t S, Seg *__restrict__ seg, uint64_t *__restrict__ pos) {
+  const uint64_t g = BID * kTB + threadIdx.x;
+  if (g >= S) return;
+  Seg s = seg[g];
+  if (!s.rem) return;
+  const uint64_t steps = s.rem < kChainSteps ? s.rem : kChainSteps;
+  for (uint64_t t = 0; t < steps; t++) {
+    pos[s.slot++] = s.x;
+    if (--s.rem) s.x = phi_inv(a, s.x);
+  }
+  seg[g] = s;
+}
+
+template <class I>
+FmArgs<I> args_of(const FmIndex &f) {
+  FmArgs<I> a{};
+  a.bwt = f.bwt.p; a.n1 = f.n1; a.codes = f.codes.p;
+  a.blk = f.blk.p; a.sbc = f.sbc.p; a.sigma = f.sigma;
+  if (f.samples) {
+    a.rbits = f.rs.bits.p; a.rdir = f.rs.dir.p; a.runs = f.runs;
+    a.rs_row = (const I *)f.rs_row.p; a.rs_sa = (const I *)f.rs_sa.p;
+    a.key = (const I *)f.phi_key.p; a.val = (const I *)f.phi_val.p; a.dir = (const I *)f.phi_dir.p;
+    a.nphi = f.nphi; a.nbk = f.nbk; a.shift = f.shift;
+  }
+  return a;
+}
+
+template <class I>
+void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10, uint64_t esa_bytes) {
+  const uint64_t n1 = f.n1;
+  f.rs.build(c, f.bwt.p, n1, 0);
+  const uint64_t r = f.runs = f.rs.runs;
+  PFP_REQUIRE(ssa_bytes == 10 * r, PFP_EFORMAT, ".ssa holds " + std::to_string(ssa_bytes) + " bytes; the BWT has " + std::to_string(r) +
+                                                    " runs, so its .ssa holds " + std::to_string(10 * r));
+  PFP_REQUIRE(esa_bytes == 10 * r, PFP_EFORMAT, ".esa holds " + std::to_string(esa_bytes) + " bytes; the BWT has " + std::to_string(r) +
+                                                    " runs, so its .esa holds " + std::to_string(10 * r));
+  f.rs_row.alloc(c, r * sizeof(I));
+  f.rs_sa.alloc(c, r * sizeof(I));
+  f.nphi = r - 1;
+  DBuf<I> key(c, r), val(c, r);
+  {
+    RunIndex re;
+    re.build(c, f.bwt.p, n1, 1);
+    DBuf<uint64_t> bad(c, 2);
+    PFP_HIP(hipMemsetAsync(bad.p, 0xFF, 16, c->stream));
+    {
+      KScope ks(c, "fm_pairs", 20 * r + 4 * r * sizeof(I));
+      fm_pairs<I><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(ssa10, esa10, r, n1, f.rs.bits.p, f.rs.dir.p, re.bits.p, re.dir.p,
+                                                              (I *)f.rs_row.p, (I *)f.rs_sa.p, key.p, val.p, bad.p);
+      PFP_HIP(hipGetLastError());
+    }
+    uint64_t h[2];
+    d2h(c, h, bad.p, 2);
+    sync(c);
+    PFP_REQUIRE(h[0] == ~0ull, PFP_EFORMAT, ".ssa pair " + std::to_string(h[0]) + " does not name run start " + std::to_string(h[0]) + " of the BWT");
+    PFP_REQUIRE(h[1] == ~0ull, PFP_EFORMAT, ".esa pair " + std::to_string(h[1]) + " does not name run end " + std::to_string(h[1]) + " of the BWT");
+  }
+  const int kb = bits_for(n1);
+  f.phi_key.alloc(c, std::max<uint64_t>(f.nphi, 1) * sizeof(I));
+  f.phi_val.alloc(c, std::max<uint64_t>(f.nphi, 1) * sizeof(I));
+  if (f.nphi) {
+    SortTag tag("phi^-1 table");
+    sort_pairs<I, I>(c, key.p, (I *)f.phi_key.p, val.p, (I *)f.phi_val.p, f.nphi, 0, kb);
+  } else {                                              // (one run: the table is never read; one entry keeps the search in bounds)
+    PFP_HIP(hipMemsetAsync(f.phi_key.p, 0, sizeof(I), c->stream));
+    PFP_HIP(hipMemsetAsync(f.phi_val.p, 0, sizeof(I), c->stream));
+  }
+  key.release(); val.release();
+  // about one key per bucket
+  f.shift = std::max(0, kb - bits_for(std::max<uint64_t>(f.nphi, 1)));
+  f.nbk = (n1 >> f.shift) + 1;
+  f.phi_dir.alloc(c, (f.nbk + 1) * sizeof(I));
+  {
+    KScope ks(c, "fm_phidir", (f.nbk + 1) * sizeof(I) * 8);
+    fm_phidir<I><<<gdim(cdiv(f.nbk + 1, kTB)), kTB, 0, c->stream>>>((const I *)f.phi_key.p, f.nphi, f.nbk, f.shift, (I *)f.phi_dir.p);
+    PFP_HIP(hipGetLastError());
+  }
+  f.samples = true;
+}
+
+}  // namespace
+
+uint64_t fm_bwt_bytes(uint64_t n1) { return ((n1 >> kBlkLog) + 1) << kBlkLog; }
+
+uint64_t FmIndex::device_bytes() const {
+  return bwt.bytes() + codes.bytes() + blk.bytes() + sbc.bytes() + rs.bits.bytes() + rs.dir.bytes() + rs_row.bytes() + rs_sa.bytes() +
+         phi_key.bytes() + phi_val.bytes() + phi_dir.bytes();
+}
+
+void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
+              uint64_t esa_bytes) {
+  PFP_REQUIRE(n1 >= 1, PFP_EFORMAT, "not a BWT: no byte 0 (an empty input)");
+  PFP_REQUIRE(n1 <= (1ull << 40), PFP_ELIMIT, "a BWT of more than 2^40 bytes (the limit of the 5-byte .sa format)");
+  PFP_REQUIRE(bwt, PFP_EINVAL, "no BWT");
+  PFP_REQUIRE(!ssa10 == !esa10, PFP_EINVAL, "the run samples come as a pair: .ssa and .esa, or neither");
+  f.c = c;
+  f.n1 = n1;
+  f.wide = c->force_wide || n1 >= (1ull << 32);
+  const uint64_t nb = (n1 >> kBlkLog) + 1, ns = (nb + kBlkPerSb - 1) / kBlkPerSb;
+  if (bwt != f.bwt.p) {                                 // (pfp_fm_build_files reads the file into f.bwt itself)
+    f.bwt.alloc(c, fm_bwt_bytes(n1));
+    PFP_HIP(hipMemcpyAsync(f.bwt.p, bwt, n1, hipMemcpyDeviceToDevice, c->stream));
+  }
+  PFP_HIP(hipMemsetAsync(f.bwt.p + n1, 0, fm_bwt_bytes(n1) - n1, c->stream));
+  uint64_t hist[256];
+  {
+    DBuf<uint64_t> d_hist(c, 256);
+    d_hist.zero();
+    {
+      KScope ks(c, "fm_bytehist", n1);
+      fm_bytehist<<<gdim(cdiv(n1, 16384)), kTB, 0, c->stream>>>(f.bwt.p, n1, (unsigned long long *)d_hist.p);
+      PFP_HIP(hipGetLastError());
+    }
+    d2h(c, hist, d_hist.p, 256);
+    sync(c);
+  }
+  PFP_REQUIRE(hist[0] == 1, PFP_EFORMAT, "not a BWT: " + std::to_string(hist[0]) + " bytes 0 among " + std::to_string(n1) + " (a BWT holds exactly one)");
+  uint8_t codes[512];
+  memset(codes, kAbsent, 256);
+  memset(codes + 256, 0, 256);
+  int sigma = 0;
+  for (int b = 1; b < 256; b++)
+    if (hist[b]) { codes[b] = (uint8_t)sigma; codes[256 + sigma] = (uint8_t)b; sigma++; }
+  f.sigma = sigma;
+  f.codes.alloc(c, 512);
+  h2d(c, f.codes.p, codes, 512);
+  f.blk.alloc(c, nb * std::max(sigma, 1));
+  f.sbc.alloc(c, ns * std::max(sigma, 1));
+  if (sigma) {
+    const uint64_t waves = cdiv(nb, kHistBlocks);
+    {
+      KScope ks(c, "fm_blockhist", n1 + nb * sigma * 2);
+      fm_blockhist<<<gdim(cdiv(waves, kTB / 64)), kTB, 0, c->stream>>>(f.bwt.p, n1, nb, f.codes.p, sigma, f.blk.p);
+      PFP_HIP(hipGetLastError());
+    }
+    DBuf<uint64_t> tot(c, ns * sigma), base(c, ns * sigma);
+    {
+      KScope ks(c, "fm_blockscan", nb * sigma * 4 + ns * sigma * 8);
+      fm_blockscan<<<gdim(cdiv(ns * sigma, kTB)), kTB, 0, c->stream>>>(f.blk.p, nb, ns, sigma, tot.p);
+      PFP_HIP(hipGetLastError());
+    }
+    exclusive_sum_u64(c, tot.p, base.p, ns * sigma);
+    fm_sbc<<<gdim(cdiv(ns * sigma, kTB)), kTB, 0, c->stream>>>(base.p, ns, sigma, f.sbc.p);
+    PFP_HIP(hipGetLastError());
+  }
+  if (ssa10) {
+    if (f.wide) build_samples<uint64_t>(c, f, ssa10, ssa_bytes, esa10, esa_bytes);
+    else build_samples<uint32_t>(c, f, ssa10, ssa_bytes, esa10, esa_bytes);
+  }
+  sync(c);
+}
+
+void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
+  pfp_ctx *c = f.c;
+  PFP_REQUIRE(!first || f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
+  if (!npat) return;
+  KScope ks(c, "fm_count", 0);
+  if (f.wide) fm_count_k<uint64_t><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<uint64_t>(f), pat, pat_off, npat, sp, ep, first);
+  else fm_count_k<uint32_t><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<uint32_t>(f), pat, pat_off, npat, sp, ep, first);
+  PFP_HIP(hipGetLastError());
+}
+
+template <class I>
+static void locate_t(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
+                     uint64_t *out_off, uint64_t *pos) {
+  pfp_ctx *c = f.c;
+  const FmArgs<I> a = args_of<I>(f);
+  DBuf<uint64_t> npos(c, npat + 1), nseg, q0, seg_off;
+  if (pos) { nseg.alloc(c, npat + 1); q0.alloc(c, npat + 1); seg_off.alloc(c, npat + 1); }
+  fm_plan<I><<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(a, npat, sp, ep, max_occ, npos.p, pos ? nseg.p : nullptr, pos ? q0.p : nullptr);
+  PFP_HIP(hipGetLastError());
+  exclusive_sum_u64(c, npos.p, out_off, npat + 1);
+  if (!pos || !npat) return;
+  exclusive_sum_u64(c, nseg.p, seg_off.p, npat + 1);
+  const uint64_t S = read_scalar(c, seg_off.p + npat);
+  if (!S) return;
+  DBuf<Seg> seg(c, S);
+  DBuf<uint64_t> maxlen(c, 1);
+  maxlen.zero();
+  {
+    KScope ks(c, "fm_expand", S * (24 + 8 * 6));
+    fm_expand<I><<<gdim(cdiv(S, kTB)), kTB, 0, c->stream>>>(a, npat, S, seg_off.p, nseg.p, q0.p, npos.p, out_off, sp, first, seg.p, maxlen.p);
+    PFP_HIP(hipGetLastError());
+  }
+  const uint64_t longest = read_scalar(c, maxlen.p);
+  KScope ks(c, "fm_chain", 0);
+  for (uint64_t done = 0; done < longest; done += kChainSteps) {
+    fm_chain<I><<<gdim(cdiv(S, kTB)), kTB, 0, c->stream>>>(a, S, seg.p, pos);
+    PFP_HIP(hipGetLastError());
+  }
+}
+
+void fm_locate(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
+               uint64_t *out_off, uint64_t *pos) {
+  PFP_REQUIRE(f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  PFP_REQUIRE(!pos || first, PFP_EINVAL, "locate needs the toehold SA[sp] of every pattern (count with first)");
+  if (f.wide) locate_t<uint64_t>(f, npat, sp, ep, first, max_occ, out_off, pos);
+  else locate_t<uint32_t>(f, npat, sp, ep, first, max_occ, out_off, pos);
+}
+
+}  // namespace pfp

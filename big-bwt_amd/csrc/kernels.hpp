@@ -285,6 +285,42 @@ struct BwtCheckArgs {
   const uint8_t *esa10 = nullptr; uint64_t esa_bytes = 0;
 };
 void invert_bwt(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res);
+// bitmap of the run starts (which = 0: j = 0 or BWT[j] != BWT[j-1]) or run ends (which = 1) of a BWT, with a popcount
+// directory: dir[b] = set bits before row 512 b (cdiv(n1, 512) + 1 entries); bit_rank (devutil.hpp) reads them
+struct RunIndex {
+  DBuf<uint64_t> bits, dir;
+  uint64_t runs = 0;
+  void build(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, int which);
+};
+
+// ---------------------------------------------------------------- searching a BWT (fmsearch.hip)
+// Count and locate over a .bwt and its run samples (the r-index of Gagie, Navarro and Prezza); see fmsearch.hip and pfpgpu.h.
+// Everything the searches read is owned here (the build copies what it needs from the caller's buffers).
+struct FmIndex {
+  pfp_ctx *c = nullptr;
+  uint64_t n1 = 0, runs = 0;
+  int sigma = 0;                         // distinct bytes other than 0 (dense codes 0..sigma-1 in byte order)
+  bool wide = false, samples = false;    // wide: rows and SA values as u64 (else u32)
+  DBuf<uint8_t> bwt;                     // the BWT, zero-padded to whole 256-row blocks (one block more than n1 >> 8)
+  DBuf<uint8_t> codes;                   // [256] byte -> code (0xFF: absent, and byte 0), [256 + k] code -> byte
+  DBuf<uint16_t> blk;                    // [block * sigma + k] occurrences of code k in the blocks of its superblock before it
+  DBuf<uint64_t> sbc;                    // [superblock * sigma + k] C[byte] + occurrences before the superblock
+  RunIndex rs;                           // run starts (samples only)
+  DBuf<uint8_t> rs_row, rs_sa;           // [runs] of I: row and SA value of run start i
+  DBuf<uint8_t> phi_key, phi_val, phi_dir;  // [runs - 1] of I: SA[e_i] sorted, SA[s_{i+1}]; [nbk + 1] first key of each bucket
+  uint64_t nphi = 0, nbk = 0;
+  int shift = 0;                         // bucket of text position x: x >> shift
+  uint64_t device_bytes() const;
+};
+uint64_t fm_bwt_bytes(uint64_t n1);      // f.bwt's size: n1 bytes and the zero padding
+// bwt == f.bwt.p (filled with n1 bytes, fm_bwt_bytes(n1) allocated): the index adopts it instead of copying
+void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
+              uint64_t esa_bytes);
+// device pointers; first may be NULL (needs samples otherwise)
+void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first);
+// out_off[0..npat] (device): exclusive sums of min(ep - sp, max_occ); pos == NULL: only those
+void fm_locate(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
+               uint64_t *out_off, uint64_t *pos);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

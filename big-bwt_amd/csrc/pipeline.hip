@@ -2,6 +2,7 @@
 // (include/pfpgpu.h).  The chain mirrors bigbwt:69-156 (newscan -> bwtparse -> pfbwt) but every
 // intermediate stays in HBM; the staged entry points ingest/emit the reference's file formats.
 #include <atomic>
+#include <memory>
 #include "kernels.hpp"
 #include "prims.hpp"
 #include "devutil.hpp"
@@ -1459,6 +1460,178 @@ int pfp_check_bwt_files(pfp_ctx *c, const char *base, const uint8_t *text, int t
   out->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PFP_OK;
   PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro
+// and Prezza: no reference counterpart)
+struct pfp_fm {
+  pfp::FmIndex f;
+};
+
+// host patterns: the bytes to copy (pat_off[npat]), once the offsets are known to be non-decreasing (no kernel reads past them)
+static uint64_t pattern_bytes(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat) {
+  if (!npat) return 0;
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p] <= pat_off[p + 1], PFP_EINVAL, "pattern offsets decrease at pattern " + std::to_string(p));
+  PFP_REQUIRE(pat || !pat_off[npat], PFP_EINVAL, "no pattern bytes");
+  return pat_off[npat];
+}
+
+int pfp_fm_build_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                     uint64_t esa_bytes, pfp_fm **out) {
+  if (!c || !d_bwt || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  auto fm = std::make_unique<pfp_fm>();
+  fm_build(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_build_files(pfp_ctx *c, const char *base, int flags, pfp_fm **out) {
+  if (!c || !base || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  const std::string b(base);
+  const int samp = flags & (PFP_FLAG_SSA | PFP_FLAG_ESA);
+  PFP_REQUIRE(samp == 0 || samp == (PFP_FLAG_SSA | PFP_FLAG_ESA), PFP_EINVAL, "the run samples come as a pair: .ssa and .esa, or neither");
+  auto fm = std::make_unique<pfp_fm>();
+  {
+    const std::string path = b + ".bwt";
+    const int fd = open(path.c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0) {
+      if (fd >= 0) close(fd);
+      throw Error(PFP_EINVAL, "cannot read " + path + ": " + strerror(errno));
+    }
+    const uint64_t n1 = (uint64_t)sb.st_size;
+    try {
+      PFP_REQUIRE(n1 <= (1ull << 40), PFP_ELIMIT, "a BWT of more than 2^40 bytes (the limit of the 5-byte .sa format)");
+      fm->f.bwt.alloc(c, fm_bwt_bytes(n1));
+      stream_h2d(c, fm->f.bwt.p, n1, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_pread(fd, off, pin, len); });
+      sync(c);
+    } catch (...) {
+      close(fd);
+      throw;
+    }
+    close(fd);
+    DBuf<uint8_t> d_ssa, d_esa;
+    uint64_t ssa_bytes = 0, esa_bytes = 0;
+    if (samp) {
+      ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa);
+      esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+    }
+    fm_build(c, fm->f, fm->f.bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes);
+  }
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_count_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t *d_sp, uint64_t *d_ep, uint64_t *d_first) {
+  if (!fm || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  fm_count(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_sp, d_ep, d_first);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_locate_dev(pfp_fm *fm, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep, const uint64_t *d_first, uint64_t max_occ,
+                      uint64_t *d_out_off, uint64_t *d_pos) {
+  if (!fm || !d_out_off || (npat && (!d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  fm_locate(fm->f, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_count(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
+  if (!fm || (npat && (!pat_off || !sp || !ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  PFP_REQUIRE(!first || fm->f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
+  if (!npat) return PFP_OK;
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16);
+  DBuf<uint64_t> d_off(c, npat + 1), d_out(c, 3 * npat);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  h2d(c, d_off.p, pat_off, npat + 1);
+  fm_count(fm->f, d_pat.p, d_off.p, npat, d_out.p, d_out.p + npat, first ? d_out.p + 2 * npat : nullptr);
+  d2h(c, sp, d_out.p, npat);
+  d2h(c, ep, d_out.p + npat, npat);
+  if (first) d2h(c, first, d_out.p + 2 * npat, npat);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
+                  uint64_t *out_off, uint64_t **pos) {
+  if (!fm || !out_off || !pos || (npat && !pat_off)) return PFP_EINVAL;
+  *pos = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16);
+  DBuf<uint64_t> d_off(c, npat + 1), d_rng(c, 3 * npat + 1), d_out_off(c, npat + 1);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  if (npat) h2d(c, d_off.p, pat_off, npat + 1);
+  fm_count(fm->f, d_pat.p, d_off.p, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat);
+  d_pat.release();
+  fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, nullptr);
+  d2h(c, out_off, d_out_off.p, npat + 1);
+  if (sp) d2h(c, sp, d_rng.p, npat);
+  if (ep) d2h(c, ep, d_rng.p + npat, npat);
+  sync(c);
+  const uint64_t total = out_off[npat];
+  if (total) {
+    DBuf<uint64_t> d_pos(c, total);
+    fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, d_pos.p);
+    uint64_t *h = host_alloc<uint64_t>(total);
+    try {
+      stream_d2h(c, (const uint8_t *)d_pos.p, total * 8, [&](const uint8_t *pin, uint64_t off, uint64_t len) { par_memcpy((uint8_t *)h + off, pin, len); });
+      sync(c);
+    } catch (...) {
+      free(h);
+      throw;
+    }
+    *pos = h;
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
+  if (!fm || !out) return PFP_EINVAL;
+  memset(out, 0, sizeof *out);
+  out->n = fm->f.n1 - 1;
+  out->runs = fm->f.samples ? fm->f.runs : 0;
+  out->sigma = (uint32_t)fm->f.sigma;
+  out->row_bits = fm->f.wide ? 64 : 32;
+  out->device_bytes = fm->f.device_bytes();
+  out->has_samples = fm->f.samples ? 1 : 0;
+  return PFP_OK;
+}
+
+void pfp_fm_free(pfp_fm *fm) {
+  if (!fm) return;
+  try {
+    PFP_HIP(hipSetDevice(fm->f.c->device));
+  } catch (...) {
+  }
+  delete fm;
 }
 
 }  // extern "C"

@@ -181,20 +181,6 @@ __global__ void __launch_bounds__(512) unbwt_runbits(const uint8_t *__restrict__
   }
 }
 
-__device__ __forceinline__ uint64_t bit_rank(const uint64_t *__restrict__ bits, const uint64_t *__restrict__ dir, uint64_t r) {
-  const uint64_t wi = r >> 6;
-  uint64_t k = dir[r >> 9];
-  for (uint64_t w = (r >> 9) << 3; w < wi; w++) k += __popcll(bits[w]);
-  return k + __popcll(bits[wi] & ((1ull << (r & 63)) - 1));
-}
-
-__device__ __forceinline__ uint64_t ld5(const uint8_t *p, uint64_t off, uint64_t bytes) {
-  if (off + 8 <= bytes) return ld8u(p + off) & 0xFFFFFFFFFFull;
-  uint64_t v = 0;
-  for (int i = 4; i >= 0; i--) v = (v << 8) | p[off + i];
-  return v;
-}
-
 struct PairFile { const uint8_t *p; uint64_t bytes, pairs; const uint64_t *bits, *dir; };
 
 __device__ __forceinline__ void check_pair(const PairFile &f, uint64_t r, uint64_t sa, uint64_t *mm) {
@@ -269,11 +255,10 @@ __global__ void __launch_bounds__(kTB) unbwt_walk2(const I *__restrict__ lf, Wal
   }
 }
 
-// .ssa / .esa bitmap, directory and run count
-struct RunIndex {
-  DBuf<uint64_t> bits, dir;
-  uint64_t runs = 0;
-  void build(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, int which) {
+}  // namespace
+
+// .ssa / .esa bitmap, directory and run count (kernels.hpp)
+void RunIndex::build(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, int which) {
     const uint64_t nsb = cdiv(n1, 512);
     bits.alloc(c, nsb * 8);
     DBuf<uint32_t> sbc(c, nsb + 1);
@@ -286,8 +271,9 @@ struct RunIndex {
     }
     exclusive_sum_u32_u64(c, sbc.p, dir.p, nsb + 1);
     runs = read_scalar(c, dir.p + nsb);
-  }
-};
+}
+
+namespace {
 
 template <class I>
 void invert_t(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res) {

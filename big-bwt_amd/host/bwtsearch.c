@@ -1,0 +1,170 @@
+/* bwtsearch.c -- count (and locate) patterns in a text through its .bwt (and .ssa / .esa) on the GPU.
+ *
+ *   bwtsearch [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
+ *
+ * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
+ * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
+ * order (the lexicographic order of the suffixes), at most MAXOCC of them (0: all).  Count needs basename.bwt only; -l also
+ * reads basename.ssa and basename.esa (bigbwt -s -e).  The definitions: include/pfpgpu.h, "Searching a BWT".
+ * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
+ * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, 2 a usage error.
+ */
+#define _GNU_SOURCE
+#include <getopt.h>
+#include <inttypes.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "pfpgpu.h"
+
+static void usage(const char *argv0) {
+  printf("usage: %s [-h] [-l] [-m MAXOCC] [--device D] PATTERNFILE basename\n\n"
+         "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
+         "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
+         "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
+         "  -l            print count<TAB>positions (in suffix order) instead of the count\n"
+         "  -m MAXOCC     with -l: at most MAXOCC positions per pattern (def. 0 = all)\n"
+         "      --device D  GPU to use (def. 0)\n",
+         argv0);
+}
+
+static int read_file(const char *path, uint8_t **out, uint64_t *len) {
+  FILE *f = fopen(path, "rb");
+  if (!f) return -1;
+  uint64_t cap = 1 << 20, n = 0;
+  uint8_t *b = malloc(cap);
+  for (;;) {
+    if (!b) { fclose(f); return -1; }
+    const size_t got = fread(b + n, 1, cap - n, f);
+    n += got;
+    if (n < cap) break;
+    cap *= 2;
+    uint8_t *nb = realloc(b, cap);
+    if (!nb) free(b);
+    b = nb;
+  }
+  const int err = ferror(f);
+  fclose(f);
+  if (err) { free(b); return -1; }
+  *out = b;
+  *len = n;
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  int locate = 0, device = 0;
+  uint64_t maxocc = 0;
+  static struct option lo[] = {{"device", required_argument, 0, 1001}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+  int c;
+  char *end;
+  while ((c = getopt_long(argc, argv, "lm:h", lo, NULL)) != -1) {
+    switch (c) {
+      case 'l': locate = 1; break;
+      case 'm':
+        maxocc = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-') { usage(argv[0]); return 2; }
+        break;
+      case 1001:
+        device = (int)strtol(optarg, &end, 10);
+        if (!*optarg || *end) { usage(argv[0]); return 2; }
+        break;
+      case 'h': usage(argv[0]); return 0;
+      default: usage(argv[0]); return 2;
+    }
+  }
+  if (optind + 2 != argc) { usage(argv[0]); return 2; }
+  const char *patfile = argv[optind], *base = argv[optind + 1];
+
+  uint8_t *pats = NULL;
+  uint64_t plen = 0;
+  if (read_file(patfile, &pats, &plen)) { perror(patfile); return 1; }
+  /* npat lines; line k = [lstart[k], lstart[k + 1] - 1) */
+  uint64_t npat = 0;
+  for (uint64_t i = 0; i < plen; i++) npat += pats[i] == '\n';
+  if (plen && pats[plen - 1] != '\n') npat++;
+  uint64_t *lstart = malloc((npat + 1) * sizeof(uint64_t));
+  if (!lstart) { fprintf(stderr, "out of memory\n"); free(pats); return 1; }
+  {
+    uint64_t k = 0, s = 0;
+    for (uint64_t i = 0; i < plen; i++)
+      if (pats[i] == '\n') { lstart[k++] = s; s = i + 1; }
+    if (k < npat) lstart[k++] = s;
+    /* line k ends one byte before lstart[k + 1]: past the last line sits its '\n', or the end of a file without one */
+    lstart[npat] = plen && pats[plen - 1] == '\n' ? plen : plen + 1;
+  }
+
+  pfp_ctx *ctx = NULL;
+  int rc = pfp_ctx_create(&ctx, device);
+  if (rc) {
+    fprintf(stderr, "Cannot initialise the GPU (%s): this tool has no CPU path\n", pfp_strerror(rc));
+    free(pats); free(lstart);
+    return 1;
+  }
+  pfp_fm *fm = NULL;
+  rc = pfp_fm_build_files(ctx, base, locate ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
+  if (rc) {
+    fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
+    pfp_ctx_destroy(ctx);
+    free(pats); free(lstart);
+    return 1;
+  }
+
+  uint64_t batch = 1 << 20;
+  const char *env = getenv("PFP_FM_BATCH");
+  if (env && strtoull(env, NULL, 10) > 0) batch = strtoull(env, NULL, 10);
+  const uint64_t max_bytes = 64ull << 20;
+  uint64_t *off = malloc((batch + 1) * sizeof(uint64_t)), *oo = malloc((batch + 1) * sizeof(uint64_t));
+  uint64_t *sp = malloc(batch * sizeof(uint64_t)), *ep = malloc(batch * sizeof(uint64_t));
+  uint8_t *buf = malloc(max_bytes + 1);
+  if (!off || !oo || !sp || !ep || !buf) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
+  static char obuf[1 << 20];
+  setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+  for (uint64_t p0 = 0; p0 < npat;) {
+    /* a batch: at most `batch` patterns and max_bytes bytes (a single longer line goes alone, from the file buffer) */
+    uint64_t k = 0, bytes = 0;
+    while (p0 + k < npat && k < batch) {
+      const uint64_t len = lstart[p0 + k + 1] - 1 - lstart[p0 + k];
+      if (k && bytes + len > max_bytes) break;
+      bytes += len;
+      k++;
+    }
+    const uint8_t *src = pats + lstart[p0];
+    const uint8_t *pat = src;
+    if (bytes <= max_bytes) {
+      /* the lines without their '\n' */
+      off[0] = 0;
+      for (uint64_t i = 0; i < k; i++) {
+        const uint64_t len = lstart[p0 + i + 1] - 1 - lstart[p0 + i];
+        memcpy(buf + off[i], pats + lstart[p0 + i], len);
+        off[i + 1] = off[i] + len;
+      }
+      pat = buf;
+    } else {
+      off[0] = 0; off[1] = bytes;
+    }
+    if (locate) {
+      uint64_t *pos = NULL;
+      rc = pfp_fm_locate(fm, pat, off, k, maxocc, sp, ep, oo, &pos);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        printf("%" PRIu64 "\t", ep[i] - sp[i]);
+        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %" PRIu64 : "%" PRIu64, pos[j]);
+        putchar('\n');
+      }
+      pfp_free(pos);
+    } else {
+      rc = pfp_fm_count(fm, pat, off, k, sp, ep, NULL);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) printf("%" PRIu64 "\n", ep[i] - sp[i]);
+    }
+    p0 += k;
+  }
+  rc = 0;
+done:
+  if (fflush(stdout) != 0 && !rc) { fprintf(stderr, "Error writing the output\n"); rc = 1; }
+  pfp_fm_free(fm);
+  pfp_ctx_destroy(ctx);
+  free(off); free(oo); free(sp); free(ep); free(buf); free(pats); free(lstart);
+  return rc;
+}

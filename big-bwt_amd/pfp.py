@@ -33,7 +33,9 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
            "pfp_dist_propose_triggers", "pfp_dist_local_parse", "pfp_dist_export_local", "pfp_dist_global", "pfp_dist_global_sort", "pfp_dist_global_finish", "pfp_dist_partition_words", "pfp_dist_export_partition",
            "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
-           "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files"]
+           "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
+           "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
+           "pfp_fm_free"]
 
 
 class PfpError(RuntimeError):
@@ -52,6 +54,92 @@ class CheckResult(C.Structure):
         for k in ("text_mismatch", "sa_mismatch", "ssa_mismatch", "esa_mismatch"):
             d[k] = None if d[k] == 2**64 - 1 else int(d[k])
         return d
+
+
+class _FmInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("runs", C.c_uint64), ("sigma", C.c_uint32), ("row_bits", C.c_uint32), ("device_bytes", C.c_uint64),
+                ("has_samples", C.c_int)]
+
+
+def _patterns(patterns):
+    """a list of bytes / str (UTF-8) / uint8 arrays -> (concatenated uint8 bytes, npat+1 uint64 offsets)"""
+    parts = [p.encode() if isinstance(p, str) else bytes(np.asarray(p, dtype=np.uint8)) if isinstance(p, np.ndarray) else bytes(p)
+             for p in patterns]
+    off = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        off[1:] = np.cumsum([len(x) for x in parts], dtype=np.uint64)
+    return np.frombuffer(b"".join(parts) + b"\0", dtype=np.uint8), off
+
+
+class FmIndex:
+    """Count and locate over a BWT and its run samples (pfp_fm, csrc/fmsearch.hip; the r-index of Gagie, Navarro and Prezza).
+    Made by Context.fm_index / fm_index_files; holds device memory of its context until close()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.lib, self._h = ctx, ctx.lib, handle
+
+    def close(self):
+        """hand the device memory back to the context (a context closed before leaves nothing to hand back)"""
+        if self._h and self.ctx._h:
+            self.lib.pfp_fm_free(self._h)
+        self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        r = _FmInfo()
+        self.ctx._check(self.lib.pfp_fm_info(self._h, C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in r._fields_}
+
+    def count(self, patterns, toehold=False):
+        """-> (sp, ep) uint64 arrays, the row range [sp, ep) of each pattern; toehold=True: (sp, ep, SA[sp]) (needs samples)"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
+        first = np.zeros(npat, dtype=np.uint64) if toehold else None
+        u64 = lambda a: _ptr(a, C.c_uint64)
+        self.ctx._check(self.lib.pfp_fm_count(self._h, _ptr(pat, C.c_uint8), u64(off), C.c_uint64(npat), u64(sp), u64(ep),
+                                              u64(first) if toehold else None))
+        return (sp, ep, first) if toehold else (sp, ep)
+
+    def locate(self, patterns, max_occ=0, ranges=False):
+        """-> (offsets, positions): pattern p's positions, in row order, are positions[offsets[p]:offsets[p+1]], at most max_occ
+        of them (0: all); ranges=True: (offsets, positions, sp, ep)"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
+        out_off = np.zeros(npat + 1, dtype=np.uint64)
+        pos = C.POINTER(C.c_uint64)()
+        u64 = lambda a: _ptr(a, C.c_uint64)
+        self.ctx._check(self.lib.pfp_fm_locate(self._h, _ptr(pat, C.c_uint8), u64(off), C.c_uint64(npat), C.c_uint64(max_occ), u64(sp),
+                                               u64(ep), u64(out_off), C.byref(pos)))
+        total = int(out_off[-1])
+        positions = np.zeros(0, dtype=np.uint64)
+        if total and pos:
+            positions = np.ctypeslib.as_array(pos, shape=(total,)).copy()
+            self.lib.pfp_free(pos)
+        return (out_off, positions, sp, ep) if ranges else (out_off, positions)
+
+    def count_dev(self, d_pat, d_pat_off, npat, d_sp, d_ep, d_first=None):
+        """device pointers: pattern bytes, npat+1 uint64 offsets -> npat uint64 sp / ep (and SA[sp] where d_first is given)"""
+        self.ctx._check(self.lib.pfp_fm_count_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp),
+                                                  C.c_void_p(d_ep), C.c_void_p(d_first) if d_first else None))
+
+    def locate_dev(self, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos=None):
+        """device pointers from count_dev -> npat+1 offsets; d_pos (room for offsets[npat]) gets the positions (None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_locate_dev(self._h, C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
+                                                   C.c_void_p(d_first) if d_first else None, C.c_uint64(max_occ), C.c_void_p(d_out_off),
+                                                   C.c_void_p(d_pos) if d_pos else None))
 
 
 class _ParseResult(C.Structure):
@@ -121,6 +209,7 @@ def load_library():
         lib.pfp_pool_trim.restype = None
         lib.pfp_parse_result_free.restype = None
         lib.pfp_bwt_result_free.restype = None
+        lib.pfp_fm_free.restype = None
         _lib = lib
     return _lib
 
@@ -458,6 +547,39 @@ class Context:
         self._check(self.lib.pfp_check_bwt_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(t, C.c_uint8) if len(t) else None, C.c_int(-1),
                                                  C.c_uint64(0), C.c_uint64(len(t)), C.c_int(flags), C.byref(r)))
         return r.as_dict()
+
+    # -- searching a BWT (csrc/fmsearch.hip): count and locate, pfpgpu.h states the definitions
+    def fm_index(self, bwt, ssa=None, esa=None):
+        """an FmIndex over host .bwt bytes and, for locate, the .ssa / .esa bytes (bigbwt -s -e); the index keeps its own copy"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        keep = []
+        for a in (bwt, ssa, esa):
+            if a is None:
+                keep.append(None)
+                continue
+            b = _arr(a, np.uint8)
+            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
+            if len(b):
+                t[:len(b)] = torch.from_numpy(b.copy())
+            keep.append((t, len(b)))
+        torch.cuda.synchronize(dev)
+        return self.fm_index_dev(keep[0][0].data_ptr(), keep[0][1], keep[1][0].data_ptr() if keep[1] else None, keep[1][1] if keep[1] else 0,
+                                 keep[2][0].data_ptr() if keep[2] else None, keep[2][1] if keep[2] else 0)
+
+    def fm_index_dev(self, d_bwt, n_plus_1, d_ssa10=None, ssa_bytes=0, d_esa10=None, esa_bytes=0):
+        """an FmIndex over device buffers (copied: the caller may free them afterwards)"""
+        h = C.c_void_p()
+        vp = lambda x: C.c_void_p(x) if x else None
+        self._check(self.lib.pfp_fm_build_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes), vp(d_esa10),
+                                              C.c_uint64(esa_bytes), C.byref(h)))
+        return FmIndex(self, h)
+
+    def fm_index_files(self, base, flags=0):
+        """an FmIndex over <base>.bwt and, when flags holds FLAG_SSA | FLAG_ESA, <base>.ssa / .esa"""
+        h = C.c_void_p()
+        self._check(self.lib.pfp_fm_build_files(self._h, C.c_char_p(os.fsencode(base)), C.c_int(flags), C.byref(h)))
+        return FmIndex(self, h)
 
     # -- multi-GPU chain, one rank's share (device pointers; collectives are the caller's: dist.py)
     def dist_propose_triggers(self, d_text_ptr, n, w, p):

@@ -452,6 +452,70 @@ int pfp_check_bwt_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, const 
 int pfp_check_bwt_files(pfp_ctx *ctx, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, int flags,
                         pfp_check_result *out);
 
+/* ------------------------------------------------------------------------------------
+ * Searching a BWT: pattern count and locate over a .bwt and its run samples (csrc/fmsearch.hip).  The reference has no
+ * counterpart: the method is the r-index of Gagie, Navarro and Prezza, "Optimal-time text indexing in BWT-runs bounded
+ * space" (SODA 2018): backward search that keeps one SA value of the range (the toehold), and phi^-1, a predecessor search
+ * over the run-end samples, for the other SA values of the range.  The conventions are unbwt's (above): the text T has n bytes,
+ * the .bwt n+1 bytes with exactly one 0, row j has SA[j] with SA[0] = n, .ssa / .esa hold the pairs <j, SA[j]> of the run
+ * starts / ends as 5-byte little-endian ints.
+ * For a pattern P of m bytes:
+ *   occurrences: the positions i in [0, n-m] with T[i..i+m) = P.  The empty pattern has the n+1 occurrences 0..n (all rows);
+ *     a pattern that holds byte 0, or is longer than n, has none.
+ *   count: the half-open row range [sp, ep) of the suffixes that start with P; the count is ep - sp; sp = ep = 0 when it is 0.
+ *     With samples, count also gives the toehold first = SA[sp] (UINT64_MAX when the count is 0).
+ *   locate: SA[sp], SA[sp+1], ... in row order (the suffixes' lexicographic order), at most max_occ per pattern (0: all).
+ * Patterns come as concatenated bytes plus npat+1 offsets (pattern p = pat[off[p] .. off[p+1])).  Every row, position and
+ * offset crosses the ABI as uint64; inside the index rows and SA values are u32 below 2^32 rows and u64 above (or when
+ * PFP_FORCE_IDX64=1 / pfp_set_index_bits(ctx, 64) forces the wide layout).
+ * Checked at build: the .bwt holds exactly one 0 (else PFP_EFORMAT, unbwt's first rule); .ssa and .esa hold 10 r bytes for the
+ * r runs of the .bwt and pair i names the i-th run start / end (else PFP_EFORMAT).  Not checked: the SA values of the pairs,
+ * which need the inversion (`unbwt --check TEXT -s -e`, pfp_check_bwt_files); wrong values give wrong positions, never a read
+ * outside the index.  Nor that LF is one cycle: bytes that are not a BWT but hold one 0 give answers for no text.
+ * Device memory of the index (pfp_fm_info's device_bytes), with sigma = distinct bytes other than 0 and w = 4 bytes below
+ * 2^32 rows, 8 above: at most (1 + sigma/128 + sigma/8192) bytes per row for count (BWT bytes, u16 block and u64 superblock
+ * counters), with samples plus 0.140625 bytes per row (run-start bitmap and directory) and 6 w per run, plus below 8 KiB.  The
+ * build peaks at the index plus at most 0.140625 bytes per row and 4 w per run, plus the scratch of the library sort and scans.
+ * Locate takes 24 bytes per segment (a run start inside a range, plus one per pattern) and 32 per pattern on top of the
+ * caller's buffers.
+ * ------------------------------------------------------------------------------------ */
+typedef struct pfp_fm pfp_fm;
+typedef struct {
+  uint64_t n;              /* text length (rows - 1) */
+  uint64_t runs;           /* runs of the BWT (0 for an index without samples) */
+  uint32_t sigma;          /* distinct bytes other than 0 */
+  uint32_t row_bits;       /* 32 or 64: width of rows and SA values inside the index */
+  uint64_t device_bytes;   /* device memory the index holds */
+  int has_samples;         /* 1: built with .ssa / .esa (locate works) */
+} pfp_fm_info_t;
+/* an index over n_plus_1 device bytes; d_ssa10 / d_esa10 (ssa_bytes / esa_bytes) both NULL: count only.  The index copies
+ * what it keeps: the caller may free its buffers afterwards.  *out is set on PFP_OK only (nothing stays allocated otherwise). */
+int pfp_fm_build_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                     uint64_t esa_bytes, pfp_fm **out);
+/* reads <base>.bwt and, when flags holds PFP_FLAG_SSA | PFP_FLAG_ESA, <base>.ssa and <base>.esa (a file that cannot be read:
+ * PFP_EINVAL naming it; one of the two flags alone: PFP_EINVAL) */
+int pfp_fm_build_files(pfp_ctx *ctx, const char *base, int flags, pfp_fm **out);
+/* device pointers: d_pat_off npat+1 non-decreasing offsets into d_pat (pattern bytes are read from d_pat[d_pat_off[0]] to
+ * d_pat[d_pat_off[npat]]; a pair of decreasing offsets counts as no occurrence); d_sp / d_ep / d_first npat entries each.
+ * d_first may be NULL; it needs samples otherwise (PFP_EINVAL). */
+int pfp_fm_count_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t *d_sp, uint64_t *d_ep,
+                     uint64_t *d_first);
+/* device pointers, from pfp_fm_count_dev: d_out_off (npat+1) gets the exclusive sums of min(ep - sp, max_occ) (max_occ = 0: no
+ * cap), so d_out_off[npat] is the total; d_pos (room for that total) gets pattern p's positions at d_out_off[p] ..
+ * d_out_off[p+1] in row order.  d_pos NULL: the offsets only.  An index without samples: PFP_EINVAL naming the files. */
+int pfp_fm_locate_dev(pfp_fm *fm, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep, const uint64_t *d_first, uint64_t max_occ,
+                      uint64_t *d_out_off, uint64_t *d_pos);
+/* host buffers: pat / pat_off as above (offsets that decrease: PFP_EINVAL); sp, ep (npat each) and first (NULL ok) are filled */
+int pfp_fm_count(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first);
+/* both phases with host buffers: sp / ep (NULL ok) get the ranges, out_off (npat+1) the offsets, *pos a malloc'ed array of
+ * out_off[npat] positions (pfp_free; NULL when there are none) */
+int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
+                  uint64_t *out_off, uint64_t **pos);
+int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out);
+/* releases the index's device memory to its context (call before pfp_ctx_destroy); NULL is a no-op.  Errors of the calls that
+ * take an index are reported through its context's pfp_last_error. */
+void pfp_fm_free(pfp_fm *fm);
+
 /* ---- micro entry points used by bench.py's roofline leg and by the parity tests ---- */
 /* copy a device-resident text into the ctx's padded staging buffer (T' = Dollar.T.Dollar^w) */
 int pfp_stage_text_dev(pfp_ctx *ctx, const void *d_text, uint64_t n, int w);
