@@ -1298,8 +1298,9 @@ static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, u
       hipLaunchKernelGGL(finish_rank_kernel<I>, gdim(cdiv(m * 8, TB)), gdim(TB), 0, c->stream, g, out.bytes, m, act_i.p, act_grp.p, flt.p, feq.p,
                          fgs.p, fov.p);
       if (read_scalar(c, fov.p) == 0) {
-        hipLaunchKernelGGL(finish_write_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, aslot.p, act_i.p, flt.p, feq.p, fgs.p,
-                           out.finbit, out.sa.p, out.grp.p, rank_p, wordrank_p);
+        { KScope kw(c, "pfp::finish_write_kernel", m * (sizeof(I) * 5 + 12));
+          hipLaunchKernelGGL(finish_write_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, aslot.p, act_i.p, flt.p, feq.p, fgs.p,
+                             out.finbit, out.sa.p, out.grp.p, rank_p, wordrank_p); }
         PFP_HIP(hipGetLastError());
         if (trace_rounds) fprintf(stderr, "[pfp] doubling N=%llu round=%llu: the last %llu suffixes ranked by comparison\n",
                                   (unsigned long long)N, (unsigned long long)out.rounds, (unsigned long long)m);
@@ -1842,7 +1843,8 @@ void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrde
   SufGeom g{MODE_PLAIN, N, WordView{}};
   DBuf<uint64_t> key(c, N);
   DBuf<I> val(c, N);
-  hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p);
+  { KScope ks(c, "pfp::init_keys_bytes_kernel", N * (16 + sizeof(I)));
+    hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p); }
   doubling<I>(c, g, key, val, 8, out);
 }
 template void sort_byte_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint32_t> &);
@@ -1875,11 +1877,13 @@ void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder 
   }
   if (64 - 2 * sb >= 6) {
     DBuf<uint32_t> v(c, N), pm(c, N);
+    KScope ks(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
     hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
     inclusive_max_u32(c, v.p, pm.p, N);
     hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, key.p,
                        val.p);
   } else {
+    KScope ks(c, "pfp::init_keys_int_kernel", N * (8 + 8 + 4));
     hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, key.p, val.p);
   }
   doubling<uint32_t>(c, g, key, val, 2, out);

@@ -30,7 +30,7 @@ ERRORS = {0: "PFP_OK", -1: "PFP_EINVAL", -2: "PFP_ENODEV", -3: "PFP_EHIP", -4: "
 SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_error", "pfp_strerror", "pfp_version", "pfp_ctx_stream",
            "pfp_free", "pfp_debug_check", "pfp_get_mem_stats", "pfp_get_pool_counters", "pfp_pool_trim", "pfp_scan", "pfp_parse", "pfp_parse_result_free", "pfp_sacak_int", "pfp_sacak", "pfp_gsacak", "pfp_sacak_int64", "pfp_sacak64", "pfp_gsacak64", "pfp_gsacak_lcp_da", "pfp_gsacak_lcp_da64",
            "pfp_bwtparse", "pfp_merge", "pfp_bwt_result_free", "pfp_bigbwt", "pfp_bigbwt_files", "pfp_bigbwt_dev", "pfp_bigbwt_formats_dev", "pfp_dev_free", "pfp_memcpy_d2h", "pfp_pack5_dev", "pfp_sample_runs_dev", "pfp_pwrite_dev", "pfp_get_stats",
-           "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
+           "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_debug_lib_sort", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
            "pfp_dist_propose_triggers", "pfp_dist_local_parse", "pfp_dist_export_local", "pfp_dist_global", "pfp_dist_global_sort", "pfp_dist_global_finish", "pfp_dist_partition_words", "pfp_dist_export_partition",
            "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
            "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
@@ -343,6 +343,29 @@ class Context:
         self._check(self.lib.pfp_debug_msd_sort(self._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                 vals.ctypes.data_as(C.POINTER(C.c_uint32)) if vals is not None else None,
                                                 C.c_uint64(len(keys)), C.c_int(lo), C.c_int(hi)))
+
+    LIB_SORT_KINDS = {"pairs_u64_u32": (0, np.uint64, np.uint32), "pairs_u64_u64": (1, np.uint64, np.uint64), "keys_db": (2, np.uint64, None),
+                      "keys_raw": (3, np.uint64, None), "seg_u32_u32": (4, np.uint32, np.uint32), "seg_u32_u64": (5, np.uint32, np.uint64),
+                      "seg_u64_u32": (6, np.uint64, np.uint32), "inclusive_max_u32": (7, np.uint32, None),
+                      "exclusive_sum_u32_u64": (8, np.uint32, np.uint64), "select_index": (9, np.uint8, np.uint32)}
+
+    def debug_lib_sort(self, kind, keys, vals=None, begin_bit=0, end_bit=64, seg_begin=None, seg_end=None):
+        """the library sorts / scans / selection behind prims.hip's wrappers on numpy arrays, in place (pfpgpu.h: pfp_debug_lib_sort);
+        select_index wants n + 1 values (the count comes back in the last one)"""
+        code, kt, vt = self.LIB_SORT_KINDS[kind]
+        n = len(keys)
+        assert keys.dtype == kt and keys.flags.c_contiguous
+        assert (vals is None and vt is None) or (vals.dtype == vt and vals.flags.c_contiguous and len(vals) == n + (code == 9))
+        nseg = 0
+        if seg_begin is not None:
+            assert seg_begin.dtype == np.uint32 and seg_end.dtype == np.uint32 and len(seg_begin) == len(seg_end)
+            assert seg_begin.flags.c_contiguous and seg_end.flags.c_contiguous
+            nseg = len(seg_begin)
+        self._check(self.lib.pfp_debug_lib_sort(self._h, C.c_int(code), keys.ctypes.data_as(C.c_void_p),
+                                                vals.ctypes.data_as(C.c_void_p) if vals is not None else None, C.c_uint64(n),
+                                                C.c_int(begin_bit), C.c_int(end_bit),
+                                                _ptr(seg_begin, C.c_uint32) if nseg else None, _ptr(seg_end, C.c_uint32) if nseg else None,
+                                                C.c_uint64(nseg)))
 
     def set_parse_density(self, density):
         """fused chain, opt-in: the window hash cuts with probability density / p (outputs unchanged, see pfpgpu.h)"""

@@ -249,6 +249,15 @@ int pfp_get_kernel_trace(pfp_ctx *ctx, pfp_kernel_stat *out, int cap);
  * in the first round of the suffix sorter) on caller data: keys, and 32-bit values if vals != NULL, sorted in place, stable on
  * key bits [lo, hi). */
 int pfp_debug_msd_sort(pfp_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n, int lo, int hi);
+/* Diagnostic (tests): the library sorts as the suffix sorter reaches them - through the wrappers of csrc/prims.hip, with their size
+ * thresholds, tuned configurations and work-arounds - on caller data, in place.  kind: 0 sort_pairs_db (u64 keys, u32 vals),
+ * 1 sort_pairs_db (u64, u64), 2 sort_keys_db (u64; vals unused), 3 sort_keys_raw (u64; vals unused), 4 segsort_pairs_u32 (u32 keys,
+ * u32 vals), 5 segsort_pairs_u32 (u32 keys, u64 vals), 6 segsort_pairs_u64_u32 (u64 keys, u32 vals); all stable on key bits
+ * [begin_bit, end_bit), the segmented ones inside each [seg_begin[k], seg_end[k]) of nseg segments (elements outside every segment
+ * stay as they were).  7 inclusive_max_u32 (keys: u32, in place), 8 exclusive_sum_u32_u64 (keys: u32 in, vals: u64 out),
+ * 9 select_index (keys: n flag bytes, vals: n + 1 u32 - the indices of the non-zero flags, their count in vals[n]). */
+int pfp_debug_lib_sort(pfp_ctx *ctx, int kind, void *keys, void *vals, uint64_t n, int begin_bit, int end_bit,
+                       const uint32_t *seg_begin, const uint32_t *seg_end, uint64_t nseg);
 void pfp_set_max_phrase(pfp_ctx *ctx, uint64_t max_phrase);
 /* Fused chain only: which function of the last w bytes cuts the text.  fast != 0 (default): a multiply-add hash of the window,
  * a third of the arithmetic of the reference's `KR_window` (newscan.cpp:168-202: mod 1999999973, then mod p) with the same 1 / p

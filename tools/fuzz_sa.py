@@ -1,3 +1,7 @@
+"""Random structured texts through gsacak / sacak_int / sacak against the oracle:
+    python tools/fuzz_sa.py SEED TRIES [OUTDIR]
+Failing inputs are saved as OUTDIR/fuzzsa_bad_<it>.npy (OUTDIR defaults to the current directory); the exit status is 1
+when anything differed."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -7,6 +11,8 @@ from test_gpu_fuzz import gen
 pkg = entry.load_package(); O = entry.load_oracle()
 ctx = pkg.Context(0)
 rng = np.random.default_rng(int(sys.argv[1])); ntr = int(sys.argv[2])
+outdir = sys.argv[3] if len(sys.argv) > 3 else "."
+os.makedirs(outdir, exist_ok=True)
 bad = 0; n1 = n2 = n3 = 0
 for it in range(ntr):
     t = gen(rng, O)
@@ -19,7 +25,7 @@ for it in range(ntr):
     a = ctx.gsacak(d); b, _ = O.gsacak(d, want_lcp=False)
     n1 += 1
     if not np.array_equal(a, b):
-        bad += 1; print("GSACAK mismatch it", it, len(d), flush=True); np.save("/root/repo/gpurun_out/fuzzsa_bad_%d.npy" % it, t)
+        bad += 1; print("GSACAK mismatch it", it, len(d), flush=True); np.save(os.path.join(outdir, "fuzzsa_bad_%d.npy" % it), t)
     s = np.concatenate([pr["parse"], np.zeros(1, np.uint32)])
     if len(s) > 2:
         n2 += 1
@@ -30,3 +36,4 @@ for it in range(ntr):
     if not np.array_equal(ctx.sacak(tt), O.sacak(tt)):
         bad += 1; print("SACAK mismatch it", it, flush=True)
 print("gsacak", n1, "sacak_int", n2, "sacak", n3, "bad", bad)
+sys.exit(1 if bad else 0)
