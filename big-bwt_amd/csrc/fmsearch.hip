@@ -17,11 +17,21 @@
 //   pattern by binary search, start row and value, output slot out_off[p] + row - sp) -> chains, one lane per segment, at
 //   most kChainSteps steps per launch; the predecessor search reads a bucket directory over text positions, then at most
 //   log2 of the bucket's keys.
-// Bounds: every loop is bounded by the pattern length, a directory's size or kChainSteps; values read from the samples only
-// ever become output values or are clamped before they index anything.
+//   Matching statistics (PHONI: Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, DCC 2021, after Bannai,
+//   Gagie, I, "Refining the r-index", 2020).  An index built with the text also keeps SA[run end] by run number.  One group of
+//   16 lanes per pattern walks it right to left with (q, pos, l), SA[q] = pos, T[pos .. pos+l) = P[i+1 .. i+1+l).  BWT[q] = c:
+//   one LF.  Otherwise the c just before q ends a run and the c just after q starts one, so both SA values are samples; the
+//   longer common extension with T[pos ..) wins (the predecessor on a tie), compared on the text 1024 bytes per group and
+//   iteration.  A launch gives every pattern kMsWork units (one per step and per LCE iteration) and leaves (i, q, pos, l) in a
+//   32-byte record; the host launches until no pattern is unfinished.  The answers depend on the inputs only.
+//   MEMs.  (i, len[i], pos[i]) with len[i] >= min_len and (i = 0 or len[i-1] <= len[i]): counted per pattern by its group, a
+//   library scan, then gathered in order of i.
+// Bounds: every loop is bounded by the pattern length, a directory's size, kChainSteps or a launch's budget; values read from
+// the samples or the text only ever become output values or are clamped before they index anything.
 #include "kernels.hpp"
 #include "prims.hpp"
 #include "devutil.hpp"
+#include <cstdlib>
 
 namespace pfp {
 
@@ -108,12 +118,13 @@ __global__ void __launch_bounds__(kTB) fm_sbc(const uint64_t *__restrict__ base,
 
 // ---------------------------------------------------------------- samples
 // pair i of .ssa / .esa: its row must be the i-th run start / end (bit set, rank i); the smallest bad pair index meets in
-// bad[0] / bad[1].  rs_row / rs_sa: the run starts; key / val: the phi^-1 table SA[e_i] -> SA[s_{i+1}], i < runs - 1
+// bad[0] / bad[1].  rs_row / rs_sa: the run starts; key / val: the phi^-1 table SA[e_i] -> SA[s_{i+1}], i < runs - 1;
+// re_sa (may be NULL): SA[e_i]
 template <class I>
 __global__ void __launch_bounds__(kTB) fm_pairs(const uint8_t *__restrict__ ssa, const uint8_t *__restrict__ esa, uint64_t runs, uint64_t n1,
                                                 const uint64_t *__restrict__ sbits, const uint64_t *__restrict__ sdir, const uint64_t *__restrict__ ebits,
                                                 const uint64_t *__restrict__ edir, I *__restrict__ rs_row, I *__restrict__ rs_sa, I *__restrict__ key,
-                                                I *__restrict__ val, uint64_t *__restrict__ bad) {
+                                                I *__restrict__ val, I *__restrict__ re_sa, uint64_t *__restrict__ bad) {
   const uint64_t i = BID * kTB + threadIdx.x;
   if (i >= runs) return;
   const uint64_t bytes = 10 * runs;
@@ -123,6 +134,7 @@ __global__ void __launch_bounds__(kTB) fm_pairs(const uint8_t *__restrict__ ssa,
   if (je >= n1 || !((ebits[je >> 6] >> (je & 63)) & 1) || bit_rank(ebits, edir, je) != i) atomic_min_u64(&bad[1], i);
   rs_row[i] = (I)js;
   rs_sa[i] = (I)vs;
+  if (re_sa) re_sa[i] = (I)ve;                         // (an index with text: SA[run end] by run number)
   if (i + 1 < runs) {
     key[i] = (I)ve;
     val[i] = (I)ld5(ssa, 10 * (i + 1) + 5, bytes);
@@ -342,6 +354,170 @@ __global__ void __launch_bounds__(kTB) fm_chain(FmArgs<I> a, uint64_t S, Seg *__
   seg[g] = s;
 }
 
+// ---------------------------------------------------------------- matching statistics and MEMs
+constexpr uint64_t kMsWork = 16384;         // units of work per pattern and launch: one per step, one per 1024 bytes compared
+struct MsRec { uint64_t t, q, pos, l; };    // the next byte to read is pat[t - 1]; SA[q] = pos; l bytes matched to the right of it
+
+// the common prefix of T[x ..) and T[y ..), at most cap bytes and never past the end of the text (x, y are clamped to n); the
+// group compares 1024 bytes per iteration: four rows of 256, 16 bytes per lane, all eight loads in flight together (a short
+// cap leaves the later rows out).  Reads stay below text + n + 16: the padding of the index's copy.
+__device__ __forceinline__ uint64_t lce16(const uint8_t *__restrict__ text, uint64_t n, uint64_t x, uint64_t y, uint64_t cap, int gl, uint64_t &work) {
+  if (x > n) x = n;
+  if (y > n) y = n;
+  const uint64_t room = n - (x > y ? x : y);
+  if (cap > room) cap = room;
+  for (uint64_t done = 0; done < cap; done += 1024) {   // (done and cap are the same in all 16 lanes)
+    uint4 u[4], v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint64_t o = done + 256 * j + 16 * (uint64_t)gl;
+      u[j] = v[j] = make_uint4(0, 0, 0, 0);
+      if (o < cap) { u[j] = ld16u(text + x + o); v[j] = ld16u(text + y + o); }
+    }
+    uint64_t mine = cap;                                // no difference below cap among this lane's bytes
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+      const uint64_t o = done + 256 * j + 16 * (uint64_t)gl;
+      const uint32_t w[4] = {u[j].x ^ v[j].x, u[j].y ^ v[j].y, u[j].z ^ v[j].z, u[j].w ^ v[j].w};
+#pragma unroll
+      for (int q = 3; q >= 0; q--)
+        if (w[q]) mine = o + 4 * q + (__ffs(w[q]) - 1) / 8;
+    }
+    if (mine > cap) mine = cap;
+    work++;
+    const uint64_t m = gmin16(mine);
+    if (m < cap) return m;
+  }
+  return cap;
+}
+
+// one group of 16 lanes per pattern; first: start from (m, 0, n, 0), else from the record.  ctr[0] += patterns left
+// unfinished, ctr[1] += patterns of 2^32 - 1 bytes or more (refused: their lengths would not fit len); stats: ctr[2] += steps
+// that jumped (step 3), ctr[3] += bytes their extensions matched
+template <class I>
+__global__ void __launch_bounds__(kTB) fm_ms_k(FmArgs<I> a, const uint8_t *__restrict__ text, const I *__restrict__ re_sa,
+                                               const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
+                                               MsRec *__restrict__ rec, int first, uint64_t budget, uint32_t *__restrict__ len_out,
+                                               uint64_t *__restrict__ pos_out, unsigned long long *__restrict__ ctr, int stats) {
+  __shared__ uint8_t code[256];
+  code[threadIdx.x] = a.codes[threadIdx.x];
+  __syncthreads();
+  const int gl = threadIdx.x & 15;
+  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
+  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
+  const uint64_t o0 = off[p], o1 = off[p + 1], n = a.n1 - 1;
+  MsRec s;
+  if (first) {
+    s = MsRec{o1 > o0 ? o1 : o0, 0, n, 0};              // (decreasing offsets: no pattern)
+    if (o1 > o0 && o1 - o0 >= 0xFFFFFFFFull) {
+      s.t = o0;
+      if (gl == 0) atomicAdd(&ctr[1], 1ull);
+    }
+  } else {
+    s = rec[p];
+  }
+  uint64_t work = 0, jumps = 0, matched = 0;
+  while (s.t > o0 && work < budget) {                   // at least one step per launch, at most budget + what the last one compares
+    s.t--;
+    work++;
+    const uint32_t c = pat[s.t], k = code[c];
+    uint64_t out = ~0ull;
+    if (k == kAbsent) {                                 // byte 0 or a byte the text does not hold: nothing matches, (q, pos) stay
+      s.l = 0;
+    } else {
+      const uint32_t c4 = c * 0x01010101u;
+      const uint64_t target = lf_at(a, s.q, c4, k, gl); // C[c] + rank_c(q): the c's before q have LF values below it
+      if (a.bwt[s.q] == c) {
+        s.q = target; s.pos -= 1; s.l += 1;
+      } else {
+        // the last c before q ends a run, the first c after q starts one (BWT[q] != c): both SA values are samples
+        const uint64_t qp = s.q ? select_first(a, 0, s.q, target - 1, c4, k, gl) : ~0ull;
+        const uint64_t qs = s.q + 1 < a.n1 ? select_first(a, s.q + 1, a.n1, target, c4, k, gl) : ~0ull;
+        int64_t lp = -1, ls = -1;                        // (a side that does not exist loses)
+        uint64_t sap = 0, sas = 0;
+        if (qp != ~0ull) {
+          uint64_t r = bit_rank(a.rbits, a.rdir, qp + 1);            // run starts in [0, qp]: qp lies in run r - 1
+          r = r ? r - 1 : 0;
+          if (r >= a.runs) r = a.runs - 1;
+          sap = (uint64_t)re_sa[r];
+          lp = s.l ? (int64_t)lce16(text, n, sap, s.pos, s.l, gl, work) : 0;
+        }
+        if (qs != ~0ull && lp < (int64_t)s.l) {        // (lp = l: the predecessor wins whatever the successor has)
+          uint64_t r = bit_rank(a.rbits, a.rdir, qs);
+          if (r >= a.runs) r = a.runs - 1;
+          sas = (uint64_t)a.rs_sa[r];
+          ls = s.l ? (int64_t)lce16(text, n, sas, s.pos, s.l, gl, work) : 0;
+        }
+        jumps++;
+        matched += (lp > 0 ? (uint64_t)lp : 0) + (ls > 0 ? (uint64_t)ls : 0);
+        if (lp < 0 && ls < 0) {                         // (no c at all: only for a directory that is not this BWT's)
+          s.l = 0;
+        } else if (lp >= ls) {
+          s.q = target - 1; s.pos = sap - 1; s.l = (uint64_t)lp + 1;
+        } else {
+          s.q = target; s.pos = sas - 1; s.l = (uint64_t)ls + 1;
+        }
+      }
+      if (s.l) out = s.pos;
+    }
+    if (gl == 0) {
+      len_out[s.t] = (uint32_t)s.l;
+      if (pos_out) pos_out[s.t] = out;
+    }
+  }
+  if (gl == 0) {
+    rec[p] = s;
+    if (s.t > o0) atomicAdd(&ctr[0], 1ull);
+    if (stats) { atomicAdd(&ctr[2], (unsigned long long)jumps); atomicAdd(&ctr[3], (unsigned long long)matched); }
+  }
+}
+
+__device__ __forceinline__ bool is_mem(const uint32_t *__restrict__ len, uint64_t t, uint64_t o0, uint64_t min_len) {
+  const uint32_t l = len[t];
+  return (uint64_t)l >= min_len && (t == o0 || len[t - 1] <= l);
+}
+
+// cnt[p] = MEMs of pattern p (one group of 16 lanes per pattern; cnt[npat] = 0: the exclusive sums end with the total)
+__global__ void __launch_bounds__(kTB) fm_mem_count(const uint64_t *__restrict__ off, uint64_t npat, const uint32_t *__restrict__ len,
+                                                    uint64_t min_len, uint64_t *__restrict__ cnt) {
+  const int gl = threadIdx.x & 15;
+  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
+  if (p > npat) return;
+  uint64_t k = 0;
+  if (p < npat) {
+    const uint64_t o0 = off[p], o1 = off[p + 1];
+    for (uint64_t t = o0 + gl; t < o1; t += 16) k += is_mem(len, t, o0, min_len);
+  }
+  k = gsum16(k);
+  if (gl == 0) cnt[p] = k;
+}
+
+// mem[3 * (mem_off[p] + j)] = {i, len, pos} of pattern p's j-th MEM, by increasing i
+__global__ void __launch_bounds__(kTB) fm_mem_gather(const uint64_t *__restrict__ off, uint64_t npat, const uint32_t *__restrict__ len,
+                                                     const uint64_t *__restrict__ pos, uint64_t min_len, const uint64_t *__restrict__ mem_off,
+                                                     uint64_t *__restrict__ mem) {
+  const int gl = threadIdx.x & 15;
+  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
+  if (p >= npat) return;
+  const uint64_t o0 = off[p], o1 = off[p + 1];
+  uint64_t slot = mem_off[p];
+  for (uint64_t base = o0; base < o1; base += 16) {     // (base, o1 and slot are the same in all 16 lanes)
+    const uint64_t t = base + gl;
+    const uint32_t f = t < o1 && is_mem(len, t, o0, min_len);
+    uint32_t incl = f;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+      const uint32_t o = __shfl_up(incl, d, 16);
+      if (gl >= d) incl += o;
+    }
+    const uint64_t mine = slot + incl - f;
+    if (f) {
+      mem[3 * mine] = t - o0; mem[3 * mine + 1] = len[t]; mem[3 * mine + 2] = pos ? pos[t] : ~0ull;
+    }
+    slot += __shfl(incl, 15, 16);
+  }
+}
+
 template <class I>
 FmArgs<I> args_of(const FmIndex &f) {
   FmArgs<I> a{};
@@ -367,6 +543,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
                                                     " runs, so its .esa holds " + std::to_string(10 * r));
   f.rs_row.alloc(c, r * sizeof(I));
   f.rs_sa.alloc(c, r * sizeof(I));
+  if (f.has_text) f.re_sa.alloc(c, r * sizeof(I));
   f.nphi = r - 1;
   DBuf<I> key(c, r), val(c, r);
   {
@@ -377,7 +554,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
     {
       KScope ks(c, "fm_pairs", 20 * r + 4 * r * sizeof(I));
       fm_pairs<I><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(ssa10, esa10, r, n1, f.rs.bits.p, f.rs.dir.p, re.bits.p, re.dir.p,
-                                                              (I *)f.rs_row.p, (I *)f.rs_sa.p, key.p, val.p, bad.p);
+                                                              (I *)f.rs_row.p, (I *)f.rs_sa.p, key.p, val.p, (I *)f.re_sa.p, bad.p);
       PFP_HIP(hipGetLastError());
     }
     uint64_t h[2];
@@ -415,7 +592,7 @@ uint64_t fm_bwt_bytes(uint64_t n1) { return ((n1 >> kBlkLog) + 1) << kBlkLog; }
 
 uint64_t FmIndex::device_bytes() const {
   return bwt.bytes() + codes.bytes() + blk.bytes() + sbc.bytes() + rs.bits.bytes() + rs.dir.bytes() + rs_row.bytes() + rs_sa.bytes() +
-         phi_key.bytes() + phi_val.bytes() + phi_dir.bytes();
+         phi_key.bytes() + phi_val.bytes() + phi_dir.bytes() + text.bytes() + re_sa.bytes();
 }
 
 void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
@@ -479,6 +656,87 @@ void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uin
     else build_samples<uint32_t>(c, f, ssa10, ssa_bytes, esa10, esa_bytes);
   }
   sync(c);
+}
+
+void fm_build_ms(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
+                 uint64_t esa_bytes, const uint8_t *text) {
+  PFP_REQUIRE(ssa10 && esa10, PFP_EINVAL, "matching statistics need the run samples: .ssa and .esa (bigbwt -s -e writes them)");
+  f.has_text = true;                                    // (build_samples keeps SA[run end] by run number)
+  fm_build(c, f, bwt, n1, ssa10, ssa_bytes, esa10, esa_bytes);
+  const uint64_t n = n1 - 1;
+  if (text != f.text.p || !text) {
+    f.text.alloc(c, n + 16);
+    if (text) {
+      PFP_HIP(hipMemcpyAsync(f.text.p, text, n, hipMemcpyDeviceToDevice, c->stream));
+    } else if (n) {
+      BwtCheckArgs in;
+      in.bwt = f.bwt.p; in.n1 = n1; in.out = f.text.p;
+      pfp_check_result res;
+      invert_bwt(c, in, &res);
+    }
+  }
+  PFP_HIP(hipMemsetAsync(f.text.p + n, 0, 16, c->stream));
+  sync(c);
+}
+
+template <class I>
+static void ms_t(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  pfp_ctx *c = f.c;
+  uint64_t budget = kMsWork;
+  if (const char *e = getenv("PFP_FM_MS_STEPS")) {      // (tests: a small budget reaches the resume path with small inputs)
+    const uint64_t v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < budget) budget = v;
+  }
+  const FmArgs<I> a = args_of<I>(f);
+  DBuf<MsRec> rec(c, npat);
+  DBuf<uint64_t> ctr(c, 4);
+  const char *se = getenv("PFP_FM_MS_STATS");           // (measurement: tools/ms_time.py reads the sums through pfp_fm_ms_stats)
+  const int stats = se && *se && *se != '0';
+  for (int first = 1;; first = 0) {                     // every launch finishes at least one step of every unfinished pattern
+    ctr.zero();
+    {
+      KScope ks(c, "fm_ms", 0);
+      fm_ms_k<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, f.text.p, (const I *)f.re_sa.p, pat, pat_off, npat, rec.p, first, budget, len,
+                                                                    pos, (unsigned long long *)ctr.p, stats);
+      PFP_HIP(hipGetLastError());
+    }
+    uint64_t h[4];
+    d2h(c, h, ctr.p, 4);
+    sync(c);
+    f.ms_stats[0] += 1; f.ms_stats[1] += h[2]; f.ms_stats[2] += h[3];
+    PFP_REQUIRE(!h[1], PFP_ELIMIT, std::to_string(h[1]) + " patterns of 2^32 - 1 bytes or more: the lengths of matching statistics are 32 bits");
+    if (!h[0]) break;
+  }
+}
+
+static void require_text(const FmIndex &f, const char *what) {
+  PFP_REQUIRE(f.has_text, PFP_EINVAL, std::string(what) + " need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                      "pfp_fm_build_ms_files");
+}
+
+void fm_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  require_text(f, "matching statistics");
+  if (!npat) return;
+  if (f.wide) ms_t<uint64_t>(f, pat, pat_off, npat, len, pos);
+  else ms_t<uint32_t>(f, pat, pat_off, npat, len, pos);
+}
+
+void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
+             uint64_t *mem_off, uint64_t *mem) {
+  pfp_ctx *c = f.c;
+  require_text(f, "maximal exact matches");
+  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
+  KScope ks(c, "fm_mems", 0);
+  {
+    DBuf<uint64_t> cnt(c, npat + 1);
+    fm_mem_count<<<gdim(cdiv(npat + 1, kTB / 16)), kTB, 0, c->stream>>>(pat_off, npat, len, min_len, cnt.p);
+    PFP_HIP(hipGetLastError());
+    exclusive_sum_u64(c, cnt.p, mem_off, npat + 1);
+  }
+  if (mem && npat) {
+    fm_mem_gather<<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(pat_off, npat, len, pos, min_len, mem_off, mem);
+    PFP_HIP(hipGetLastError());
+  }
 }
 
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {

@@ -310,12 +310,25 @@ struct FmIndex {
   DBuf<uint8_t> phi_key, phi_val, phi_dir;  // [runs - 1] of I: SA[e_i] sorted, SA[s_{i+1}]; [nbk + 1] first key of each bucket
   uint64_t nphi = 0, nbk = 0;
   int shift = 0;                         // bucket of text position x: x >> shift
+  bool has_text = false;                 // built by fm_build_ms: the two arrays below exist (matching statistics read them)
+  DBuf<uint8_t> text;                    // the text, n1 - 1 bytes and 16 bytes of zero padding (whole 16-byte loads stay in bounds)
+  DBuf<uint8_t> re_sa;                   // [runs] of I: SA value of run end i
+  uint64_t ms_stats[3] = {0, 0, 0};      // fm_ms launches; with PFP_FM_MS_STATS=1 also steps that jumped and bytes their LCEs matched
   uint64_t device_bytes() const;
 };
 uint64_t fm_bwt_bytes(uint64_t n1);      // f.bwt's size: n1 bytes and the zero padding
 // bwt == f.bwt.p (filled with n1 bytes, fm_bwt_bytes(n1) allocated): the index adopts it instead of copying
 void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
               uint64_t esa_bytes);
+// the same (samples required) plus what matching statistics need: the SA value of every run end and the text.  text == NULL:
+// inverted from the BWT (invert_bwt: not one LF cycle -> PFP_EFORMAT); text == f.text.p (n1 + 15 bytes allocated): adopted
+void fm_build_ms(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,
+                 uint64_t esa_bytes, const uint8_t *text);
+// matching statistics (PHONI; pfpgpu.h states the definitions): len / pos run parallel to pat, pos may be NULL
+void fm_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos);
+// maximal exact matches from fm_ms's outputs: mem_off[0..npat] exclusive sums of the counts; mem == NULL: only those
+void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
+             uint64_t *mem_off, uint64_t *mem);
 // device pointers; first may be NULL (needs samples otherwise)
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first);
 // out_off[0..npat] (device): exclusive sums of min(ep - sp, max_occ); pos == NULL: only those

@@ -1613,6 +1613,150 @@ int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint6
   PFP_CATCH(c)
 }
 
+// ---------------------------------------------------------------- matching statistics and MEMs (fmsearch.hip: PHONI)
+int pfp_fm_build_ms_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                        uint64_t esa_bytes, const void *d_text, pfp_fm **out) {
+  if (!c || !d_bwt || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  auto fm = std::make_unique<pfp_fm>();
+  fm_build_ms(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes,
+              (const uint8_t *)d_text);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_build_ms_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, pfp_fm **out) {
+  if (!c || !base || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  const std::string b(base);
+  auto fm = std::make_unique<pfp_fm>();
+  DBuf<uint8_t> d_bwt, d_ssa, d_esa;
+  const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
+  PFP_REQUIRE(n1 <= (1ull << 40), PFP_ELIMIT, "a BWT of more than 2^40 bytes (the limit of the 5-byte .sa format)");
+  const bool given = text || text_fd >= 0;
+  PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
+                                                     " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
+  const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+  if (given) {
+    fm->f.text.alloc(c, n + 16);
+    if (text) stream_h2d(c, fm->f.text.p, n, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_memcpy(pin, text + off, len); });
+    else stream_h2d(c, fm->f.text.p, n, [&](uint8_t *pin, uint64_t off, uint64_t len) { par_pread(text_fd, text_offset + off, pin, len); });
+    sync(c);
+  }
+  fm_build_ms(c, fm->f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? fm->f.text.p : nullptr);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
+  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  fm_ms(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_mems_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_len, const uint64_t *d_pos, uint64_t min_len,
+                    uint64_t *d_mem_off, uint64_t *d_mem) {
+  if (!fm || !d_mem_off || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  fm_mems(fm->f, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// host patterns -> device patterns, lengths and positions (entry t of the device arrays belongs to pattern byte t)
+struct MsOnDevice {
+  DBuf<uint8_t> pat; DBuf<uint64_t> off, pos; DBuf<uint32_t> len;
+  uint64_t first = 0, total = 0;
+};
+static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MsOnDevice &d) {
+  pfp_ctx *c = fm->f.c;
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  d.first = npat ? pat_off[0] : 0;
+  d.total = bytes - d.first;
+  d.pat.alloc(c, bytes + 16);
+  d.off.alloc(c, npat + 1);
+  d.len.alloc(c, bytes + 1);
+  d.pos.alloc(c, bytes + 1);
+  if (bytes) h2d(c, d.pat.p, pat, bytes);
+  if (npat) h2d(c, d.off.p, pat_off, npat + 1);
+  fm_ms(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
+}
+
+int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
+  if (!fm || !out) return PFP_EINVAL;
+  memcpy(out, fm->f.ms_stats, sizeof fm->f.ms_stats);
+  memset(fm->f.ms_stats, 0, sizeof fm->f.ms_stats);
+  return PFP_OK;
+}
+
+int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  if (!fm || (npat && (!pat_off || !len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "matching statistics need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                          "pfp_fm_build_ms_files");
+  if (!npat) return PFP_OK;
+  MsOnDevice d;
+  ms_on_device(fm, pat, pat_off, npat, d);
+  if (d.total) {
+    stream_d2h(c, (const uint8_t *)(d.len.p + d.first), d.total * 4, [&](const uint8_t *pin, uint64_t off, uint64_t n) { par_memcpy((uint8_t *)len + off, pin, n); });
+    sync(c);      // (the next stream_d2h fills the same pinned buffers)
+    if (pos) stream_d2h(c, (const uint8_t *)(d.pos.p + d.first), d.total * 8, [&](const uint8_t *pin, uint64_t off, uint64_t n) { par_memcpy((uint8_t *)pos + off, pin, n); });
+  }
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
+  if (!fm || !mem_off || !mems || (npat && !pat_off)) return PFP_EINVAL;
+  *mems = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY(c)
+  PFP_HIP(hipSetDevice(c->device));
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "maximal exact matches need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                          "pfp_fm_build_ms_files");
+  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
+  MsOnDevice d;
+  ms_on_device(fm, pat, pat_off, npat, d);
+  d.pat.release();
+  DBuf<uint64_t> d_mem_off(c, npat + 1);
+  fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
+  d2h(c, mem_off, d_mem_off.p, npat + 1);
+  sync(c);
+  const uint64_t total = mem_off[npat];
+  if (total) {
+    DBuf<uint64_t> d_mem(c, 3 * total);
+    fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, d_mem.p);
+    uint64_t *h = host_alloc<uint64_t>(3 * total);
+    try {
+      stream_d2h(c, (const uint8_t *)d_mem.p, total * 24, [&](const uint8_t *pin, uint64_t off, uint64_t n) { par_memcpy((uint8_t *)h + off, pin, n); });
+      sync(c);
+    } catch (...) {
+      free(h);
+      throw;
+    }
+    *mems = h;
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
 int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
   if (!fm || !out) return PFP_EINVAL;
   memset(out, 0, sizeof *out);

@@ -1,32 +1,45 @@
 /* bwtsearch.c -- count (and locate) patterns in a text through its .bwt (and .ssa / .esa) on the GPU.
  *
  *   bwtsearch [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
+ *   bwtsearch --ms | --mems L [--text FILE] [--device D] PATTERNFILE basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
  * order (the lexicographic order of the suffixes), at most MAXOCC of them (0: all).  Count needs basename.bwt only; -l also
  * reads basename.ssa and basename.esa (bigbwt -s -e).  The definitions: include/pfpgpu.h, "Searching a BWT".
+ * --ms prints the matching statistics of every pattern, `len:pos` for every byte of the line separated by one space, `0:-` where
+ * the length is 0; --mems L its maximal exact matches of at least L bytes, `count<TAB>i:len:pos i:len:pos ...` (the definitions:
+ * include/pfpgpu.h, "Matching statistics").  Both read basename.bwt, .ssa and .esa, and the text from FILE, or without --text by
+ * inverting basename.bwt.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, 2 a usage error.
  */
 #define _GNU_SOURCE
+#include <fcntl.h>
 #include <getopt.h>
 #include <inttypes.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include "pfpgpu.h"
 
 static void usage(const char *argv0) {
-  printf("usage: %s [-h] [-l] [-m MAXOCC] [--device D] PATTERNFILE basename\n\n"
+  printf("usage: %s [-h] [-l] [-m MAXOCC] [--device D] PATTERNFILE basename\n"
+         "       %s --ms | --mems L [--text FILE] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
          "  -l            print count<TAB>positions (in suffix order) instead of the count\n"
          "  -m MAXOCC     with -l: at most MAXOCC positions per pattern (def. 0 = all)\n"
+         "      --ms        print the matching statistics: len:pos for every byte of the line (0:- where nothing matches);\n"
+         "                  reads basename.bwt, .ssa and .esa\n"
+         "      --mems L    print count<TAB>i:len:pos ... : the maximal exact matches of at least L >= 1 bytes; reads the same files\n"
+         "      --text FILE with --ms / --mems: the text (def. inverted from basename.bwt)\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0);
+         argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -53,9 +66,11 @@ static int read_file(const char *path, uint8_t **out, uint64_t *len) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0;
-  uint64_t maxocc = 0;
-  static struct option lo[] = {{"device", required_argument, 0, 1001}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0;
+  uint64_t maxocc = 0, min_len = 0;
+  const char *textfile = NULL;
+  static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
+                               {"text", required_argument, 0, 1004}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
   int c;
   char *end;
   while ((c = getopt_long(argc, argv, "lm:h", lo, NULL)) != -1) {
@@ -64,7 +79,15 @@ int main(int argc, char **argv) {
       case 'm':
         maxocc = strtoull(optarg, &end, 10);
         if (!*optarg || *end || optarg[0] == '-') { usage(argv[0]); return 2; }
+        have_m = 1;
         break;
+      case 1002: ms = 1; break;
+      case 1003:
+        min_len = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-' || min_len < 1) { usage(argv[0]); return 2; }
+        mems = 1;
+        break;
+      case 1004: textfile = optarg; break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -74,6 +97,7 @@ int main(int argc, char **argv) {
     }
   }
   if (optind + 2 != argc) { usage(argv[0]); return 2; }
+  if (ms + mems + locate > 1 || ((ms || mems) && have_m) || (textfile && !ms && !mems)) { usage(argv[0]); return 2; }
   const char *patfile = argv[optind], *base = argv[optind + 1];
 
   uint8_t *pats = NULL;
@@ -102,7 +126,27 @@ int main(int argc, char **argv) {
     return 1;
   }
   pfp_fm *fm = NULL;
-  rc = pfp_fm_build_files(ctx, base, locate ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
+  if (ms || mems) {
+    int fd = -1;
+    uint64_t n = 0;
+    if (textfile) {
+      struct stat sb;
+      fd = open(textfile, O_RDONLY);
+      if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        perror(textfile);
+        if (fd >= 0) close(fd);
+        pfp_ctx_destroy(ctx);
+        free(pats); free(lstart);
+        return 1;
+      }
+      n = (uint64_t)sb.st_size;
+    }
+    rc = pfp_fm_build_ms_files(ctx, base, NULL, fd, 0, n, &fm);
+    if (fd >= 0) close(fd);
+    if (rc && textfile) fprintf(stderr, "%s: ", textfile);
+  } else {
+    rc = pfp_fm_build_files(ctx, base, locate ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
+  }
   if (rc) {
     fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
     pfp_ctx_destroy(ctx);
@@ -143,7 +187,34 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    if (locate) {
+    if (ms) {
+      const uint64_t total = off[k];
+      uint32_t *len = malloc((total + 1) * sizeof(uint32_t));
+      uint64_t *pos = malloc((total + 1) * sizeof(uint64_t));
+      if (!len || !pos) { fprintf(stderr, "out of memory\n"); free(len); free(pos); rc = 1; goto done; }
+      rc = pfp_fm_ms(fm, pat, off, k, len, pos);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); free(len); free(pos); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        for (uint64_t j = off[i]; j < off[i + 1]; j++) {
+          if (j > off[i]) putchar(' ');
+          if (len[j]) printf("%" PRIu32 ":%" PRIu64, len[j], pos[j]);
+          else fputs("0:-", stdout);
+        }
+        putchar('\n');
+      }
+      free(len); free(pos);
+    } else if (mems) {
+      uint64_t *m = NULL;
+      rc = pfp_fm_mems(fm, pat, off, k, min_len, oo, &m);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);
+        for (uint64_t j = oo[i]; j < oo[i + 1]; j++)
+          printf(j > oo[i] ? " %" PRIu64 ":%" PRIu64 ":%" PRIu64 : "%" PRIu64 ":%" PRIu64 ":%" PRIu64, m[3 * j], m[3 * j + 1], m[3 * j + 2]);
+        putchar('\n');
+      }
+      pfp_free(m);
+    } else if (locate) {
       uint64_t *pos = NULL;
       rc = pfp_fm_locate(fm, pat, off, k, maxocc, sp, ep, oo, &pos);
       if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }

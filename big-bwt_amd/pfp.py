@@ -35,7 +35,7 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
            "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
            "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
-           "pfp_fm_free"]
+           "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats"]
 
 
 class PfpError(RuntimeError):
@@ -129,6 +129,53 @@ class FmIndex:
             positions = np.ctypeslib.as_array(pos, shape=(total,)).copy()
             self.lib.pfp_free(pos)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
+
+    def matching_statistics(self, patterns):
+        """-> (off, len, pos): for byte i of pattern p, len[off[p] + i] (uint32) is the length of the longest prefix of
+        patterns[p][i:] that occurs in the text and pos[off[p] + i] (uint64) one place where it occurs (2**64 - 1 where the
+        length is 0).  Needs an index with text (Context.fm_index_ms*)."""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        total = int(off[-1])
+        ln, pos = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint64)
+        self.ctx._check(self.lib.pfp_fm_ms(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(ln, C.c_uint32),
+                                           _ptr(pos, C.c_uint64)))
+        return off, ln, pos
+
+    def mems(self, patterns, min_len=1):
+        """-> (mem_off, mems): the maximal exact matches of pattern p of at least min_len bytes are the rows
+        mems[mem_off[p]:mem_off[p+1]] of a (k, 3) uint64 array, each (i, len, pos), by increasing i"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        mem_off = np.zeros(npat + 1, dtype=np.uint64)
+        out = C.POINTER(C.c_uint64)()
+        self.ctx._check(self.lib.pfp_fm_mems(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_len),
+                                             _ptr(mem_off, C.c_uint64), C.byref(out)))
+        total = int(mem_off[-1])
+        mems = np.zeros((0, 3), dtype=np.uint64)
+        if total and out:
+            mems = np.ctypeslib.as_array(out, shape=(3 * total,)).copy().reshape(total, 3)
+            self.lib.pfp_free(out)
+        return mem_off, mems
+
+    def ms_stats(self):
+        """{launches, jumps, matched} of the matching-statistics calls since the last look; jumps (steps that took step 3) and
+        matched (bytes their extensions matched) are collected only under PFP_FM_MS_STATS=1"""
+        out = (C.c_uint64 * 3)()
+        self.ctx._check(self.lib.pfp_fm_ms_stats(self._h, out))
+        return dict(launches=int(out[0]), jumps=int(out[1]), matched=int(out[2]))
+
+    def matching_statistics_dev(self, d_pat, d_pat_off, npat, d_len, d_pos=None):
+        """device pointers: pattern bytes, npat+1 uint64 offsets -> uint32 d_len / uint64 d_pos, entry t for pattern byte d_pat[t]"""
+        self.ctx._check(self.lib.pfp_fm_ms_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
+                                               C.c_void_p(d_pos) if d_pos else None))
+
+    def mems_dev(self, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem=None):
+        """device pointers from matching_statistics_dev -> npat+1 offsets; d_mem (room for 3 * offsets[npat] uint64) gets the
+        triples (None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_mems_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
+                                                 C.c_void_p(d_pos) if d_pos else None, C.c_uint64(min_len), C.c_void_p(d_mem_off),
+                                                 C.c_void_p(d_mem) if d_mem else None))
 
     def count_dev(self, d_pat, d_pat_off, npat, d_sp, d_ep, d_first=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat uint64 sp / ep (and SA[sp] where d_first is given)"""
@@ -602,6 +649,53 @@ class Context:
         """an FmIndex over <base>.bwt and, when flags holds FLAG_SSA | FLAG_ESA, <base>.ssa / .esa"""
         h = C.c_void_p()
         self._check(self.lib.pfp_fm_build_files(self._h, C.c_char_p(os.fsencode(base)), C.c_int(flags), C.byref(h)))
+        return FmIndex(self, h)
+
+    # -- matching statistics and MEMs: an index that also keeps the text and the run-end values
+    def fm_index_ms(self, bwt, ssa, esa, text=None):
+        """an FmIndex for matching_statistics / mems over host .bwt, .ssa and .esa bytes; text=None: the text is inverted from
+        the BWT on the GPU, else a numpy array / bytes of len(bwt) - 1 bytes"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if ssa is None or esa is None:
+            raise PfpError(-1, "matching statistics need the run samples: .ssa and .esa (bigbwt -s -e writes them)")
+        keep = []
+        for a in (bwt, ssa, esa, text):
+            if a is None:
+                keep.append(None)
+                continue
+            b = _arr(a, np.uint8)
+            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
+            if len(b):
+                t[:len(b)] = torch.from_numpy(b.copy())
+            keep.append((t, len(b)))
+        if keep[3] is not None and keep[3][1] + 1 != keep[0][1]:
+            raise PfpError(-1, f"the text holds {keep[3][1]} bytes; the BWT holds {keep[0][1]} rows, so its text holds {max(keep[0][1], 1) - 1}")
+        torch.cuda.synchronize(dev)
+        return self.fm_index_ms_dev(keep[0][0].data_ptr(), keep[0][1], keep[1][0].data_ptr(), keep[1][1], keep[2][0].data_ptr(), keep[2][1],
+                                    keep[3][0].data_ptr() if keep[3] else None)
+
+    def fm_index_ms_dev(self, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text=None):
+        """the same over device buffers (copied); d_text: n_plus_1 - 1 device bytes, None: inverted"""
+        h = C.c_void_p()
+        vp = lambda x: C.c_void_p(x) if x else None
+        self._check(self.lib.pfp_fm_build_ms_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes),
+                                                 vp(d_esa10), C.c_uint64(esa_bytes), vp(d_text), C.byref(h)))
+        return FmIndex(self, h)
+
+    def fm_index_ms_files(self, base, text=None):
+        """the same over <base>.bwt / .ssa / .esa; text=None: inverted"""
+        h = C.c_void_p()
+        if text is None:
+            self._check(self.lib.pfp_fm_build_ms_files(self._h, C.c_char_p(os.fsencode(base)), None, C.c_int(-1), C.c_uint64(0), C.c_uint64(0),
+                                                       C.byref(h)))
+        else:
+            t = _arr(text, np.uint8)
+            if not len(t):
+                t = np.zeros(1, dtype=np.uint8)[:0]
+            buf = np.concatenate([t, np.zeros(1, dtype=np.uint8)])       # (never a NULL pointer for an empty text)
+            self._check(self.lib.pfp_fm_build_ms_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(buf, C.c_uint8), C.c_int(-1), C.c_uint64(0),
+                                                       C.c_uint64(len(t)), C.byref(h)))
         return FmIndex(self, h)
 
     # -- multi-GPU chain, one rank's share (device pointers; collectives are the caller's: dist.py)

@@ -525,6 +525,62 @@ int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out);
  * take an index are reported through its context's pfp_last_error. */
 void pfp_fm_free(pfp_fm *fm);
 
+/* ------------------------------------------------------------------------------------
+ * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
+ * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
+ * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
+ * steps over the BWT, and where the BWT byte differs a jump to the nearest row above or below that carries the wanted byte - a run
+ * end or a run start, so its SA value is a sample - chosen by a longest-common-extension query on the text.
+ * Conventions as in "Searching a BWT".  For a pattern P of m bytes and every i in [0, m):
+ *   len[i] = the largest l <= m - i such that P[i .. i+l) occurs in T.  It is 0 where P[i] is byte 0 or a byte T does not hold.
+ *   pos[i] = a text position with T[pos[i] .. pos[i]+len[i]) = P[i .. i+len[i]); UINT64_MAX where len[i] = 0.  Several positions
+ *     can qualify; which one is returned is fixed by the algorithm below, so it depends on the inputs only - not on the batch,
+ *     the launch budget or the schedule.
+ *   a MEM of P is a triple (i, len[i], pos[i]) with len[i] >= min_len (>= 1) and (i = 0 or len[i-1] <= len[i]).  (len[i-1] <=
+ *     len[i] + 1 always holds; the match at i extends to the left exactly when len[i-1] = len[i] + 1.  It cannot extend to the
+ *     right by the definition of len.)  The MEMs of a pattern are listed by increasing i.
+ * Algorithm, per pattern, right to left, state (q, pos, l) with SA[q] = pos and T[pos .. pos+l) = P[i+1 .. i+1+l); start with
+ * q = 0, pos = n, l = 0.  For i = m-1 .. 0, c = P[i]:
+ *   1. c is byte 0 or a byte T does not hold: l = 0, len[i] = 0, (q, pos) stay.
+ *   2. BWT[q] = c: q = LF(q), pos -= 1, l += 1.
+ *   3. otherwise q_p = the last row before q and q_s = the first row after q whose BWT byte is c (a run end and a run start);
+ *      l_p = min(l, LCE(SA[q_p], pos)), l_s = min(l, LCE(SA[q_s], pos)), a side that does not exist loses; take q_p if l_p >= l_s,
+ *      else q_s; with the chosen row x: q = LF(x), pos = SA[x] - 1, l = l_x + 1.  When l = 0 no text is read.
+ *   4. len[i] = l, pos[i] = pos.
+ * A pattern that mismatches at every step compares O(m^2) bytes; the work of one kernel launch is bounded per pattern and the
+ * library launches until every pattern is done (PFP_FM_MS_STEPS=K in the environment, read per call, lowers that bound: tests).
+ * len is 32 bits: the two arrays have one entry per pattern BYTE; a single pattern of 2^32 - 1 bytes or more is PFP_ELIMIT.
+ * Not checked: that the text given is the BWT's (wrong text or wrong SA values give wrong answers, never a read outside the
+ * index).  Device memory: an index with text holds at most (n + 256) bytes and w bytes per run more than the plain index with
+ * samples; a query takes 32 bytes per pattern on top of the caller's buffers; building by inversion peaks at the index plus what
+ * pfp_unbwt_dev needs (its 4 / 8 bytes per row are transient).  pfp_fm_count* / pfp_fm_locate* work on such an index as on a
+ * plain one.  pfp_fm_ms* / pfp_fm_mems* on an index without text: PFP_EINVAL.
+ * ------------------------------------------------------------------------------------ */
+/* as pfp_fm_build_dev with both sample files (required: PFP_EINVAL otherwise), plus the text: d_text = n_plus_1 - 1 device bytes,
+ * or NULL: the library inverts d_bwt itself (bytes that are not one LF cycle: PFP_EFORMAT).  The index copies what it keeps. */
+int pfp_fm_build_ms_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes,
+                        const void *d_esa10, uint64_t esa_bytes, const void *d_text, pfp_fm **out);
+/* reads <base>.bwt / .ssa / .esa; the text as in pfp_check_bwt_files (host pointer, or bytes [text_offset, text_offset + n) of
+ * text_fd), or text == NULL and text_fd < 0: inverted.  n != rows - 1 -> PFP_EINVAL naming both numbers. */
+int pfp_fm_build_ms_files(pfp_ctx *ctx, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n,
+                          pfp_fm **out);
+/* d_len (uint32) and d_pos (uint64, may be NULL) run parallel to d_pat: entry t belongs to pattern byte d_pat[t],
+ * d_pat_off[0] <= t < d_pat_off[npat]; entries outside that range are not touched.  A pair of decreasing offsets: no pattern. */
+int pfp_fm_ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos);
+/* from pfp_fm_ms_dev's outputs: d_mem_off (npat + 1) = exclusive sums of the patterns' MEM counts; d_mem (NULL: offsets only)
+ * = 3 uint64 per MEM {i, len, pos}, i counted from the pattern's first byte.  min_len = 0: PFP_EINVAL. */
+int pfp_fm_mems_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_len, const uint64_t *d_pos,
+                    uint64_t min_len, uint64_t *d_mem_off, uint64_t *d_mem);
+/* measurement: out = {kernel launches of the matching-statistics calls, steps that took step 3, bytes their extensions matched}
+ * since the index was built or this was last called; the last two are collected only while PFP_FM_MS_STATS=1 is in the
+ * environment (two atomic additions per pattern and launch) */
+int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]);
+/* host buffers; len / pos hold pat_off[npat] - pat_off[0] entries (pos NULL ok); offsets that decrease: PFP_EINVAL */
+int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos);
+/* mem_off (npat + 1) and *mems, a malloc'ed array of 3 mem_off[npat] uint64 (pfp_free; NULL when there are none) */
+int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off,
+                uint64_t **mems);
+
 /* ---- micro entry points used by bench.py's roofline leg and by the parity tests ---- */
 /* copy a device-resident text into the ctx's padded staging buffer (T' = Dollar.T.Dollar^w) */
 int pfp_stage_text_dev(pfp_ctx *ctx, const void *d_text, uint64_t n, int w);
