@@ -1,0 +1,274 @@
+// api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
+// reference counterpart): struct pfp_fm and every pfp_fm_* call.
+#include <memory>
+#include "api.hpp"
+
+using namespace pfp;
+
+struct pfp_fm {
+  pfp::FmIndex f;
+};
+
+extern "C" {
+
+// host patterns: the bytes to copy (pat_off[npat]), once the offsets are known to be non-decreasing (no kernel reads past them)
+static uint64_t pattern_bytes(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat) {
+  if (!npat) return 0;
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p] <= pat_off[p + 1], PFP_EINVAL, "pattern offsets decrease at pattern " + std::to_string(p));
+  PFP_REQUIRE(pat || !pat_off[npat], PFP_EINVAL, "no pattern bytes");
+  return pat_off[npat];
+}
+
+int pfp_fm_build_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                     uint64_t esa_bytes, pfp_fm **out) {
+  if (!c || !d_bwt || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY_DEV(c)
+  auto fm = std::make_unique<pfp_fm>();
+  fm_build(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_build_files(pfp_ctx *c, const char *base, int flags, pfp_fm **out) {
+  if (!c || !base || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY_DEV(c)
+  const std::string b(base);
+  const int samp = flags & (PFP_FLAG_SSA | PFP_FLAG_ESA);
+  PFP_REQUIRE(samp == 0 || samp == (PFP_FLAG_SSA | PFP_FLAG_ESA), PFP_EINVAL, "the run samples come as a pair: .ssa and .esa, or neither");
+  auto fm = std::make_unique<pfp_fm>();
+  // (the index adopts the buffer the file is read into: it has the room fm_build wants behind the rows)
+  const uint64_t n1 = file_to_dev(c, b + ".bwt", fm->f.bwt, [](uint64_t rows) { check_bwt_rows(rows); return fm_bwt_bytes(rows); });
+  DBuf<uint8_t> d_ssa, d_esa;
+  uint64_t ssa_bytes = 0, esa_bytes = 0;
+  if (samp) {
+    ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa);
+    esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+  }
+  fm_build(c, fm->f, fm->f.bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_count_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t *d_sp, uint64_t *d_ep, uint64_t *d_first) {
+  if (!fm || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_count(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_sp, d_ep, d_first);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_locate_dev(pfp_fm *fm, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep, const uint64_t *d_first, uint64_t max_occ,
+                      uint64_t *d_out_off, uint64_t *d_pos) {
+  if (!fm || !d_out_off || (npat && (!d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_locate(fm->f, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_count(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
+  if (!fm || (npat && (!pat_off || !sp || !ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(!first || fm->f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
+  if (!npat) return PFP_OK;
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16);
+  DBuf<uint64_t> d_off(c, npat + 1), d_out(c, 3 * npat);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  h2d(c, d_off.p, pat_off, npat + 1);
+  fm_count(fm->f, d_pat.p, d_off.p, npat, d_out.p, d_out.p + npat, first ? d_out.p + 2 * npat : nullptr);
+  d2h(c, sp, d_out.p, npat);
+  d2h(c, ep, d_out.p + npat, npat);
+  if (first) d2h(c, first, d_out.p + 2 * npat, npat);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
+                  uint64_t *out_off, uint64_t **pos) {
+  if (!fm || !out_off || !pos || (npat && !pat_off)) return PFP_EINVAL;
+  *pos = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16);
+  DBuf<uint64_t> d_off(c, npat + 1), d_rng(c, 3 * npat + 1), d_out_off(c, npat + 1);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  if (npat) h2d(c, d_off.p, pat_off, npat + 1);
+  fm_count(fm->f, d_pat.p, d_off.p, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat);
+  d_pat.release();
+  fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, nullptr);
+  d2h(c, out_off, d_out_off.p, npat + 1);
+  if (sp) d2h(c, sp, d_rng.p, npat);
+  if (ep) d2h(c, ep, d_rng.p + npat, npat);
+  sync(c);
+  const uint64_t total = out_off[npat];
+  if (total) {
+    DBuf<uint64_t> d_pos(c, total);
+    fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, d_pos.p);
+    *pos = (uint64_t *)fetch_bytes(c, (const uint8_t *)d_pos.p, total * 8);
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- matching statistics and MEMs (fmsearch.hip: PHONI)
+int pfp_fm_build_ms_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                        uint64_t esa_bytes, const void *d_text, pfp_fm **out) {
+  if (!c || !d_bwt || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY_DEV(c)
+  auto fm = std::make_unique<pfp_fm>();
+  fm_build_ms(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes,
+              (const uint8_t *)d_text);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_build_ms_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, pfp_fm **out) {
+  if (!c || !base || !out) return PFP_EINVAL;
+  *out = nullptr;
+  PFP_TRY_DEV(c)
+  const std::string b(base);
+  auto fm = std::make_unique<pfp_fm>();
+  DBuf<uint8_t> d_bwt, d_ssa, d_esa;
+  const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
+  check_bwt_rows(n1);
+  const bool given = text || text_fd >= 0;
+  PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
+                                                     " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
+  const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+  if (given) {
+    fm->f.text.alloc(c, n + 16);
+    upload_text(c, fm->f.text.p, text, text_fd, text_offset, n);
+    sync(c);
+  }
+  fm_build_ms(c, fm->f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? fm->f.text.p : nullptr);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
+  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_ms(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_mems_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_len, const uint64_t *d_pos, uint64_t min_len,
+                    uint64_t *d_mem_off, uint64_t *d_mem) {
+  if (!fm || !d_mem_off || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_mems(fm->f, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// host patterns -> device patterns, lengths and positions (entry t of the device arrays belongs to pattern byte t)
+struct MsOnDevice {
+  DBuf<uint8_t> pat; DBuf<uint64_t> off, pos; DBuf<uint32_t> len;
+  uint64_t first = 0, total = 0;
+};
+static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MsOnDevice &d) {
+  pfp_ctx *c = fm->f.c;
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  d.first = npat ? pat_off[0] : 0;
+  d.total = bytes - d.first;
+  d.pat.alloc(c, bytes + 16);
+  d.off.alloc(c, npat + 1);
+  d.len.alloc(c, bytes + 1);
+  d.pos.alloc(c, bytes + 1);
+  if (bytes) h2d(c, d.pat.p, pat, bytes);
+  if (npat) h2d(c, d.off.p, pat_off, npat + 1);
+  fm_ms(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
+}
+
+int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
+  if (!fm || !out) return PFP_EINVAL;
+  memcpy(out, fm->f.ms_stats, sizeof fm->f.ms_stats);
+  memset(fm->f.ms_stats, 0, sizeof fm->f.ms_stats);
+  return PFP_OK;
+}
+
+int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  if (!fm || (npat && (!pat_off || !len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "matching statistics need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                          "pfp_fm_build_ms_files");
+  if (!npat) return PFP_OK;
+  MsOnDevice d;
+  ms_on_device(fm, pat, pat_off, npat, d);
+  if (d.total) {
+    download(c, len, (const uint8_t *)(d.len.p + d.first), d.total * 4);
+    sync(c);      // (the next download fills the same pinned buffers)
+    if (pos) download(c, pos, (const uint8_t *)(d.pos.p + d.first), d.total * 8);
+  }
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
+  if (!fm || !mem_off || !mems || (npat && !pat_off)) return PFP_EINVAL;
+  *mems = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "maximal exact matches need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                          "pfp_fm_build_ms_files");
+  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
+  MsOnDevice d;
+  ms_on_device(fm, pat, pat_off, npat, d);
+  d.pat.release();
+  DBuf<uint64_t> d_mem_off(c, npat + 1);
+  fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
+  d2h(c, mem_off, d_mem_off.p, npat + 1);
+  sync(c);
+  const uint64_t total = mem_off[npat];
+  if (total) {
+    DBuf<uint64_t> d_mem(c, 3 * total);
+    fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, d_mem.p);
+    *mems = (uint64_t *)fetch_bytes(c, (const uint8_t *)d_mem.p, total * 24);
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
+  if (!fm || !out) return PFP_EINVAL;
+  memset(out, 0, sizeof *out);
+  out->n = fm->f.n1 - 1;
+  out->runs = fm->f.samples ? fm->f.runs : 0;
+  out->sigma = (uint32_t)fm->f.sigma;
+  out->row_bits = fm->f.wide ? 64 : 32;
+  out->device_bytes = fm->f.device_bytes();
+  out->has_samples = fm->f.samples ? 1 : 0;
+  return PFP_OK;
+}
+
+void pfp_fm_free(pfp_fm *fm) {
+  if (!fm) return;
+  (void)hipSetDevice(fm->f.c->device);
+  delete fm;
+}
+
+}  // extern "C"

@@ -12,7 +12,9 @@
 #include <thread>
 #include "../../include/pfpgpu.h"
 
+struct K1Scratch; struct DistState;      // api_debug.hip, api_dist.hip
 namespace pfp {
+struct StagedText;     // kernels.hpp
 
 // special bytes of the parse (utils.h:6-8)
 constexpr uint8_t kDollar = 2, kEndOfWord = 1, kEndOfDict = 0;
@@ -247,10 +249,10 @@ struct pfp_ctx {
   int n_cu = 256;
   // pinned staging scalars for D2H counters
   uint64_t *h_scalars = nullptr;  // 16 x u64, pinned
-  void *staged = nullptr;         // pfp::StagedText kept by pfp_stage_text_dev
-  void *k1scratch = nullptr;      // scratch of pfp_scan_k1_enqueue
-  void *dist = nullptr;           // DistState of the multi-GPU entry points
-  // two pinned staging buffers for chunked, double-buffered host <-> device streams (allocated on first use)
+  pfp::StagedText *staged = nullptr;      // text kept by pfp_stage_text_dev
+  K1Scratch *k1scratch = nullptr;         // scratch of pfp_scan_k1_enqueue
+  DistState *dist = nullptr;              // state of the multi-GPU entry points
+  // two pinned staging buffers for chunked, double-buffered host <-> device streams (hostio.hip: allocated on first use)
   static constexpr size_t kPinBytes = 32u << 20;
   void *pin[2] = {nullptr, nullptr};
   hipEvent_t pin_ev[2] = {nullptr, nullptr};

@@ -1,7 +1,7 @@
 // multi.hip -- pfp_bigbwt_files_multi: one BWT on N GPUs of one node from ONE process.
 //
 // One host thread and one pfp_ctx per GPU; the threads run the multi-GPU chain (the
-// pfp_dist_* calls of pipeline.hip) and meet in collectives: RCCL over xGMI (grouped ncclSend / ncclRecv of the ranks' pieces,
+// pfp_dist_* calls of api_dist.hip) and meet in collectives: RCCL over xGMI (grouped ncclSend / ncclRecv of the ranks' pieces,
 // one communicator per thread from ncclCommInitAll; librccl is loaded with dlopen when the first multi-GPU call comes, so a
 // single-GPU user of the library never maps it), or - PFP_MULTI_LOOPBACK=1, for tests on a one-GPU box: every rank on the same
 // device - plain device copies between the ranks' buffers.  This is the host side of `bigbwt -G N` (host/bigbwt.c); the

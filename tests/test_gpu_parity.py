@@ -194,7 +194,7 @@ def test_suffix_sorters_match_oracle(O, wctx):
 def test_lcp_of_long_repeats(O, wctx):
     """gsacak's LCP output on a collection full of long exact repeats - a 150 K run of one letter (149 999 ... 1 between
     neighbouring suffixes), the same 30 K string twice plus a prefix of it, a 80 K periodic string: nearly every pair shares
-    more than the 2 KB one thread compares, and goes through the text-order pass (pipeline.hip lcp_long_kernel)"""
+    more than the 2 KB one thread compares, and goes through the text-order pass (api_stages.hip lcp_long_kernel)"""
     rng = np.random.default_rng(5)
     r = rng.integers(65, 70, size=30000).astype(np.uint8)
     coll = np.concatenate([np.full(150000, ord("N"), np.uint8), [1], r, [1], np.tile(np.frombuffer(b"ACGT", np.uint8), 20000), [1], r, [1],
@@ -490,7 +490,7 @@ def test_c_driver_end_to_end(golden, O, tmp_path):
 @pytest.mark.parametrize("where", ["memory_fs", "tmp_path"])
 def test_c_driver_outputs_through_mapped_files(golden, O, tmp_path, where):
     """the .bwt and .sa whose sizes the text fixes are copied from HBM straight into the mapped pages of their files
-    (pipeline.hip MappedOut: files of 64 MB and more in a memory file system; PFP_MAP_MIN_BYTES brings the small ones of this
+    (hostio.hpp MappedOut: files of 64 MB and more in a memory file system; PFP_MAP_MIN_BYTES brings the small ones of this
     test in): same bytes as the pinned-buffer path, in /dev/shm and in a directory that may not be a memory file system (the
     ordinary path there)"""
     import shutil, tempfile

@@ -79,6 +79,21 @@ def test_edge_cases(wctx):
     assert np.array_equal(wctx.unbwt(bwt), t)
 
 
+@pytest.mark.parametrize("n1", [(8 << 20) + 1, (12 << 20) + 2])
+def test_transfer_sizes_that_split_unevenly(ctx, n1):
+    """a host <-> device copy is cut into whole 4 KiB pages for a few threads; a size that leaves a remainder of a byte or two
+    over the threads (8 MiB + 1 over two, 12 MiB + 2 and 12 MiB + 1 over three) must arrive whole"""
+    import torch
+    n = n1 - 1                                                              # T = a^(n-1) b: BWT = b, 0, a^(n-1) - its last byte is not 0
+    bwt = np.full(n1, ord("a"), dtype=np.uint8)
+    bwt[0], bwt[1] = ord("b"), 0
+    text = ctx.unbwt(bwt)                                                   # n1 bytes in, n out
+    assert len(text) == n and text[-1] == ord("b") and (text[:-1] == ord("a")).all()
+    src = torch.randint(0, 256, (n1,), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()                                                # (the library copies on its own stream)
+    assert np.array_equal(ctx.fetch_dev(src.data_ptr(), n1), src.cpu().numpy())
+
+
 def test_unbwt_dev(O, ctx):
     import torch
     text = O.gen_fasta(60000, 4, 0.002, 5)
