@@ -972,12 +972,30 @@ __global__ void finish_write_kernel(SufGeom g, uint64_t m, const I *__restrict__
 }
 
 // after the first round, pivot rounds are tried while the groups are families (average size up to
-// kPivotAvg) and each one at least halves the unresolved set; at most kPivotCap bytes per comparison
+// kPivotAvg) and each one at least halves the unresolved set; at most kSwitch.pivot_cap bytes per comparison
 constexpr uint32_t kPivotAvg = 1024u;
-static const uint32_t kPivotCap = []() { const char *e = getenv("PFP_PIVOT_CAP"); uint32_t v = e ? (uint32_t)atoll(e) : 512u; return v > kPivCapMax ? kPivCapMax : v; }();
 
 // the first round leaves more than N/kLazyRatio suffixes unresolved -> scatter all ranks after all
 constexpr uint64_t kLazyRatio = 8ull;
+
+// the library's segmented sort is tried from this average group size on
+constexpr uint32_t kSegMinAvg = 24u;
+
+// the process-wide switches of the round loop, read once.  (PFP_KEYSONLY and PFP_PARSE_PIVOT_MIN are read per call: the tests
+// switch them inside one process.)
+struct SorterSwitches {
+  // the first round's sort: rocPRIM's onesweep, or (PFP_OWN_SORT=1) the hand-written MSD sort of radix.hip - bit-exact, and measured
+  // slower on every workload of round 4 (configs[2] 5.0 vs 3.8 ms, configs[1] 14.0 vs 13.4): the alphabetic code's bits carry ~0.8 bit
+  // of entropy each, so a partition by key BITS needs three passes where 16 uniform bits would do, and each pass reads its input
+  // twice (DESIGN.md section 4)
+  bool lib_sort = getenv("PFP_OWN_SORT") == nullptr;
+  bool finflag = getenv("PFP_NO_FINFLAG") == nullptr;          // (tests: without it, the length-gather path)
+  bool finisher = getenv("PFP_NO_FINISHER") == nullptr;
+  bool small_seg = getenv("PFP_NO_SMALLSEG") == nullptr;
+  bool trace_rounds = getenv("PFP_TRACE_ROUNDS") != nullptr;
+  uint32_t pivot_cap = []() { const char *e = getenv("PFP_PIVOT_CAP"); uint32_t v = e ? (uint32_t)atoll(e) : 512u; return v > kPivCapMax ? kPivCapMax : v; }();
+};
+static const SorterSwitches kSwitch;
 
 template <class I>
 RankViewT<I> rank_view(const SuffixOrderT<I> &so) {
@@ -986,244 +1004,248 @@ RankViewT<I> rank_view(const SuffixOrderT<I> &so) {
 template RankViewT<uint32_t> rank_view(const SuffixOrderT<uint32_t> &);
 template RankViewT<uint64_t> rank_view(const SuffixOrderT<uint64_t> &);
 
+// what doubling() is asked for
+struct DoublingOpts {
+  int key_bits = 64;                     // width of the first-round keys
+  bool dict = false;                     // dictionary mode: out.lut/bytes/kbits are set by the caller, ranks are lazy
+  std::optional<uint64_t> list_len;      // range mode: key/val hold this many suffixes (the ones of this rank's key range), not all g.N
+  int idx_bits = 0;                      // keys-only first round: the words are (key << idx_bits | position) and val is empty
+};
+
+// The sort that the regroup step finds: where its sorted keys are and what they mean.
+enum class Round {
+  FirstDict,            // first round of a dictionary: packed keys in keyo (heads0 / write_back0, which also start the lazy ranks)
+  FirstPlain,           // first round of a parse or a byte text: keys in keyo, no groups before it
+  DictPivotGlobal,      // dictionary pivot round ordered by one device-wide sort: (group, order key) in keyo
+  DictPivotGrouped,     // ... ordered inside its groups: order keys in k32o
+  ParsePivot,           // parse pivot round: 64-bit keys in keyo, ordered inside its groups
+  DoublingGlobal,       // doubling round ordered device-wide: (group, continuation's rank) in keyo (dkeyo in the 64-bit index build)
+  DoublingGrouped,      // ... ordered inside its groups: ranks in k32o
+};
+
+// The state of doubling()'s round loop, and one member function per step of it.
 template <class I>
-static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, uint64_t h0, SuffixOrderT<I> &out,
-                     int key0_bits = 64, bool dict_keys = false, uint64_t n_elems = ~0ull, int idx_bits = 0) {
-  // precondition: key/val hold the initial (prefix key, position) pairs of the N suffixes to sort: all
-  // NP positions, or (range mode, n_elems given) the ones of this rank's key range
+struct Rounds {
   using K = typename IdxTraits<I>::DKey;        // key of a doubling round: (group head, 1 + rank of the continuation)
-  constexpr bool kWide = sizeof(I) == 8;
-  const uint64_t NP = g.N;
-  const bool range_mode = n_elems != ~0ull;
-  const uint64_t N = range_mode ? n_elems : NP;
-  const int TB = 256;
-  out.N = N; out.NP = NP; out.range = range_mode; out.complete = true;
-  out.rounds = 0;
-  if (N == 0) { out.sa.alloc(c, 1); out.grp.alloc(c, 8); out.rank.alloc(c, 1); return; }
-  const bool lazy = dict_keys;      // dictionary mode: out.lut/bytes/kbits are set by the caller
-  // ---- first round: one device-wide sort of all N (key, position) pairs, ping-ponging between the two buffer
-  //      pairs (no third copy inside the library); afterwards keyo/valo hold the sorted pairs
-  DBuf<uint64_t> keyo(c, N);
-  DBuf<I> valo(c, N);
-  // the first round's sort: rocPRIM's onesweep, or (PFP_OWN_SORT=1) the hand-written MSD sort of radix.hip - bit-exact, and measured
-  // slower on every workload of round 4 (configs[2] 5.0 vs 3.8 ms, configs[1] 14.0 vs 13.4): the alphabetic code's bits carry ~0.8 bit
-  // of entropy each, so a partition by key BITS needs three passes where 16 uniform bits would do, and each pass reads its input
-  // twice (DESIGN.md section 4)
-  static const bool lib_sort = getenv("PFP_OWN_SORT") == nullptr;
-  SortTag first_tag(g.mode == MODE_DICT ? "dictionary, first round" : "parse, first round");
-  if (idx_bits) {
-    // keys-only first round: the words are (key << idx_bits | position), 16 bytes per element and pass instead of 24;
-    // the sort is stable on the key bits alone, so ties stay in position order; one streaming pass splits the result
-    if (lib_sort) sort_keys_db(c, key, keyo, N, idx_bits, idx_bits + key0_bits);
-    else msd_sort_keys_db(c, key, keyo, N, idx_bits, idx_bits + key0_bits);
-    KScope ks(c, "pfp::split_keys_kernel", N * (16 + sizeof(I)));
-    hipLaunchKernelGGL(split_keys_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, key.p, N, idx_bits, keyo.p, valo.p);
-  } else {
-    if (lib_sort) sort_pairs_db(c, key, keyo, val, valo, N, 0, key0_bits);
-    else msd_sort_pairs_db<I>(c, key, keyo, val, valo, N, 0, key0_bits);
-    std::swap(key, keyo); std::swap(val, valo);
-  }
-  SortTag later_tag(g.mode == MODE_DICT ? "dictionary, later rounds" : "parse, later rounds");
-  if (lazy) { key.release(); val.release(); }      // dictionary mode: later rounds sort the (much smaller) unresolved set
-  // (allocated only now: while the first sort holds its four buffers - 32 bytes per suffix in the wide build - nothing else
-  //  of that size is live: a 4.8 GB dictionary peaked at 206 GB with the group array next to them, 168 GB without)
-  DBuf<uint8_t> hd(c, N + 1), keep(c, N);
-  out.grp.alloc(c, N + 8);
-  // active list (slot, suffix, group) of the unresolved suffixes and per-round scratch, `cap` elements each;
+  static constexpr bool kWide = sizeof(I) == 8;
+  static constexpr int TB = 256;
+
+  // ---- fixed when the loop starts
+  pfp_ctx *const c;
+  const SufGeom g;
+  SuffixOrderT<I> &out;
+  const DoublingOpts o;
+  const uint64_t NP, N;         // positions of the string; suffixes sorted here (fewer in range mode)
+  const bool lazy;
+  // a share of the suffix array (multi-GPU) never runs a doubling round - it stops where one would be needed - and finds
+  // its whole words by looking at its own slots (gather_slots_range): no rank per dictionary position is kept
+  const bool range_mode;
+  const int nb;                 // key of a later round = (group head << nb) | (1 + rank of the continuation)
+  bool lazy_active = false, late_rank = false;      // (see start_rounds)
+  I *rank_p = nullptr, *wordrank_p = nullptr;
+
+  // ---- the loop's variables
+  Round kind;                   // the sort that was just run
+  uint64_t m, h, m2 = 0, ngrp = 0;      // list length and sorted prefix of that sort; what its regrouping left unresolved, in how many groups
+  uint32_t piv_cap = kSwitch.pivot_cap;      // bytes compared per member in the next pivot round
+  bool pivot_ok = true;         // dictionary pivot rounds still halve the unresolved set
+  bool ipiv_ok = true;          // parse: the pivot round (farthest rare symbol) has not given up yet
+  bool small_failed = false;    // a direct-placement attempt met a group longer than its window
+  bool finisher_ok = true;      // the comparison finisher has not refused yet
+  // freshness of rank[]
+  bool rank_alloc = false;
+  bool lazy_pending = false;    // dictionary mode: rank[] of the suffixes settled by the first round not scattered (yet)
+  bool ranks_stale = false;     // pivot rounds skipped rank[] of settled suffixes that are not whole words
+  bool active_stale = false;    // ... and the first round / pivot rounds skipped rank[] of the suffixes that stay unresolved
+
+  // ---- buffers of the first round only
+  DBuf<uint64_t> &key;          // (the caller's; with keyo/valo the ping-pong pairs of every device-wide sort)
+  DBuf<I> &val;
+  DBuf<I> tile_last, tile_scan;      // dictionary mode: last head per 256 slots, and its running maximum
+  // ---- every round
+  DBuf<uint64_t> keyo;
+  DBuf<I> valo;
+  DBuf<uint8_t> hd, keep;
+  // active list (slot, suffix, group) of the unresolved suffixes and per-round scratch, list_cap elements each;
   // dictionary mode allocates them when the first round has told how many suffixes stay unresolved
   DBuf<I> aslot, aslot2, hv, newhead, act_i, act_grp;
   uint64_t list_cap = 0;
-  auto alloc_lists = [&](uint64_t cap) {
+  DBuf<uint32_t> tile_keep, tile_heads;
+  DBuf<I> tile_off, tile_hoff;
+  // ---- dictionary mode, after the first round / on the first pivot round
+  DBuf<uint8_t> keep0, veto;
+  DBuf<uint32_t> wstart_bits;   // which positions start a word (their ranks order the dictionary)
+  // ---- allocated on first use by the rounds ordered inside their groups
+  DBuf<uint8_t> gs, bigf;
+  DBuf<uint32_t> k32, k32o, segb, sege, nseg_d, ovf_d;
+  DBuf<uint64_t> nsel_d;
+  // ---- allocated on the first doubling round
+  DBuf<K> dkey, dkeyo;          // wide build: 128-bit doubling keys (the 32-bit build keeps them in key/keyo)
+
+  Rounds(pfp_ctx *c_, const SufGeom &g_, DBuf<uint64_t> &key_, DBuf<I> &val_, uint64_t h0, SuffixOrderT<I> &out_, const DoublingOpts &o_)
+      : c(c_), g(g_), out(out_), o(o_), NP(g_.N), N(o_.list_len.value_or(g_.N)), lazy(o_.dict), range_mode(o_.list_len.has_value()),
+        nb(bits_for(N)), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_), val(val_) {}
+
+  static uint64_t blocks(uint64_t n) { return cdiv(n, TB); }
+
+  // ---- first round: one device-wide sort of all N (key, position) pairs, ping-ponging between the two buffer
+  //      pairs (no third copy inside the library); afterwards keyo/valo hold the sorted pairs
+  void first_round_sort() {
+    keyo.alloc(c, N); valo.alloc(c, N);
+    SortTag first_tag(g.mode == MODE_DICT ? "dictionary, first round" : "parse, first round");
+    if (o.idx_bits) {
+      // keys-only first round: the words are (key << idx_bits | position), 16 bytes per element and pass instead of 24;
+      // the sort is stable on the key bits alone, so ties stay in position order; one streaming pass splits the result
+      if (kSwitch.lib_sort) sort_keys_db(c, key, keyo, N, o.idx_bits, o.idx_bits + o.key_bits);
+      else msd_sort_keys_db(c, key, keyo, N, o.idx_bits, o.idx_bits + o.key_bits);
+      KScope ks(c, "pfp::split_keys_kernel", N * (16 + sizeof(I)));
+      hipLaunchKernelGGL(split_keys_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, key.p, N, o.idx_bits, keyo.p, valo.p);
+    } else {
+      if (kSwitch.lib_sort) sort_pairs_db(c, key, keyo, val, valo, N, 0, o.key_bits);
+      else msd_sort_pairs_db<I>(c, key, keyo, val, valo, N, 0, o.key_bits);
+      std::swap(key, keyo); std::swap(val, valo);
+    }
+  }
+
+  void alloc_lists(uint64_t cap) {
     aslot.alloc(c, cap); aslot2.alloc(c, cap); hv.alloc(c, cap); newhead.alloc(c, cap); act_i.alloc(c, cap); act_grp.alloc(c, cap);
     list_cap = cap;
-  };
-  // a share of the suffix array (multi-GPU) never runs a doubling round - it stops where one would be needed - and finds
-  // its whole words by looking at its own slots (gather_slots_range): no rank per dictionary position is kept
-  const bool no_rank = range_mode;
-  if (!lazy) {
-    out.sa.alloc(c, N);
-    alloc_lists(N);
-    hipLaunchKernelGGL(iota_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, aslot.p, N);
   }
-  uint64_t m = N, h = h0;
-  bool first = true;
-  if (lazy) {
-    const int tb = std::min(key0_bits, std::max(8, std::min(24, bits_for(N) - 5)));
-    out.shift = key0_bits - tb;
-    out.T = 1u << tb;
-    out.tab.alloc(c, out.T);
-    hipLaunchKernelGGL(fill_kernel<I>, gdim(cdiv(out.T, TB)), gdim(TB), 0, c->stream, out.tab.p, (uint64_t)out.T,
-                       (I)(IdxTraits<I>::kNone - (I)N));
-  }
-  const int nb = bits_for(N);           // key of a later round = (group head << nb) | (1 + rank of the continuation)
-  const int keybits = 2 * nb;
-  static const bool no_finflag = getenv("PFP_NO_FINFLAG") != nullptr;      // tests: force the length-gather path
-  // (the flag rides in the top bit of a POSITION: it needs positions below 2^31 in the 32-bit build - all NP of them, also when
-  //  only a share of N < 2^31 suffixes is sorted here)
-  out.finbit = (g.mode == MODE_DICT && (kWide || NP < (1ull << 31)) && !no_finflag) ? IdxTraits<I>::kTop : (I)0;
-  constexpr bool use_segsort = true;
-  DBuf<uint8_t> gs;
-  DBuf<uint32_t> k32, k32o, segb, sege, nseg_d;
-  DBuf<uint64_t> nsel_d;
-  DBuf<K> dkey, dkeyo;          // wide build: 128-bit doubling keys (the 32-bit build keeps them in key/keyo)
-  bool seg_round = false;       // the keys of this round live in k32o (segmented path) instead of keyo
-  bool pivot_round = false;     // the keys of this round are pivot order keys (build_keys_pivot_kernel)
-  bool dbl_round = false;       // the keys of this round are doubling keys (type K)
-  bool pivot_ok = true;
-  bool ipiv_round = false, ipiv_ok = true;      // parse: pivot rounds with the farthest-rare-symbol pivot (keys in keyo, sorted inside the groups)
-  bool lazy_pending = false;    // dictionary mode: rank[] of the suffixes settled by the first round not scattered (yet)
-  DBuf<uint8_t> veto, keep0;
-  constexpr bool lazy_pivot_ranks = true;
-  bool ranks_stale = false;     // pivot rounds skipped rank[] of settled suffixes that are not whole words
-  bool active_stale = false;    // ... and the first round / pivot rounds skipped rank[] of the suffixes that stay unresolved
-  DBuf<uint32_t> wstart_bits;   // pivot rounds: which positions start a word (their ranks order the dictionary)
-  // lazy ranks are possible when pivot rounds (which never read rank[]) can follow the first round
-  const bool lazy_active = lazy && lazy_pivot_ranks && out.finbit && g.mode == MODE_DICT && kPivotCap >= 16 && (uint64_t)nb + kPivBits <= 64;
-  // rank[] (one entry per dictionary position: 4 / 8 bytes each, 38 GB for a 4.8 GB dictionary in the wide build) exists
-  // from the start only where a round may read it.  With lazy ranks nothing reads it before the first doubling round - and a
-  // dictionary of word families never gets there - so it is allocated when (if) that round comes (late_rank); until then the
-  // whole words, whose ranks order the dictionary, report to wordrank[d].  (PFP_DEBUG validates every rank: eager.)
-  const bool late_rank = !no_rank && lazy_active && !c->debug;
-  bool rank_alloc = false;
-  I *rank_p = nullptr;
-  auto alloc_rank = [&]() {
+  void alloc_rank() {
     out.rank.alloc(c, NP);
     if (lazy) PFP_HIP(hipMemsetAsync(out.rank.p, 0xff, NP * sizeof(I), c->stream));
     rank_p = out.rank.p; rank_alloc = true;
-  };
-  if (!no_rank && !late_rank) alloc_rank();
-  if (late_rank) {
-    out.wordrank.alloc(c, (uint64_t)g.wv.d + 1);
-    PFP_HIP(hipMemsetAsync(out.wordrank.p, 0xff, ((uint64_t)g.wv.d + 1) * sizeof(I), c->stream));
   }
-  I *const wordrank_p = late_rank ? out.wordrank.p : (I *)nullptr;
-  auto repair_ranks = [&](uint64_t m_active, const I *aslot_list) {
-    if (!ranks_stale) return;
-    DBuf<uint8_t> act(c, N);
-    act.zero();
-    if (m_active) hipLaunchKernelGGL(mark_slots_kernel<I>, gdim(cdiv(m_active, TB)), gdim(TB), 0, c->stream, m_active, aslot_list, act.p);
-    KScope ks(c, "pfp::repair_ranks_kernel", N * 6);
-    hipLaunchKernelGGL(repair_ranks_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, N, keep0.p, act.p, out.sa.p, out.grp.p,
-                       out.finbit, out.rank.p);
-    ranks_stale = false;
-  };
-  DBuf<uint32_t> ovf_d;
-  auto seg_bufs = [&]() {
-    if (!gs.p) { gs.alloc(c, list_cap + 1); k32.alloc(c, list_cap); k32o.alloc(c, list_cap); nseg_d.alloc(c, 2); nsel_d.alloc(c, 1); ovf_d.alloc(c, 1); }
-  };
-  // k32/val -> k32o/valo, every group of the (grouped) active list sorted by its 32-bit key; false: some group has
-  // more than kSmallSeg members (nothing usable was written)
-  // 32-bit index build: the groups of more than kSmallSeg members are passed through in place, flagged, and finished
-  // by ONE library sort of just their elements (a few long families no longer send the whole round to the library)
-  constexpr bool big_side = true;
-  DBuf<uint8_t> bigf;
-  auto seg_small_sort = [&](uint64_t mm) -> bool {
-    ovf_d.zero();
-    const bool side = big_side && !kWide;
-    if (side && (!bigf.p || bigf.n < mm + 16)) bigf.alloc(c, list_cap + 16);
-    { KScope ks(c, "pfp::seg_small_sort_kernel", mm * (8 + 3 * sizeof(I) + 1));
-      hipLaunchKernelGGL((seg_small_sort_kernel<I, uint32_t>), gdim(cdiv(mm, TB)), gdim(TB), 0, c->stream, mm, act_grp.p, k32.p, val.p, gs.p, k32o.p,
-                         valo.p, ovf_d.p, side ? bigf.p : (uint8_t *)nullptr); }
-    if (read_scalar(c, ovf_d.p) == 0) return true;
-    if (!side) return false;
-    PFP_HIP(hipMemsetAsync(bigf.p + mm, 0, 16, c->stream));      // (the flag reader looks at 16 bytes at a time)
-    const uint64_t nbig = count_flags(c, bigf.p, mm);
-    if (nbig * 2 > mm) return false;                // mostly long groups: the round is the library's after all
-    DBuf<I> idx(c, nbig + 1), sv(c, nbig), sva(c, nbig);
-    DBuf<uint64_t> sk(c, nbig), ska(c, nbig), cnt(c, 1);
-    select_index<I>(c, bigf.p, idx.p, cnt.p, mm);
-    hipLaunchKernelGGL(big_seg_gather_kernel<I>, gdim(cdiv(nbig, TB)), gdim(TB), 0, c->stream, nbig, idx.p, act_grp.p, k32o.p, valo.p, sk.p, sv.p);
-    sort_pairs_db(c, sk, ska, sv, sva, nbig, 0, 32 + nb);
-    hipLaunchKernelGGL(big_seg_scatter_kernel<I>, gdim(cdiv(nbig, TB)), gdim(TB), 0, c->stream, nbig, idx.p, sk.p, sv.p, k32o.p, valo.p);
-    PFP_HIP(hipGetLastError());
-    return true;
-  };
-  // (n_groups: the compaction that built the list counted its group heads - no read-back of the selection's count)
-  auto seg_setup = [&](uint64_t mm, uint64_t n_groups, uint32_t &ng, uint32_t &maxlen) {      // segments = groups of the (grouped) active list
-    seg_bufs();
-    if (!segb.p) { segb.alloc(c, list_cap + 1); sege.alloc(c, list_cap + 1); }
-    hipLaunchKernelGGL(group_starts_kernel<I>, gdim(cdiv(mm, TB)), gdim(TB), 0, c->stream, mm, act_grp.p, gs.p);
-    select_index<uint32_t>(c, gs.p, segb.p, nsel_d.p, mm);
-    PFP_HIP(hipMemsetAsync(nseg_d.p + 1, 0, 4, c->stream));
-    ng = (uint32_t)n_groups;
-    if (c->debug) PFP_REQUIRE(read_scalar(c, nsel_d.p) == n_groups, PFP_EHIP, "group count of the active list differs from the compaction's");
-    hipLaunchKernelGGL(seg_end_kernel, gdim(cdiv(ng, TB)), gdim(TB), 0, c->stream, ng, (uint32_t)mm, segb.p, sege.p, nseg_d.p + 1);
-    maxlen = read_scalar(c, nseg_d.p + 1);
-  };
-  DBuf<uint32_t> tile_keep, tile_heads;
-  DBuf<I> tile_off, tile_hoff;
-  uint32_t piv_cap = kPivotCap;  // bytes compared per member in the next pivot round
-  bool small_failed = false;     // a direct-placement attempt met a group longer than its window
-  bool finisher_ok = true;       // the comparison finisher has not refused yet
-  for (;;) {
-    DBuf<I> tile_last, tile_scan;      // first round of dictionary mode: last head per 256 slots, and its running maximum
-    if (first && lazy) {
-      tile_last.alloc(c, cdiv64(m, 256)); tile_scan.alloc(c, cdiv64(m, 256));
-      { KScope ks(c, "pfp::heads0_kernel", m * 13);
-        hipLaunchKernelGGL(heads0_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, keyo.p, out.keymask, out.shift, out.T,
-                           hd.p, tile_last.p, out.tab.p); }
-      inclusive_max<I>(c, out.tab.p, out.tab.p, out.T);
-      inclusive_max<I>(c, tile_last.p, tile_scan.p, cdiv64(m, 256));
-    } else if (ipiv_round) {
-      KScope ks(c, "pfp::heads64seg_kernel", m * 18);
-      hipLaunchKernelGGL(heads64seg_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, gs.p, keyo.p, aslot.p, hd.p, hv.p);
-    } else if (seg_round) {
-      KScope ks(c, "pfp::heads32_kernel", m * 14);
-      hipLaunchKernelGGL(heads32_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, gs.p, k32o.p, aslot.p, hd.p, hv.p);
-    } else if (dbl_round && kWide) {
-      KScope ks(c, "pfp::heads_kernel", m * 25);
-      hipLaunchKernelGGL((heads_kernel<I, K>), gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, dkeyo.p, aslot.p, hd.p, hv.p);
+
+  // what every later round works on, allocated once the first sort is done
+  void start_rounds() {
+    if (lazy) { key.release(); val.release(); }      // dictionary mode: later rounds sort the (much smaller) unresolved set
+    // (allocated only now: while the first sort holds its four buffers - 32 bytes per suffix in the wide build - nothing else
+    //  of that size is live: a 4.8 GB dictionary peaked at 206 GB with the group array next to them, 168 GB without)
+    hd.alloc(c, N + 1); keep.alloc(c, N);
+    out.grp.alloc(c, N + 8);
+    if (!lazy) {
+      out.sa.alloc(c, N);
+      alloc_lists(N);
+      hipLaunchKernelGGL(iota_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, aslot.p, N);
     } else {
-      KScope ks(c, "pfp::heads_kernel", m * 17);
-      hipLaunchKernelGGL((heads_kernel<I, uint64_t>), gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, keyo.p, aslot.p, hd.p, hv.p);
+      const int tb = std::min(o.key_bits, std::max(8, std::min(24, bits_for(N) - 5)));
+      out.shift = o.key_bits - tb;
+      out.T = 1u << tb;
+      out.tab.alloc(c, out.T);
+      hipLaunchKernelGGL(fill_kernel<I>, gdim(blocks(out.T)), gdim(TB), 0, c->stream, out.tab.p, (uint64_t)out.T,
+                         (I)(IdxTraits<I>::kNone - (I)N));
     }
-    const bool round0 = first && lazy;
-    first = false;
-    if (!round0) inclusive_max<I>(c, hv.p, newhead.p, m);
-    if (round0) {
-      { KScope ks(c, "pfp::write_back0_kernel", m * (4 + 4 + 1 + 8 + 4 + 1));
-        hipLaunchKernelGGL(write_back0_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, valo.p, tile_scan.p, hd.p, keyo.p,
-                           rank_p, out.grp.p, keep.p, (lazy_active || no_rank) ? 0 : 1); }
-      if (lazy_active) active_stale = true;
-      // the sorted keys and the sorted positions stay with the result; later rounds sort the (smaller) active set elsewhere
-      out.skeys = std::move(keyo);
-      out.sa = std::move(valo);
-    } else {
-      if (pivot_round) {
-        if (!veto.p) veto.alloc(c, N);
-        // only the entries of this round's groups are looked at: clear those (m bytes at most), not all N
-        hipLaunchKernelGGL(veto_clear_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, newhead.p, veto.p);
-        hipLaunchKernelGGL(pivot_veto_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, keyo.p,
-                           seg_round ? k32o.p : (const uint32_t *)nullptr, valo.p, newhead.p, out.finbit, veto.p);
-      }
-      // previous group head of the element now at a: the high part of its sort key, or (segmented
-      // rounds keep every element inside its segment) the group of list position a.  The first round
-      // of plain mode has neither: everything is written.
-      const bool have_prev = out.rounds > 0;
-      KScope ks(c, "pfp::write_back_kernel", m * (13 + 4 + 13));
-      const uint8_t *vetop = pivot_round ? veto.p : (const uint8_t *)nullptr;
-      if (pivot_round && lazy_pivot_ranks && !wstart_bits.p) {
-        wstart_bits.alloc(c, cdiv64(NP, 32));
-        hipLaunchKernelGGL(word_start_bits_kernel, gdim(cdiv(cdiv64(NP, 32), TB)), gdim(TB), 0, c->stream, out.bytes, NP, wstart_bits.p);
-      }
-      const uint32_t *lazyb = (pivot_round && lazy_pivot_ranks) ? wstart_bits.p : (const uint32_t *)nullptr;
-      const I *prevgrp = (have_prev && seg_round) ? act_grp.p : (const I *)nullptr;
-      if (dbl_round && kWide && !seg_round)
-        hipLaunchKernelGGL((write_back_kernel<I, K>), gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, aslot.p, valo.p, newhead.p, hd.p,
-                           out.finbit, have_prev ? dkeyo.p : (const K *)nullptr, nb, prevgrp, vetop, lazyb, out.sa.p, rank_p,
-                           wordrank_p, out.grp.p, keep.p);
-      else
-        hipLaunchKernelGGL((write_back_kernel<I, uint64_t>), gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, aslot.p, valo.p, newhead.p,
-                           hd.p, out.finbit, (have_prev && !seg_round) ? keyo.p : (const uint64_t *)nullptr, pivot_round ? kPivBits : nb,
-                           prevgrp, vetop, lazyb, out.sa.p, rank_p, wordrank_p, out.grp.p, keep.p);
-      if (pivot_round && lazy_pivot_ranks) { ranks_stale = true; active_stale = true; }
+    // (the flag rides in the top bit of a POSITION: it needs positions below 2^31 in the 32-bit build - all NP of them, also when
+    //  only a share of N < 2^31 suffixes is sorted here)
+    out.finbit = (g.mode == MODE_DICT && (kWide || NP < (1ull << 31)) && kSwitch.finflag) ? IdxTraits<I>::kTop : (I)0;
+    // lazy ranks are possible when pivot rounds (which never read rank[]) can follow the first round
+    lazy_active = lazy && pivot_rounds_possible();
+    // rank[] (one entry per dictionary position: 4 / 8 bytes each, 38 GB for a 4.8 GB dictionary in the wide build) exists
+    // from the start only where a round may read it.  With lazy ranks nothing reads it before the first doubling round - and a
+    // dictionary of word families never gets there - so it is allocated when (if) that round comes (late_rank); until then the
+    // whole words, whose ranks order the dictionary, report to wordrank[d].  (PFP_DEBUG validates every rank: eager.)
+    late_rank = !range_mode && lazy_active && !c->debug;
+    if (!range_mode && !late_rank) alloc_rank();
+    if (late_rank) {
+      out.wordrank.alloc(c, (uint64_t)g.wv.d + 1);
+      PFP_HIP(hipMemsetAsync(out.wordrank.p, 0xff, ((uint64_t)g.wv.d + 1) * sizeof(I), c->stream));
+      wordrank_p = out.wordrank.p;
     }
-    uint64_t m2 = 0, ngrp = 0;
+  }
+  bool pivot_rounds_possible() const {
+    return g.mode == MODE_DICT && out.finbit && kSwitch.pivot_cap >= 16 && (uint64_t)nb + kPivBits <= 64;
+  }
+
+  // ---- regrouping: heads of the new groups -> slots, group ids, ranks -> compaction of what stays unresolved
+  template <class KT>
+  void heads(const KT *keys, int bytes) {
+    KScope ks(c, "pfp::heads_kernel", m * bytes);
+    hipLaunchKernelGGL((heads_kernel<I, KT>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, keys, aslot.p, hd.p, hv.p);
+  }
+  void heads_k32() {
+    KScope ks(c, "pfp::heads32_kernel", m * 14);
+    hipLaunchKernelGGL(heads32_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, gs.p, k32o.p, aslot.p, hd.p, hv.p);
+  }
+
+  void first_dict_heads_and_write_back() {
+    tile_last.alloc(c, cdiv64(m, 256)); tile_scan.alloc(c, cdiv64(m, 256));
+    { KScope ks(c, "pfp::heads0_kernel", m * 13);
+      hipLaunchKernelGGL(heads0_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, keyo.p, out.keymask, out.shift, out.T,
+                         hd.p, tile_last.p, out.tab.p); }
+    inclusive_max<I>(c, out.tab.p, out.tab.p, out.T);
+    inclusive_max<I>(c, tile_last.p, tile_scan.p, cdiv64(m, 256));
+    { KScope ks(c, "pfp::write_back0_kernel", m * (4 + 4 + 1 + 8 + 4 + 1));
+      hipLaunchKernelGGL(write_back0_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, valo.p, tile_scan.p, hd.p, keyo.p,
+                         rank_p, out.grp.p, keep.p, (lazy_active || range_mode) ? 0 : 1); }
+    if (lazy_active) active_stale = true;
+    // the sorted keys and the sorted positions stay with the result; later rounds sort the (smaller) active set elsewhere
+    out.skeys = std::move(keyo);
+    out.sa = std::move(valo);
+  }
+
+  // The one place that knows, per kind of round, which heads kernel reads which keys and what the write-back is told of the
+  // element now at list position a: its previous group head - the high part of its device-wide sort key, or (a round ordered
+  // inside its groups keeps every element in its segment) the group of list position a; the first round of plain mode has
+  // neither: everything is written - and, after a pivot round, the vetoes and the word starts.
+  void heads_and_write_back() {
+    const uint64_t *keys = nullptr;      // (group head << keybits | ...) of a device-wide sort
+    const K *dkeys = nullptr;            // ... of the wide build's doubling round
+    const I *prevgrp = nullptr;
+    const uint32_t *pivk32 = nullptr;
+    bool pivot = false;
+    switch (kind) {
+      case Round::FirstDict: return first_dict_heads_and_write_back();
+      case Round::FirstPlain: heads(keyo.p, 17); break;
+      case Round::DictPivotGlobal: heads(keyo.p, 17); keys = keyo.p; pivot = true; break;
+      case Round::DictPivotGrouped: heads_k32(); prevgrp = act_grp.p; pivk32 = k32o.p; pivot = true; break;
+      case Round::ParsePivot: {
+        KScope ks(c, "pfp::heads64seg_kernel", m * 18);
+        hipLaunchKernelGGL(heads64seg_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, gs.p, keyo.p, aslot.p, hd.p, hv.p);
+        prevgrp = act_grp.p;
+      } break;
+      case Round::DoublingGlobal:
+        if constexpr (kWide) { heads(dkeyo.p, 25); dkeys = dkeyo.p; }
+        else { heads(keyo.p, 17); keys = keyo.p; }
+        break;
+      case Round::DoublingGrouped: heads_k32(); prevgrp = act_grp.p; break;
+    }
+    inclusive_max<I>(c, hv.p, newhead.p, m);
+    if (pivot) {
+      if (!veto.p) veto.alloc(c, N);
+      // only the entries of this round's groups are looked at: clear those (m bytes at most), not all N
+      hipLaunchKernelGGL(veto_clear_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, newhead.p, veto.p);
+      hipLaunchKernelGGL(pivot_veto_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, keyo.p, pivk32, valo.p, newhead.p, out.finbit, veto.p);
+    }
+    KScope ks(c, "pfp::write_back_kernel", m * (13 + 4 + 13));
+    if (pivot && !wstart_bits.p) {
+      wstart_bits.alloc(c, cdiv64(NP, 32));
+      hipLaunchKernelGGL(word_start_bits_kernel, gdim(blocks(cdiv64(NP, 32))), gdim(TB), 0, c->stream, out.bytes, NP, wstart_bits.p);
+    }
+    const uint8_t *vetop = pivot ? veto.p : (const uint8_t *)nullptr;
+    const uint32_t *lazyb = pivot ? wstart_bits.p : (const uint32_t *)nullptr;
+    if (dkeys)
+      hipLaunchKernelGGL((write_back_kernel<I, K>), gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, h, aslot.p, valo.p, newhead.p, hd.p,
+                         out.finbit, dkeys, nb, prevgrp, vetop, lazyb, out.sa.p, rank_p, wordrank_p, out.grp.p, keep.p);
+    else
+      hipLaunchKernelGGL((write_back_kernel<I, uint64_t>), gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, h, aslot.p, valo.p, newhead.p,
+                         hd.p, out.finbit, keys, pivot ? kPivBits : nb, prevgrp, vetop, lazyb, out.sa.p, rank_p, wordrank_p, out.grp.p, keep.p);
+    if (pivot) { ranks_stale = true; active_stale = true; }
+  }
+
+  // kept suffixes / kept group heads per tile -> offsets -> placement into the next active list; sets m2 and ngrp
+  void compact() {
+    const bool round0 = kind == Round::FirstDict;
+    const uint64_t ntile = cdiv64(m, kTile);
+    if (!tile_keep.p) { tile_keep.alloc(c, cdiv64(N, kTile) + 1); tile_heads.alloc(c, cdiv64(N, kTile) + 1);
+                        tile_off.alloc(c, cdiv64(N, kTile) + 1); tile_hoff.alloc(c, cdiv64(N, kTile) + 1); }
+    auto read_counts = [&]() {
+      sync(c);
+      I t0, t1;
+      memcpy(&t0, c->h_scalars, sizeof(I)); memcpy(&t1, c->h_scalars + 1, sizeof(I));
+      m2 = t0; ngrp = t1;
+    };
     {
-      // kept suffixes / kept group heads per tile -> offsets -> placement
-      const uint64_t ntile = cdiv64(m, kTile);
-      if (!tile_keep.p) { tile_keep.alloc(c, cdiv64(N, kTile) + 1); tile_heads.alloc(c, cdiv64(N, kTile) + 1);
-                          tile_off.alloc(c, cdiv64(N, kTile) + 1); tile_hoff.alloc(c, cdiv64(N, kTile) + 1); }
       PFP_HIP(hipMemsetAsync(tile_keep.p + ntile, 0, 4, c->stream));
       PFP_HIP(hipMemsetAsync(tile_heads.p + ntile, 0, 4, c->stream));
       KScope ks(c, "pfp::active_place_kernel", m * 2 + 0);      // (+ active_count_kernel and the two tile scans)
@@ -1234,10 +1256,7 @@ static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, u
       PFP_HIP(hipMemcpyAsync(c->h_scalars, tile_off.p + ntile, sizeof(I), hipMemcpyDeviceToHost, c->stream));
       PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, tile_hoff.p + ntile, sizeof(I), hipMemcpyDeviceToHost, c->stream));
       if (round0) {      // the lists are sized by what the first round left unresolved
-        sync(c);
-        I t0, t1;
-        memcpy(&t0, c->h_scalars, sizeof(I)); memcpy(&t1, c->h_scalars + 1, sizeof(I));
-        m2 = t0; ngrp = t1;
+        read_counts();
         if (m2) alloc_lists(m2);
       }
       if (!round0 || m2)
@@ -1246,13 +1265,14 @@ static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, u
                            aslot2.p, act_i.p, act_grp.p);
       PFP_HIP(hipGetLastError());
     }
-    if (!round0) {
-      sync(c);
-      I t0, t1;
-      memcpy(&t0, c->h_scalars, sizeof(I)); memcpy(&t1, c->h_scalars + 1, sizeof(I));
-      m2 = t0; ngrp = t1;
-    }
-    if (round0 && m2) {
+    if (!round0) read_counts();
+  }
+
+  // regroup what the last round sorted
+  void regroup() {
+    heads_and_write_back();
+    compact();
+    if (kind == Round::FirstDict && m2) {
       // whether the settled ranks get scattered after all is decided when (if) a doubling round
       // first needs them: pivot rounds read the strings, not rank[]
       lazy_pending = true;
@@ -1265,133 +1285,195 @@ static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, u
         PFP_HIP(hipMemsetAsync(out.refined.p + N, 0, 16, c->stream));
       }
     }
-
-    static const bool trace_rounds = getenv("PFP_TRACE_ROUNDS") != nullptr;
-    if (trace_rounds)
+    if (kSwitch.trace_rounds) {
+      const bool grouped = kind == Round::DictPivotGrouped || kind == Round::ParsePivot || kind == Round::DoublingGrouped;
       fprintf(stderr, "[pfp] doubling N=%llu round=%llu h=%llu m=%llu -> %llu unresolved in %llu groups%s\n", (unsigned long long)N,
               (unsigned long long)out.rounds, (unsigned long long)h, (unsigned long long)m, (unsigned long long)m2,
-              (unsigned long long)ngrp, seg_round ? " (seg)" : (pivot_round ? " (pivot)" : ""));
-    // a pivot round that did not at least halve the unresolved set: what is left are members equal to
-    // their pivot for the whole comparison window.  The window then grows fourfold (512 -> 2 K -> 8 K bytes) as long
-    // as the bytes such a round may read - every member the full window - stay below 256 per dictionary byte; the
-    // variants of long phrases settle there (-p 200: 3.3 M suffixes went through nine doubling rounds instead).
-    // After the widest window the rest is doubling's business.
-    if (ipiv_round && m2 * 4 > m) ipiv_ok = false;      // a parse pivot round that left more than a quarter: doubling from here
-    if (pivot_round && m2 * 2 > m) {
+              (unsigned long long)ngrp, grouped ? " (seg)" : (kind == Round::DictPivotGlobal ? " (pivot)" : ""));
+    }
+  }
+
+  // a pivot round that did not at least halve the unresolved set: what is left are members equal to
+  // their pivot for the whole comparison window.  The window then grows fourfold (512 -> 2 K -> 8 K bytes) as long
+  // as the bytes such a round may read - every member the full window - stay below 256 per dictionary byte; the
+  // variants of long phrases settle there (-p 200: 3.3 M suffixes went through nine doubling rounds instead).
+  // After the widest window the rest is doubling's business.
+  void judge_pivot_round() {
+    if (kind == Round::ParsePivot && m2 * 4 > m) ipiv_ok = false;      // a parse pivot round that left more than a quarter: doubling from here
+    if ((kind == Round::DictPivotGlobal || kind == Round::DictPivotGrouped) && m2 * 2 > m) {
       const uint32_t next_cap = std::min<uint32_t>(piv_cap * 4, kPivCapMax - 16);
       if (piv_cap < kPivCapMax - 16 && piv_cap >= 16 && m2 * (uint64_t)next_cap < N * 128) piv_cap = next_cap;
       else pivot_ok = false;
     }
+  }
+
+  // the unresolved suffixes become the list of the next sort
+  void next_list() {
     std::swap(aslot, aslot2);
     m = m2;
-    if (m == 0) break;
+    if (m == 0) return;
     PFP_REQUIRE(h < 2 * NP, PFP_EHIP, "suffix sort failed to converge");
     if (!keyo.p || keyo.n < m) keyo.alloc(c, m);
     if (!key.p || key.n < m) key.alloc(c, m);
     if (!valo.p || valo.n < m) valo.alloc(c, m);
     if (!val.p || val.n < m) val.alloc(c, m);
-    static const bool use_finisher = getenv("PFP_NO_FINISHER") == nullptr;
-    if (use_finisher && finisher_ok && m <= kFinishMax && out.rounds >= 1 && (g.mode == MODE_DICT || (g.mode == MODE_PLAIN && g.sym))) {
-      DBuf<uint32_t> flt(c, m), feq(c, m), fgs(c, m), fov(c, 1);
-      fov.zero();
-      KScope ks(c, "pfp::finish_rank_kernel", m * (sizeof(I) * 4 + 12));
-      hipLaunchKernelGGL(finish_rank_kernel<I>, gdim(cdiv(m * 8, TB)), gdim(TB), 0, c->stream, g, out.bytes, m, act_i.p, act_grp.p, flt.p, feq.p,
-                         fgs.p, fov.p);
-      if (read_scalar(c, fov.p) == 0) {
-        { KScope kw(c, "pfp::finish_write_kernel", m * (sizeof(I) * 5 + 12));
-          hipLaunchKernelGGL(finish_write_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, aslot.p, act_i.p, flt.p, feq.p, fgs.p,
-                             out.finbit, out.sa.p, out.grp.p, rank_p, wordrank_p); }
-        PFP_HIP(hipGetLastError());
-        if (trace_rounds) fprintf(stderr, "[pfp] doubling N=%llu round=%llu: the last %llu suffixes ranked by comparison\n",
-                                  (unsigned long long)N, (unsigned long long)out.rounds, (unsigned long long)m);
-        out.rounds++;
-        m = 0;
-        break;
-      }
+  }
+
+  // the comparison finisher (see finish_rank_kernel); false: not tried, or it refused and nothing was written
+  bool try_finisher() {
+    if (!(kSwitch.finisher && finisher_ok && m <= kFinishMax && out.rounds >= 1 && (g.mode == MODE_DICT || (g.mode == MODE_PLAIN && g.sym))))
+      return false;
+    DBuf<uint32_t> flt(c, m), feq(c, m), fgs(c, m), fov(c, 1);
+    fov.zero();
+    KScope ks(c, "pfp::finish_rank_kernel", m * (sizeof(I) * 4 + 12));
+    hipLaunchKernelGGL(finish_rank_kernel<I>, gdim(blocks(m * 8)), gdim(TB), 0, c->stream, g, out.bytes, m, act_i.p, act_grp.p, flt.p, feq.p,
+                       fgs.p, fov.p);
+    if (read_scalar(c, fov.p) != 0) {
       finisher_ok = false;      // a long group or a long common prefix: the rounds go on as they would have
+      return false;
     }
-    // Rounds after the first: the unresolved suffixes are already grouped, only the 32-bit "next"
-    // key has to be ordered inside every group.  When the groups are many and of moderate size (a
-    // dictionary of near-identical variants) a segmented sort moves 16 B per suffix instead of the
-    // 7 x 24 B of a global 53-bit radix sort (big: 240 -> 126 ms of sorting).  rocPRIM's segmented
-    // sort serialises a giant segment on one workgroup (the 300 k run of one symbol in a parse cost
-    // 68 ms), and for tiny groups its bookkeeping eats the gain, so the choice is per round.
-    seg_round = false; dbl_round = false; ipiv_round = false;
-    pivot_round = pivot_ok && g.mode == MODE_DICT && out.finbit && kPivotCap >= 16 && ngrp && m / ngrp <= kPivotAvg &&
-                  (uint64_t)nb + kPivBits <= 64;
-    if (pivot_round) {
-      // few suffixes left: the widest window at once.  (A compare reads only as far as the strings agree; the window bounds
-      // the worst case, m x window bytes.  What is left after two rounds are mostly members of phrases longer than the
-      // 512-byte window: without this they cost one round that settles nothing and quadruples the window, then another.)
-      if (piv_cap >= 16 && piv_cap < kPivCapMax - 16 && out.rounds >= 2 && m * (uint64_t)(kPivCapMax - 16) < N * 128) piv_cap = kPivCapMax - 16;
-      // large families (a collection of hundreds of copies): the members are already grouped, a
-      // segmented sort of the 23-bit order key moves 16 B per suffix instead of 7 x 24 B
-      bool seg = false, small = false;
-      uint32_t ng = 0;
-      constexpr uint32_t seg_min_avg = 24u;
-      static const bool use_small = getenv("PFP_NO_SMALLSEG") == nullptr;
-      // families of a handful of members: placed directly (after a group proved too long, only once the average is tiny)
-      // (32-bit build: long families go to the side sort, so the average may be larger)
-      small = use_segsort && use_small && m / ngrp <= (kWide ? kSmallSeg / 4 : kSmallSeg / 2) && (!small_failed || m / ngrp <= 3);
-      auto try_seg = [&]() {
-        if (use_segsort && m >= (1u << 20) && m < 0xFFFFFFFFull && m / ngrp >= seg_min_avg) {
-          uint32_t maxlen = 0;
-          seg_setup(m, ngrp, ng, maxlen);
-          seg = maxlen <= (1u << 15) && m / ng >= seg_min_avg;
-        }
-      };
-      if (!small) try_seg();
-      if (small) seg_bufs();
-      // both key forms are written when the direct placement is tried: should a group prove too long, the
-      // device-wide sort takes over with the 64-bit keys
-      { KScope ks(c, "pfp::build_keys_pivot_kernel", m * (4 + 4 + 4 + 12 + 64));
-        hipLaunchKernelGGL(build_keys_pivot_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, out.bytes, m, h, piv_cap, act_i.p,
-                           act_grp.p, out.sa.p, out.finbit, key.p, (seg || small) ? k32.p : (uint32_t *)nullptr, val.p, small ? 1 : 0); }
-      if (small && seg_small_sort(m)) seg_round = true;
-      else if (small && (small_failed = true, try_seg(), false)) {}
-      else if (seg) { segsort_pairs_u32<I>(c, k32.p, k32o.p, val.p, valo.p, m, ng, segb.p, sege.p, 0, kPivBits); seg_round = true; }
-      else { sort_pairs_db(c, key, keyo, val, valo, m, 0, nb + kPivBits); std::swap(key, keyo); std::swap(val, valo); }
-      out.rounds++;
-      continue;                 // the sorted prefix common to all groups is still h: no doubling of h
+    { KScope kw(c, "pfp::finish_write_kernel", m * (sizeof(I) * 5 + 12));
+      hipLaunchKernelGGL(finish_write_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, aslot.p, act_i.p, flt.p, feq.p, fgs.p,
+                         out.finbit, out.sa.p, out.grp.p, rank_p, wordrank_p); }
+    PFP_HIP(hipGetLastError());
+    if (kSwitch.trace_rounds) fprintf(stderr, "[pfp] doubling N=%llu round=%llu: the last %llu suffixes ranked by comparison\n",
+                                      (unsigned long long)N, (unsigned long long)out.rounds, (unsigned long long)m);
+    out.rounds++;
+    m = 0;
+    return true;
+  }
+
+  // ---- ordering the keys of the (grouped) active list inside their groups.
+  // Rounds after the first: the unresolved suffixes are already grouped, only the 32-bit "next"
+  // key has to be ordered inside every group.  When the groups are many and of moderate size (a
+  // dictionary of near-identical variants) a segmented sort moves 16 B per suffix instead of the
+  // 7 x 24 B of a global 53-bit radix sort (big: 240 -> 126 ms of sorting).  rocPRIM's segmented
+  // sort serialises a giant segment on one workgroup (the 300 k run of one symbol in a parse cost
+  // 68 ms), and for tiny groups its bookkeeping eats the gain, so the choice is per round.
+
+  // families of a handful of members: placed directly in LDS (after a group proved too long, only once the average is tiny)
+  // (32-bit build: long families go to the side sort, so the average may be larger)
+  bool small_groups() const {
+    return kSwitch.small_seg && ngrp && m / ngrp <= (kWide ? kSmallSeg / 4 : kSmallSeg / 2) && (!small_failed || m / ngrp <= 3);
+  }
+  // large families (a collection of hundreds of copies): the library's segmented sort is worth its set-up
+  // (m < 2^32 - its offsets are 32-bit - always holds in the 32-bit index build)
+  bool segmented_worthwhile() const { return ngrp && m >= (1u << 20) && m < 0xFFFFFFFFull && m / ngrp >= kSegMinAvg; }
+
+  void seg_bufs() {
+    if (!gs.p) { gs.alloc(c, list_cap + 1); k32.alloc(c, list_cap); k32o.alloc(c, list_cap); nseg_d.alloc(c, 2); nsel_d.alloc(c, 1); ovf_d.alloc(c, 1); }
+  }
+  // kin/val -> kout/valo, every group of the list sorted by its key; false: some group has more than kSmallSeg
+  // members (nothing usable was written).
+  // 32-bit keys in the 32-bit index build: the groups of more than kSmallSeg members are passed through in place, flagged, and
+  // finished by ONE library sort of just their elements (a few long families no longer send the whole round to the library)
+  template <class KT>
+  bool place_small_groups(const KT *kin, KT *kout) {
+    constexpr bool side = !kWide && sizeof(KT) == 4;
+    seg_bufs();
+    ovf_d.zero();
+    if (side && (!bigf.p || bigf.n < m + 16)) bigf.alloc(c, list_cap + 16);
+    { KScope ks(c, "pfp::seg_small_sort_kernel", m * (2 * sizeof(KT) + 3 * sizeof(I) + 1));
+      hipLaunchKernelGGL((seg_small_sort_kernel<I, KT>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, act_grp.p, kin, val.p, gs.p, kout,
+                         valo.p, ovf_d.p, side ? bigf.p : (uint8_t *)nullptr); }
+    if (read_scalar(c, ovf_d.p) == 0) return true;
+    if (!side) return false;
+    PFP_HIP(hipMemsetAsync(bigf.p + m, 0, 16, c->stream));      // (the flag reader looks at 16 bytes at a time)
+    const uint64_t nbig = count_flags(c, bigf.p, m);
+    if (nbig * 2 > m) return false;                // mostly long groups: the round is the library's after all
+    DBuf<I> idx(c, nbig + 1), sv(c, nbig), sva(c, nbig);
+    DBuf<uint64_t> sk(c, nbig), ska(c, nbig), cnt(c, 1);
+    select_index<I>(c, bigf.p, idx.p, cnt.p, m);
+    hipLaunchKernelGGL(big_seg_gather_kernel<I>, gdim(blocks(nbig)), gdim(TB), 0, c->stream, nbig, idx.p, act_grp.p, k32o.p, valo.p, sk.p, sv.p);
+    sort_pairs_db(c, sk, ska, sv, sva, nbig, 0, 32 + nb);
+    hipLaunchKernelGGL(big_seg_scatter_kernel<I>, gdim(blocks(nbig)), gdim(TB), 0, c->stream, nbig, idx.p, sk.p, sv.p, k32o.p, valo.p);
+    PFP_HIP(hipGetLastError());
+    return true;
+  }
+  // segments of the library's sort = groups of the list (segb/sege; the compaction that built the list counted its group heads - no
+  // read-back of the selection's count); false: a group of more than 2^15 members, too long for it
+  bool library_segments() {
+    seg_bufs();
+    if (!segb.p) { segb.alloc(c, list_cap + 1); sege.alloc(c, list_cap + 1); }
+    hipLaunchKernelGGL(group_starts_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, act_grp.p, gs.p);
+    select_index<uint32_t>(c, gs.p, segb.p, nsel_d.p, m);
+    PFP_HIP(hipMemsetAsync(nseg_d.p + 1, 0, 4, c->stream));
+    if (c->debug) PFP_REQUIRE(read_scalar(c, nsel_d.p) == ngrp, PFP_EHIP, "group count of the active list differs from the compaction's");
+    hipLaunchKernelGGL(seg_end_kernel, gdim(blocks(ngrp)), gdim(TB), 0, c->stream, (uint32_t)ngrp, (uint32_t)m, segb.p, sege.p, nseg_d.p + 1);
+    return read_scalar(c, nseg_d.p + 1) <= (1u << 15);
+  }
+  // the fallback: (group, key) pairs of the whole list through one device-wide sort, key/val -> keyo/valo
+  void sort_device_wide(int bits) {
+    sort_pairs_db(c, key, keyo, val, valo, m, 0, bits);
+    std::swap(key, keyo); std::swap(val, valo);
+  }
+
+  // ---- the rounds.  A pivot round leaves the sorted prefix common to all groups at h: only a doubling round doubles it.
+  bool dict_pivot_wanted() const { return pivot_ok && pivot_rounds_possible() && ngrp && m / ngrp <= kPivotAvg; }
+  void dict_pivot_round() {
+    // few suffixes left: the widest window at once.  (A compare reads only as far as the strings agree; the window bounds
+    // the worst case, m x window bytes.  What is left after two rounds are mostly members of phrases longer than the
+    // 512-byte window: without this they cost one round that settles nothing and quadruples the window, then another.)
+    if (piv_cap >= 16 && piv_cap < kPivCapMax - 16 && out.rounds >= 2 && m * (uint64_t)(kPivCapMax - 16) < N * 128) piv_cap = kPivCapMax - 16;
+    // a segmented sort of the 23-bit order key moves 16 B per suffix instead of 7 x 24 B
+    bool small = small_groups();
+    bool seg = !small && segmented_worthwhile() && library_segments();
+    if (small) seg_bufs();
+    // both key forms are written when the direct placement is tried: should a group prove too long, the
+    // device-wide sort takes over with the 64-bit keys
+    { KScope ks(c, "pfp::build_keys_pivot_kernel", m * (4 + 4 + 4 + 12 + 64));
+      hipLaunchKernelGGL(build_keys_pivot_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, out.bytes, m, h, piv_cap, act_i.p,
+                         act_grp.p, out.sa.p, out.finbit, key.p, (seg || small) ? k32.p : (uint32_t *)nullptr, val.p, small ? 1 : 0); }
+    if (small && !place_small_groups(k32.p, k32o.p)) {
+      small = false; small_failed = true;
+      seg = segmented_worthwhile() && library_segments();
     }
-    if constexpr (sizeof(I) == 4) {
-      // the parse of a collection: a pivot round with the member whose next rare symbol is farthest (see ipivot_select_kernel)
-      // (a share of the parse - range mode - has no doubling rounds to fall back on: it tries whatever the list's size)
-      if (g.mode == MODE_PLAIN && g.dist && g.sym && ipiv_ok && ngrp && (range_mode || m >= parse_pivot_min()) && m < 0xFFFFFFFFull && m / ngrp >= 2) {
-        {
-          DBuf<unsigned long long> best(c, N);
-          best.zero();
-          KScope ks(c, "pfp::ipivot_keys_kernel", m * (4 + 4 + 4 + 8 + 16 + 12 + 64));
-          hipLaunchKernelGGL(ipivot_select_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, NP, h, act_i.p, act_grp.p, g.dist, best.p);
-          hipLaunchKernelGGL(ipivot_keys_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, NP, h, kIntPivCap, g.sym, act_i.p,
-                             act_grp.p, best.p, key.p, val.p);
-        }
-        bool sorted = false;
-        if (m / ngrp <= kSmallSeg / 2) {      // small groups (pairs of copies with a common SNP): placed by counting in LDS
-          seg_bufs();
-          ovf_d.zero();
-          { KScope ks(c, "pfp::seg_small_sort_kernel", m * (16 + 3 * sizeof(I) + 1));
-            hipLaunchKernelGGL((seg_small_sort_kernel<I, uint64_t>), gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, act_grp.p, key.p, val.p, gs.p,
-                               keyo.p, valo.p, ovf_d.p, (uint8_t *)nullptr); }
-          sorted = read_scalar(c, ovf_d.p) == 0;
-        }
-        if (!sorted && (m / ngrp >= 4 || range_mode)) {      // (a share has nothing else to fall back on)
-          uint32_t ng = 0, maxlen = 0;
-          seg_setup(m, ngrp, ng, maxlen);
-          if (maxlen <= (1u << 15)) {
-            segsort_pairs_u64_u32(c, key.p, keyo.p, val.p, valo.p, m, ng, segb.p, sege.p, 0, 32 + bits_for(2 * kIntPivCap + 3));
-            sorted = true;
-          }
-        }
-        if (sorted) {
-          seg_round = true; ipiv_round = true;
-          out.rounds++;
-          continue;               // the sorted prefix common to all groups is still h
-        }
-        ipiv_ok = false;
-      }
+    if (seg) segsort_pairs_u32<I>(c, k32.p, k32o.p, val.p, valo.p, m, (uint32_t)ngrp, segb.p, sege.p, 0, kPivBits);
+    else if (!small) sort_device_wide(nb + kPivBits);
+    kind = (small || seg) ? Round::DictPivotGrouped : Round::DictPivotGlobal;
+    out.rounds++;
+  }
+
+  // the parse of a collection: a pivot round with the member whose next rare symbol is farthest (see ipivot_select_kernel)
+  // (a share of the parse - range mode - has no doubling rounds to fall back on: it tries whatever the list's size)
+  bool parse_pivot_wanted() const {
+    return g.mode == MODE_PLAIN && g.dist && g.sym && ipiv_ok && ngrp && (range_mode || m >= parse_pivot_min()) && m < 0xFFFFFFFFull && m / ngrp >= 2;
+  }
+  // (32-bit index build only.)  There is no device-wide fallback: false, and no more parse pivot rounds, where neither way of
+  // ordering the groups took them
+  bool parse_pivot_round() {
+    {
+      DBuf<unsigned long long> best(c, N);
+      best.zero();
+      KScope ks(c, "pfp::ipivot_keys_kernel", m * (4 + 4 + 4 + 8 + 16 + 12 + 64));
+      hipLaunchKernelGGL(ipivot_select_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, act_i.p, act_grp.p, g.dist, best.p);
+      hipLaunchKernelGGL(ipivot_keys_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, kIntPivCap, g.sym, act_i.p,
+                         act_grp.p, best.p, key.p, val.p);
     }
-    if (range_mode) { out.complete = false; break; }     // doubling would read ranks of suffixes other ranks hold
+    // small groups (pairs of copies with a common SNP): placed by counting in LDS, whatever PFP_NO_SMALLSEG says
+    bool sorted = m / ngrp <= kSmallSeg / 2 && place_small_groups(key.p, keyo.p);
+    if (!sorted && (m / ngrp >= 4 || range_mode) && library_segments()) {      // (a share has nothing else to fall back on)
+      segsort_pairs_u64_u32(c, key.p, keyo.p, val.p, valo.p, m, (uint32_t)ngrp, segb.p, sege.p, 0, 32 + bits_for(2 * kIntPivCap + 3));
+      sorted = true;
+    }
+    if (!sorted) { ipiv_ok = false; return false; }
+    kind = Round::ParsePivot;
+    out.rounds++;
+    return true;
+  }
+
+  // a doubling round reads rank[] of arbitrary positions: whatever the first round and the pivot rounds left out is filled in
+  void repair_ranks(uint64_t m_active, const I *aslot_list) {
+    if (!ranks_stale) return;
+    DBuf<uint8_t> act(c, N);
+    act.zero();
+    if (m_active) hipLaunchKernelGGL(mark_slots_kernel<I>, gdim(blocks(m_active)), gdim(TB), 0, c->stream, m_active, aslot_list, act.p);
+    KScope ks(c, "pfp::repair_ranks_kernel", N * 6);
+    hipLaunchKernelGGL(repair_ranks_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, N, keep0.p, act.p, out.sa.p, out.grp.p,
+                       out.finbit, out.rank.p);
+    ranks_stale = false;
+  }
+  void prepare_ranks_for_doubling() {
     if (late_rank && !rank_alloc) {      // the first doubling round: rank[] is needed after all
       alloc_rank();
       ranks_stale = true;               // whatever pivot rounds settled (whole words included) is filled in from the slots
@@ -1400,60 +1482,90 @@ static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, u
       lazy_pending = false;
       if (m * kLazyRatio > N) {      // most lookups would need the search: scatter the settled ranks once
         KScope ks(c, "pfp::scatter_settled_kernel", N * (4 + 4 + 1 + 4));
-        hipLaunchKernelGGL(scatter_settled_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, N, out.sa.p, out.grp.p, keep0.p,
+        hipLaunchKernelGGL(scatter_settled_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, N, out.sa.p, out.grp.p, keep0.p,
                            out.finbit, out.rank.p);
         if (!out.paybits) out.skeys.release();      // with payload the merge still reads the records from skeys
         out.tab.release();
       }
     }
-    repair_ranks(m, aslot.p);                 // a doubling round reads rank[] of arbitrary positions
+    repair_ranks(m, aslot.p);
     if (active_stale) {
-      hipLaunchKernelGGL(active_ranks_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, m, act_i.p, act_grp.p, out.rank.p);
+      hipLaunchKernelGGL(active_ranks_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, act_i.p, act_grp.p, out.rank.p);
       active_stale = false;
     }
+  }
+
+  void build_keys32(const RankViewT<I> &L) {
+    KScope ks(c, "pfp::build_keys32_kernel", m * (4 + 4 + 8));
+    hipLaunchKernelGGL(build_keys32_kernel, gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, h, act_i.p, L, k32.p, val.p);
+  }
+  void doubling_round() {
     const RankViewT<I> L = rank_view(out);
-    dbl_round = true;
-    if constexpr (!kWide) {
-      static const bool use_small = getenv("PFP_NO_SMALLSEG") == nullptr;
-      if (use_segsort && use_small && ngrp && m / ngrp <= (kWide ? kSmallSeg / 4 : kSmallSeg / 2) && (!small_failed || m / ngrp <= 3)) {
+    const int keybits = 2 * nb;
+    kind = Round::DoublingGlobal;
+    if constexpr (kWide) {
+      if (!dkey.p || dkey.n < m) { dkey.alloc(c, m); dkeyo.alloc(c, m); }
+      { KScope ks(c, "pfp::build_keys_kernel", m * (8 + 8 + 8 + 24));
+        hipLaunchKernelGGL(build_keys_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, h, act_i.p, act_grp.p, L, nb, dkey.p, val.p); }
+      sort_pairs_db(c, dkey, dkeyo, val, valo, m, 0, keybits);
+      std::swap(dkey, dkeyo); std::swap(val, valo);
+    } else {
+      // the direct placement is decided on before any key is built, and k32 is built only where a sort inside the groups takes it
+      if (small_groups()) {
         seg_bufs();
-        { KScope ks(c, "pfp::build_keys32_kernel", m * (4 + 4 + 8));
-          hipLaunchKernelGGL(build_keys32_kernel, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, act_i.p, L, k32.p, val.p); }
-        seg_round = seg_small_sort(m);
-        if (!seg_round) small_failed = true;
+        build_keys32(L);
+        if (place_small_groups(k32.p, k32o.p)) kind = Round::DoublingGrouped;
+        else small_failed = true;
       }
-      if (seg_round) {
-      } else if (use_segsort && m >= (1u << 20) && ngrp && m / ngrp >= 24) {
-        uint32_t ng = 0, maxlen = 0;
-        seg_setup(m, ngrp, ng, maxlen);
-        if (maxlen <= (1u << 15) && m / ng >= 24) {
-          { KScope ks(c, "pfp::build_keys32_kernel", m * (4 + 4 + 8));
-            hipLaunchKernelGGL(build_keys32_kernel, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, act_i.p, L, k32.p, val.p); }
-          segsort_pairs_u32<I>(c, k32.p, k32o.p, val.p, valo.p, m, ng, segb.p, sege.p, 0, bits_for(N));
-          seg_round = true;
-        }
+      if (kind != Round::DoublingGrouped && segmented_worthwhile() && library_segments()) {
+        build_keys32(L);
+        segsort_pairs_u32<I>(c, k32.p, k32o.p, val.p, valo.p, m, (uint32_t)ngrp, segb.p, sege.p, 0, bits_for(N));
+        kind = Round::DoublingGrouped;
       }
-    }
-    if (!seg_round) {
-      if constexpr (kWide) {
-        if (!dkey.p || dkey.n < m) { dkey.alloc(c, m); dkeyo.alloc(c, m); }
-        { KScope ks(c, "pfp::build_keys_kernel", m * (8 + 8 + 8 + 24));
-          hipLaunchKernelGGL(build_keys_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, act_i.p, act_grp.p, L, nb, dkey.p, val.p); }
-        sort_pairs_db(c, dkey, dkeyo, val, valo, m, 0, keybits);
-        std::swap(dkey, dkeyo); std::swap(val, valo);
-      } else {
+      if (kind != Round::DoublingGrouped) {
         { KScope ks(c, "pfp::build_keys_kernel", m * (4 + 4 + 4 + 12));
-          hipLaunchKernelGGL(build_keys_kernel<I>, gdim(cdiv(m, TB)), gdim(TB), 0, c->stream, g, m, h, act_i.p, act_grp.p, L, nb, key.p, val.p); }
-        sort_pairs_db(c, key, keyo, val, valo, m, 0, keybits);
-        std::swap(key, keyo); std::swap(val, valo);
+          hipLaunchKernelGGL(build_keys_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, h, act_i.p, act_grp.p, L, nb, key.p, val.p); }
+        sort_device_wide(keybits);
       }
     }
     h *= 2;
     out.rounds++;
   }
+
+  // choose and run the next round; false: only a doubling round could go on, and this is a share of a suffix array
+  bool next_round() {
+    if (dict_pivot_wanted()) { dict_pivot_round(); return true; }
+    if constexpr (!kWide) {
+      if (parse_pivot_wanted() && parse_pivot_round()) return true;
+    }
+    if (range_mode) { out.complete = false; return false; }     // doubling would read ranks of suffixes other ranks hold
+    prepare_ranks_for_doubling();
+    doubling_round();
+    return true;
+  }
+};
+
+template <class I>
+static void doubling(pfp_ctx *c, SufGeom g, DBuf<uint64_t> &key, DBuf<I> &val, uint64_t h0, SuffixOrderT<I> &out, const DoublingOpts &o) {
+  // precondition: key/val hold the initial (prefix key, position) pairs of the N suffixes to sort: all
+  // g.N positions, or (range mode, o.list_len given) the ones of this rank's key range
+  Rounds<I> r(c, g, key, val, h0, out, o);
+  out.N = r.N; out.NP = r.NP; out.range = r.range_mode; out.complete = true;
+  out.rounds = 0;
+  if (r.N == 0) { out.sa.alloc(c, 1); out.grp.alloc(c, 8); out.rank.alloc(c, 1); return; }
+  r.first_round_sort();
+  SortTag later_tag(g.mode == MODE_DICT ? "dictionary, later rounds" : "parse, later rounds");
+  r.start_rounds();
+  for (;;) {
+    r.regroup();
+    r.judge_pivot_round();
+    r.next_list();
+    if (r.m == 0 || r.try_finisher() || !r.next_round()) break;
+    r.tile_last.release(); r.tile_scan.release();      // (the first round's, kept until its successor is sorted)
+  }
   // PFP_DEBUG validates the rank of every position: fill in what the pivot rounds left out
-  if (c->debug && out.complete && !no_rank) repair_ranks(0, nullptr);
-  if (rank_alloc) out.wordrank.release();      // every rank is in rank[]
+  if (c->debug && out.complete && !r.range_mode) r.repair_ranks(0, nullptr);
+  if (r.rank_alloc) out.wordrank.release();      // every rank is in rank[]
 }
 
 template <class I>
@@ -1536,7 +1648,9 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
   PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
   sync(c);      // kc is a stack object
   out.bytes = bytes; out.kbits = kc.kbits;
-  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, kc.kbits + 1, true, ~0ull, idx_bits);
+  DoublingOpts o;
+  o.key_bits = kc.kbits + 1, o.dict = true, o.idx_bits = idx_bits;
+  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
 }
 template void sort_dict_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint32_t> &, const SlotPayloadSrc *);
 template void sort_dict_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint64_t> &, const SlotPayloadSrc *);
@@ -1728,7 +1842,9 @@ static void sort_suffix_list(pfp_ctx *c, const SufGeom &g, const KeyCode &kc, in
   PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
   sync(c);      // kc may be a stack object of the caller
   out.bytes = g.wv.bytes; out.kbits = kc.kbits;
-  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, kc.kbits + 1, true, (uint64_t)n, idx_bits);
+  DoublingOpts o;
+  o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = n, o.idx_bits = idx_bits;
+  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
 }
 
 template <class I>
@@ -1845,7 +1961,7 @@ void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrde
   DBuf<I> val(c, N);
   { KScope ks(c, "pfp::init_keys_bytes_kernel", N * (16 + sizeof(I)));
     hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p); }
-  doubling<I>(c, g, key, val, 8, out);
+  doubling<I>(c, g, key, val, 8, out, DoublingOpts{});
 }
 template void sort_byte_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint32_t> &);
 template void sort_byte_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint64_t> &);
@@ -1886,7 +2002,7 @@ void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder 
     KScope ks(c, "pfp::init_keys_int_kernel", N * (8 + 8 + 4));
     hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, key.p, val.p);
   }
-  doubling<uint32_t>(c, g, key, val, 2, out);
+  doubling<uint32_t>(c, g, key, val, 2, out, DoublingOpts{});
 }
 
 // ---- one rank's share of the parse's suffix array (multi-GPU chain).  The parse is replicated, its suffix array was too; with the
@@ -1990,7 +2106,9 @@ void sort_int_suffixes_range(pfp_ctx *c, const uint32_t *sym, uint64_t N, uint32
   PFP_HIP(hipGetLastError());
   key.release(); idx.release();
   ks_sel.reset();
-  doubling<uint32_t>(c, g, lkey, lval, 2, out, 64, false, n_mine, 0);
+  DoublingOpts o;
+  o.list_len = n_mine;
+  doubling<uint32_t>(c, g, lkey, lval, 2, out, o);
   out.slot_base = slot_base; out.klo = klo; out.khi = khi_open ? ~0ull : khi;
 }
 

@@ -171,14 +171,14 @@ case("fam_small", "gsa", lambda: collection(family_block(_rng(2), 1000, 8, 150, 
 # one pair sort of their own in the same round; wide build: the whole round goes to the device-wide sort
 case("fam_small_one_big", "gsa", lambda: collection(family_block(_rng(3), 1000, 8, 150, 2), family_block(_rng(4), 1, 100, 150, 2)),
      lambda w: W([PIVOT, SMALL, later_pairs(w)], [SEG32]))
-# pivot round, segmented sort: m >= 2^20 unresolved, average family >= seg_min_avg = 24, longest <= 2^15
+# pivot round, segmented sort: m >= 2^20 unresolved, average family >= kSegMinAvg = 24, longest <= 2^15
 case("fam_segmented", "gsa", lambda: collection(family_block(_rng(5), 300, 40, 150, 2)),
      lambda w: W([PIVOT, SEG32]))
 # the same with one family above 2^15 (40 000 words that differ in their first four bytes only): the device-wide sort
 case("fam_segmented_giant", "gsa",
      lambda: collection(family_block(_rng(6), 300, 40, 100, 2), family_block(_rng(7), 1, 40000, 40, 2, 0, 4)),
      lambda w: W([PIVOT, later_pairs(w)], [SEG32]))
-# comparison finisher: after the first pivot round (window kPivotCap = 512) what is left - variants that agree for more than
+# comparison finisher: after the first pivot round (window kSwitch.pivot_cap = 512) what is left - variants that agree for more than
 # 512 bytes - is below kFinishMax = 2^17, in groups of 4 <= kFinishGrp, with common prefixes below kFinishCmp = 8192
 case("finisher", "gsa", lambda: collection(family_block(_rng(8), 20, 4, 1500, 2)),
      lambda w: W([PIVOT, FINISH, FINISH_WRITE], [DBL, DBL32], maximum={PIVOT: 1}))
