@@ -1,5 +1,5 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
-// reference counterpart): struct pfp_fm and every pfp_fm_* call.
+// reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*.
 #include <memory>
 #include "api.hpp"
 
@@ -188,7 +188,7 @@ struct MsOnDevice {
   DBuf<uint8_t> pat; DBuf<uint64_t> off, pos; DBuf<uint32_t> len;
   uint64_t first = 0, total = 0;
 };
-static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MsOnDevice &d) {
+static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MsOnDevice &d, bool thr = false) {
   pfp_ctx *c = fm->f.c;
   const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
   d.first = npat ? pat_off[0] : 0;
@@ -199,7 +199,8 @@ static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off
   d.pos.alloc(c, bytes + 1);
   if (bytes) h2d(c, d.pat.p, pat, bytes);
   if (npat) h2d(c, d.off.p, pat_off, npat + 1);
-  fm_ms(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
+  if (thr) fm_ms_thr(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
+  else fm_ms(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
 }
 
 int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
@@ -209,15 +210,20 @@ int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
   return PFP_OK;
 }
 
-int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+static void require_thresholds(const pfp_fm *fm) {
+  PFP_REQUIRE(fm->f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
+}
+
+static int ms_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos, bool thr) {
   if (!fm || (npat && (!pat_off || !len))) return PFP_EINVAL;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
   PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "matching statistics need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
                                           "pfp_fm_build_ms_files");
+  if (thr) require_thresholds(fm);
   if (!npat) return PFP_OK;
   MsOnDevice d;
-  ms_on_device(fm, pat, pat_off, npat, d);
+  ms_on_device(fm, pat, pat_off, npat, d, thr);
   if (d.total) {
     download(c, len, (const uint8_t *)(d.len.p + d.first), d.total * 4);
     sync(c);      // (the next download fills the same pinned buffers)
@@ -228,16 +234,25 @@ int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
   PFP_CATCH(c)
 }
 
-int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
+int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  return ms_host(fm, pat, pat_off, npat, len, pos, false);
+}
+int pfp_fm_ms_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
+  return ms_host(fm, pat, pat_off, npat, len, pos, true);
+}
+
+static int mems_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems,
+                     bool thr) {
   if (!fm || !mem_off || !mems || (npat && !pat_off)) return PFP_EINVAL;
   *mems = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
   PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "maximal exact matches need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
                                           "pfp_fm_build_ms_files");
+  if (thr) require_thresholds(fm);
   PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
   MsOnDevice d;
-  ms_on_device(fm, pat, pat_off, npat, d);
+  ms_on_device(fm, pat, pat_off, npat, d, thr);
   d.pat.release();
   DBuf<uint64_t> d_mem_off(c, npat + 1);
   fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
@@ -253,6 +268,99 @@ int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_
   PFP_CATCH(c)
 }
 
+int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
+  return mems_host(fm, pat, pat_off, npat, min_len, mem_off, mems, false);
+}
+int pfp_fm_mems_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
+  return mems_host(fm, pat, pat_off, npat, min_len, mem_off, mems, true);
+}
+
+int pfp_fm_ms_thr_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
+  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_ms_thr(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- the LCP array and thresholds (lcp.hip)
+int pfp_fm_thresholds_dev(pfp_fm *fm, const void *d_thr5, uint64_t bytes) {
+  if (!fm) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  if (d_thr5) {
+    fm_load_thresholds(fm->f, (const uint8_t *)d_thr5, bytes);
+  } else {
+    LcpOut o;
+    o.keep = true;
+    fm_lcp(fm->f, o);
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_thresholds_files(pfp_fm *fm, const char *base) {
+  if (!fm || !base) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "thresholds need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                          "pfp_fm_build_ms_files");
+  DBuf<uint8_t> d_thr;
+  const uint64_t bytes = file_to_dev(c, std::string(base) + ".thr_pos", d_thr);
+  fm_load_thresholds(fm->f, d_thr.p, bytes);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_lcp_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10, uint64_t esa_bytes,
+                const void *d_text, uint64_t *d_lcp, uint64_t *d_thr, uint64_t *runs) {
+  if (!c || !d_bwt) return PFP_EINVAL;
+  PFP_TRY_DEV(c)
+  FmIndex f;
+  fm_build_ms(c, f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes,
+              (const uint8_t *)d_text);
+  if (runs) *runs = f.runs;
+  LcpOut o;
+  o.lcp64 = d_lcp; o.thr64 = d_thr;
+  if (d_lcp || d_thr) fm_lcp(f, o);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_lcp_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, int what) {
+  if (!c || !base) return PFP_EINVAL;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(what && !(what & ~(PFP_LCP_LCP | PFP_LCP_THR)), PFP_EINVAL, "what: PFP_LCP_LCP, PFP_LCP_THR or both");
+  const std::string b(base);
+  FmIndex f;
+  {
+    DBuf<uint8_t> d_bwt, d_ssa, d_esa;
+    const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
+    check_bwt_rows(n1);
+    const bool given = text || text_fd >= 0;
+    PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
+                                                       " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
+    const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+    if (given) {
+      f.text.alloc(c, n + 16);
+      upload_text(c, f.text.p, text, text_fd, text_offset, n);
+      sync(c);
+    }
+    fm_build_ms(c, f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? f.text.p : nullptr);
+  }
+  DBuf<uint8_t> lcp5, thr5;
+  LcpOut o;
+  if (what & PFP_LCP_LCP) { lcp5.alloc(c, 5 * f.n1 + 16); o.lcp5 = lcp5.p; }
+  if (what & PFP_LCP_THR) { thr5.alloc(c, 5 * f.runs + 16); o.thr5 = thr5.p; }
+  fm_lcp(f, o);
+  if (o.lcp5) write_dev_file(c, b + ".lcp", 0, lcp5.p, 5 * f.n1, true);
+  if (o.thr5) write_dev_file(c, b + ".thr_pos", 0, thr5.p, 5 * f.runs, true);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
 int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
   if (!fm || !out) return PFP_EINVAL;
   memset(out, 0, sizeof *out);
@@ -262,6 +370,7 @@ int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
   out->row_bits = fm->f.wide ? 64 : 32;
   out->device_bytes = fm->f.device_bytes();
   out->has_samples = fm->f.samples ? 1 : 0;
+  out->has_thresholds = fm->f.has_thr ? 1 : 0;
   return PFP_OK;
 }
 

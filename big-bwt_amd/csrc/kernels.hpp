@@ -314,6 +314,8 @@ struct FmIndex {
   DBuf<uint8_t> text;                    // the text, n1 - 1 bytes and 16 bytes of zero padding (whole 16-byte loads stay in bounds)
   DBuf<uint8_t> re_sa;                   // [runs] of I: SA value of run end i
   uint64_t ms_stats[3] = {0, 0, 0};      // fm_ms launches; with PFP_FM_MS_STATS=1 also steps that jumped and bytes their LCEs matched
+  bool has_thr = false;                  // fm_lcp (keep) or fm_load_thresholds filled the array below
+  DBuf<uint8_t> thr;                     // [runs] of I: the threshold row of run k (lcp.hip)
   uint64_t device_bytes() const;
 };
 uint64_t fm_bwt_bytes(uint64_t n1);      // f.bwt's size: n1 bytes and the zero padding
@@ -329,6 +331,20 @@ void fm_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npa
 // maximal exact matches from fm_ms's outputs: mem_off[0..npat] exclusive sums of the counts; mem == NULL: only those
 void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
              uint64_t *mem_off, uint64_t *mem);
+// the LCP array and thresholds of an index with text (lcp.hip; pfpgpu.h states the definitions).  Device outputs, each may be
+// NULL: lcp64 n1 values, thr64 runs values, lcp5 / thr5 the same as 5-byte ints; keep: the index keeps the thresholds (fm_ms_thr)
+struct LcpOut {
+  uint64_t *lcp64 = nullptr, *thr64 = nullptr;
+  uint8_t *lcp5 = nullptr, *thr5 = nullptr;
+  bool keep = false;
+};
+void fm_lcp(FmIndex &f, const LcpOut &o);
+// thresholds from a .thr_pos image (5 bytes per run; another size -> PFP_EFORMAT)
+void fm_load_thresholds(FmIndex &f, const uint8_t *thr5, uint64_t bytes);
+// matching statistics in two passes with thresholds: fm_ms's arguments and lengths; an index without thresholds -> PFP_EINVAL
+void fm_ms_thr(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos);
+// lcp[j] = plcp[SA[j]] for every row j through the inverter's splitter walk (unbwt.hip): plcp in text order, n1 entries each
+template <class I> void lcp_by_rows(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, const I *plcp, I *lcp);
 // device pointers; first may be NULL (needs samples otherwise)
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first);
 // out_off[0..npat] (device): exclusive sums of min(ep - sp, max_occ); pos == NULL: only those

@@ -255,6 +255,22 @@ __global__ void __launch_bounds__(kTB) unbwt_walk2(const I *__restrict__ lf, Wal
   }
 }
 
+// one lane per splitter, the same walk with SA[r] = n - k in hand: lcp[r] = plcp[SA[r]] (plcp in text order, n1 entries)
+template <class I>
+__global__ void __launch_bounds__(kTB) unbwt_walk_lcp(const I *__restrict__ lf, uint64_t n1, uint64_t m, const uint64_t *__restrict__ seg,
+                                                      const uint64_t *__restrict__ dist, const I *__restrict__ plcp, I *__restrict__ lcp) {
+  const uint64_t s = BID * kTB + threadIdx.x;
+  if (s >= m) return;
+  const uint64_t n = n1 - 1, len = seg[s];
+  uint64_t k = n1 - dist[s];
+  uint64_t r = spl_row(s, n1), rn = lf[r];
+  for (uint64_t st = 0; st < len; st++, k++) {
+    const uint64_t rnn = st + 1 < len ? (uint64_t)lf[rn] : 0;       // the next load is in flight during this row's work
+    if (k <= n && r < n1) lcp[r] = plcp[n - k];
+    r = rn; rn = rnn;
+  }
+}
+
 }  // namespace
 
 // .ssa / .esa bitmap, directory and run count (kernels.hpp)
@@ -275,60 +291,77 @@ void RunIndex::build(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, int which) {
 
 namespace {
 
+// LF and, by list ranking, every splitter's segment length and distance to the end of the cycle: what the second walk starts
+// from (invert_t: decode / check; lcp_by_rows: the gather through SA)
+template <class I>
+struct LfRanks {
+  DBuf<I> lf;
+  DBuf<uint64_t> C, seg, dist;
+  uint64_t m = 0;
+};
+
+template <class I>
+void lf_ranks(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, LfRanks<I> &w) {
+  const uint64_t nt = cdiv(n1, kTile), m = w.m = cdiv(n1, kSpl);
+  w.lf.alloc(c, n1);
+  DBuf<uint32_t> cnt(c, 256 * nt);
+  DBuf<uint64_t> base(c, 256 * nt);
+  w.C.alloc(c, 257);
+  {
+    KScope ks(c, "unbwt_hist", n1 + 256 * nt * 4);
+    unbwt_hist<<<gdim(cdiv(nt, kTB / 64)), kTB, 0, c->stream>>>(bwt, n1, nt, cnt.p);
+    PFP_HIP(hipGetLastError());
+  }
+  exclusive_sum_u32_u64(c, cnt.p, base.p, 256 * nt);
+  unbwt_ctab<<<1, 256, 0, c->stream>>>(base.p, nt, n1, w.C.p);
+  PFP_HIP(hipGetLastError());
+  uint64_t hC[257];
+  d2h(c, hC, w.C.p, 257);
+  sync(c);
+  const uint64_t zeros = hC[1] - hC[0];
+  PFP_REQUIRE(zeros == 1, PFP_EFORMAT, "not a BWT: " + std::to_string(zeros) + " bytes 0 among " + std::to_string(n1) + " (a BWT holds exactly one)");
+  {
+    KScope ks(c, "unbwt_rank", n1 + n1 * sizeof(I) + 256 * nt * 8);
+    unbwt_rank<I><<<gdim(cdiv(nt, kTB / 64)), kTB, 0, c->stream>>>(bwt, n1, nt, base.p, w.lf.p);
+    PFP_HIP(hipGetLastError());
+  }
+  cnt.release(); base.release();
+
+  DBuf<uint32_t> nxt(c, m), nxt2(c, m);
+  DBuf<uint64_t> dist2(c, m);
+  w.seg.alloc(c, m); w.dist.alloc(c, m);
+  {
+    KScope ks(c, "unbwt_walk1", n1 * sizeof(I) + m * 12);
+    unbwt_walk1<I><<<gdim(cdiv(m, kTB)), kTB, 0, c->stream>>>(w.lf.p, n1, m, nxt.p, w.seg.p);
+    PFP_HIP(hipGetLastError());
+  }
+  PFP_HIP(hipMemcpyAsync(w.dist.p, w.seg.p, m * 8, hipMemcpyDeviceToDevice, c->stream));
+  {
+    const int rounds = m > 1 ? bits_for(m - 1) : 0;      // ceil(log2 m) launches, each reads 2 x 12 and writes 12 bytes per splitter
+    KScope ks(c, "unbwt_jump", (uint64_t)rounds * m * 36);
+    for (int round = 0; round < rounds; round++) {
+      unbwt_jump<<<gdim(cdiv(m, kTB)), kTB, 0, c->stream>>>(m, nxt.p, w.dist.p, nxt2.p, dist2.p);
+      PFP_HIP(hipGetLastError());
+      std::swap(nxt, nxt2); std::swap(w.dist, dist2);
+    }
+  }
+  nxt2.release(); dist2.release();
+  const uint64_t cyc = read_scalar(c, w.dist.p);
+  PFP_REQUIRE(cyc == n1, PFP_EFORMAT, "not a BWT: the LF mapping has more than one cycle (the cycle through row 0 has " + std::to_string(cyc) +
+                                          " of " + std::to_string(n1) + " rows)");
+}
+
 template <class I>
 void invert_t(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res) {
   const uint64_t n1 = in.n1, n = n1 - 1;
-  const uint64_t nt = cdiv(n1, kTile), m = cdiv(n1, kSpl);
-  DBuf<I> lf(c, n1);
+  LfRanks<I> w;
+  lf_ranks<I>(c, in.bwt, n1, w);
+  const uint64_t m = w.m;
+  DBuf<I> &lf = w.lf;
   {
-    DBuf<uint32_t> cnt(c, 256 * nt);
-    DBuf<uint64_t> base(c, 256 * nt);
-    DBuf<uint64_t> C(c, 257);
-    {
-      KScope ks(c, "unbwt_hist", n1 + 256 * nt * 4);
-      unbwt_hist<<<gdim(cdiv(nt, kTB / 64)), kTB, 0, c->stream>>>(in.bwt, n1, nt, cnt.p);
-      PFP_HIP(hipGetLastError());
-    }
-    exclusive_sum_u32_u64(c, cnt.p, base.p, 256 * nt);
-    unbwt_ctab<<<1, 256, 0, c->stream>>>(base.p, nt, n1, C.p);
-    PFP_HIP(hipGetLastError());
-    uint64_t hC[257];
-    d2h(c, hC, C.p, 257);
-    sync(c);
-    const uint64_t zeros = hC[1] - hC[0];
-    PFP_REQUIRE(zeros == 1, PFP_EFORMAT, "not a BWT: " + std::to_string(zeros) + " bytes 0 among " + std::to_string(n1) + " (a BWT holds exactly one)");
-    {
-      KScope ks(c, "unbwt_rank", n1 + n1 * sizeof(I) + 256 * nt * 8);
-      unbwt_rank<I><<<gdim(cdiv(nt, kTB / 64)), kTB, 0, c->stream>>>(in.bwt, n1, nt, base.p, lf.p);
-      PFP_HIP(hipGetLastError());
-    }
-    cnt.release(); base.release();
-
-    DBuf<uint32_t> nxt(c, m), nxt2(c, m);
-    DBuf<uint64_t> seg(c, m), dist(c, m), dist2(c, m);
-    {
-      KScope ks(c, "unbwt_walk1", n1 * sizeof(I) + m * 12);
-      unbwt_walk1<I><<<gdim(cdiv(m, kTB)), kTB, 0, c->stream>>>(lf.p, n1, m, nxt.p, seg.p);
-      PFP_HIP(hipGetLastError());
-    }
-    PFP_HIP(hipMemcpyAsync(dist.p, seg.p, m * 8, hipMemcpyDeviceToDevice, c->stream));
-    {
-      const int rounds = m > 1 ? bits_for(m - 1) : 0;      // ceil(log2 m) launches, each reads 2 x 12 and writes 12 bytes per splitter
-      KScope ks(c, "unbwt_jump", (uint64_t)rounds * m * 36);
-      for (int round = 0; round < rounds; round++) {
-        unbwt_jump<<<gdim(cdiv(m, kTB)), kTB, 0, c->stream>>>(m, nxt.p, dist.p, nxt2.p, dist2.p);
-        PFP_HIP(hipGetLastError());
-        std::swap(nxt, nxt2); std::swap(dist, dist2);
-      }
-    }
-    nxt2.release(); dist2.release();
-    const uint64_t cyc = read_scalar(c, dist.p);
-    PFP_REQUIRE(cyc == n1, PFP_EFORMAT, "not a BWT: the LF mapping has more than one cycle (the cycle through row 0 has " + std::to_string(cyc) +
-                                            " of " + std::to_string(n1) + " rows)");
-
     RunIndex rs, re;
     Walk2Args a{};
-    a.n1 = n1; a.m = m; a.C = C.p; a.seg = seg.p; a.dist = dist.p;
+    a.n1 = n1; a.m = m; a.C = w.C.p; a.seg = w.seg.p; a.dist = w.dist.p;
     a.out = in.out;
     a.text = in.text; a.text_len = in.text_len;
     DBuf<uint64_t> mm(c, 4);
@@ -368,6 +401,17 @@ void invert_t(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res) {
 }
 
 }  // namespace
+
+template <class I>
+void lcp_by_rows(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, const I *plcp, I *lcp) {
+  LfRanks<I> w;
+  lf_ranks<I>(c, bwt, n1, w);
+  KScope ks(c, "unbwt_walk_lcp", n1 * 3 * sizeof(I) + w.m * 16);
+  unbwt_walk_lcp<I><<<gdim(cdiv(w.m, kTB)), kTB, 0, c->stream>>>(w.lf.p, n1, w.m, w.seg.p, w.dist.p, plcp, lcp);
+  PFP_HIP(hipGetLastError());
+}
+template void lcp_by_rows<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const uint32_t *, uint32_t *);
+template void lcp_by_rows<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, const uint64_t *, uint64_t *);
 
 void invert_bwt(pfp_ctx *c, const BwtCheckArgs &in, pfp_check_result *res) {
   const auto t0 = std::chrono::steady_clock::now();

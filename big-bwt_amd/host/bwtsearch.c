@@ -1,7 +1,7 @@
 /* bwtsearch.c -- count (and locate) patterns in a text through its .bwt (and .ssa / .esa) on the GPU.
  *
  *   bwtsearch [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
- *   bwtsearch --ms | --mems L [--text FILE] [--device D] PATTERNFILE basename
+ *   bwtsearch --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -10,7 +10,9 @@
  * --ms prints the matching statistics of every pattern, `len:pos` for every byte of the line separated by one space, `0:-` where
  * the length is 0; --mems L its maximal exact matches of at least L bytes, `count<TAB>i:len:pos i:len:pos ...` (the definitions:
  * include/pfpgpu.h, "Matching statistics").  Both read basename.bwt, .ssa and .esa, and the text from FILE, or without --text by
- * inverting basename.bwt.
+ * inverting basename.bwt.  --thresholds computes them in two passes with thresholds (the same lengths; positions by that
+ * algorithm's own rule): it reads basename.thr_pos if that file exists (unbwt --thresholds writes it) and computes the thresholds
+ * otherwise.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, 2 a usage error.
  */
@@ -28,7 +30,7 @@
 
 static void usage(const char *argv0) {
   printf("usage: %s [-h] [-l] [-m MAXOCC] [--device D] PATTERNFILE basename\n"
-         "       %s --ms | --mems L [--text FILE] [--device D] PATTERNFILE basename\n\n"
+         "       %s --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -38,6 +40,7 @@ static void usage(const char *argv0) {
          "                  reads basename.bwt, .ssa and .esa\n"
          "      --mems L    print count<TAB>i:len:pos ... : the maximal exact matches of at least L >= 1 bytes; reads the same files\n"
          "      --text FILE with --ms / --mems: the text (def. inverted from basename.bwt)\n"
+         "      --thresholds with --ms / --mems: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --device D  GPU to use (def. 0)\n",
          argv0, argv0);
 }
@@ -66,11 +69,12 @@ static int read_file(const char *path, uint8_t **out, uint64_t *len) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0;
   uint64_t maxocc = 0, min_len = 0;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
-                               {"text", required_argument, 0, 1004}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+                               {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
+                               {0, 0, 0, 0}};
   int c;
   char *end;
   while ((c = getopt_long(argc, argv, "lm:h", lo, NULL)) != -1) {
@@ -88,6 +92,7 @@ int main(int argc, char **argv) {
         mems = 1;
         break;
       case 1004: textfile = optarg; break;
+      case 1005: thresholds = 1; break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -97,7 +102,7 @@ int main(int argc, char **argv) {
     }
   }
   if (optind + 2 != argc) { usage(argv[0]); return 2; }
-  if (ms + mems + locate > 1 || ((ms || mems) && have_m) || (textfile && !ms && !mems)) { usage(argv[0]); return 2; }
+  if (ms + mems + locate > 1 || ((ms || mems) && have_m) || ((textfile || thresholds) && !ms && !mems)) { usage(argv[0]); return 2; }
   const char *patfile = argv[optind], *base = argv[optind + 1];
 
   uint8_t *pats = NULL;
@@ -144,6 +149,12 @@ int main(int argc, char **argv) {
     rc = pfp_fm_build_ms_files(ctx, base, NULL, fd, 0, n, &fm);
     if (fd >= 0) close(fd);
     if (rc && textfile) fprintf(stderr, "%s: ", textfile);
+    if (!rc && thresholds) {
+      char thrname[4096];
+      snprintf(thrname, sizeof thrname, "%s.thr_pos", base);
+      rc = access(thrname, R_OK) == 0 ? pfp_fm_thresholds_files(fm, base) : pfp_fm_thresholds_dev(fm, NULL, 0);
+      if (rc) { pfp_fm_free(fm); fm = NULL; }
+    }
   } else {
     rc = pfp_fm_build_files(ctx, base, locate ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
   }
@@ -192,7 +203,7 @@ int main(int argc, char **argv) {
       uint32_t *len = malloc((total + 1) * sizeof(uint32_t));
       uint64_t *pos = malloc((total + 1) * sizeof(uint64_t));
       if (!len || !pos) { fprintf(stderr, "out of memory\n"); free(len); free(pos); rc = 1; goto done; }
-      rc = pfp_fm_ms(fm, pat, off, k, len, pos);
+      rc = thresholds ? pfp_fm_ms_thr(fm, pat, off, k, len, pos) : pfp_fm_ms(fm, pat, off, k, len, pos);
       if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); free(len); free(pos); rc = 1; goto done; }
       for (uint64_t i = 0; i < k; i++) {
         for (uint64_t j = off[i]; j < off[i + 1]; j++) {
@@ -205,7 +216,7 @@ int main(int argc, char **argv) {
       free(len); free(pos);
     } else if (mems) {
       uint64_t *m = NULL;
-      rc = pfp_fm_mems(fm, pat, off, k, min_len, oo, &m);
+      rc = thresholds ? pfp_fm_mems_thr(fm, pat, off, k, min_len, oo, &m) : pfp_fm_mems(fm, pat, off, k, min_len, oo, &m);
       if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
       for (uint64_t i = 0; i < k; i++) {
         printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);

@@ -2,11 +2,15 @@
  *
  *   unbwt [-o outfile] basename                          <basename>.bwt -> the text, in <basename>.out (or outfile)
  *   unbwt --check TEXTFILE [-S] [-s] [-e] basename       <basename>.bwt (and .sa / .ssa / .esa) against TEXTFILE
+ *   unbwt --thresholds [--lcp] [--text FILE] basename    <basename>.bwt / .ssa / .esa -> <basename>.thr_pos (and <basename>.lcp)
  *
  * The output name follows the reference's `unparse` (<basename>.out).  The reference's readme suggests checking large
  * outputs "by some other means (for example inverting it)"; --check does that for any .bwt / .sa / .ssa / .esa of the
  * reference's formats, whichever tool wrote them, and exits 1 on any difference.  A file that is not a BWT (not exactly
  * one byte 0, or an LF mapping of several cycles) is reported and exits 1.
+ * --thresholds writes one threshold row per run of the BWT, --lcp with it the LCP array of all n + 1 rows, both as 5-byte
+ * little-endian ints (the definitions: include/pfpgpu.h, "The LCP array and thresholds"); the text comes from FILE, or without
+ * --text by inverting basename.bwt.
  */
 #define _GNU_SOURCE
 #include <fcntl.h>
@@ -23,7 +27,8 @@
 
 static void usage(const char *argv0) {
   printf("usage: %s [-h] [-o OUTFILE] basename\n"
-         "       %s --check TEXTFILE [-S] [-s] [-e] basename\n\n"
+         "       %s --check TEXTFILE [-S] [-s] [-e] basename\n"
+         "       %s --thresholds [--lcp] [--text FILE] basename\n\n"
          "Inverts basename.bwt on the GPU (MI355X), or checks existing outputs against their text.\n\n"
          "  basename         reads basename.bwt (one byte 0; the bigbwt output format)\n"
          "  -o OUTFILE       write the text to OUTFILE (def. basename.out)\n"
@@ -31,14 +36,18 @@ static void usage(const char *argv0) {
          "  -S               with --check: also check basename.sa (full suffix array, 5-byte entries)\n"
          "  -s               with --check: also check basename.ssa (run starts)\n"
          "  -e               with --check: also check basename.esa (run ends)\n"
+         "      --thresholds write basename.thr_pos: one threshold row per run; reads basename.bwt, .ssa and .esa\n"
+         "      --lcp        with --thresholds: also write basename.lcp (the LCP array, n + 1 entries)\n"
+         "      --text FILE  with --thresholds: the text (def. inverted from basename.bwt)\n"
          "      --device D   GPU to use (def. 0)\n",
-         argv0, argv0);
+         argv0, argv0, argv0);
 }
 
 int main(int argc, char **argv) {
-  const char *outname = NULL, *textfile = NULL;
-  int flags = 0, device = 0;
+  const char *outname = NULL, *textfile = NULL, *thrtext = NULL;
+  int flags = 0, device = 0, thresholds = 0, lcp = 0;
   static struct option lo[] = {{"check", required_argument, 0, 1000}, {"device", required_argument, 0, 1001},
+                               {"thresholds", no_argument, 0, 1002}, {"lcp", no_argument, 0, 1003}, {"text", required_argument, 0, 1004},
                                {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "o:Sseh", lo, NULL)) != -1) {
@@ -49,11 +58,15 @@ int main(int argc, char **argv) {
       case 'e': flags |= PFP_FLAG_ESA; break;
       case 1000: textfile = optarg; break;
       case 1001: device = atoi(optarg); break;
+      case 1002: thresholds = 1; break;
+      case 1003: lcp = 1; break;
+      case 1004: thrtext = optarg; break;
       case 'h': usage(argv[0]); return 0;
       default: usage(argv[0]); return 2;
     }
   }
   if (optind + 1 != argc || (flags && !textfile) || (outname && textfile)) { usage(argv[0]); return 2; }
+  if (((lcp || thrtext) && !thresholds) || (thresholds && (textfile || outname))) { usage(argv[0]); return 2; }
   const char *base = argv[optind];
 
   pfp_ctx *ctx = NULL;
@@ -63,7 +76,28 @@ int main(int argc, char **argv) {
     return 1;
   }
   int status = 0;
-  if (textfile) {
+  if (thresholds) {
+    int fd = -1;
+    uint64_t n = 0;
+    if (thrtext) {
+      struct stat sb;
+      fd = open(thrtext, O_RDONLY);
+      if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        perror(thrtext);
+        if (fd >= 0) close(fd);
+        pfp_ctx_destroy(ctx);
+        return 1;
+      }
+      n = (uint64_t)sb.st_size;
+    }
+    rc = pfp_lcp_files(ctx, base, NULL, fd, 0, n, PFP_LCP_THR | (lcp ? PFP_LCP_LCP : 0));
+    if (fd >= 0) close(fd);
+    if (rc) {
+      if (thrtext) fprintf(stderr, "%s: ", thrtext);
+      fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
+      status = 1;
+    }
+  } else if (textfile) {
     const int fd = open(textfile, O_RDONLY);
     struct stat sb;
     if (fd < 0 || fstat(fd, &sb) != 0) { perror(textfile); pfp_ctx_destroy(ctx); return 1; }

@@ -35,7 +35,10 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
            "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
            "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
-           "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats"]
+           "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats",
+           "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr"]
+
+LCP_LCP, LCP_THR = 1, 2
 
 
 class PfpError(RuntimeError):
@@ -58,7 +61,7 @@ class CheckResult(C.Structure):
 
 class _FmInfo(C.Structure):
     _fields_ = [("n", C.c_uint64), ("runs", C.c_uint64), ("sigma", C.c_uint32), ("row_bits", C.c_uint32), ("device_bytes", C.c_uint64),
-                ("has_samples", C.c_int)]
+                ("has_samples", C.c_int), ("has_thresholds", C.c_int)]
 
 
 def _patterns(patterns):
@@ -130,27 +133,53 @@ class FmIndex:
             self.lib.pfp_free(pos)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
 
-    def matching_statistics(self, patterns):
+    def add_thresholds(self, thr=None):
+        """give the index its thresholds (pfpgpu.h, "The LCP array and thresholds"): thr=None computes them on the GPU, else the
+        bytes of a .thr_pos file (5 per run), or a path base whose base.thr_pos is read"""
+        if thr is None:
+            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, None, C.c_uint64(0)))
+        elif isinstance(thr, (str, os.PathLike)):
+            self.ctx._check(self.lib.pfp_fm_thresholds_files(self._h, C.c_char_p(os.fsencode(thr))))
+        else:
+            import torch
+            b = _arr(thr, np.uint8)
+            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+            if len(b):
+                t[:len(b)] = torch.from_numpy(b.copy())
+            torch.cuda.synchronize()
+            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, C.c_void_p(t.data_ptr()), C.c_uint64(len(b))))
+        return self
+
+    def add_thresholds_dev(self, d_thr5, nbytes):
+        """the same from a device image of a .thr_pos file (5 bytes per run)"""
+        self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, C.c_void_p(d_thr5), C.c_uint64(nbytes)))
+        return self
+
+    def matching_statistics(self, patterns, thresholds=False):
         """-> (off, len, pos): for byte i of pattern p, len[off[p] + i] (uint32) is the length of the longest prefix of
         patterns[p][i:] that occurs in the text and pos[off[p] + i] (uint64) one place where it occurs (2**64 - 1 where the
-        length is 0).  Needs an index with text (Context.fm_index_ms*)."""
+        length is 0).  Needs an index with text (Context.fm_index_ms*).  thresholds=True: the two passes with thresholds
+        (add_thresholds first): the same len, pos by their own rule."""
         pat, off = _patterns(patterns)
         npat = len(off) - 1
         total = int(off[-1])
         ln, pos = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint64)
-        self.ctx._check(self.lib.pfp_fm_ms(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(ln, C.c_uint32),
-                                           _ptr(pos, C.c_uint64)))
+        call = self.lib.pfp_fm_ms_thr if thresholds else self.lib.pfp_fm_ms
+        self.ctx._check(call(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(ln, C.c_uint32),
+                             _ptr(pos, C.c_uint64)))
         return off, ln, pos
 
-    def mems(self, patterns, min_len=1):
+    def mems(self, patterns, min_len=1, thresholds=False):
         """-> (mem_off, mems): the maximal exact matches of pattern p of at least min_len bytes are the rows
-        mems[mem_off[p]:mem_off[p+1]] of a (k, 3) uint64 array, each (i, len, pos), by increasing i"""
+        mems[mem_off[p]:mem_off[p+1]] of a (k, 3) uint64 array, each (i, len, pos), by increasing i; thresholds as in
+        matching_statistics"""
         pat, off = _patterns(patterns)
         npat = len(off) - 1
         mem_off = np.zeros(npat + 1, dtype=np.uint64)
         out = C.POINTER(C.c_uint64)()
-        self.ctx._check(self.lib.pfp_fm_mems(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_len),
-                                             _ptr(mem_off, C.c_uint64), C.byref(out)))
+        call = self.lib.pfp_fm_mems_thr if thresholds else self.lib.pfp_fm_mems
+        self.ctx._check(call(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_len),
+                             _ptr(mem_off, C.c_uint64), C.byref(out)))
         total = int(mem_off[-1])
         mems = np.zeros((0, 3), dtype=np.uint64)
         if total and out:
@@ -159,16 +188,17 @@ class FmIndex:
         return mem_off, mems
 
     def ms_stats(self):
-        """{launches, jumps, matched} of the matching-statistics calls since the last look; jumps (steps that took step 3) and
-        matched (bytes their extensions matched) are collected only under PFP_FM_MS_STATS=1"""
+        """{launches, jumps, matched} of the matching-statistics calls (and add_thresholds) since the last look; jumps (steps
+        that took step 3) and matched (bytes the extensions matched) are collected only under PFP_FM_MS_STATS=1"""
         out = (C.c_uint64 * 3)()
         self.ctx._check(self.lib.pfp_fm_ms_stats(self._h, out))
         return dict(launches=int(out[0]), jumps=int(out[1]), matched=int(out[2]))
 
-    def matching_statistics_dev(self, d_pat, d_pat_off, npat, d_len, d_pos=None):
+    def matching_statistics_dev(self, d_pat, d_pat_off, npat, d_len, d_pos=None, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> uint32 d_len / uint64 d_pos, entry t for pattern byte d_pat[t]"""
-        self.ctx._check(self.lib.pfp_fm_ms_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
-                                               C.c_void_p(d_pos) if d_pos else None))
+        call = self.lib.pfp_fm_ms_thr_dev if thresholds else self.lib.pfp_fm_ms_dev
+        self.ctx._check(call(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
+                             C.c_void_p(d_pos) if d_pos else None))
 
     def mems_dev(self, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem=None):
         """device pointers from matching_statistics_dev -> npat+1 offsets; d_mem (room for 3 * offsets[npat] uint64) gets the
@@ -697,6 +727,59 @@ class Context:
             self._check(self.lib.pfp_fm_build_ms_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(buf, C.c_uint8), C.c_int(-1), C.c_uint64(0),
                                                        C.c_uint64(len(t)), C.byref(h)))
         return FmIndex(self, h)
+
+    # -- the LCP array and thresholds (csrc/lcp.hip; pfpgpu.h states the definitions)
+    def lcp(self, bwt, ssa, esa, text=None, want=("lcp", "thr")):
+        """host .bwt / .ssa / .esa bytes (text=None: inverted) -> dict with "lcp" (n + 1 uint64) and / or "thr" (one uint64 per run)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        keep = []
+        for a in (bwt, ssa, esa, text):
+            if a is None:
+                keep.append(None)
+                continue
+            b = _arr(a, np.uint8)
+            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
+            if len(b):
+                t[:len(b)] = torch.from_numpy(b.copy())
+            keep.append((t, len(b)))
+        if keep[1] is None or keep[2] is None:
+            raise PfpError(-1, "the LCP array needs the run samples: .ssa and .esa (bigbwt -s -e writes them)")
+        if keep[3] is not None and keep[3][1] + 1 != keep[0][1]:
+            raise PfpError(-1, f"the text holds {keep[3][1]} bytes; the BWT holds {keep[0][1]} rows, so its text holds {max(keep[0][1], 1) - 1}")
+        n1 = keep[0][1]
+        args = (keep[0][0].data_ptr(), n1, keep[1][0].data_ptr(), keep[1][1], keep[2][0].data_ptr(), keep[2][1],
+                keep[3][0].data_ptr() if keep[3] else None)
+        runs = keep[1][1] // 10          # (a .ssa of another size is refused before anything is written)
+        d_lcp = torch.zeros(n1 + 1, dtype=torch.int64, device=dev) if "lcp" in want else None
+        d_thr = torch.zeros(runs + 1, dtype=torch.int64, device=dev) if "thr" in want else None
+        torch.cuda.synchronize(dev)
+        runs = self.lcp_dev(*args, d_lcp=d_lcp.data_ptr() if d_lcp is not None else None, d_thr=d_thr.data_ptr() if d_thr is not None else None)
+        out = {}
+        if d_lcp is not None:
+            out["lcp"] = d_lcp[:n1].cpu().numpy().view(np.uint64)
+        if d_thr is not None:
+            out["thr"] = d_thr[:runs].cpu().numpy().view(np.uint64)
+        return out
+
+    def lcp_dev(self, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text=None, d_lcp=None, d_thr=None):
+        """device pointers; d_lcp: room for n_plus_1 uint64, d_thr: one uint64 per run; -> the number of runs (both None: only that)"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        runs = C.c_uint64()
+        self._check(self.lib.pfp_lcp_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes), vp(d_esa10),
+                                         C.c_uint64(esa_bytes), vp(d_text), vp(d_lcp), vp(d_thr), C.byref(runs)))
+        return int(runs.value)
+
+    def lcp_files(self, base, text=None, want=("lcp", "thr")):
+        """<base>.bwt / .ssa / .esa (text=None: inverted) -> <base>.lcp and / or <base>.thr_pos, 5-byte ints"""
+        what = (LCP_LCP if "lcp" in want else 0) | (LCP_THR if "thr" in want else 0)
+        if text is None:
+            self._check(self.lib.pfp_lcp_files(self._h, C.c_char_p(os.fsencode(base)), None, C.c_int(-1), C.c_uint64(0), C.c_uint64(0), C.c_int(what)))
+        else:
+            t = _arr(text, np.uint8)
+            buf = np.concatenate([t, np.zeros(1, dtype=np.uint8)])       # (never a NULL pointer for an empty text)
+            self._check(self.lib.pfp_lcp_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(buf, C.c_uint8), C.c_int(-1), C.c_uint64(0),
+                                               C.c_uint64(len(t)), C.c_int(what)))
 
     # -- multi-GPU chain, one rank's share (device pointers; collectives are the caller's: dist.py)
     def dist_propose_triggers(self, d_text_ptr, n, w, p):

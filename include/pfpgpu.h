@@ -496,6 +496,7 @@ typedef struct {
   uint32_t row_bits;       /* 32 or 64: width of rows and SA values inside the index */
   uint64_t device_bytes;   /* device memory the index holds */
   int has_samples;         /* 1: built with .ssa / .esa (locate works) */
+  int has_thresholds;      /* 1: pfp_fm_thresholds_* gave it thresholds (pfp_fm_ms_thr* work) */
 } pfp_fm_info_t;
 /* an index over n_plus_1 device bytes; d_ssa10 / d_esa10 (ssa_bytes / esa_bytes) both NULL: count only.  The index copies
  * what it keeps: the caller may free its buffers afterwards.  *out is set on PFP_OK only (nothing stays allocated otherwise). */
@@ -580,6 +581,64 @@ int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
 /* mem_off (npat + 1) and *mems, a malloc'ed array of 3 mem_off[npat] uint64 (pfp_free; NULL when there are none) */
 int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off,
                 uint64_t **mems);
+
+/* ------------------------------------------------------------------------------------
+ * The LCP array and thresholds of a BWT, and matching statistics in two passes with thresholds (csrc/lcp.hip).  The reference
+ * has no counterpart.  Sources: Karkkainen, Manzini, Puglisi, "Permuted longest-common-prefix array" (CPM 2009); Bannai, Gagie,
+ * I, "Refining the r-index" (2020); Rossi, Oliva, Langmead, Gagie, Boucher, "MONI: a pangenomic index for finding maximal exact
+ * matches" (2022).  Conventions as in "Inverting and checking a BWT": rows j = 0..n, SA[0] = n.
+ *   LCP[0] = 0; for j >= 1, LCP[j] = the length of the common prefix of T[SA[j-1]..n) and T[SA[j]..n).  So LCP[1] = 0.
+ *   Runs k = 0..r-1 of the BWT have start row s_k, end row e_k and byte c_k; prev(k) = the largest k' < k with c_k' = c_k.
+ *   thr[k] = 0 if prev(k) does not exist; otherwise the SMALLEST row t in (e_prev(k), s_k] with LCP[t] = min LCP(e_prev(k), s_k].
+ *     (The range holds at least run k-1 and s_k.)
+ *   Irreducible values: row j starts a run exactly when LCP[j] is irreducible.  Then SA[j] is an .ssa value, SA[j-1] the .esa
+ *     value of the run before, and LCP[j] their longest common extension on the text.  In text order PLCP[i] = PLCP[i0] - (i - i0)
+ *     with i0 the largest run-start SA value <= i (position 0 always is one: the byte before it is the 0), and LCP[j] =
+ *     PLCP[SA[j]]: r extensions and one pass that knows SA[j] at every row (the inverter's walk) give the whole array.
+ * Matching statistics with thresholds, per pattern P of m bytes; len and pos mean what they mean in "Matching statistics".
+ *   Pass 1, for i = m-1 .. 0, state (q, pos) starting from (0, n), c = P[i]:
+ *     1. c is byte 0 or a byte T does not hold: pos[i] = none, the state stays.
+ *     2. BWT[q] = c: q = LF(q), pos -= 1.
+ *     3. otherwise q_p and q_s as in PHONI's step 3.  Only one exists: take it.  Else, with k the run q_s starts: take q_p if
+ *        q < thr[k], else q_s.  With the chosen row x: q = LF(x), pos = SA[x] - 1.
+ *     4. pos[i] = pos.
+ *   Pass 2, for i = 0 .. m-1, starting with l = 0: pos[i] none: l = 0.  Otherwise l = max(l - 1, 0), then l grows while
+ *     i + l < m, pos[i] + l < n and P[i+l] = T[pos[i]+l].  len[i] = l; pos[i] becomes UINT64_MAX where len[i] = 0.
+ *   len equals what pfp_fm_ms* gives.  pos may differ from PHONI's where several positions qualify; it is fixed by the rules
+ *   above, so it depends on the inputs only - not on the batch, the launch budget or the schedule.  Pass 1 reads no text; pass 2
+ *   matches at most m bytes of a pattern of m bytes, whatever the input (PHONI compares O(m^2) in the worst case).
+ * Work per launch is bounded in every kernel and unfinished work resumes from a small record, as in pfp_fm_ms*: an irreducible
+ * value can be as long as the text (a^n has one of n - 1 bytes).  PFP_FM_MS_STEPS=K lowers these bounds too.
+ * Files: <base>.lcp holds n + 1 and <base>.thr_pos r values as 5-byte little-endian ints, like .sa.  This is the project's own
+ * format; MONI's pfp-thresholds is believed to write .thr_pos in the same layout, which has not been checked.
+ * Not checked: the SA values of the samples and that the text is the BWT's (pfp_check_bwt_files checks both); wrong ones, or wrong
+ * thresholds, give wrong answers, never a read outside the index.
+ * Device memory, with w = 4 bytes below 2^32 rows, 8 above: the index keeps w bytes per run more.  Computing LCP or thresholds
+ * peaks at the index with text plus 3 w bytes per row (PLCP, LCP and the walk's LF, all transient) plus 0.1875 bytes per row
+ * (the LF build's histograms) plus at most 16 + 7.75 w bytes per run, plus the scratch of a library scan and of a library sort
+ * of the runs; pfp_lcp_files adds 5 bytes per row and / or per run for the file images.
+ * ------------------------------------------------------------------------------------ */
+#define PFP_LCP_LCP 1
+#define PFP_LCP_THR 2
+/* device pointers as in pfp_fm_build_ms_dev (d_text NULL: inverted); d_lcp (n_plus_1 uint64) and d_thr (runs uint64) may each be
+ * NULL; *runs (NULL ok) gets r, so a call with both NULL tells the size d_thr needs.  Nothing stays allocated. */
+int pfp_lcp_dev(pfp_ctx *ctx, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
+                uint64_t esa_bytes, const void *d_text, uint64_t *d_lcp, uint64_t *d_thr, uint64_t *runs);
+/* reads <base>.bwt / .ssa / .esa, the text as in pfp_fm_build_ms_files; writes <base>.lcp (what & PFP_LCP_LCP) and / or
+ * <base>.thr_pos (what & PFP_LCP_THR) */
+int pfp_lcp_files(pfp_ctx *ctx, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, int what);
+/* gives an index built by pfp_fm_build_ms_* its thresholds: from d_thr5 (device image of a .thr_pos, bytes != 5 r: PFP_EFORMAT;
+ * values above the rows count as the row count), or d_thr5 NULL: computed from the index.  An index without text: PFP_EINVAL. */
+int pfp_fm_thresholds_dev(pfp_fm *fm, const void *d_thr5, uint64_t bytes);
+/* the same from <base>.thr_pos (a file that cannot be read: PFP_EINVAL naming it) */
+int pfp_fm_thresholds_files(pfp_fm *fm, const char *base);
+/* pfp_fm_ms_dev / pfp_fm_ms / pfp_fm_mems by the two passes above; an index without thresholds: PFP_EINVAL.  pfp_fm_mems_dev
+ * works on the outputs of pfp_fm_ms_thr_dev unchanged.  pfp_fm_ms_stats counts their launches (and those that compute
+ * thresholds) and, under PFP_FM_MS_STATS=1, the steps of pass 1 that jumped and the bytes pass 2 matched. */
+int pfp_fm_ms_thr_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos);
+int pfp_fm_ms_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos);
+int pfp_fm_mems_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off,
+                    uint64_t **mems);
 
 /* ---- micro entry points used by bench.py's roofline leg and by the parity tests ---- */
 /* copy a device-resident text into the ctx's padded staging buffer (T' = Dollar.T.Dollar^w) */
