@@ -1,5 +1,6 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
-// reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*.
+// reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
+// of a collection (seqmap.hip).
 #include <memory>
 #include "api.hpp"
 
@@ -7,6 +8,22 @@ using namespace pfp;
 
 struct pfp_fm {
   pfp::FmIndex f;
+};
+
+// a malloc'ed result array that grows group by group
+template <class T>
+struct HostOut {
+  T *p = nullptr;
+  uint64_t n = 0;
+  ~HostOut() { free(p); }
+  // room for `more` entries behind the n held; returns where they go
+  T *grow(uint64_t more) {
+    T *q = (T *)realloc(p, (n + more ? n + more : 1) * sizeof(T));
+    if (!q) throw Error(PFP_ENOMEM, "host malloc failed");
+    p = q;
+    return p + n;
+  }
+  T *release() { T *q = n ? p : nullptr; if (!n) free(p); p = nullptr; return q; }
 };
 
 extern "C" {
@@ -361,6 +378,164 @@ int pfp_lcp_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd
   PFP_CATCH(c)
 }
 
+// ---------------------------------------------------------------- sequences of a collection (seqmap.hip)
+int pfp_fm_set_seqs(pfp_fm *fm, const uint64_t *starts, uint64_t nseq) {
+  if (!fm) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_set_seqs(fm->f, starts, nseq);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_seqmap_dev(pfp_fm *fm, const uint64_t *d_pos, uint64_t count, uint32_t *d_seq, uint64_t *d_off) {
+  if (!fm || (count && !d_pos)) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_seqmap(fm->f, d_pos, count, d_seq, d_off);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_locate_seqs_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
+                           const uint64_t *d_first, uint64_t max_occ, uint64_t *d_out_off, uint32_t *d_seq, uint64_t *d_off) {
+  if (!fm || !d_out_off || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_locate_seqs(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq, d_off);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_doclist_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
+                       const uint64_t *d_first, uint64_t *d_doc_off, uint32_t *d_doc, uint64_t *d_cnt) {
+  if (!fm || !d_doc_off || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  DocOut o;
+  o.doc = d_doc; o.cnt = d_cnt;
+  fm_doclist(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, o);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// host patterns counted on the device, and what plain locate would list for them: uoff = its npat + 1 offsets, on the host
+struct SeqCall {
+  DBuf<uint64_t> off, rng;
+  std::vector<uint64_t> uoff;
+  uint64_t budget = PFP_SEQ_BUDGET;
+  // pattern p's entry of the ranges: which = 0 sp, 1 ep, 2 the toehold
+  const uint64_t *range(uint64_t p, uint64_t npat, int which) const { return rng.p + which * npat + p; }
+  // the end of the group of consecutive patterns that starts at p0: at most `budget` positions, a pattern with more goes alone
+  uint64_t group_end(uint64_t p0, uint64_t npat) const {
+    uint64_t p1 = p0 + 1;
+    while (p1 < npat && uoff[p1 + 1] - uoff[p0] <= budget) p1++;
+    return p1;
+  }
+};
+static void seq_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
+                           SeqCall &s) {
+  pfp_ctx *c = fm->f.c;
+  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  PFP_REQUIRE(fm->f.nseq, PFP_EINVAL, "this index has no sequence table: give it one with pfp_fm_set_seqs (bigbwt -f --seqs writes it)");
+  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
+    const uint64_t v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < s.budget) s.budget = v;
+  }
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16);
+  DBuf<uint64_t> d_uoff(c, npat + 1);
+  s.off.alloc(c, npat + 1);
+  s.rng.alloc(c, 3 * npat + 1);
+  s.uoff.assign(npat + 1, 0);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  if (npat) h2d(c, s.off.p, pat_off, npat + 1);
+  fm_count(fm->f, d_pat.p, s.off.p, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat);
+  fm_locate(fm->f, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat, max_occ, d_uoff.p, nullptr);
+  d2h(c, s.uoff.data(), d_uoff.p, npat + 1);
+  if (sp) d2h(c, sp, s.rng.p, npat);
+  if (ep) d2h(c, ep, s.rng.p + npat, npat);
+  sync(c);
+}
+int pfp_fm_locate_seqs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp,
+                       uint64_t *ep, uint64_t *out_off, uint32_t **seq, uint64_t **off) {
+  if (!fm || !out_off || !seq || !off || (npat && !pat_off)) return PFP_EINVAL;
+  *seq = nullptr; *off = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  SeqCall s;
+  seq_call_begin(fm, pat, pat_off, npat, max_occ, sp, ep, s);
+  HostOut<uint32_t> h_seq;
+  HostOut<uint64_t> h_off;
+  std::vector<uint64_t> go;
+  out_off[0] = 0;
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
+    p1 = s.group_end(p0, npat);
+    const uint64_t k = p1 - p0, U = s.uoff[p1] - s.uoff[p0];
+    DBuf<uint64_t> d_go(c, k + 1), d_o(c, U);
+    DBuf<uint32_t> d_s(c, U);
+    fm_locate_seqs(fm->f, s.off.p + p0, k, s.range(p0, npat, 0), s.range(p0, npat, 1), s.range(p0, npat, 2), max_occ, d_go.p, d_s.p, d_o.p);
+    go.resize(k + 1);
+    d2h(c, go.data(), d_go.p, k + 1);
+    sync(c);
+    for (uint64_t i = 1; i <= k; i++) out_off[p0 + i] = out_off[p0] + go[i];
+    const uint64_t kept = go[k];
+    if (kept) {
+      download(c, h_seq.grow(kept), (const uint8_t *)d_s.p, kept * 4);
+      sync(c);      // (the next download fills the same pinned buffers)
+      download(c, h_off.grow(kept), (const uint8_t *)d_o.p, kept * 8);
+      sync(c);
+      h_seq.n += kept; h_off.n += kept;
+    }
+  }
+  *seq = h_seq.release();
+  *off = h_off.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_doclist(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *doc_off, uint32_t **doc,
+                   uint64_t **cnt) {
+  if (!fm || !doc_off || !doc || !cnt || (npat && !pat_off)) return PFP_EINVAL;
+  *doc = nullptr; *cnt = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  SeqCall s;
+  seq_call_begin(fm, pat, pat_off, npat, 0, nullptr, nullptr, s);
+  HostOut<uint32_t> h_doc;
+  HostOut<uint64_t> h_cnt;
+  std::vector<uint64_t> go;
+  doc_off[0] = 0;
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
+    p1 = s.group_end(p0, npat);
+    const uint64_t k = p1 - p0;
+    DBuf<uint64_t> d_go(c, k + 1), d_c;
+    DBuf<uint32_t> d_d;
+    DocOut o;
+    o.own_doc = &d_d; o.own_cnt = &d_c;      // (sized inside, once the group's total is known: nothing is listed twice)
+    fm_doclist(fm->f, s.off.p + p0, k, s.range(p0, npat, 0), s.range(p0, npat, 1), s.range(p0, npat, 2), d_go.p, o);
+    go.resize(k + 1);
+    d2h(c, go.data(), d_go.p, k + 1);
+    sync(c);
+    for (uint64_t i = 1; i <= k; i++) doc_off[p0 + i] = doc_off[p0] + go[i];
+    const uint64_t docs = go[k];
+    if (docs) {
+      download(c, h_doc.grow(docs), (const uint8_t *)d_d.p, docs * 4);
+      sync(c);
+      download(c, h_cnt.grow(docs), (const uint8_t *)d_c.p, docs * 8);
+      sync(c);
+      h_doc.n += docs; h_cnt.n += docs;
+    }
+  }
+  *doc = h_doc.release();
+  *cnt = h_cnt.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
 int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
   if (!fm || !out) return PFP_EINVAL;
   memset(out, 0, sizeof *out);
@@ -371,6 +546,7 @@ int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out) {
   out->device_bytes = fm->f.device_bytes();
   out->has_samples = fm->f.samples ? 1 : 0;
   out->has_thresholds = fm->f.has_thr ? 1 : 0;
+  out->nseq = fm->f.nseq;
   return PFP_OK;
 }
 

@@ -96,6 +96,22 @@ __device__ __forceinline__ uint64_t select_first(const FmArgs<I> &a, uint64_t sp
   return j >= sp && j < ep ? j : ~0ull;
 }
 
+// the bucket directory of a predecessor search over sorted keys: dir[b] = first index of a key >= b << shift (b = 0..nbk).  A
+// search for x then starts in [dir[x >> shift], dir[(x >> shift) + 1]): about one key with the shift its callers choose
+template <class K, class D>
+__global__ void __launch_bounds__(kTB) bucket_dir_k(const K *__restrict__ key, uint64_t nkeys, uint64_t nbk, int shift, D *__restrict__ dir) {
+  const uint64_t b = BID * kTB + threadIdx.x;
+  if (b > nbk) return;
+  const uint64_t x = b << shift;
+  uint64_t lo = 0, hi = nkeys;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)key[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  dir[b] = (D)lo;
+}
+
 constexpr uint64_t kMsWork = 16384;         // units of work per pattern and launch: one per step, one per 1024 bytes compared
 struct MsRec { uint64_t t, q, pos, l; };    // the next byte to read is pat[t - 1]; SA[q] = pos; l bytes matched to the right of it
 

@@ -137,21 +137,6 @@ __global__ void __launch_bounds__(kTB) fm_pairs(const uint8_t *__restrict__ ssa,
   }
 }
 
-// dir[b] = first index of a key >= b << shift (b = 0..nbk; the keys are sorted)
-template <class I>
-__global__ void __launch_bounds__(kTB) fm_phidir(const I *__restrict__ key, uint64_t nkeys, uint64_t nbk, int shift, I *__restrict__ dir) {
-  const uint64_t b = BID * kTB + threadIdx.x;
-  if (b > nbk) return;
-  const uint64_t x = b << shift;
-  uint64_t lo = 0, hi = nkeys;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if ((uint64_t)key[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  dir[b] = (I)lo;
-}
-
 // ---------------------------------------------------------------- searches
 // one group of 16 lanes per pattern
 template <class I>
@@ -444,7 +429,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
   f.phi_dir.alloc(c, (f.nbk + 1) * sizeof(I));
   {
     KScope ks(c, "fm_phidir", (f.nbk + 1) * sizeof(I) * 8);
-    fm_phidir<I><<<gdim(cdiv(f.nbk + 1, kTB)), kTB, 0, c->stream>>>((const I *)f.phi_key.p, f.nphi, f.nbk, f.shift, (I *)f.phi_dir.p);
+    bucket_dir_k<I, I><<<gdim(cdiv(f.nbk + 1, kTB)), kTB, 0, c->stream>>>((const I *)f.phi_key.p, f.nphi, f.nbk, f.shift, (I *)f.phi_dir.p);
     PFP_HIP(hipGetLastError());
   }
   f.samples = true;
@@ -456,7 +441,8 @@ uint64_t fm_bwt_bytes(uint64_t n1) { return ((n1 >> kBlkLog) + 1) << kBlkLog; }
 
 uint64_t FmIndex::device_bytes() const {
   return bwt.bytes() + codes.bytes() + blk.bytes() + sbc.bytes() + rs.bits.bytes() + rs.dir.bytes() + rs_row.bytes() + rs_sa.bytes() +
-         phi_key.bytes() + phi_val.bytes() + phi_dir.bytes() + text.bytes() + re_sa.bytes() + thr.bytes();
+         phi_key.bytes() + phi_val.bytes() + phi_dir.bytes() + text.bytes() + re_sa.bytes() + thr.bytes() + seq_start.bytes() +
+         seq_dir.bytes();
 }
 
 void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uint8_t *ssa10, uint64_t ssa_bytes, const uint8_t *esa10,

@@ -316,6 +316,11 @@ struct FmIndex {
   uint64_t ms_stats[3] = {0, 0, 0};      // fm_ms launches; with PFP_FM_MS_STATS=1 also steps that jumped and bytes their LCEs matched
   bool has_thr = false;                  // fm_lcp (keep) or fm_load_thresholds filled the array below
   DBuf<uint8_t> thr;                     // [runs] of I: the threshold row of run k (lcp.hip)
+  uint64_t nseq = 0;                     // sequences of the collection (seqmap.hip); 0: no table was set
+  DBuf<uint8_t> seq_start;               // [nseq + 1] of I: first text position of sequence k; seq_start[nseq] = n
+  DBuf<uint32_t> seq_dir;                // [seq_nbk + 1] first k with seq_start[k] >= b << seq_shift (about one start per bucket)
+  uint64_t seq_nbk = 0;
+  int seq_shift = 0;
   uint64_t device_bytes() const;
 };
 uint64_t fm_bwt_bytes(uint64_t n1);      // f.bwt's size: n1 bytes and the zero padding
@@ -350,6 +355,24 @@ void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
 // out_off[0..npat] (device): exclusive sums of min(ep - sp, max_occ); pos == NULL: only those
 void fm_locate(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
                uint64_t *out_off, uint64_t *pos);
+// the sequences of a collection (seqmap.hip; pfpgpu.h states the definitions).  starts: nseq + 1 host values; replaces a table
+// set before.  The calls below need a table (PFP_EINVAL otherwise)
+void fm_set_seqs(FmIndex &f, const uint64_t *starts, uint64_t nseq);
+// seq[i] (u32) / off[i] (u64) of pos[i]; either output may be NULL
+void fm_seqmap(FmIndex &f, const uint64_t *pos, uint64_t count, uint32_t *seq, uint64_t *off);
+// fm_locate's positions that lie inside one sequence, in row order: out_off[0..npat] exclusive sums of the kept counts; seq / off
+// (room for the unfiltered total, both or neither) get the kept hits
+void fm_locate_seqs(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
+                    uint64_t max_occ, uint64_t *out_off, uint32_t *seq, uint64_t *off);
+// per pattern the distinct sequences of its kept hits, ascending, with their numbers of hits: doc_off[0..npat], and doc / cnt in the
+// caller's device buffers (both NULL: the offsets only) or, where own_doc / own_cnt are given, in buffers allocated once the total is
+// known (a caller that cannot size them without listing twice)
+struct DocOut {
+  uint32_t *doc = nullptr; uint64_t *cnt = nullptr;
+  DBuf<uint32_t> *own_doc = nullptr; DBuf<uint64_t> *own_cnt = nullptr;
+};
+void fm_doclist(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
+                uint64_t *doc_off, DocOut &o);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

@@ -140,6 +140,23 @@ void segsort_pairs_u64_u32(pfp_ctx *c, const uint64_t *kin, uint64_t *kout, cons
                                                      (unsigned)bb, (unsigned)eb, c->stream)));
 }
 
+void segsort_keys_u32(pfp_ctx *c, const uint32_t *kin, uint32_t *kout, size_t n, size_t nseg, const uint32_t *seg_begin,
+                      const uint32_t *seg_end, int bb, int eb) {
+  if (!n || !nseg) return;
+  PFP_REQUIRE(n < 0xFFFFFFFFull, PFP_ELIMIT, "segmented sort of 2^32 or more elements");
+  KScope ks(c, "rocprim::segmented_radix_sort_keys<u32>", n * 8 + nseg * 8);
+  PRIM2((rocprim::segmented_radix_sort_keys<SegCfg>(tmp, tb, kin, kout, (unsigned)n, (unsigned)nseg, seg_begin, seg_end, (unsigned)bb,
+                                                    (unsigned)eb, c->stream)));
+}
+
+struct NeU32 { uint32_t v; __host__ __device__ uint64_t operator()(uint32_t x) const { return x != v; } };
+void exclusive_count_ne_u32(pfp_ctx *c, const uint32_t *in, uint32_t value, uint64_t *out, size_t n) {
+  if (!n) return;
+  auto it = rocprim::make_transform_iterator(in, NeU32{value});
+  KScope ks(c, "rocprim::scan<u32->u64>", n * 12);
+  PRIM2(rocprim::exclusive_scan(tmp, tb, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream));
+}
+
 void exclusive_sum_u32(pfp_ctx *c, const uint32_t *in, uint32_t *out, size_t n) {
   if (!n) return;
   KScope ks(c, "rocprim::scan<u32>", n * 8);

@@ -21,6 +21,8 @@
  * PFP_MULTI_PYTHON=1 starts N processes of ../dist_main.py under torch.distributed instead (the driver the bench uses).
  * --verify checks the files just written by inverting the BWT on the GPU (pfp_check_bwt_files: O(n), no suffix sort), the
  * way the reference's readme suggests for inputs too large for -c; exit status 1 on any difference.
+ * -f --seqs also writes input.seqs, the sequence table of the text -f builds (seqs.h): the records are concatenated with no
+ * separator, and the table is what lets `bwtsearch --seqs` keep a match inside one record and name it.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -131,7 +133,7 @@ static int run_ranks(int gpus, const char *textfile, const char *base, int w, un
 }
 
 static void usage(const char *argv0) {
-  printf("usage: %s [-h] [-w WSIZE] [-p MOD] [-t T] [-s] [-e] [-S] [-k] [-v] [-c] [-f] [--sum]\n"
+  printf("usage: %s [-h] [-w WSIZE] [-p MOD] [-t T] [-s] [-e] [-S] [-k] [-v] [-c] [-f] [--seqs] [--sum]\n"
          "              [--parsing] [--compress] [--probing] [-G N] [--verify] input\n\n"
          "MI355X build of the prefix-free-parsing BWT tool (drop-in for alshai/Big-BWT's bigbwt).\n\n"
          "  input            input file name\n"
@@ -145,6 +147,7 @@ static void usage(const char *argv0) {
          "  -v               verbose\n"
          "  -c               check BWT against the whole-text suffix array (reference: SACA-K)\n"
          "  -f               read fasta/fastq, plain or gzip (headers and newlines dropped, upper-cased)\n"
+         "      --seqs       with -f: also write input.seqs, one line name<TAB>start<TAB>length per record (for bwtsearch --seqs)\n"
          "  --sum            compute output files sha256sum\n"
          "      --verify     check the outputs by inverting the BWT on the GPU (exit 1 on any difference; not with --parsing / --compress)\n"
          "  --parsing        stop after the parsing phase (debug only)\n"
@@ -160,7 +163,7 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
   const double t_main = now_s();
   int w = 10, th = 0, s = 0, e = 0, S = 0, keep = 0, verbose = 0, check = 0, fasta = 0, sum = 0, parsing = 0,
-      compress = 0, device = 0, gpus = 1, verify = 0;
+      compress = 0, device = 0, gpus = 1, verify = 0, seqs = 0;
   unsigned long long p = 100, halo = 1ull << 20;
   double density = 0;
   static struct option lo[] = {{"wsize", required_argument, 0, 'w'}, {"mod", required_argument, 0, 'p'},
@@ -169,6 +172,7 @@ int main(int argc, char **argv) {
                                {"device", required_argument, 0, 1003}, {"help", no_argument, 0, 'h'},
                                {"gpus", required_argument, 0, 'G'},  {"halo", required_argument, 0, 1004},
                                {"density", required_argument, 0, 1005}, {"verify", no_argument, 0, 1006},
+                               {"seqs", no_argument, 0, 1007},
                                {0, 0, 0, 0}};
   int c;
   while ((c = getopt_long(argc, argv, "w:p:t:seSkvcfPhG:", lo, NULL)) != -1) {
@@ -191,6 +195,7 @@ int main(int argc, char **argv) {
       case 1004: halo = strtoull(optarg, NULL, 10); break;
       case 1005: density = atof(optarg); break;
       case 1006: verify = 1; break;
+      case 1007: seqs = 1; break;
       case 'G': gpus = atoi(optarg); break;
       case 'h': usage(argv[0]); return 0;
       default: usage(argv[0]); return 2;
@@ -199,6 +204,7 @@ int main(int argc, char **argv) {
   if (optind + 1 != argc) { usage(argv[0]); return 2; }
   const char *input = argv[optind];
   (void)th;
+  if (seqs && !fasta) { usage(argv[0]); return 2; }      /* the table describes the records -f reads */
   if (S && (s || e)) {   /* bigbwt:59-61 */
     printf("You can either compute the full SA or a sample of it, not both. Exiting...\n");
     return 0;
@@ -237,7 +243,16 @@ int main(int argc, char **argv) {
     if (!raw) { perror(input); return 1; }
     uint8_t *seq = malloc(raw_n ? raw_n : 1);
     if (!seq) { fprintf(stderr, "out of memory\n"); return 1; }
-    n = pfp_fasta_text(raw, raw_n, seq);
+    pfp_seqs tab;
+    pfp_seqs_init(&tab);
+    n = pfp_fasta_text_seqs(raw, raw_n, seq, seqs ? &tab : NULL);
+    if (n == (size_t)-1) { fprintf(stderr, "out of memory\n"); return 1; }
+    if (seqs) {      /* made where the filtered text is made: the same for one GPU and for -G N */
+      char name[4096 + 8];
+      snprintf(name, sizeof name, "%s.seqs", input);
+      if (pfp_seqs_write(name, &tab)) { perror(name); return 1; }
+      pfp_seqs_free(&tab);
+    }
     free(raw);
     text = seq;
   } else {

@@ -2,6 +2,7 @@
  *
  *   bwtsearch [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
  *   bwtsearch --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
+ *   bwtsearch -l --seqs[=FILE] | --docs [--seqs=FILE] ... PATTERNFILE basename        (any mode: --rc)
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -13,8 +14,16 @@
  * inverting basename.bwt.  --thresholds computes them in two passes with thresholds (the same lengths; positions by that
  * algorithm's own rule): it reads basename.thr_pos if that file exists (unbwt --thresholds writes it) and computes the thresholds
  * otherwise.
+ * --seqs[=FILE] loads the sequence table of a collection (seqs.h; FILE defaults to basename.seqs, which bigbwt -f --seqs writes).
+ * With -l the line becomes `count<TAB>name:offset name:offset ...`: of the at most MAXOCC rows examined, the hits that lie inside
+ * one sequence, each as its sequence's name and the offset in it (the offset is what follows the LAST ':': names may hold one).
+ * count stays ep - sp, the rows - matches that span two sequences included.  --docs (implies --seqs) prints
+ * `ndocs<TAB>name:hits name:hits ...`: the sequences that hold the pattern inside them, in table order, with their numbers of
+ * hits; every occurrence counts.  --rc searches every line as given and then as its reverse complement (reversed, A<->T, C<->G,
+ * a<->t, c<->g, other bytes as they are): two output lines per input line, in that order, in every mode.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
- * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, 2 a usage error.
+ * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
+ * malformed or does not sum to the text's length, 2 a usage error.
  */
 #define _GNU_SOURCE
 #include <fcntl.h>
@@ -27,10 +36,12 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include "pfpgpu.h"
+#include "seqs.h"
 
 static void usage(const char *argv0) {
-  printf("usage: %s [-h] [-l] [-m MAXOCC] [--device D] PATTERNFILE basename\n"
-         "       %s --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename\n\n"
+  printf("usage: %s [-h] [-l] [-m MAXOCC] [--seqs[=FILE]] [--rc] [--device D] PATTERNFILE basename\n"
+         "       %s --docs [--seqs=FILE] [--rc] [--device D] PATTERNFILE basename\n"
+         "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -41,8 +52,14 @@ static void usage(const char *argv0) {
          "      --mems L    print count<TAB>i:len:pos ... : the maximal exact matches of at least L >= 1 bytes; reads the same files\n"
          "      --text FILE with --ms / --mems: the text (def. inverted from basename.bwt)\n"
          "      --thresholds with --ms / --mems: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
+         "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
+         "                  count<TAB>name:offset ... : the hits inside one sequence among the at most MAXOCC rows examined;\n"
+         "                  count stays the number of rows, matches that span two sequences included\n"
+         "      --docs      print ndocs<TAB>name:hits ... : the sequences that hold the pattern, in table order (implies --seqs;\n"
+         "                  reads basename.ssa and .esa; every occurrence counts)\n"
+         "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0);
+         argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -68,12 +85,27 @@ static int read_file(const char *path, uint8_t **out, uint64_t *len) {
   return 0;
 }
 
+/* out = the reverse complement of the len bytes at in */
+static void revcomp(const uint8_t *in, uint64_t len, uint8_t *out) {
+  static uint8_t map[256];
+  if (!map['A']) {
+    for (int i = 0; i < 256; i++) map[i] = (uint8_t)i;
+    map['A'] = 'T'; map['T'] = 'A'; map['C'] = 'G'; map['G'] = 'C';
+    map['a'] = 't'; map['t'] = 'a'; map['c'] = 'g'; map['g'] = 'c';
+  }
+  for (uint64_t i = 0; i < len; i++) out[i] = map[in[len - 1 - i]];
+}
+
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0;
+  const char *seqsfile = NULL;
+  pfp_seqs tab;
+  pfp_seqs_init(&tab);
   uint64_t maxocc = 0, min_len = 0;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
+                               {"seqs", optional_argument, 0, 1006}, {"docs", no_argument, 0, 1007}, {"rc", no_argument, 0, 1008},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -93,6 +125,9 @@ int main(int argc, char **argv) {
         break;
       case 1004: textfile = optarg; break;
       case 1005: thresholds = 1; break;
+      case 1006: seqs = 1; if (optarg) seqsfile = optarg; break;
+      case 1007: docs = seqs = 1; break;
+      case 1008: rcomp = 1; break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -102,7 +137,10 @@ int main(int argc, char **argv) {
     }
   }
   if (optind + 2 != argc) { usage(argv[0]); return 2; }
-  if (ms + mems + locate > 1 || ((ms || mems) && have_m) || ((textfile || thresholds) && !ms && !mems)) { usage(argv[0]); return 2; }
+  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems) || ((ms || mems) && seqs)) {
+    usage(argv[0]);
+    return 2;
+  }
   const char *patfile = argv[optind], *base = argv[optind + 1];
 
   uint8_t *pats = NULL;
@@ -156,7 +194,7 @@ int main(int argc, char **argv) {
       if (rc) { pfp_fm_free(fm); fm = NULL; }
     }
   } else {
-    rc = pfp_fm_build_files(ctx, base, locate ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
+    rc = pfp_fm_build_files(ctx, base, locate || docs ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
   }
   if (rc) {
     fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
@@ -165,13 +203,33 @@ int main(int argc, char **argv) {
     return 1;
   }
 
+  if (seqs) {
+    char name[4096 + 8], err[1024];
+    pfp_fm_info_t inf;
+    if (!seqsfile) { snprintf(name, sizeof name, "%s.seqs", base); seqsfile = name; }
+    pfp_fm_info(fm, &inf);
+    if (pfp_seqs_read(seqsfile, inf.n, &tab, err, sizeof err)) {
+      fprintf(stderr, "%s\n", err);
+      rc = 1;
+    } else if ((rc = pfp_fm_set_seqs(fm, tab.start, tab.nseq)) != 0) {
+      fprintf(stderr, "%s: %s: %s\n", seqsfile, pfp_strerror(rc), pfp_last_error(ctx));
+    }
+    if (rc) {
+      pfp_seqs_free(&tab);
+      pfp_fm_free(fm);
+      pfp_ctx_destroy(ctx);
+      free(pats); free(lstart);
+      return 1;
+    }
+  }
+
   uint64_t batch = 1 << 20;
   const char *env = getenv("PFP_FM_BATCH");
   if (env && strtoull(env, NULL, 10) > 0) batch = strtoull(env, NULL, 10);
-  const uint64_t max_bytes = 64ull << 20;
-  uint64_t *off = malloc((batch + 1) * sizeof(uint64_t)), *oo = malloc((batch + 1) * sizeof(uint64_t));
-  uint64_t *sp = malloc(batch * sizeof(uint64_t)), *ep = malloc(batch * sizeof(uint64_t));
-  uint8_t *buf = malloc(max_bytes + 1);
+  const uint64_t max_bytes = 64ull << 20, mult = rcomp ? 2 : 1;      /* --rc: every line gives two patterns */
+  uint64_t *off = malloc((mult * batch + 1) * sizeof(uint64_t)), *oo = malloc((mult * batch + 1) * sizeof(uint64_t));
+  uint64_t *sp = malloc(mult * batch * sizeof(uint64_t)), *ep = malloc(mult * batch * sizeof(uint64_t));
+  uint8_t *buf = malloc(mult * max_bytes + 1), *big = NULL;
   if (!off || !oo || !sp || !ep || !buf) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
   static char obuf[1 << 20];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
@@ -186,15 +244,29 @@ int main(int argc, char **argv) {
     }
     const uint8_t *src = pats + lstart[p0];
     const uint8_t *pat = src;
-    if (bytes <= max_bytes) {
-      /* the lines without their '\n' */
-      off[0] = 0;
-      for (uint64_t i = 0; i < k; i++) {
-        const uint64_t len = lstart[p0 + i + 1] - 1 - lstart[p0 + i];
-        memcpy(buf + off[i], pats + lstart[p0 + i], len);
-        off[i + 1] = off[i] + len;
+    const uint64_t lines = k;
+    if (bytes <= max_bytes || rcomp) {
+      /* the lines without their '\n' (--rc: each followed by its reverse complement) */
+      uint8_t *dst = buf;
+      if (bytes > max_bytes) {
+        free(big);
+        dst = big = malloc(2 * bytes + 1);
+        if (!big) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
       }
-      pat = buf;
+      off[0] = 0;
+      k = 0;
+      for (uint64_t i = 0; i < lines; i++) {
+        const uint64_t len = lstart[p0 + i + 1] - 1 - lstart[p0 + i];
+        memcpy(dst + off[k], pats + lstart[p0 + i], len);
+        off[k + 1] = off[k] + len;
+        k++;
+        if (rcomp) {
+          revcomp(pats + lstart[p0 + i], len, dst + off[k]);
+          off[k + 1] = off[k] + len;
+          k++;
+        }
+      }
+      pat = dst;
     } else {
       off[0] = 0; off[1] = bytes;
     }
@@ -225,6 +297,28 @@ int main(int argc, char **argv) {
         putchar('\n');
       }
       pfp_free(m);
+    } else if (docs) {
+      uint32_t *doc = NULL;
+      uint64_t *cnt = NULL;
+      rc = pfp_fm_doclist(fm, pat, off, k, oo, &doc, &cnt);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);
+        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %s:%" PRIu64 : "%s:%" PRIu64, tab.name[doc[j]], cnt[j]);
+        putchar('\n');
+      }
+      pfp_free(doc); pfp_free(cnt);
+    } else if (locate && seqs) {
+      uint32_t *sq = NULL;
+      uint64_t *so = NULL;
+      rc = pfp_fm_locate_seqs(fm, pat, off, k, maxocc, sp, ep, oo, &sq, &so);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        printf("%" PRIu64 "\t", ep[i] - sp[i]);
+        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %s:%" PRIu64 : "%s:%" PRIu64, tab.name[sq[j]], so[j]);
+        putchar('\n');
+      }
+      pfp_free(sq); pfp_free(so);
     } else if (locate) {
       uint64_t *pos = NULL;
       rc = pfp_fm_locate(fm, pat, off, k, maxocc, sp, ep, oo, &pos);
@@ -240,13 +334,14 @@ int main(int argc, char **argv) {
       if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
       for (uint64_t i = 0; i < k; i++) printf("%" PRIu64 "\n", ep[i] - sp[i]);
     }
-    p0 += k;
+    p0 += lines;
   }
   rc = 0;
 done:
   if (fflush(stdout) != 0 && !rc) { fprintf(stderr, "Error writing the output\n"); rc = 1; }
   pfp_fm_free(fm);
   pfp_ctx_destroy(ctx);
-  free(off); free(oo); free(sp); free(ep); free(buf); free(pats); free(lstart);
+  pfp_seqs_free(&tab);
+  free(off); free(oo); free(sp); free(ep); free(buf); free(big); free(pats); free(lstart);
   return rc;
 }

@@ -9,7 +9,10 @@
 #include <string.h>
 #include <zlib.h>
 
-size_t pfp_fasta_text(const uint8_t *in, size_t n, uint8_t *out) {
+size_t pfp_fasta_text(const uint8_t *in, size_t n, uint8_t *out) { return pfp_fasta_text_seqs(in, n, out, NULL); }
+
+/* the one scanner: the text, and for a caller that wants it one table line per record DELIVERED (its name, the bytes it gave) */
+size_t pfp_fasta_text_seqs(const uint8_t *in, size_t n, uint8_t *out, pfp_seqs *tab) {
   size_t pos = 0, o = 0;
   int last_char = 0;
   for (;;) {
@@ -21,7 +24,9 @@ size_t pfp_fasta_text(const uint8_t *in, size_t n, uint8_t *out) {
     }
     /* header: name up to white space, then the rest of the line */
     if (pos >= n) return o;
+    const size_t name0 = pos;
     while (pos < n && !isspace(in[pos])) pos++;
+    const size_t name_len = pos - name0;
     if (pos < n) { int d = in[pos++]; if (d != '\n') { while (pos < n && in[pos] != '\n') pos++; if (pos < n) pos++; } }
     /* sequence lines */
     size_t rec0 = o;
@@ -57,11 +62,14 @@ size_t pfp_fasta_text(const uint8_t *in, size_t n, uint8_t *out) {
       if (ql != seqlen) { o = rec0; return o; }
     }
     /* newscan.cpp:338-349: upper-case, stop at the first byte <= Dollar */
+    size_t end = o;
     for (size_t i = rec0; i < o; i++) {
       int u = toupper(out[i]);
-      if (u <= 2) return i;
+      if (u <= 2) { end = i; break; }
       out[i] = (uint8_t)u;
     }
+    if (tab && pfp_seqs_add(tab, (const char *)in + name0, name_len, end - rec0)) return (size_t)-1;
+    if (end < o) return end;                     /* the last record is cut at the stop */
     if (pos >= n && c != '>' && c != '@') return o;
   }
 }

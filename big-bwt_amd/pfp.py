@@ -36,7 +36,8 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
            "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
            "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats",
-           "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr"]
+           "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
+           "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist"]
 
 LCP_LCP, LCP_THR = 1, 2
 
@@ -61,7 +62,38 @@ class CheckResult(C.Structure):
 
 class _FmInfo(C.Structure):
     _fields_ = [("n", C.c_uint64), ("runs", C.c_uint64), ("sigma", C.c_uint32), ("row_bits", C.c_uint32), ("device_bytes", C.c_uint64),
-                ("has_samples", C.c_int), ("has_thresholds", C.c_int)]
+                ("has_samples", C.c_int), ("has_thresholds", C.c_int), ("nseq", C.c_uint64)]
+
+
+class _Seqs(C.Structure):
+    """pfp_seqs of host/seqs.h (libpfphost.so)"""
+    _fields_ = [("nseq", C.c_uint64), ("cap", C.c_uint64), ("start", C.POINTER(C.c_uint64)), ("name", C.POINTER(C.c_char_p))]
+
+
+_RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def reverse_complement(patterns):
+    """each pattern reversed with A<->T, C<->G, a<->t, c<->g swapped; every other byte stays as it is (DNA reads: the other strand)"""
+    return [(p.encode() if isinstance(p, str) else bytes(p)).translate(_RC)[::-1] for p in patterns]
+
+
+def read_seqs_file(path, n):
+    """(names, starts) of a .seqs file (host/seqs.h) whose lengths must sum to n; the parser is the one bwtsearch uses"""
+    host = C.CDLL(os.path.join(HERE, "libpfphost.so"))
+    host.pfp_seqs_read.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(_Seqs), C.c_char_p, C.c_size_t]
+    host.pfp_seqs_free.argtypes = [C.POINTER(_Seqs)]
+    host.pfp_seqs_free.restype = None
+    t, err = _Seqs(), C.create_string_buffer(1024)
+    rc = host.pfp_seqs_read(os.fsencode(path), C.c_uint64(n), C.byref(t), err, len(err))
+    if rc:
+        raise PfpError(-1 if rc == -1 else -6, err.value.decode(errors="replace"))
+    try:
+        names = [t.name[k] for k in range(t.nseq)]
+        starts = np.ctypeslib.as_array(t.start, shape=(t.nseq + 1,)).astype(np.uint64) if t.nseq else np.zeros(1, dtype=np.uint64)
+    finally:
+        host.pfp_seqs_free(C.byref(t))
+    return names, starts
 
 
 def _patterns(patterns):
@@ -132,6 +164,82 @@ class FmIndex:
             positions = np.ctypeslib.as_array(pos, shape=(total,)).copy()
             self.lib.pfp_free(pos)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
+
+    def set_sequences(self, starts):
+        """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the
+        first 0, non-decreasing, the last n; a second call replaces the table"""
+        st = _arr(np.asarray(starts), np.uint64)
+        self.ctx._check(self.lib.pfp_fm_set_seqs(self._h, _ptr(st, C.c_uint64), C.c_uint64(max(len(st), 1) - 1)))
+        return self
+
+    def set_sequences_file(self, path):
+        """the same from a .seqs file (bigbwt -f --seqs writes it; host/seqs.h); -> the names (bytes), in table order"""
+        names, starts = read_seqs_file(path, self.info()["n"])
+        self.set_sequences(starts)
+        return names
+
+    def seqmap(self, positions):
+        """-> (seq uint32, off uint64) of text positions; (2**32 - 1, 2**64 - 1) for a position >= n"""
+        import torch
+        pos = _arr(np.asarray(positions), np.uint64)
+        dev = torch.device("cuda", self.ctx.device)
+        d_pos = torch.from_numpy(pos.view(np.int64).copy()).to(dev)
+        d_seq = torch.zeros(len(pos), dtype=torch.int32, device=dev)
+        d_off = torch.zeros(len(pos), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        self.seqmap_dev(d_pos.data_ptr(), len(pos), d_seq.data_ptr(), d_off.data_ptr())
+        return d_seq.cpu().numpy().view(np.uint32), d_off.cpu().numpy().view(np.uint64)
+
+    def locate_seqs(self, patterns, max_occ=0, ranges=False):
+        """-> (off, seq, offset): the hits of pattern p that lie inside one sequence, among the at most max_occ rows locate() would
+        list (0: all), in row order, are (seq[i], offset[i]) for i in off[p]:off[p+1]; ranges=True: (off, seq, offset, sp, ep)"""
+        pat, poff = _patterns(patterns)
+        npat = len(poff) - 1
+        sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
+        out_off = np.zeros(npat + 1, dtype=np.uint64)
+        seq, off = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
+        u64 = lambda a: _ptr(a, C.c_uint64)
+        self.ctx._check(self.lib.pfp_fm_locate_seqs(self._h, _ptr(pat, C.c_uint8), u64(poff), C.c_uint64(npat), C.c_uint64(max_occ), u64(sp),
+                                                    u64(ep), u64(out_off), C.byref(seq), C.byref(off)))
+        total = int(out_off[-1])
+        seqs, offs = _take(seq, total, np.uint32), _take(off, total, np.uint64)
+        self.lib.pfp_free(seq)
+        self.lib.pfp_free(off)
+        return (out_off, seqs, offs, sp, ep) if ranges else (out_off, seqs, offs)
+
+    def doclist(self, patterns):
+        """-> (off, doc, cnt): the distinct sequences that hold a hit of pattern p inside one sequence are doc[off[p]:off[p+1]]
+        (uint32, ascending) and cnt (uint64) their numbers of such hits; every occurrence counts"""
+        pat, poff = _patterns(patterns)
+        npat = len(poff) - 1
+        doc_off = np.zeros(npat + 1, dtype=np.uint64)
+        doc, cnt = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
+        self.ctx._check(self.lib.pfp_fm_doclist(self._h, _ptr(pat, C.c_uint8), _ptr(poff, C.c_uint64), C.c_uint64(npat),
+                                                _ptr(doc_off, C.c_uint64), C.byref(doc), C.byref(cnt)))
+        total = int(doc_off[-1])
+        docs, cnts = _take(doc, total, np.uint32), _take(cnt, total, np.uint64)
+        self.lib.pfp_free(doc)
+        self.lib.pfp_free(cnt)
+        return doc_off, docs, cnts
+
+    def seqmap_dev(self, d_pos, count, d_seq=None, d_off=None):
+        """device pointers: count uint64 positions -> uint32 d_seq / uint64 d_off (either may be None)"""
+        self.ctx._check(self.lib.pfp_fm_seqmap_dev(self._h, C.c_void_p(d_pos), C.c_uint64(count), C.c_void_p(d_seq) if d_seq else None,
+                                                   C.c_void_p(d_off) if d_off else None))
+
+    def locate_seqs_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq=None, d_off=None):
+        """device pointers from count_dev -> npat+1 offsets of the kept hits; d_seq (uint32) / d_off (uint64), each with room for
+        what locate_dev's offsets-only call reports, get them (both None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_locate_seqs_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
+                                                        C.c_void_p(d_first) if d_first else None, C.c_uint64(max_occ), C.c_void_p(d_out_off),
+                                                        C.c_void_p(d_seq) if d_seq else None, C.c_void_p(d_off) if d_off else None))
+
+    def doclist_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, d_doc=None, d_cnt=None):
+        """device pointers from count_dev -> npat+1 offsets of the documents; d_doc (uint32) / d_cnt (uint64), room for
+        offsets[npat] each, get them (both None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_doclist_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
+                                                    C.c_void_p(d_first) if d_first else None, C.c_void_p(d_doc_off),
+                                                    C.c_void_p(d_doc) if d_doc else None, C.c_void_p(d_cnt) if d_cnt else None))
 
     def add_thresholds(self, thr=None):
         """give the index its thresholds (pfpgpu.h, "The LCP array and thresholds"): thr=None computes them on the GPU, else the

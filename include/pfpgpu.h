@@ -497,6 +497,7 @@ typedef struct {
   uint64_t device_bytes;   /* device memory the index holds */
   int has_samples;         /* 1: built with .ssa / .esa (locate works) */
   int has_thresholds;      /* 1: pfp_fm_thresholds_* gave it thresholds (pfp_fm_ms_thr* work) */
+  uint64_t nseq;           /* sequences of the table pfp_fm_set_seqs gave it (0: none) */
 } pfp_fm_info_t;
 /* an index over n_plus_1 device bytes; d_ssa10 / d_esa10 (ssa_bytes / esa_bytes) both NULL: count only.  The index copies
  * what it keeps: the caller may free its buffers afterwards.  *out is set on PFP_OK only (nothing stays allocated otherwise). */
@@ -639,6 +640,70 @@ int pfp_fm_ms_thr_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, 
 int pfp_fm_ms_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos);
 int pfp_fm_mems_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off,
                     uint64_t **mems);
+
+/* ------------------------------------------------------------------------------------
+ * Sequences of a collection: locate that stays inside one sequence, positions as (sequence, offset), and document listing
+ * (csrc/seqmap.hip).  The reference has no counterpart.  `bigbwt -f` concatenates the records of a FASTA / FASTQ file with no
+ * separator, so the index alone cannot tell a match inside a record from one that begins in the tail of a record and ends in
+ * the head of the next; `bigbwt -f --seqs` also writes the table these calls need (host/seqs.h: the <base>.seqs format).
+ * Conventions as in "Searching a BWT".  A table is nseq + 1 values starts[0..nseq] with starts[0] = 0, starts[k] <= starts[k+1]
+ * and starts[nseq] = n: sequence k is T[starts[k] .. starts[k+1]), and it may be empty.
+ *   seq(x), for a text position x < n: the one k with starts[k] <= x < starts[k+1] - never an empty sequence; off(x) = x - starts[k].
+ *     For x >= n (SA[0] = n, and UINT64_MAX, the "none" of matching statistics): seq = UINT32_MAX, off = UINT64_MAX.
+ *   kept: an occurrence x of a pattern of m bytes is kept when x < n and x + m <= starts[seq(x) + 1]: it lies inside one sequence.
+ *     The empty pattern keeps every x < n.
+ *   locate with sequences: the positions pfp_fm_locate_dev lists for the same arguments (row order, at most max_occ ROWS per
+ *     pattern, 0: all) that are kept, still in row order, as (seq, off).  The cap applies before the filter.
+ *   document listing: per pattern the distinct seq(x) over ALL its kept occurrences (no cap), by increasing sequence number, each
+ *     with its number of kept occurrences.  The results depend on the inputs only - not on the batch or the schedule.
+ * Checked by pfp_fm_set_seqs: the three rules above and nseq in [1, 2^32 - 2] (else PFP_EINVAL naming the first bad entry).  Not
+ * checked: that the table is the one the text was built with - another table of the same total gives answers for that table.
+ * Every other call of this section on an index without a table: PFP_EINVAL.
+ * Method.  seq(x) is a predecessor search, done as phi^-1 does it: a directory over text positions with about one start per
+ * bucket, then a binary search among the bucket's starts.  Locate with sequences: the plain locate, one lane per position for
+ * seq(x) and the test, a library scan of the flags, a scatter.  Document listing, on the kept hits: with at most 4096 sequences one
+ * workgroup per 32768 hits of a pattern counts them in an LDS histogram (a pattern with more hits is split, its pieces meet in
+ * a counter row in device memory) and the non-zero counters are written in order; with more sequences each pattern's
+ * sequence numbers are sorted by the library's segmented sort and run-length encoded.  Work per launch is bounded in every
+ * kernel (PFP_FM_MS_STEPS=K lowers the hits per workgroup to K: tests).
+ * Device memory, with w = 4 bytes below 2^32 rows, 8 above: the index keeps at most (w + 8) (nseq + 1) + 16 bytes for the table
+ * and its directory (in pfp_fm_info's device_bytes).  With U = the positions plain locate lists for the same arguments (what its
+ * offsets-only call reports) and K <= U the kept ones: pfp_fm_locate_seqs_dev takes 20 U bytes and 8 per pattern on top of
+ * what pfp_fm_locate_dev takes and of the caller's buffers; pfp_fm_doclist_dev takes that and 4 K + 8 per pattern, then - the
+ * 20 U released - at most 16 K + 8 bytes per document listed + 16 per pattern (sort regime) or 5 K + 48 per pattern (histogram
+ * regime: 4 K, and 8 nseq per pattern of more than 32768 kept hits), plus the scratch of the library's scans and sort.  2^32 - 1
+ * or more kept hits in one call of the sort regime: PFP_ELIMIT.
+ * The host-buffer calls bound this: they hold at most PFP_SEQ_BUDGET = 2^26 located positions on the device at once (at most 32
+ * bytes each with their own output buffers, 2.1 GB, plus locate's 24 per segment) and take the patterns of a call in consecutive
+ * groups under that budget; a pattern with more positions goes alone.  The sizes come from the offsets-only locate, so no
+ * pattern is located twice.  On top of that they keep 40 bytes per pattern of the call on the device.  PFP_FM_SEQ_BUDGET=K in the
+ * environment, read per call, lowers the budget (tests).
+ * ------------------------------------------------------------------------------------ */
+#define PFP_SEQ_BUDGET (1ull << 26)
+/* starts: nseq + 1 host values.  The index copies them (as u32 below 2^32 rows, u64 above) and builds the directory; a second
+ * call replaces the table. */
+int pfp_fm_set_seqs(pfp_fm *fm, const uint64_t *starts, uint64_t nseq);
+/* device pointers: d_seq (uint32) and d_off (uint64) get seq(x) and off(x) of the count positions d_pos; either may be NULL.  Any
+ * positions do: locate's, those of matching statistics, or the third column of MEM triples gathered by the caller. */
+int pfp_fm_seqmap_dev(pfp_fm *fm, const uint64_t *d_pos, uint64_t count, uint32_t *d_seq, uint64_t *d_off);
+/* device pointers; d_pat_off / npat / d_sp / d_ep / d_first / max_occ as pfp_fm_count_dev gave and pfp_fm_locate_dev takes them
+ * (only the patterns' lengths are read from d_pat_off).  d_out_off (npat + 1): exclusive sums of the kept counts, so
+ * d_out_off[npat] is the number kept.  d_seq (uint32) / d_off (uint64): pattern p's kept hits at d_out_off[p] .. d_out_off[p+1];
+ * both need room for the UNFILTERED total, which is what the offsets-only call of pfp_fm_locate_dev reports - one pass is
+ * then enough.  Both NULL: the offsets only; one NULL: PFP_EINVAL. */
+int pfp_fm_locate_seqs_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
+                           const uint64_t *d_first, uint64_t max_occ, uint64_t *d_out_off, uint32_t *d_seq, uint64_t *d_off);
+/* device pointers as above.  d_doc_off (npat + 1): exclusive sums of the patterns' document counts; d_doc (uint32) / d_cnt
+ * (uint64), room for d_doc_off[npat] each: the documents and their hit counts.  Both NULL: the offsets only. */
+int pfp_fm_doclist_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
+                       const uint64_t *d_first, uint64_t *d_doc_off, uint32_t *d_doc, uint64_t *d_cnt);
+/* count, locate and filter with host buffers: sp / ep (NULL ok) get the row ranges, out_off (npat + 1) the offsets of the kept
+ * hits, *seq / *off malloc'ed arrays of out_off[npat] entries (pfp_free; NULL when there are none) */
+int pfp_fm_locate_seqs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp,
+                       uint64_t *ep, uint64_t *out_off, uint32_t **seq, uint64_t **off);
+/* the same for document listing: doc_off (npat + 1), *doc / *cnt malloc'ed arrays of doc_off[npat] entries */
+int pfp_fm_doclist(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *doc_off, uint32_t **doc,
+                   uint64_t **cnt);
 
 /* ---- micro entry points used by bench.py's roofline leg and by the parity tests ---- */
 /* copy a device-resident text into the ctx's padded staging buffer (T' = Dollar.T.Dollar^w) */
