@@ -595,9 +595,9 @@ int pfp_dist_merge(pfp_ctx *c, const void *d_sym, uint64_t P, const void *d_last
       PFP_REQUIRE(so.complete, PFP_EINVAL, "this share of the suffix array is incomplete: redo pfp_dist_global_sort with parts = 1");
       PFP_REQUIRE(out_hi - out_lo == ds->local_total, PFP_EINVAL, "output range does not match this share's occurrence count");
       if (so.N == 0) { empty_share = true; return; }      // an empty share of the key space emits nothing
-      merge_bwt<I>(c, ds->G, ds->ix, so, pb, ds->occ_lex.p, ds->w, flags, ds->local_total, bo, 0, ~0ull, out_lo, n_total + 1);
+      merge_bwt<I>(c, ds->G, ds->ix, so, pb, ds->occ_lex.p, MergeOpts::slot_range(ds->w, flags, ds->local_total, out_lo, n_total + 1), bo);
     } else {
-      merge_bwt<I>(c, ds->G, ds->ix, so, pb, ds->occ_lex.p, ds->w, flags, n_total + 1, bo, out_lo, out_hi);
+      merge_bwt<I>(c, ds->G, ds->ix, so, pb, ds->occ_lex.p, MergeOpts::slice(ds->w, flags, n_total + 1, out_lo, out_hi), bo);
     }
   });
   (void)empty_share;

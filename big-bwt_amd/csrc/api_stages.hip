@@ -413,7 +413,7 @@ int pfp_merge(pfp_ctx *c, const uint8_t *dict, uint64_t dict_size, const uint32_
   bo.d_bwt = d_bwt.p; bo.d_sa = d_sa.p;
   with_width(ord.wide, [&](auto tag) {
     using I = decltype(tag);
-    merge_bwt<I>(c, D, ix, ord.get<I>(), pb, occ_lex.p, w, flags, expect, bo);
+    merge_bwt<I>(c, D, ix, ord.get<I>(), pb, occ_lex.p, MergeOpts::whole(w, flags, expect), bo);
   });
   c->stats.hard_groups = bo.hard_groups; c->stats.hard_chars = bo.hard_chars;
   fetch_outputs(c, d_bwt.p, sa_view(bo), expect, flags, out);

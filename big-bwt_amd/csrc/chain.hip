@@ -120,7 +120,7 @@ static void run_chain_dev(pfp_ctx *c, Chain &ch, uint64_t n, int w, uint64_t p, 
     bo.d_bwt = d_bwt; bo.d_sa = d_sa;
     with_width(ch.ord.wide, [&](auto tag) {
       using I = decltype(tag);
-      merge_bwt<I>(c, ch.D, ch.ix, ch.ord.get<I>(), ch.pb, ch.occ_lex.p, w, flags, ch.n_used + 1, bo);
+      merge_bwt<I>(c, ch.D, ch.ix, ch.ord.get<I>(), ch.pb, ch.occ_lex.p, MergeOpts::whole(w, flags, ch.n_used + 1), bo);
     });
     st.hard_groups = bo.hard_groups; st.hard_chars = bo.hard_chars;
     st.hard_big_groups = bo.hard_big_groups; st.hard_max_chars = bo.hard_max_chars; st.hard_max_members = bo.hard_max_members;

@@ -296,6 +296,14 @@ struct DBuf {
   size_t bytes() const { return n * sizeof(T); }
 };
 
+// counts for an exclusive sum over n + 1 entries, whose last entry is then the total: n elements for the caller to fill and a
+// zeroed one behind them (pad: elements allocated past the n, for kernels that store whole vectors)
+template <class T>
+inline void alloc_counts(pfp_ctx *c, DBuf<T> &b, size_t n, size_t pad = 1, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+  b.alloc(c, n + pad, file, line);
+  PFP_HIP(hipMemsetAsync(b.p + n, 0, sizeof(T), c->stream));
+}
+
 template <class T>
 inline void d2h(pfp_ctx *c, T *dst, const T *src, size_t count) {
   PFP_HIP(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));

@@ -8,6 +8,7 @@ namespace pfp {
 // gfx950 runs with unaligned-access mode on: a dwordx4 global load/store may start at any byte.
 struct __attribute__((packed, aligned(1))) U128u { uint32_t x, y, z, w; };
 struct __attribute__((packed, aligned(1))) U64u { uint64_t v; };
+struct __attribute__((packed, aligned(1))) U16u { uint16_t v; };
 
 __device__ __forceinline__ uint4 ld16u(const uint8_t *p) {
   U128u v = *reinterpret_cast<const U128u *>(p);
@@ -73,6 +74,29 @@ __device__ __forceinline__ void load_flags16(const uint8_t *__restrict__ flags, 
   } else {
     w[0] = w[1] = w[2] = w[3] = 0;
     for (int k = 0; k < 16; k++) if (base + k < n && flags[base + k]) w[k >> 2] |= 1u << (8 * (k & 3));
+  }
+}
+// which of the 16 positions from `base` on of a BWT slice of cnt bytes start a run (run_end = 0: differ from the byte before) or
+// end one (run_end = 1: differ from the byte after), as flag bytes like load_flags16; left / right: the byte just outside the
+// slice, or -1 (then the edge position counts)
+__device__ __forceinline__ void run_mask16(const uint8_t *__restrict__ bwt, uint64_t base, uint64_t cnt, int left, int right,
+                                           int run_end, uint32_t m[4]) {
+  m[0] = m[1] = m[2] = m[3] = 0;
+  if (base >= cnt) return;
+  if (base + 17 <= cnt && base >= 1) {          // interior: both neighbours of all 16 positions are inside the slice
+    const uint4 x = ld16u(bwt + base);
+    const uint4 y = run_end ? ld16u(bwt + base + 1) : ld16u(bwt + base - 1);
+    m[0] = nonzero_bytes(x.x ^ y.x); m[1] = nonzero_bytes(x.y ^ y.y); m[2] = nonzero_bytes(x.z ^ y.z); m[3] = nonzero_bytes(x.w ^ y.w);
+    return;
+  }
+  for (int k = 0; k < 16; k++) {
+    const uint64_t i = base + k;
+    if (i >= cnt) break;
+    const int b = bwt[i];
+    int nb;
+    if (run_end) nb = i + 1 < cnt ? (int)bwt[i + 1] : right;
+    else nb = i ? (int)bwt[i - 1] : left;
+    if (nb < 0 || nb != b) m[k >> 2] |= 1u << (8 * (k & 3));
   }
 }
 // rank in a bitmap with a popcount directory of 512-bit superblocks: set bits of bits[] before bit r (bits[r >> 6] must exist)

@@ -181,7 +181,7 @@ void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder 
 // plain suffix array of a byte string with s[N-1]==0 unique smallest (sacak)
 template <class I> void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrderT<I> &out);
 
-// ---------------------------------------------------------------- stage 2+3 (merge.hip)
+// ---------------------------------------------------------------- the dictionary index and the words' ranks (dictindex.hip)
 struct DictIndex {        // word lookup over the dictionary (wordview.hpp): |D| / 16 + 8 d bytes, no per-position array
   DBuf<uint32_t> blk_word;   // [dsize / 64 + 1] word containing position 64 b
   DBuf<uint64_t> wend;       // [d+1] terminator position of word j (wend[d] = dsize-1)
@@ -199,6 +199,7 @@ template <class I> void compute_lexrank(pfp_ctx *c, const Dictionary &D, SuffixO
 void compute_lexrank_from_slots(pfp_ctx *c, const Dictionary &D, const uint64_t *d_wslot_all, uint32_t parts, DictIndex &ix);
 template <class I> uint64_t count_slot_outputs(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const SuffixOrderT<I> &so, int w);
 
+// ---------------------------------------------------------------- stage 2 (parsebwt.hip)
 struct ParseBWT {         // outputs of bwtparse.c in HBM
   uint64_t P = 0;
   DBuf<uint32_t> ilist;    // [P+1]
@@ -211,6 +212,7 @@ struct ParseBWT {         // outputs of bwtparse.c in HBM
 void parse_bwt(pfp_ctx *c, const uint32_t *parse_sym, uint64_t P, const uint8_t *last, const uint64_t *sai,
                const uint32_t *occ_lex, uint64_t d, ParseBWT &out, const uint32_t *sa_given = nullptr);
 
+// ---------------------------------------------------------------- stage 3 (merge.hip)
 struct BwtOutputs {
   uint64_t n_out = 0;      // n+1
   uint8_t *d_bwt = nullptr;    // [n+1] device, caller-provided
@@ -246,13 +248,30 @@ inline SaView sa_view(const BwtOutputs &o) {
   } else v.dense = o.d_sa;
   return v;
 }
-// emits BWT positions [out_lo,out_hi) into out.d_bwt[0..) / out.d_sa[0..) (default: everything)
+// what merge_bwt is asked for: the window, the outputs (PFP_FLAG_*), the number of positions the slots must emit (0: not
+// checked), and which part of the BWT this call emits into out.d_bwt[0..) / out.d_sa[0..)
+struct MergeOpts {
+  int w = 0, flags = 0;
+  uint64_t expect_n_out = 0;
+  uint64_t out_lo = 0, out_hi = ~0ull;          // positions [out_lo, out_hi) of the order's output are emitted
+  uint64_t pos_base = 0, n_out_global = 0;      // global position of the order's first output; global n + 1 (0: what the order emits)
+  // a whole suffix order, everything it emits
+  static MergeOpts whole(int w, int flags, uint64_t expect_n_out) { MergeOpts o; o.w = w; o.flags = flags; o.expect_n_out = expect_n_out; return o; }
+  // multi-GPU, replicated sort: a whole suffix order, positions [out_lo, out_hi) of it
+  static MergeOpts slice(int w, int flags, uint64_t expect_n_out, uint64_t out_lo, uint64_t out_hi) {
+    MergeOpts o = whole(w, flags, expect_n_out); o.out_lo = out_lo; o.out_hi = out_hi; return o;
+  }
+  // multi-GPU, sort sharded by key range: the held slots are one contiguous range of SA(D); all they emit, expect_n_out positions
+  // that start at position pos_base of the n_out_global of the whole BWT
+  static MergeOpts slot_range(int w, int flags, uint64_t expect_n_out, uint64_t pos_base, uint64_t n_out_global) {
+    MergeOpts o = whole(w, flags, expect_n_out); o.pos_base = pos_base; o.n_out_global = n_out_global; return o;
+  }
+};
 template <class I>
 void merge_bwt(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const SuffixOrderT<I> &so, const ParseBWT &pb,
-               const uint32_t *occ_lex, int w, int flags, uint64_t expect_n_out, BwtOutputs &out, uint64_t out_lo = 0,
-               uint64_t out_hi = ~0ull, uint64_t pos_base = 0, uint64_t n_out_global = 0);
+               const uint32_t *occ_lex, const MergeOpts &o, BwtOutputs &out);
 
-// 5-byte packing and run sampling of finished device outputs
+// ---------------------------------------------------------------- 5-byte packing and run sampling of finished device outputs (runsample.hip)
 void pack5_dev(pfp_ctx *c, const uint64_t *vals, uint64_t cnt, uint8_t *out5);
 void unpack5_dev(pfp_ctx *c, const uint8_t *in5, uint64_t cnt, uint64_t *vals);
 // pairs (pos,sa) packed as 10 bytes each; returns pair count; out buffer allocated inside

@@ -1,6 +1,6 @@
-// merge.hip -- stage 2 (BWT of the parse, inverted lists) and stage 3 (final BWT / SA).
+// merge.hip -- stage 3: the final BWT / SA from the suffix order of the dictionary and the BWT of the parse.
 //
-// Stage 2 replaces bwtparse.c:212-322; stage 3 replaces bwt() (pfbwt.cpp:109-242), its
+// Replaces bwt() (pfbwt.cpp:109-242), its
 // writers fwrite_chars_same_suffix{,_sa,_ssa} (pfbwt.cpp:520-676) and the threaded variant
 // (pfthreads.hpp:83-518).  The reference walks SA(D) serially and fputc()s each char; here
 // the walk is a data-parallel decomposition (the same one pfthreads.hpp:456-493 uses for its
@@ -11,6 +11,7 @@
 //   * groups of equal suffixes whose members disagree (or any multi-word group when SA values
 //     are requested) are merged by rank computation over the members' inverted lists - the
 //     data-parallel form of the reference's heap merge (pfbwt.cpp:537-556).
+// The kernels come first; the host side (struct Merge: one member function per step, run() is the list) closes the file.
 #include "kernels.hpp"
 #include "prims.hpp"
 #include "devutil.hpp"
@@ -22,235 +23,7 @@ namespace pfp {
 static constexpr int TB = 256;
 constexpr int kOffTileLog = 11;      // slots per offset tile (= one expand workgroup): 2048
 
-// ------------------------------------------------------------------ dictionary index
-
-// Word lookup over the dictionary (wordview.hpp): terminators per 64-byte line, scanned, and the word ends from the
-// word table.  |D| / 16 + 8 d bytes instead of the 8 bytes per dictionary byte of pos_word[] / slen[] (rounds 1-2).
-__global__ __launch_bounds__(256) void line_terms_kernel(const uint8_t *__restrict__ b, uint64_t N, uint64_t nlines, uint32_t *__restrict__ cnt) {
-  const uint64_t ln = (uint64_t)BID * 256 + threadIdx.x;
-  if (ln > nlines) return;
-  if (ln == nlines) { cnt[ln] = 0; return; }
-  const uint64_t b0 = ln * 64;
-  const uint32_t nb = N - b0 >= 64 ? 64u : (uint32_t)(N - b0);      // (the padding behind the dictionary is zero, but keep the count exact)
-  const uint4 *line = reinterpret_cast<const uint4 *>(b + b0);
-  uint32_t n = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) if (nb > 16u * q) n += count_term_bytes16(line[q], nb - 16u * q < 16u ? nb - 16u * q : 16u);
-  cnt[ln] = n;
-}
-__global__ void word_ends_kernel(uint32_t d, const uint64_t *__restrict__ woff, const uint32_t *__restrict__ wlen, uint64_t dsize,
-                                 uint64_t *__restrict__ wend) {
-  const uint32_t j = BID * blockDim.x + threadIdx.x;
-  if (j > d) return;
-  wend[j] = j == d ? dsize - 1 : woff[j] + wlen[j];      // the word's 0x01; the final 0x00 is its own word
-}
-
-void build_dict_index(pfp_ctx *c, const Dictionary &D, DictIndex &ix) {
-  const uint64_t N = D.dsize;
-  PFP_REQUIRE(D.woff.p && D.wlen.p, PFP_EINVAL, "dictionary without a word table");
-  PFP_REQUIRE(((uintptr_t)D.bytes.p & 63) == 0, PFP_EINVAL, "dictionary bytes must be 64-byte aligned");
-  const uint64_t nlines = cdiv64(N, 64);
-  DBuf<uint32_t> cnt(c, nlines + 1);
-  ix.blk_word.alloc(c, nlines + 1);
-  ix.wend.alloc(c, D.d + 1);
-  KScope ks(c, "pfp::line_terms_kernel", N + nlines * 12 + D.d * 20);
-  hipLaunchKernelGGL(line_terms_kernel, gdim(cdiv(nlines + 1, TB)), gdim(TB), 0, c->stream, D.bytes.p, N, nlines, cnt.p);
-  exclusive_sum_u32(c, cnt.p, ix.blk_word.p, nlines + 1);
-  hipLaunchKernelGGL(word_ends_kernel, gdim(cdiv((uint64_t)D.d + 1, TB)), gdim(TB), 0, c->stream, (uint32_t)D.d, D.woff.p, D.wlen.p, N, ix.wend.p);
-  PFP_HIP(hipGetLastError());
-}
-
-// word table of a dictionary given as bytes (words + 0x01, closed by 0x00): terminator positions by
-// compaction of the 0x01 bytes, then starts and lengths
-__global__ void words_from_ends_kernel(uint32_t d, const uint64_t *__restrict__ ends, uint64_t dsize, uint64_t *__restrict__ woff,
-                                       uint32_t *__restrict__ wlen) {
-  uint32_t j = BID * blockDim.x + threadIdx.x;
-  if (j == 0) woff[d] = dsize - 1;
-  if (j >= d) return;
-  const uint64_t s0 = j ? (uint64_t)ends[j - 1] + 1 : 0;
-  woff[j] = s0;
-  wlen[j] = (uint32_t)(ends[j] - s0);
-}
-void word_table_from_bytes(pfp_ctx *c, Dictionary &D, uint64_t max_words) {
-  DBuf<uint64_t> ends(c, max_words + 1), cnt(c, 1);
-  select_byte_index<uint64_t>(c, D.bytes.p, kEndOfWord, ends.p, cnt.p, D.dsize);
-  D.d = read_scalar(c, cnt.p);
-  PFP_REQUIRE(D.d <= max_words, PFP_EFORMAT, "more words in the dictionary bytes than announced");
-  D.woff.alloc(c, D.d + 1); D.wlen.alloc(c, std::max<uint64_t>(D.d, 1));
-  if (D.d)
-    hipLaunchKernelGGL(words_from_ends_kernel, gdim(cdiv(D.d, TB)), gdim(TB), 0, c->stream, (uint32_t)D.d, ends.p, D.dsize, D.woff.p,
-                       D.wlen.p);
-  PFP_HIP(hipGetLastError());
-}
-
-// Lexicographic rank of every word.  A whole word is a singleton group in SA(D) (the parse is
-// prefix free), so rank[start of word] is its slot: sorting the d words by that slot gives the
-// order std::sort produces in the reference (newscan.cpp:622-636) without touching all N slots.
-__global__ void iota_u32_kernel(uint32_t d, uint32_t *__restrict__ val) {
-  uint32_t j = BID * blockDim.x + threadIdx.x;
-  if (j < d) val[j] = j;
-}
-__global__ void lexrank_from_order_kernel(uint32_t d, const uint32_t *__restrict__ word_sorted, uint32_t *__restrict__ lexrank) {
-  uint32_t r = BID * blockDim.x + threadIdx.x;
-  if (r < d) lexrank[word_sorted[r]] = r;
-}
-
-// multi-GPU: every share of the suffix array reported 1 + slot for the words it holds, 0 for the others
-__global__ void combine_word_slots_kernel(uint32_t d, uint32_t parts, const uint64_t *__restrict__ wslot_all,
-                                          uint64_t *__restrict__ key, uint32_t *__restrict__ missing) {
-  uint32_t j = BID * blockDim.x + threadIdx.x;
-  if (j >= d) return;
-  uint64_t v = 0;
-  for (uint32_t r = 0; r < parts; r++) { const uint64_t x = wslot_all[(uint64_t)r * d + j]; v = x > v ? x : v; }
-  if (v == 0) atomicAdd(missing, 1u);
-  key[j] = v - 1;
-}
-void compute_lexrank_from_slots(pfp_ctx *c, const Dictionary &D, const uint64_t *d_wslot_all, uint32_t parts, DictIndex &ix) {
-  const uint32_t d = (uint32_t)D.d;
-  ix.lexrank.alloc(c, d);
-  DBuf<uint64_t> key(c, d), keyo(c, d);
-  DBuf<uint32_t> val(c, d), valo(c, d), missing(c, 1);
-  missing.zero();
-  hipLaunchKernelGGL(combine_word_slots_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, parts, d_wslot_all, key.p, missing.p);
-  PFP_REQUIRE(read_scalar(c, missing.p) == 0, PFP_EFORMAT, "a dictionary word was claimed by no share of the suffix array");
-  hipLaunchKernelGGL(iota_u32_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, val.p);
-  sort_pairs_u64_u32(c, key.p, keyo.p, val.p, valo.p, d, 0, bits_for(D.dsize));
-  hipLaunchKernelGGL(lexrank_from_order_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, valo.p, ix.lexrank.p);
-  PFP_HIP(hipGetLastError());
-  ix.wslot_lex = std::move(keyo);      // the slots in ascending order = in the words' lexicographic order
-}
-
-// number of BWT positions the slots of `so` emit (sum of the occurrence counts of their words)
-template <class I>
-__global__ __launch_bounds__(256) void slot_output_count_kernel(uint64_t n, const I *__restrict__ sa, WordView wv,
-                                                                const uint32_t *__restrict__ wocc, uint32_t d, int w,
-                                                                unsigned long long *__restrict__ total) {
-  __shared__ unsigned long long ws[4];
-  unsigned long long cnt = 0;
-  for (uint64_t t = (uint64_t)BID * 256 + threadIdx.x; t < n; t += (uint64_t)GDIM * 256) {
-    const I i = sa[t];
-    const uint32_t wd = word_of(wv, i);
-    if (wd < d && wv.wend[wd] - i > (uint64_t)w) cnt += wocc[wd];
-  }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) { const unsigned long long t2 = ws[0] + ws[1] + ws[2] + ws[3]; if (t2) atomicAdd(total, t2); }
-}
-template <class I>
-uint64_t count_slot_outputs(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const SuffixOrderT<I> &so, int w) {
-  DBuf<unsigned long long> total(c, 1);
-  total.zero();
-  if (so.N)
-    hipLaunchKernelGGL(slot_output_count_kernel<I>, gdim((int)std::min<uint64_t>(cdiv64(so.N, 256), (uint64_t)c->n_cu * 16)), gdim(256),
-                       0, c->stream, so.N, so.sa.p, word_view(D, ix), D.wocc.p, (uint32_t)D.d, w, total.p);
-  PFP_HIP(hipGetLastError());
-  PFP_HIP(hipMemcpyAsync(c->h_scalars, total.p, 8, hipMemcpyDeviceToHost, c->stream));
-  sync(c);
-  return c->h_scalars[0];
-}
-template uint64_t count_slot_outputs<uint32_t>(pfp_ctx *, const Dictionary &, const DictIndex &, const SuffixOrderT<uint32_t> &, int);
-template uint64_t count_slot_outputs<uint64_t>(pfp_ctx *, const Dictionary &, const DictIndex &, const SuffixOrderT<uint64_t> &, int);
-
-template <class I>
-__global__ void widen_kernel(uint32_t n, const I *__restrict__ in, uint64_t *__restrict__ out) {
-  uint32_t j = BID * blockDim.x + threadIdx.x;
-  if (j < n) out[j] = (uint64_t)in[j];
-}
-template <class I>
-void compute_lexrank(pfp_ctx *c, const Dictionary &D, SuffixOrderT<I> &so, DictIndex &ix) {
-  const uint32_t d = (uint32_t)D.d;
-  ix.lexrank.alloc(c, d);
-  DBuf<I> key(c, d), keyo(c, d);
-  DBuf<uint32_t> val(c, d), valo(c, d);
-  gather_ranks<I>(c, so, D.woff.p, d, key.p);
-  hipLaunchKernelGGL(iota_u32_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, val.p);
-  sort_pairs<I, uint32_t>(c, key.p, keyo.p, val.p, valo.p, d, 0, bits_for(D.dsize));
-  hipLaunchKernelGGL(lexrank_from_order_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, valo.p, ix.lexrank.p);
-  ix.wslot_lex.alloc(c, d);
-  hipLaunchKernelGGL((widen_kernel<I>), gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, keyo.p, ix.wslot_lex.p);
-  PFP_HIP(hipGetLastError());
-}
-template void compute_lexrank<uint32_t>(pfp_ctx *, const Dictionary &, SuffixOrderT<uint32_t> &, DictIndex &);
-template void compute_lexrank<uint64_t>(pfp_ctx *, const Dictionary &, SuffixOrderT<uint64_t> &, DictIndex &);
-
-// ------------------------------------------------------------------ stage 2: BWT of the parse
-
-// bwtparse.c:242-267: BWT(P)[j] = P[SA[j]-1]; bwlast = last of the phrase before that one
-// (cyclically), bwsai = sai of that phrase; SA[j]==0 -> dummy zeros.
-// From ONE record per phrase (round 4; three gathers - sym, last, sai - before): {symbol, last char of the phrase before, sai} packed in parse order by a streaming
-// pass, so that the suffix-array order costs one random 16-byte (8-byte without sai) access per phrase instead of three.
-__global__ void parse_pack16_kernel(uint64_t P, const uint32_t *__restrict__ sym, const uint8_t *__restrict__ last,
-                                    const uint64_t *__restrict__ sai, uint4 *__restrict__ rec) {
-  const uint64_t t = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (t >= P) return;
-  const uint64_t v = sai[t];
-  rec[t] = make_uint4(sym[t], (uint32_t)(t == 0 ? last[P - 1] : last[t - 1]), (uint32_t)v, (uint32_t)(v >> 32));
-}
-__global__ void parse_pack8_kernel(uint64_t P, const uint32_t *__restrict__ sym, const uint8_t *__restrict__ last, uint2 *__restrict__ rec) {
-  const uint64_t t = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (t >= P) return;
-  rec[t] = make_uint2(sym[t], (uint32_t)(t == 0 ? last[P - 1] : last[t - 1]));
-}
-template <class R>
-__global__ void parse_gather_rec_kernel(uint64_t P, const uint32_t *__restrict__ sa, const R *__restrict__ rec,
-                                        uint32_t *__restrict__ bwtp, uint8_t *__restrict__ bwlast,
-                                        uint64_t *__restrict__ bwsai, uint32_t *__restrict__ jidx) {
-  const uint64_t j = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (j > P) return;
-  const uint64_t s = sa[j];
-  jidx[j] = (uint32_t)j;
-  if (s == 0) {
-    bwtp[j] = 0; bwlast[j] = 0;
-    if constexpr (sizeof(R) == 16) bwsai[j] = 0;
-  } else {
-    const R r = rec[s - 1];
-    bwtp[j] = r.x; bwlast[j] = (uint8_t)r.y;
-    if constexpr (sizeof(R) == 16) bwsai[j] = (uint64_t)r.z | ((uint64_t)r.w << 32);
-  }
-}
-
-void parse_bwt(pfp_ctx *c, const uint32_t *parse_sym, uint64_t P, const uint8_t *last, const uint64_t *sai,
-               const uint32_t *occ_lex, uint64_t d, ParseBWT &out, const uint32_t *sa_given) {
-  PFP_REQUIRE(P >= 2, PFP_ESHORT, "parse has fewer than 2 phrases (bwtparse.c:244)");
-  out.P = P;
-  DBuf<uint32_t> sym(c, P + 1);
-  PFP_HIP(hipMemcpyAsync(sym.p, parse_sym, P * 4, hipMemcpyDeviceToDevice, c->stream));
-  PFP_HIP(hipMemsetAsync(sym.p + P, 0, 4, c->stream));
-  SuffixOrder so;
-  if (sa_given) {      // multi-GPU chain: the ranks sorted a share each and gathered them (pfp_dist_parse_sort)
-    so.N = so.NP = P + 1;
-    so.sa.alloc(c, P + 1);
-    PFP_HIP(hipMemcpyAsync(so.sa.p, sa_given, (P + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
-  } else
-    sort_int_suffixes(c, sym.p, P + 1, so, d, occ_lex, (uint32_t)d);      // symbols are 1-based word ranks <= d; occ_lex[rank] = the word's count
-  if (c->debug) validate_int_sa(c, sym.p, so);
-  out.rounds = so.rounds;
-  out.ilist.alloc(c, P + 1);
-  out.bwlast.alloc(c, P + 1);
-  if (sai) out.bwsai.alloc(c, P + 1);
-  DBuf<uint32_t> bwtp(c, P + 1), bwtp_s(c, P + 1), jidx(c, P + 1);
-  if (sai) {
-    DBuf<uint4> rec(c, P);
-    { KScope ks(c, "pfp::parse_pack16_kernel", P * (13 + 16));
-      hipLaunchKernelGGL(parse_pack16_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, (const uint32_t *)sym.p, last, sai, rec.p); }
-    KScope ks(c, "pfp::parse_gather_rec_kernel", (P + 1) * (4 + 16 + 4 + 1 + 8 + 4));
-    hipLaunchKernelGGL(parse_gather_rec_kernel<uint4>, gdim(cdiv(P + 1, TB)), gdim(TB), 0, c->stream, P, (const uint32_t *)so.sa.p, (const uint4 *)rec.p,
-                       bwtp.p, out.bwlast.p, out.bwsai.p, jidx.p);
-  } else {
-    DBuf<uint2> rec(c, P);
-    { KScope ks(c, "pfp::parse_pack8_kernel", P * (5 + 8));
-      hipLaunchKernelGGL(parse_pack8_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, (const uint32_t *)sym.p, last, rec.p); }
-    KScope ks(c, "pfp::parse_gather_rec_kernel", (P + 1) * (4 + 8 + 4 + 1 + 4));
-    hipLaunchKernelGGL(parse_gather_rec_kernel<uint2>, gdim(cdiv(P + 1, TB)), gdim(TB), 0, c->stream, P, (const uint32_t *)so.sa.p, (const uint2 *)rec.p,
-                       bwtp.p, out.bwlast.p, (uint64_t *)nullptr, jidx.p);
-  }
-  // bwtparse.c:281-303: positions grouped by symbol, ascending inside a group == stable sort
-  { SortTag tag("inverted list"); sort_pairs_u32_u32(c, bwtp.p, bwtp_s.p, jidx.p, out.ilist.p, P + 1, 0, bits_for(d)); }
-  PFP_HIP(hipGetLastError());
-}
-
-// ------------------------------------------------------------------ stage 3: merge
+// ------------------------------------------------------------------ stage 3: the kernels
 
 template <class I> struct alignas(16) Idx8 { I v[8]; };
 // whole-word slots (preceding char = EndOfWord) of the block's 2048 slots -> tile_full[block]; smallest such slot -> first_full
@@ -628,7 +401,7 @@ __device__ __forceinline__ void expand_stage(const MergeArgsT<I> &a, ExpandLds &
       const uint64_t t = t0 + s;
       uint8_t ch = a.pc[t];
       cls = ch == 0 ? CLS_NONE : (ch == kEndOfWord ? CLS_FULL : CLS_FILL);
-      if (cls == CLS_FILL && a.pass != PASS_SA) {      // (the SA-only round of the sparse mode looks at whole words only)
+      if (cls == CLS_FILL && a.pass != PASS_SA) {      // (always true: no launch of the expand kernels is SA-only; kept so that their code stays as it is)
         const I g = a.grp[t];
         if (a.hard[g]) {
           cls = CLS_HARD;
@@ -715,22 +488,19 @@ __device__ __forceinline__ void expand_sa_1(const MergeArgsT<I> &a, const Expand
 }
 
 // Sparse SA mode (-s / -e without -S): SA values are only looked at where a run of the BWT starts or ends.
-//   * a whole word's occurrences carry unrelated chars (bwlast): all their SA values are written here, by the
-//     workgroup that expands them (P positions in all);
+//   * a whole word's occurrences carry unrelated chars (bwlast): all their SA values are written, P positions in
+//     all - word_sa_kernel;
 //   * a slot, or a group of slots, whose chars all agree fills its range with one char: only the first and
 //     the last position of that range can be run boundaries - unit_edges_kernel;
 //   * hard groups: the two ends (unit_edges_kernel) and what the hard-group kernels find inside.
-template <class I, int SPARSE>
+template <class I>
 __global__ __launch_bounds__(256) void expand_kernel(MergeArgsT<I> a, uint32_t *__restrict__ heavy, uint32_t *__restrict__ nheavy,
                                                      uint32_t heavy_cap) {
   __shared__ ExpandLds L;
-  __shared__ uint32_t nfull, fpre[SPARSE ? kSlots + 1 : 1], wsum[4];
-  __shared__ uint16_t fulls[SPARSE ? kSlots : 1];
   const uint64_t t0 = (uint64_t)BID * kSlots;
   if (t0 >= a.N) return;      // a workgroup of the padded last grid row
   const int ns = (a.N - t0) >= (uint64_t)kSlots ? kSlots : (int)(a.N - t0);
   const uint64_t base = slot_off(a, t0);
-  if (SPARSE && threadIdx.x == 0) nfull = 0;
   expand_stage(a, L, t0, ns, base, BID);
   const uint64_t Ltot = L.loff[ns];
   if (base + Ltot <= a.out_lo || base >= a.out_hi) return;
@@ -741,46 +511,8 @@ __global__ __launch_bounds__(256) void expand_kernel(MergeArgsT<I> a, uint32_t *
   if (a.pass & PASS_BWT)
     for (uint64_t x0 = (uint64_t)threadIdx.x * 16; x0 < mine; x0 += 256 * 16) expand_16(a, L, t0, ns, base, x0, Ltot);
   if (!(a.pass & PASS_SA)) return;
-  if (SPARSE) {
-    // the whole-word slots of the block and the positions they emit, laid end to end: one lane per position (a loop over
-    // the slots with 256 lanes on each - most words occur a few times - was a chain of ~20 dependent gathers per block)
-    for (int s = threadIdx.x; s < ns; s += 256)
-      if (L.lcls[s] == CLS_FULL) fulls[atomicAdd(&nfull, 1u)] = (uint16_t)s;
-    __syncthreads();
-    const uint32_t nf = nfull;
-    if (nf == 0) return;
-    const uint32_t chunk = (nf + 255u) / 256u, q0 = threadIdx.x * chunk, q1 = q0 + chunk < nf ? q0 + chunk : nf;
-    uint32_t own = 0;
-    for (uint32_t q = q0; q < q1; q++) {
-      const int sl = (int)fulls[q];
-      const uint64_t b = L.loff[sl], e = L.loff[sl + 1] < mine ? L.loff[sl + 1] : mine;
-      const uint32_t cq = e > b ? (uint32_t)(e - b) : 0u;
-      fpre[q] = cq;
-      own += cq;
-    }
-    uint32_t inc = own;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    uint32_t run = inc - own;
-    for (int q = 0; q < wv; q++) run += wsum[q];
-    for (uint32_t q = q0; q < q1; q++) { const uint32_t cq = fpre[q]; fpre[q] = run; run += cq; }
-    const uint32_t total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    if (threadIdx.x == 0) fpre[nf] = total;
-    __syncthreads();
-    for (uint32_t idx = threadIdx.x; idx < total; idx += 256) {
-      uint32_t lo = 0, hi = nf;                    // fpre[lo] <= idx < fpre[hi]
-      while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (fpre[mid] <= idx) lo = mid; else hi = mid; }
-      const int sl = (int)fulls[lo];
-      const uint64_t x = L.loff[sl] + (idx - fpre[lo]);
-      if (!sa_wanted(a, base + x)) continue;
-      const uint64_t pos = a.ilist[L.lfist[sl] + (uint32_t)(x - L.loff[sl])];
-      sa_put(a, base + x, a.pos_base + base + x == 0 ? a.n_out_global - 1 : a.bwsai[pos] - slot_slen(a, t0 + sl));
-    }
-  } else if (a.want_sa) {
+  if (a.want_sa)
     for (uint64_t x = threadIdx.x; x < mine; x += 256) expand_sa_1(a, L, t0, ns, base, x);
-  }
 }
 
 template <class I>
@@ -806,11 +538,10 @@ __global__ __launch_bounds__(256) void expand_heavy_kernel(MergeArgsT<I> a, cons
 // they emit can be a run boundary.  One lane per occurrence e of the inverted lists laid end to end (ilist[1 + e], read
 // coalesced): its word is the one of lexicographic rank q with istart_lex[q] <= e (bisection over d entries that stay in
 // L2), the word's slot is wslot_lex[q], the position is that slot's offset plus the occurrence's index in its list.
-// Replaces the second launch of expand_kernel over all N slots (every tile staged again to find its dozen whole words).
+// (Staging every tile of expand_kernel again would find a dozen whole words in each.)
 template <class I>
 __global__ __launch_bounds__(256) void word_sa_kernel(MergeArgsT<I> a, uint64_t P, const uint64_t *__restrict__ wslot_lex,
-                                                      uint64_t slot_base, const uint32_t *__restrict__ wlen_lex_word,
-                                                      const uint32_t *__restrict__ word_len) {
+                                                      uint64_t slot_base) {
   const uint64_t e = (uint64_t)BID * 256 + threadIdx.x;
   if (e >= P) return;
   uint32_t lo = 0, hi = a.d;                 // istart_lex[lo] <= e < istart_lex[hi]  (istart_lex[d] = P)
@@ -821,7 +552,6 @@ __global__ __launch_bounds__(256) void word_sa_kernel(MergeArgsT<I> a, uint64_t 
   const uint64_t x = slot_off(a, t) + (e - (uint64_t)a.istart_lex[lo]);
   if (!sa_wanted(a, x)) return;
   const uint64_t pos = a.ilist[e + 1];       // +1: ilist[0] is the EOS symbol (pfbwt.cpp:389)
-  (void)wlen_lex_word; (void)word_len;
   sa_put(a, x, a.pos_base + x == 0 ? a.n_out_global - 1 : a.bwsai[pos] - slot_slen(a, t));
 }
 
@@ -928,28 +658,6 @@ __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
 // Boundaries of the runs of the BWT slice [out_lo, out_hi): bit r of the map = position out_lo + r starts a run
 // (differs from the byte before) or ends one (differs from the byte after); the slice's own first and last position
 // always count - their neighbours belong to another rank.
-constexpr int kRunTile = 4096;
-__device__ __forceinline__ void run_mask16(const uint8_t *__restrict__ bwt, uint64_t base, uint64_t cnt, int left, int right,
-                                           int run_end, uint32_t m[4]) {
-  m[0] = m[1] = m[2] = m[3] = 0;
-  if (base >= cnt) return;
-  if (base + 17 <= cnt && base >= 1) {          // interior: both neighbours of all 16 positions are inside the slice
-    const uint4 x = ld16u(bwt + base);
-    const uint4 y = run_end ? ld16u(bwt + base + 1) : ld16u(bwt + base - 1);
-    m[0] = nonzero_bytes(x.x ^ y.x); m[1] = nonzero_bytes(x.y ^ y.y); m[2] = nonzero_bytes(x.z ^ y.z); m[3] = nonzero_bytes(x.w ^ y.w);
-    return;
-  }
-  for (int k = 0; k < 16; k++) {
-    const uint64_t i = base + k;
-    if (i >= cnt) break;
-    const int b = bwt[i];
-    int nb;
-    if (run_end) nb = i + 1 < cnt ? (int)bwt[i + 1] : right;
-    else nb = i ? (int)bwt[i - 1] : left;
-    if (nb < 0 || nb != b) m[k >> 2] |= 1u << (8 * (k & 3));
-  }
-}
-struct __attribute__((packed, aligned(1))) U16u { uint16_t v; };
 __device__ __forceinline__ uint32_t pack_byte_flags(uint32_t m) {      // flags at bits 0, 8, 16, 24 -> bits 0..3
   return (m & 1u) | ((m >> 7) & 2u) | ((m >> 14) & 4u) | ((m >> 21) & 8u);
 }
@@ -975,31 +683,6 @@ __global__ __launch_bounds__(256) void run_bitmap_kernel(const uint8_t *__restri
     bmap[w] = vs | ve; wcnt[w] = (uint32_t)__popcll(vs | ve);
     if (smap) { smap[w] = vs; scnt[w] = (uint32_t)__popcll(vs); }
     if (emap) { emap[w] = ve; ecnt[w] = (uint32_t)__popcll(ve); }
-  }
-}
-// .ssa / .esa pairs of the whole BWT from the bitmaps: one thread per word of the start (end) map, the SA value of a
-// set bit from its rank among all boundaries
-__global__ __launch_bounds__(256) void bitmap_place_kernel(const uint64_t *__restrict__ map, const uint64_t *__restrict__ pre,
-                                                           const uint64_t *__restrict__ bmap, const uint64_t *__restrict__ bpre,
-                                                           const uint64_t *__restrict__ sa_c, uint64_t nw, uint8_t *__restrict__ out10,
-                                                           uint64_t pos_base, int drop_first, uint64_t drop_pos) {
-  const uint64_t w = (uint64_t)BID * 256 + threadIdx.x;
-  if (w >= nw) return;
-  uint64_t m = map[w];
-  uint64_t o = pre[w];
-  // a slice's edge that is no boundary after all (multi-GPU): position 0 leaves the list and every later pair moves
-  // up by one; drop_pos (the slice's last position, or ~0) just leaves
-  if (drop_first) { if (w == 0) m &= ~1ull; else o -= 1; }
-  if ((drop_pos >> 6) == w) m &= ~(1ull << (drop_pos & 63));
-  if (!m) return;
-  const uint64_t all = bmap[w], rb = bpre[w];
-  while (m) {
-    const int b = __builtin_ctzll(m);
-    m &= m - 1;
-    const uint64_t x = pos_base + w * 64 + b, v = sa_c[rb + (uint64_t)__popcll(all & ((1ull << b) - 1ull))];
-    uint8_t *dst = out10 + 10 * o++;
-    reinterpret_cast<U64u *>(dst)->v = (x & 0xFFFFFFFFFFull) | (v << 40);       // 5 bytes of x, 3 low bytes of v
-    reinterpret_cast<U16u *>(dst + 8)->v = (uint16_t)(v >> 24);                  // bytes 3, 4 of v
   }
 }
 __global__ void count_unset_kernel(const uint64_t *__restrict__ v, uint64_t n, unsigned long long *__restrict__ total) {
@@ -1521,327 +1204,447 @@ __global__ __launch_bounds__(256) void slot_loc_kernel(const uint32_t *__restric
   }
 }
 
+// ------------------------------------------------------------------ stage 3: the host side
+
+// where a slot's record (occurrences, preceding char, first / last BWT(P) position, suffix length) comes from
+enum class RecordSource {
+  SortKeys,      // the sorter carried it in the spare bits of its first-round keys: already at the slot
+  Gathered,      // one 16-byte record per dictionary position, written by a streaming pass, gathered once per slot
+  PerSlot,       // every slot computes its record from the dictionary line and its word's entry
+};
+
+// the test switches of a call.  Read per call: the tests switch them inside one process
+struct MergeSwitches {
+  int prec_direct = -1;                  // PFP_PREC_DIRECT: 1 / 0 forces RecordSource::PerSlot / Gathered where the sort keys carry no record
+  uint32_t big_cap = 0;                  // PFP_BIG_CAP: capacity of the queue of large hard groups (0: by size)
+  uint64_t big_budget = 1ull << 27;      // PFP_BIG_BUDGET: occurrences of queued groups sorted at once
+  static MergeSwitches read() {
+    MergeSwitches s;
+    if (const char *e = getenv("PFP_PREC_DIRECT")) s.prec_direct = atoi(e) != 0;
+    if (const char *e = getenv("PFP_BIG_CAP")) { if (atoll(e) > 0) s.big_cap = (uint32_t)atoll(e); }
+    if (const char *e = getenv("PFP_BIG_BUDGET")) s.big_budget = strtoull(e, nullptr, 10);
+    return s;
+  }
+};
+
 template <class I>
-void merge_bwt(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const SuffixOrderT<I> &so, const ParseBWT &pb,
-               const uint32_t *occ_lex, int w, int flags, uint64_t expect_n_out, BwtOutputs &out, uint64_t out_lo,
-               uint64_t out_hi, uint64_t pos_base, uint64_t n_out_global) {
-  // NP dictionary positions; N suffix-array slots held by `so` (all of them, or - multi-GPU, key-range
-  // sharded sort - one contiguous range of SA(D) whose first output position is pos_base)
-  const uint64_t NP = D.dsize;
-  const uint64_t N = so.N;
-  const uint32_t d = (uint32_t)D.d;
-  PFP_REQUIRE(!flags || pb.bwsai.p, PFP_EINVAL, "SA output requested without sa info");
-  // istart in lexicographic order (pfbwt.cpp:388-396), looked up per word
-  DBuf<uint32_t> istart_lex(c, d), wistart(c, d);
-  exclusive_sum_u32(c, occ_lex, istart_lex.p, d);
-  // SA values: none, all (-S), or only where the sampled files can look (-s / -e): run boundaries of the BWT
-  const int sa_mode = !flags ? SA_NONE : ((flags & PFP_FLAG_SA) ? SA_DENSE : SA_SPARSE);
-  const int samode = sa_mode;
-  const bool dense = samode == SA_DENSE;
-  DBuf<WordRec> wrec(c, d);      // per word: list start, occurrences, smallest / largest BWT(P) position, terminator
-  hipLaunchKernelGGL(wistart_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, ix.lexrank.p, istart_lex.p, D.wocc.p, pb.ilist.p,
-                     ix.wend.p, wistart.p, wrec.p);
-  const WordView wv = word_view(D, ix);
-  DBuf<PosRec> prec;
-  DBuf<uint32_t> cnt, sfirst, slast, ssl;
+static RecordSource choose_record_source(pfp_ctx *c, uint64_t N, uint64_t NP, int sa_mode, const SuffixOrderT<I> &so, const MergeSwitches &sw) {
   // records already sit at their slots - unless most slots were re-ordered after the first round (a
   // dictionary of near-identical variants), where fetching each such record costs more than the gather
-  const bool from_keys = !dense && so.paybits == 16 && so.skeys.p && so.n_refined * 5 < N;
+  if (sa_mode != SA_DENSE && so.paybits == 16 && so.skeys.p && so.n_refined * 5 < N) return RecordSource::SortKeys;
   // everything else: ONE 16-byte gather per slot (slot_records_kernel); full SA output included - its per-slot inverted-list
-  // start travels in the record's `first` field
-  const bool fused = !from_keys;
-  if (!fused) { cnt.alloc(c, N + 8); PFP_HIP(hipMemsetAsync(cnt.p + N, 0, 4, c->stream)); }
-  DBuf<uint8_t> pc(c, N + 8), hard(c, N);
-  const uint64_t ntile = (N >> kOffTileLog) + 1;        // covers slot index N (one past the last)
-  DBuf<uint32_t> loc(c, ntile << kOffTileLog), ovf(c, 1);
-  DBuf<uint64_t> tsum(c, ntile + 1), tbase(c, ntile + 1);
-  hard.zero();
-  DBuf<uint32_t> tile_full(c, ntile + 1), fullbase(c, ntile + 1), fullbase0(c, 1);
-  DBuf<unsigned long long> first_full(c, 1);
-  tile_full.zero();
-  PFP_HIP(hipMemsetAsync(first_full.p, 0xFF, 8, c->stream));
-  ovf.zero();
-  PFP_HIP(hipMemsetAsync(tsum.p + ntile, 0, 8, c->stream));
-  if (fused) {
-    // 16 bytes per dictionary position, written by one streaming pass and gathered once per slot - unless the slots are a
-    // small share of the positions (a rank's range of the multi-GPU chain: the pass over all NP positions is replicated
-    // work, 14 GB of records for a 0.9 GB dictionary) or the records would take more than an eighth of the device
-    // (a 30 GB dictionary: 480 GB): then every slot computes its record itself from the dictionary line and its word's
-    // entry (posrec_at: two random sectors per slot instead of one).  PFP_PREC_DIRECT=1/0 forces the choice (tests).
-    bool direct = N * 4 <= NP;
-    {
-      const uint64_t dev_bytes = c->pool.soft_limit ? c->pool.soft_limit / 7 * 10 : (64ull << 30);
-      if (NP * sizeof(PosRec) > dev_bytes / 8) direct = true;
-      const char *e = getenv("PFP_PREC_DIRECT");
-      if (e) direct = atoi(e) != 0;
-    }
-    if (!direct) {
-      const uint64_t np256 = cdiv64(NP, 256) * 256;
-      prec.alloc(c, np256);
-      KScope ks(c, "pfp::pprec16_kernel", NP * (1 + 16) + (uint64_t)d * 40);
-      hipLaunchKernelGGL(pprec16_kernel, gdim(cdiv(np256, TB)), gdim(TB), 0, c->stream, wv, w, reinterpret_cast<const uint4 *>(wrec.p),
-                         dense ? 1 : 0, (uint64_t)0, NP, prec.p);
-    }
-    // per-slot copies of what the unit-edge / minority kernels ask about a slot's word (read coalesced there); full SA:
-    // the list start of every slot's word and its suffix length
-    sfirst.alloc(c, ntile << kOffTileLog);
-    if (!dense) slast.alloc(c, ntile << kOffTileLog);
-    if (samode != SA_NONE) ssl.alloc(c, ntile << kOffTileLog);
-    { KScope ks(c, "pfp::slot_records_kernel", N * (2 * sizeof(I) + (direct ? 64 + 32 : 16) + 4 + 1 + 4 + (slast.p ? 4 : 0) + (ssl.p ? 4 : 0)));
-      hipLaunchKernelGGL(slot_records_kernel<I>, gdim((unsigned)ntile), gdim(256), 0, c->stream, N, so.sa.p, so.grp.p,
-                         direct ? (const PosRec *)nullptr : prec.p, loc.p, pc.p, sfirst.p, slast.p, ssl.p, tsum.p, ovf.p, tile_full.p,
-                         first_full.p, hard.p, dense ? 1 : 0, wv, w, reinterpret_cast<const uint4 *>(wrec.p), dense ? 1 : 0); }
-    prec.release();
-  } else {
+  // start travels in the record's `first` field.
+  // 16 bytes per dictionary position, written by one streaming pass and gathered once per slot - unless the slots are a
+  // small share of the positions (a rank's range of the multi-GPU chain: the pass over all NP positions is replicated
+  // work, 14 GB of records for a 0.9 GB dictionary) or the records would take more than an eighth of the device
+  // (a 30 GB dictionary: 480 GB): then every slot computes its record itself from the dictionary line and its word's
+  // entry (posrec_at: two random sectors per slot instead of one).  PFP_PREC_DIRECT=1/0 forces the choice (tests).
+  bool direct = N * 4 <= NP;
+  const uint64_t dev_bytes = c->pool.soft_limit ? c->pool.soft_limit / 7 * 10 : (64ull << 30);
+  if (NP * sizeof(PosRec) > dev_bytes / 8) direct = true;
+  if (sw.prec_direct >= 0) direct = sw.prec_direct != 0;
+  return direct ? RecordSource::PerSlot : RecordSource::Gathered;
+}
+
+// which heads the LDS kernels (hard_groups_kernel) work through, and where the list's length lives on the device
+template <class I>
+struct HeadList {
+  const I *heads;
+  const uint64_t *n_dev;
+  uint64_t n;
+};
+
+// The state of one merge_bwt call, and one member function per step of it (run() is the list).  The buffers are grouped by
+// what they describe; every group lives to the end of the call, what is needed for a shorter time is a local of its step.
+template <class I>
+struct Merge {
+  // ---- fixed when the call starts
+  pfp_ctx *const c;
+  const Dictionary &D;
+  const DictIndex &ix;
+  const SuffixOrderT<I> &so;
+  const ParseBWT &pb;
+  const uint32_t *const occ_lex;
+  const MergeOpts o;
+  BwtOutputs &out;
+  // NP dictionary positions; N suffix-array slots held by `so` (all of them, or - multi-GPU, key-range
+  // sharded sort - one contiguous range of SA(D) whose first output position is o.pos_base)
+  const uint64_t NP, N;
+  const uint32_t d;
+  // SA values: none, all (-S), or only where the sampled files can look (-s / -e): run boundaries of the BWT
+  const int sa_mode;
+  const MergeSwitches sw;
+  const RecordSource src;
+  const WordView wv;
+  const uint64_t ntile;         // offset tiles: covers slot index N (one past the last)
+  const uint32_t nblk;          // expand workgroups
+  // what one launch writes in the first round: chars and SA values together (dense), or chars first and - once the finished
+  // BWT says where the sampled files can look - SA values in a second round of the same kernels (sparse)
+  const int first_pass;
+
+  MergeArgsT<I> a{};            // what the kernels get (its `pass` comes from with_pass)
+  uint64_t n_out = 0;
+
+  // ---- per word
+  struct {
+    DBuf<uint32_t> istart_lex, wistart;      // istart in lexicographic order (pfbwt.cpp:388-396), looked up per word
+    DBuf<WordRec> wrec;                      // list start, occurrences, smallest / largest BWT(P) position, terminator
+  } word;
+  // ---- per slot
+  struct {
+    DBuf<uint8_t> pc, hard;
+    DBuf<uint32_t> loc, ovf;
+    DBuf<uint64_t> tsum, tbase;
+    DBuf<uint32_t> tile_full, fullbase, fullbase0;
+    DBuf<unsigned long long> first_full;
+    DBuf<uint32_t> sfirst, slast, ssl;
+  } slot;
+  // ---- hard groups
+  enum { kAllHeads = 0, kFallbackHeads = 1 };      // entries of hg.list_len
+  struct {
+    DBuf<unsigned long long> hstats;
+    uint64_t n_heads = 0;
+    uint32_t big_cap = 0, mid_cap = 0;
+    DBuf<BigGroup> big, mid;      // queues of hard_groups_kernel: groups of more than 1024 / more than kHardSortMin occurrences
+    DBuf<I> heads;
+    DBuf<uint64_t> list_len;      // [kAllHeads] heads selected, [kFallbackHeads] fallback heads selected
+    DBuf<unsigned long long> mstat;      // chars and members of the hard groups the minority path takes
+    // BWT only / sparse SA: majority fill + minority placement
+    DBuf<uint8_t> gmaj, fallback;
+    DBuf<HardGroupInfo> ginfo;
+    DBuf<uint32_t> minor_cnt, mm_cnt;
+    DBuf<uint64_t> minor_off, mm_off;
+    DBuf<MinorMember> mm_list;
+    uint64_t n_mm = 0, sum_k = 0, n_minor = 0;
+    DBuf<I> fb_heads;
+    DBuf<MinorRec> recs;          // sparse SA: what a minority occurrence found, for the second round
+    int gpb = 64;                 // groups per wave batch of hard_groups_kernel
+    uint32_t nmid = 0, nbig = 0;
+    DBuf<uint64_t> estart;        // occurrences of the queued groups, laid end to end
+    std::vector<uint64_t> es;     // ... and their host copy
+  } hg;
+  DBuf<uint32_t> heavy, nheavy;   // expand workgroups beyond their quota
+
+  Merge(pfp_ctx *c_, const Dictionary &D_, const DictIndex &ix_, const SuffixOrderT<I> &so_, const ParseBWT &pb_, const uint32_t *occ_lex_,
+        const MergeOpts &o_, BwtOutputs &out_)
+      : c(c_), D(D_), ix(ix_), so(so_), pb(pb_), occ_lex(occ_lex_), o(o_), out(out_), NP(D_.dsize), N(so_.N), d((uint32_t)D_.d),
+        sa_mode(!o_.flags ? SA_NONE : ((o_.flags & PFP_FLAG_SA) ? SA_DENSE : SA_SPARSE)), sw(MergeSwitches::read()),
+        src(choose_record_source<I>(c_, N, NP, sa_mode, so_, sw)), wv(word_view(D_, ix_)), ntile((N >> kOffTileLog) + 1),
+        nblk((uint32_t)cdiv64(N, kSlots)), first_pass(sa_mode == SA_SPARSE ? PASS_BWT : (PASS_BWT | PASS_SA)) {}
+
+  MergeArgsT<I> with_pass(int pass) const { MergeArgsT<I> x = a; x.pass = pass; return x; }
+
+  // ---- 1. word records
+  void word_records() {
+    word.istart_lex.alloc(c, d); word.wistart.alloc(c, d);
+    exclusive_sum_u32(c, occ_lex, word.istart_lex.p, d);
+    word.wrec.alloc(c, d);
+    hipLaunchKernelGGL(wistart_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, ix.lexrank.p, word.istart_lex.p, D.wocc.p, pb.ilist.p,
+                       ix.wend.p, word.wistart.p, word.wrec.p);
+  }
+
+  // ---- 2. slot tables: chars, hard flags, counts per tile, from wherever the records are (cnt: the from-keys counts)
+  void alloc_slot_tables() {
+    slot.pc.alloc(c, N + 8); slot.hard.alloc(c, N);
+    slot.loc.alloc(c, ntile << kOffTileLog); slot.ovf.alloc(c, 1);
+    alloc_counts(c, slot.tsum, ntile); slot.tbase.alloc(c, ntile + 1);
+    slot.hard.zero();
+    slot.tile_full.alloc(c, ntile + 1); slot.fullbase.alloc(c, ntile + 1); slot.fullbase0.alloc(c, 1);
+    slot.first_full.alloc(c, 1);
+    slot.tile_full.zero();
+    PFP_HIP(hipMemsetAsync(slot.first_full.p, 0xFF, 8, c->stream));
+    slot.ovf.zero();
+  }
+  void slot_tables_from_keys(DBuf<uint32_t> &cnt) {
     { KScope ks(c, "pfp::slot_payload_kernel", N * (8 + 1 + 5));
       hipLaunchKernelGGL(slot_payload_kernel<I>, gdim(cdiv(cdiv64(N, 8), 256)), gdim(256), 0, c->stream, N, so.sa.p, so.skeys.p,
-                         so.refined.p, D.bytes.p, wv, D.wocc.p, d, w, cnt.p, pc.p, tile_full.p, first_full.p); }
+                         so.refined.p, D.bytes.p, wv, D.wocc.p, d, o.w, cnt.p, slot.pc.p, slot.tile_full.p, slot.first_full.p); }
     { KScope ks(c, "pfp::slot_loc_kernel", N * 8);
-      hipLaunchKernelGGL(slot_loc_kernel, gdim((unsigned)ntile), gdim(256), 0, c->stream, cnt.p, N, loc.p, tsum.p, ovf.p); }
+      hipLaunchKernelGGL(slot_loc_kernel, gdim((unsigned)ntile), gdim(256), 0, c->stream, cnt.p, N, slot.loc.p, slot.tsum.p, slot.ovf.p); }
     { KScope ks(c, "pfp::group_flags_kernel", N * 5);
-      hipLaunchKernelGGL(group_flags_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, N, so.grp.p, pc.p, 0, hard.p); }
+      hipLaunchKernelGGL(group_flags_kernel<I>, gdim(cdiv(N, TB)), gdim(TB), 0, c->stream, N, so.grp.p, slot.pc.p, 0, slot.hard.p); }
   }
-  exclusive_sum_u64(c, tsum.p, tbase.p, ntile + 1);
-  exclusive_sum_u32(c, tile_full.p, fullbase.p, ntile + 1);
-  hipLaunchKernelGGL(full_base0_kernel<I>, dim3(1), dim3(1), 0, c->stream, first_full.p, so.sa.p, wv, ix.lexrank.p, fullbase0.p);
-  PFP_REQUIRE(read_scalar(c, ovf.p) == 0, PFP_ELIMIT, "2048 consecutive suffix-array slots emit 2^32 or more BWT positions");
-  const uint64_t n_out = read_scalar(c, tbase.p + ntile);
-  PFP_REQUIRE(expect_n_out == 0 || n_out == expect_n_out, PFP_EFORMAT,
-              "merge: sum of occurrence counts (" + std::to_string(n_out) + ") != text length + 1 (" +
-                  std::to_string(expect_n_out) + ")");
-  out.n_out = n_out;
-  cnt.release();
-  MergeArgsT<I> a{};
-  a.N = N; a.n_out = n_out; a.d = d; a.w = w; a.want_sa = samode;
-  a.pos_base = pos_base; a.n_out_global = n_out_global ? n_out_global : n_out;
-  a.sa = so.sa.p; a.grp = so.grp.p; a.wv = wv;
-  a.ist = dense ? sfirst.p : nullptr;          // full SA: the record's `first` field held the list start
-  a.wistart = wistart.p; a.wrec = wrec.p;
-  a.sfirst = dense ? nullptr : sfirst.p; a.slast = slast.p; a.ssl = ssl.p;
-  a.pc = pc.p; a.hard = hard.p; a.tbase = tbase.p; a.loc = loc.p;
-  a.ilist = pb.ilist.p; a.bwlast = pb.bwlast.p; a.bwsai = pb.bwsai.p;
-  a.istart_lex = istart_lex.p; a.fullbase = fullbase.p; a.fullbase0 = fullbase0.p;
-  // the caller's buffers hold positions [out_lo, out_hi): rebase so that kernels index by global position
-  a.out_lo = out_lo; a.out_hi = out_hi < n_out ? out_hi : n_out;
-  a.bwt = out.d_bwt - out_lo; a.out_sa = out.d_sa ? out.d_sa - out_lo : nullptr;
-  DBuf<unsigned long long> hstats(c, 5);
-  hstats.zero();
-  // hard[] marks exactly the heads of the hard groups (group_flags_kernel): count, then compact them once
-  const uint64_t n_heads = count_flags(c, hard.p, N);
-  // queue of the groups of more than 1024 occurrences: each emits more than 1024 positions and is a hard group; redone larger
-  // if it overflows all the same (PFP_BIG_CAP: tests)
-  uint32_t big_cap = (uint32_t)std::min<uint64_t>({(uint64_t)1u << 20, n_heads + 1, n_out / 1024 + 1});
-  { const char *e = getenv("PFP_BIG_CAP"); if (e && atoll(e) > 0) big_cap = (uint32_t)atoll(e); }
-  DBuf<BigGroup> big(c, big_cap);
-  // such a group emits > kHardSortMin positions
-  const uint32_t mid_cap = (uint32_t)std::min<uint64_t>(n_out / (kHardSortMin + 1) + 64, 0x7FFFFFFFull);
-  DBuf<BigGroup> mid(c, mid_cap);
-  DBuf<I> heads(c, n_heads + 1);
-  DBuf<uint64_t> nheads(c, 2);
-  select_index<I>(c, hard.p, heads.p, nheads.p, N);
-  // BWT only / sparse SA: majority fill + minority placement; groups it leaves (no dominating char) go to the LDS kernels
-  DBuf<uint8_t> gmaj, fallback;
-  DBuf<unsigned long long> mstat(c, 2);      // chars and members of the hard groups the minority path takes
-  mstat.zero();
-  DBuf<HardGroupInfo> ginfo;
-  DBuf<uint32_t> minor_cnt, mm_cnt;
-  DBuf<uint64_t> minor_off, mm_off;
-  DBuf<MinorMember> mm_list;
-  uint64_t n_mm = 0, sum_k = 0;
-  DBuf<I> fb_heads;
-  const I *hard_list = heads.p;             // what hard_groups_kernel works through
-  const uint64_t *hard_list_n = nheads.p;
-  uint64_t n_minor = 0, n_fallback = n_heads;
-  if (!dense && n_heads) {
-    gmaj.alloc(c, N); fallback.alloc(c, n_heads); ginfo.alloc(c, n_heads); minor_cnt.alloc(c, n_heads + 1); minor_off.alloc(c, n_heads + 1);
-    mm_cnt.alloc(c, n_heads + 1); mm_off.alloc(c, n_heads + 1);
-    PFP_HIP(hipMemsetAsync(minor_cnt.p + n_heads, 0, 4, c->stream));
-    PFP_HIP(hipMemsetAsync(mm_cnt.p + n_heads, 0, 4, c->stream));
-    a.gmaj = gmaj.p;
+  void slot_tables_gathered() {
+    const int dense = sa_mode == SA_DENSE ? 1 : 0;
+    const uint64_t np256 = cdiv64(NP, 256) * 256;
+    DBuf<PosRec> prec(c, np256);      // (16 bytes per dictionary position: gone when the slots have their copies)
+    { KScope ks(c, "pfp::pprec16_kernel", NP * (1 + 16) + (uint64_t)d * 40);
+      hipLaunchKernelGGL(pprec16_kernel, gdim(cdiv(np256, TB)), gdim(TB), 0, c->stream, wv, o.w, reinterpret_cast<const uint4 *>(word.wrec.p),
+                         dense, (uint64_t)0, NP, prec.p); }
+    slot_records(prec.p);
+  }
+  void slot_tables_per_slot() { slot_records(nullptr); }
+  void slot_records(const PosRec *prec) {
+    const int dense = sa_mode == SA_DENSE ? 1 : 0;
+    // per-slot copies of what the unit-edge / minority kernels ask about a slot's word (read coalesced there); full SA:
+    // the list start of every slot's word and its suffix length
+    slot.sfirst.alloc(c, ntile << kOffTileLog);
+    if (!dense) slot.slast.alloc(c, ntile << kOffTileLog);
+    if (sa_mode != SA_NONE) slot.ssl.alloc(c, ntile << kOffTileLog);
+    KScope ks(c, "pfp::slot_records_kernel", N * (2 * sizeof(I) + (prec ? 16 : 64 + 32) + 4 + 1 + 4 + (slot.slast.p ? 4 : 0) + (slot.ssl.p ? 4 : 0)));
+    hipLaunchKernelGGL(slot_records_kernel<I>, gdim((unsigned)ntile), gdim(256), 0, c->stream, N, so.sa.p, so.grp.p, prec, slot.loc.p,
+                       slot.pc.p, slot.sfirst.p, slot.slast.p, slot.ssl.p, slot.tsum.p, slot.ovf.p, slot.tile_full.p, slot.first_full.p,
+                       slot.hard.p, dense, wv, o.w, reinterpret_cast<const uint4 *>(word.wrec.p), dense);
+  }
+
+  // ---- 3. offsets and totals
+  void offsets_and_totals() {
+    exclusive_sum_u64(c, slot.tsum.p, slot.tbase.p, ntile + 1);
+    exclusive_sum_u32(c, slot.tile_full.p, slot.fullbase.p, ntile + 1);
+    hipLaunchKernelGGL(full_base0_kernel<I>, dim3(1), dim3(1), 0, c->stream, slot.first_full.p, so.sa.p, wv, ix.lexrank.p, slot.fullbase0.p);
+    PFP_REQUIRE(read_scalar(c, slot.ovf.p) == 0, PFP_ELIMIT, "2048 consecutive suffix-array slots emit 2^32 or more BWT positions");
+    n_out = read_scalar(c, slot.tbase.p + ntile);
+    PFP_REQUIRE(o.expect_n_out == 0 || n_out == o.expect_n_out, PFP_EFORMAT,
+                "merge: sum of occurrence counts (" + std::to_string(n_out) + ") != text length + 1 (" +
+                    std::to_string(o.expect_n_out) + ")");
+    out.n_out = n_out;
+  }
+
+  // ---- 4. what the kernels get
+  void fill_args() {
+    const bool dense = sa_mode == SA_DENSE;
+    a.N = N; a.n_out = n_out; a.d = d; a.w = o.w; a.want_sa = sa_mode;
+    a.pos_base = o.pos_base; a.n_out_global = o.n_out_global ? o.n_out_global : n_out;
+    a.sa = so.sa.p; a.grp = so.grp.p; a.wv = wv;
+    a.ist = dense ? slot.sfirst.p : nullptr;          // full SA: the record's `first` field held the list start
+    a.wistart = word.wistart.p; a.wrec = word.wrec.p;
+    a.sfirst = dense ? nullptr : slot.sfirst.p; a.slast = slot.slast.p; a.ssl = slot.ssl.p;
+    a.pc = slot.pc.p; a.hard = slot.hard.p; a.tbase = slot.tbase.p; a.loc = slot.loc.p;
+    a.ilist = pb.ilist.p; a.bwlast = pb.bwlast.p; a.bwsai = pb.bwsai.p;
+    a.istart_lex = word.istart_lex.p; a.fullbase = slot.fullbase.p; a.fullbase0 = slot.fullbase0.p;
+    // the caller's buffers hold positions [out_lo, out_hi): rebase so that kernels index by global position
+    a.out_lo = o.out_lo; a.out_hi = o.out_hi < n_out ? o.out_hi : n_out;
+    a.bwt = out.d_bwt - o.out_lo; a.out_sa = out.d_sa ? out.d_sa - o.out_lo : nullptr;
+  }
+
+  // ---- 5. hard groups: their heads, and the queues the LDS kernels fill
+  void find_hard_groups() {
+    hg.hstats.alloc(c, 5);
+    hg.hstats.zero();
+    // hard[] marks exactly the heads of the hard groups (group_flags_kernel): count, then compact them once
+    hg.n_heads = count_flags(c, slot.hard.p, N);
+    // queue of the groups of more than 1024 occurrences: each emits more than 1024 positions and is a hard group; redone larger
+    // if it overflows all the same (PFP_BIG_CAP: tests)
+    hg.big_cap = sw.big_cap ? sw.big_cap : (uint32_t)std::min<uint64_t>({(uint64_t)1u << 20, hg.n_heads + 1, n_out / 1024 + 1});
+    hg.big.alloc(c, hg.big_cap);
+    // such a group emits > kHardSortMin positions
+    hg.mid_cap = (uint32_t)std::min<uint64_t>(n_out / (kHardSortMin + 1) + 64, 0x7FFFFFFFull);
+    hg.mid.alloc(c, hg.mid_cap);
+    hg.heads.alloc(c, hg.n_heads + 1);
+    hg.list_len.alloc(c, 2);
+    select_index<I>(c, slot.hard.p, hg.heads.p, hg.list_len.p + kAllHeads, N);
+    hg.mstat.alloc(c, 2);
+    hg.mstat.zero();
+  }
+
+  // ---- 6. BWT only / sparse SA: majority fill + minority placement; groups it leaves (no dominating char) go to the LDS
+  //         kernels - the list that is returned
+  HeadList<I> classify() {
+    const uint64_t n_heads = hg.n_heads;
+    hg.gmaj.alloc(c, N); hg.fallback.alloc(c, n_heads); hg.ginfo.alloc(c, n_heads);
+    alloc_counts(c, hg.minor_cnt, n_heads); hg.minor_off.alloc(c, n_heads + 1);
+    alloc_counts(c, hg.mm_cnt, n_heads); hg.mm_off.alloc(c, n_heads + 1);
+    a.gmaj = hg.gmaj.p;
     { KScope ks(c, "pfp::hard_classify_kernel", n_heads * 40);
-      hipLaunchKernelGGL(hard_classify_kernel<I>, gdim(cdiv(n_heads, 256)), gdim(256), 0, c->stream, a, heads.p, n_heads, gmaj.p,
-                         ginfo.p, minor_cnt.p, fallback.p, mstat.p, mm_cnt.p); }
-    exclusive_sum_u32_u64(c, minor_cnt.p, minor_off.p, n_heads + 1);
-    exclusive_sum_u32_u64(c, mm_cnt.p, mm_off.p, n_heads + 1);
-    n_mm = read_scalar(c, mm_off.p + n_heads);
-    sum_k = read_scalar(c, (const uint64_t *)mstat.p + 1);
-    if (n_mm) {
-      mm_list.alloc(c, n_mm);
-      KScope ks(c, "pfp::hard_minor_fill_kernel", n_heads * 40 + n_mm * 16);
-      hipLaunchKernelGGL(hard_minor_fill_kernel<I>, gdim(cdiv(n_heads * 8, 256)), gdim(256), 0, c->stream, a, ginfo.p, n_heads, mm_off.p,
-                         minor_off.p, gmaj.p, mm_list.p);
+      hipLaunchKernelGGL(hard_classify_kernel<I>, gdim(cdiv(n_heads, 256)), gdim(256), 0, c->stream, a, hg.heads.p, n_heads, hg.gmaj.p,
+                         hg.ginfo.p, hg.minor_cnt.p, hg.fallback.p, hg.mstat.p, hg.mm_cnt.p); }
+    exclusive_sum_u32_u64(c, hg.minor_cnt.p, hg.minor_off.p, n_heads + 1);
+    exclusive_sum_u32_u64(c, hg.mm_cnt.p, hg.mm_off.p, n_heads + 1);
+    hg.n_mm = read_scalar(c, hg.mm_off.p + n_heads);
+    hg.sum_k = read_scalar(c, (const uint64_t *)hg.mstat.p + 1);
+    if (hg.n_mm) {
+      hg.mm_list.alloc(c, hg.n_mm);
+      KScope ks(c, "pfp::hard_minor_fill_kernel", n_heads * 40 + hg.n_mm * 16);
+      hipLaunchKernelGGL(hard_minor_fill_kernel<I>, gdim(cdiv(n_heads * 8, 256)), gdim(256), 0, c->stream, a, hg.ginfo.p, n_heads, hg.mm_off.p,
+                         hg.minor_off.p, hg.gmaj.p, hg.mm_list.p);
     }
-    n_fallback = count_flags(c, fallback.p, n_heads);
-    n_minor = read_scalar(c, minor_off.p + n_heads);
-    fb_heads.alloc(c, n_fallback + 1);
+    const uint64_t n_fallback = count_flags(c, hg.fallback.p, n_heads);
+    hg.n_minor = read_scalar(c, hg.minor_off.p + n_heads);
+    hg.fb_heads.alloc(c, n_fallback + 1);
     {  // heads of the fallback groups = heads[] where fallback[] is set
       DBuf<I> fidx(c, n_fallback + 1);
-      select_index<I>(c, fallback.p, fidx.p, nheads.p + 1, n_heads);
+      select_index<I>(c, hg.fallback.p, fidx.p, hg.list_len.p + kFallbackHeads, n_heads);
       if (n_fallback) hipLaunchKernelGGL(gather_idx_kernel<I>, gdim(cdiv(n_fallback, 256)), gdim(256), 0, c->stream, n_fallback, fidx.p,
-                                         heads.p, fb_heads.p);
+                                         hg.heads.p, hg.fb_heads.p);
       PFP_HIP(hipGetLastError());
       sync(c);
     }
-    hard_list = fb_heads.p; hard_list_n = nheads.p + 1;
+    return HeadList<I>{hg.fb_heads.p, hg.list_len.p + kFallbackHeads, n_fallback};
   }
-  const bool sparse = samode == SA_SPARSE;
-  // what one launch writes: chars and SA values together (dense), or chars first and - once the finished BWT says where
-  // the sampled files can look - SA values in a second round of the same kernels (sparse)
-  a.pass = sparse ? PASS_BWT : (PASS_BWT | PASS_SA);
-  const uint32_t nblk = (uint32_t)cdiv64(N, kSlots);
-  DBuf<uint32_t> heavy(c, nblk), nheavy(c, 1);
-  nheavy.zero();
-  uint32_t nh = 0;
-  auto run_expand = [&]() {
-    { KScope ks(c, "pfp::expand_kernel", a.pass == PASS_SA ? N * 5 + pb.P * 28 : N * 14 + n_out * (dense ? 17 : 1));
-      // (the whole-word list of the sparse SA round costs 12 KB of LDS: only that round's launch carries it)
-      if (sparse && (a.pass & PASS_SA)) hipLaunchKernelGGL((expand_kernel<I, 1>), gdim(nblk), gdim(256), 0, c->stream, a, heavy.p, nheavy.p, nblk);
-      else hipLaunchKernelGGL((expand_kernel<I, 0>), gdim(nblk), gdim(256), 0, c->stream, a, heavy.p, nheavy.p, nblk); }
-    if (a.pass & PASS_BWT) nh = read_scalar(c, nheavy.p);
+
+  // ---- 7. expand: fill and whole-word entries, the majority chars of the hard groups
+  void expand() {
+    const MergeArgsT<I> ap = with_pass(first_pass);
+    heavy.alloc(c, nblk); nheavy.alloc(c, 1);
+    nheavy.zero();
+    { KScope ks(c, "pfp::expand_kernel", N * 14 + n_out * (sa_mode == SA_DENSE ? 17 : 1));
+      hipLaunchKernelGGL(expand_kernel<I>, gdim(nblk), gdim(256), 0, c->stream, ap, heavy.p, nheavy.p, nblk); }
+    const uint32_t nh = read_scalar(c, nheavy.p);
     KScope ks2(c, "pfp::expand_heavy_kernel", 0);   // bytes are accounted in expand_kernel's n_out term
-    if (nh) hipLaunchKernelGGL(expand_heavy_kernel<I>, gdim(c->n_cu * 4), gdim(256), 0, c->stream, a, heavy.p, nh);
+    if (nh) hipLaunchKernelGGL(expand_heavy_kernel<I>, gdim(c->n_cu * 4), gdim(256), 0, c->stream, ap, heavy.p, nh);
     PFP_HIP(hipGetLastError());
-  };
-  run_expand();
-  DBuf<MinorRec> recs;
-  if (n_mm) {
-    if (sparse) recs.alloc(c, n_minor + 1);
-    KScope ks(c, "pfp::hard_minor_kernel", n_minor * 64);
-    // lanes per minority member: eight, or the wave where the groups average more than 32 members
-    const uint64_t avg_k = sum_k / std::max<uint64_t>(n_heads - n_fallback, 1);
-    if (avg_k > 32)
-      hipLaunchKernelGGL((hard_minor_kernel<I, 64>), gdim((unsigned)std::min<uint64_t>(cdiv64(n_mm, 4), (uint64_t)c->n_cu * 64)), gdim(256), 0,
-                         c->stream, a, mm_list.p, n_mm, recs.p);
-    else
-      hipLaunchKernelGGL((hard_minor_kernel<I, 8>), gdim((unsigned)std::min<uint64_t>(cdiv64(n_mm, 32), (uint64_t)c->n_cu * 64)), gdim(256), 0,
-                         c->stream, a, mm_list.p, n_mm, recs.p);
   }
-  PFP_HIP(hipGetLastError());
-  int gpb = 64;      // groups per wave batch: down to 8 while that still leaves every wave of the launch a batch
-  while (gpb > 8 && n_fallback / gpb < (uint64_t)c->n_cu * 32) gpb >>= 1;
-  for (;;) {
-    if (!n_fallback) { PFP_HIP(hipMemsetAsync(hstats.p, 0, 40, c->stream)); }
-    else { KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-      hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, a, hard_list, hard_list_n, hstats.p, big.p,
-                         big_cap, mid.p, mid_cap, gpb); }
+
+  // ---- 8. minority occurrences, ranked against their group's lists and written over the fill
+  void place_minority(const HeadList<I> &lds) {
+    if (hg.n_mm) {
+      const MergeArgsT<I> ap = with_pass(first_pass);
+      if (sa_mode == SA_SPARSE) hg.recs.alloc(c, hg.n_minor + 1);
+      KScope ks(c, "pfp::hard_minor_kernel", hg.n_minor * 64);
+      // lanes per minority member: eight, or the wave where the groups average more than 32 members
+      const uint64_t avg_k = hg.sum_k / std::max<uint64_t>(hg.n_heads - lds.n, 1);
+      if (avg_k > 32)
+        hipLaunchKernelGGL((hard_minor_kernel<I, 64>), gdim((unsigned)std::min<uint64_t>(cdiv64(hg.n_mm, 4), (uint64_t)c->n_cu * 64)), gdim(256), 0,
+                           c->stream, ap, hg.mm_list.p, hg.n_mm, hg.recs.p);
+      else
+        hipLaunchKernelGGL((hard_minor_kernel<I, 8>), gdim((unsigned)std::min<uint64_t>(cdiv64(hg.n_mm, 32), (uint64_t)c->n_cu * 64)), gdim(256), 0,
+                           c->stream, ap, hg.mm_list.p, hg.n_mm, hg.recs.p);
+    }
     PFP_HIP(hipGetLastError());
-    PFP_HIP(hipMemcpyAsync(c->h_scalars, hstats.p, 40, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    if (c->h_scalars[2] <= big_cap) break;
-    big_cap = (uint32_t)std::min<uint64_t>(c->h_scalars[2], 0xFFFFFFFFull);   // rare: redo with a queue that fits
-    big.alloc(c, big_cap);
-    hstats.zero();
   }
-  out.hard_chars = c->h_scalars[0];
-  out.hard_groups = c->h_scalars[1];
-  out.hard_minor_groups = n_heads - n_fallback; out.hard_minor_chars = n_minor;
-  out.hard_big_groups = c->h_scalars[2]; out.hard_max_chars = 0; out.hard_max_members = c->h_scalars[4];
-  const uint32_t nmid = (uint32_t)std::min<uint64_t>(c->h_scalars[3], mid_cap);
-  PFP_REQUIRE(c->h_scalars[3] <= mid_cap, PFP_EHIP, "more sorted-path hard groups than the output can hold");
-  const uint32_t nbig = (uint32_t)c->h_scalars[2];
-  out.hard_chars += read_scalar(c, (const uint64_t *)mstat.p);      // all chars of hard groups, whichever path wrote them
-  out.hard_groups += n_heads - n_fallback;
-  DBuf<uint64_t> estart;
-  std::vector<uint64_t> es(nbig + 1, 0);
-  // (read per call: the tests switch them inside one process)
-  const uint64_t big_budget = [] { const char *e = getenv("PFP_BIG_BUDGET"); return e ? strtoull(e, nullptr, 10) : (1ull << 27); }();
-  if (nbig) {
-    // occurrences of the queued groups, laid end to end
+
+  // ---- 9. the groups of the list ranked in LDS; larger ones are queued (hg.mid, hg.big) - redone when the big queue overflows
+  void rank_in_lds(const HeadList<I> &lds) {
+    const MergeArgsT<I> ap = with_pass(first_pass);
+    // groups per wave batch: down to 8 while that still leaves every wave of the launch a batch
+    while (hg.gpb > 8 && lds.n / hg.gpb < (uint64_t)c->n_cu * 32) hg.gpb >>= 1;
+    for (;;) {
+      if (!lds.n) { PFP_HIP(hipMemsetAsync(hg.hstats.p, 0, 40, c->stream)); }
+      else { KScope ks(c, "pfp::hard_groups_kernel", N * 5);
+        hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.n_dev, hg.hstats.p, hg.big.p,
+                           hg.big_cap, hg.mid.p, hg.mid_cap, hg.gpb); }
+      PFP_HIP(hipGetLastError());
+      PFP_HIP(hipMemcpyAsync(c->h_scalars, hg.hstats.p, 40, hipMemcpyDeviceToHost, c->stream));
+      sync(c);
+      if (c->h_scalars[2] <= hg.big_cap) break;
+      hg.big_cap = (uint32_t)std::min<uint64_t>(c->h_scalars[2], 0xFFFFFFFFull);   // rare: redo with a queue that fits
+      hg.big.alloc(c, hg.big_cap);
+      hg.hstats.zero();
+    }
+    out.hard_chars = c->h_scalars[0];
+    out.hard_groups = c->h_scalars[1];
+    out.hard_minor_groups = hg.n_heads - lds.n; out.hard_minor_chars = hg.n_minor;
+    out.hard_big_groups = c->h_scalars[2]; out.hard_max_members = c->h_scalars[4];
+    hg.nmid = (uint32_t)std::min<uint64_t>(c->h_scalars[3], hg.mid_cap);
+    PFP_REQUIRE(c->h_scalars[3] <= hg.mid_cap, PFP_EHIP, "more sorted-path hard groups than the output can hold");
+    hg.nbig = (uint32_t)c->h_scalars[2];
+    out.hard_chars += read_scalar(c, (const uint64_t *)hg.mstat.p);      // all chars of hard groups, whichever path wrote them
+    out.hard_groups += hg.n_heads - lds.n;
+  }
+
+  // ---- 10. occurrences of the queued groups, laid end to end
+  void lay_out_queued() {
+    const uint32_t nbig = hg.nbig;
+    hg.es.assign(nbig + 1, 0);
+    if (!nbig) return;
     std::vector<BigGroup> hb(nbig);
-    PFP_HIP(hipMemcpyAsync(hb.data(), big.p, nbig * sizeof(BigGroup), hipMemcpyDeviceToHost, c->stream));
+    PFP_HIP(hipMemcpyAsync(hb.data(), hg.big.p, nbig * sizeof(BigGroup), hipMemcpyDeviceToHost, c->stream));
     sync(c);
-    for (uint32_t q = 0; q < nbig; q++) es[q + 1] = es[q] + hb[q].E;
-    estart.alloc(c, nbig + 1);
-    PFP_HIP(hipMemcpyAsync(estart.p, es.data(), (nbig + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    for (uint32_t q = 0; q < nbig; q++) hg.es[q + 1] = hg.es[q] + hb[q].E;
+    hg.estart.alloc(c, nbig + 1);
+    PFP_HIP(hipMemcpyAsync(hg.estart.p, hg.es.data(), (nbig + 1) * 8, hipMemcpyHostToDevice, c->stream));
     sync(c);
   }
-  auto run_queued = [&]() {
-    if (nmid) {
-      KScope ks(c, "pfp::hard_sort_kernel", (uint64_t)nmid * (kHardSortMin + 1) * (samode ? 21 : 5));      // lower bound: ilist entry + char (+ SA) per occurrence
-      hipLaunchKernelGGL(hard_sort_kernel<I>, gdim(c->n_cu * 4), gdim(256), 0, c->stream, a, mid.p, nmid);
+
+  // ---- 11. the queued groups: sorted in LDS (mid), merged by device-wide sorts or ranked occurrence by occurrence (big)
+  void queued_groups(int pass) {
+    const MergeArgsT<I> ap = with_pass(pass);
+    const std::vector<uint64_t> &es = hg.es;
+    if (hg.nmid) {
+      KScope ks(c, "pfp::hard_sort_kernel", (uint64_t)hg.nmid * (kHardSortMin + 1) * (sa_mode ? 21 : 5));      // lower bound: ilist entry + char (+ SA) per occurrence
+      hipLaunchKernelGGL(hard_sort_kernel<I>, gdim(c->n_cu * 4), gdim(256), 0, c->stream, ap, hg.mid.p, hg.nmid);
       PFP_HIP(hipGetLastError());
     }
     // queued groups in chunks of at most big_budget occurrences: keys, one sort, placement (a single group beyond the
     // budget is ranked occurrence by occurrence - its sort scratch is not worth the memory)
-    for (uint32_t q0 = 0; q0 < nbig;) {
+    for (uint32_t q0 = 0; q0 < hg.nbig;) {
       uint32_t q1 = q0 + 1;
-      while (q1 < nbig && es[q1 + 1] - es[q0] <= big_budget) q1++;
+      while (q1 < hg.nbig && es[q1 + 1] - es[q0] <= sw.big_budget) q1++;
       const uint64_t cnt = es[q1] - es[q0];
-      if (cnt > big_budget) {
+      if (cnt > sw.big_budget) {
         const int nb = (int)std::min<uint64_t>(cdiv64(cnt, 256), (uint64_t)c->n_cu * 32);
-        KScope ks(c, "pfp::hard_big_kernel", cnt * (samode ? 21 : 5));
-        hipLaunchKernelGGL(hard_big_kernel<I>, gdim(nb), gdim(256), 0, c->stream, a, big.p + q0, q1 - q0, estart.p + q0, cnt);
+        KScope ks(c, "pfp::hard_big_kernel", cnt * (sa_mode ? 21 : 5));
+        hipLaunchKernelGGL(hard_big_kernel<I>, gdim(nb), gdim(256), 0, c->stream, ap, hg.big.p + q0, q1 - q0, hg.estart.p + q0, cnt);
       } else {
         DBuf<uint64_t> bk(c, cnt), bka(c, cnt), bv(c, cnt), bva(c, cnt);
         { KScope ks(c, "pfp::big_keys_kernel", cnt * 28);
-          hipLaunchKernelGGL(big_keys_kernel<I>, gdim(cdiv(cnt, 256)), gdim(256), 0, c->stream, a, big.p, q0, q1, estart.p, cnt, bk.p, bv.p); }
+          hipLaunchKernelGGL(big_keys_kernel<I>, gdim(cdiv(cnt, 256)), gdim(256), 0, c->stream, ap, hg.big.p, q0, q1, hg.estart.p, cnt, bk.p, bv.p); }
         { SortTag tag("large hard groups"); sort_pairs_db<uint64_t, uint64_t>(c, bk, bka, bv, bva, cnt, 0, 32 + bits_for(q1 - q0)); }
-        { KScope ks(c, "pfp::big_place_kernel", cnt * (samode ? 34 : 18));
-          hipLaunchKernelGGL(big_place_kernel<I>, gdim(cdiv(cnt, 256)), gdim(256), 0, c->stream, a, big.p, q0, estart.p, cnt, bk.p, bv.p); }
+        { KScope ks(c, "pfp::big_place_kernel", cnt * (sa_mode ? 34 : 18));
+          hipLaunchKernelGGL(big_place_kernel<I>, gdim(cdiv(cnt, 256)), gdim(256), 0, c->stream, ap, hg.big.p, q0, hg.estart.p, cnt, bk.p, bv.p); }
       }
       PFP_HIP(hipGetLastError());
       q0 = q1;
     }
-  };
-  run_queued();
-  if (!sparse) { sync(c); return; }
+  }
 
-  // ---- sparse SA, second round: where can the sampled files look?
-  const uint64_t cnt_slice = a.out_hi > a.out_lo ? a.out_hi - a.out_lo : 0;
-  const uint64_t nw = cdiv64(cnt_slice, 64);
-  out.bmap.alloc(c, nw + 1); out.bpre.alloc(c, nw + 1);
-  // ... and no SA array to write to: the sampled files come from bitmaps (a slice's two edge positions count as run
-  // starts / ends here; the multi-GPU caller drops them again when the neighbour's halo byte says so)
-  const bool want_s = !out.d_sa && (flags & PFP_FLAG_SSA), want_e = !out.d_sa && (flags & PFP_FLAG_ESA);
-  out.slice_n = cnt_slice;
-  {
-    DBuf<uint32_t> wcnt(c, nw + 1), scnt, ecnt;
-    PFP_HIP(hipMemsetAsync(wcnt.p + nw, 0, 4, c->stream));
-    PFP_HIP(hipMemsetAsync(out.bmap.p + nw, 0, 8, c->stream));
-    if (want_s) { out.smap.alloc(c, nw + 1); out.spre.alloc(c, nw + 1); scnt.alloc(c, nw + 1); PFP_HIP(hipMemsetAsync(scnt.p + nw, 0, 4, c->stream)); }
-    if (want_e) { out.emap.alloc(c, nw + 1); out.epre.alloc(c, nw + 1); ecnt.alloc(c, nw + 1); PFP_HIP(hipMemsetAsync(ecnt.p + nw, 0, 4, c->stream)); }
-    if (nw) {
-      KScope ks(c, "pfp::run_bitmap_kernel", cnt_slice + nw * (12 + (want_s ? 12 : 0) + (want_e ? 12 : 0)));
-      hipLaunchKernelGGL(run_bitmap_kernel, gdim(cdiv(cdiv64(cnt_slice, 16), 256)), gdim(256), 0, c->stream, out.d_bwt, cnt_slice,
-                         out.bmap.p, wcnt.p, out.smap.p, scnt.p, out.emap.p, ecnt.p);
+  // ---- 12. sparse SA, second round: where can the sampled files look?  The run boundaries of the finished BWT slice
+  void mark_run_boundaries() {
+    const uint64_t cnt_slice = a.out_hi > a.out_lo ? a.out_hi - a.out_lo : 0;
+    const uint64_t nw = cdiv64(cnt_slice, 64);
+    out.bmap.alloc(c, nw + 1); out.bpre.alloc(c, nw + 1);
+    // ... and no SA array to write to: the sampled files come from bitmaps (a slice's two edge positions count as run
+    // starts / ends here; the multi-GPU caller drops them again when the neighbour's halo byte says so)
+    const bool want_s = !out.d_sa && (o.flags & PFP_FLAG_SSA), want_e = !out.d_sa && (o.flags & PFP_FLAG_ESA);
+    out.slice_n = cnt_slice;
+    {
+      DBuf<uint32_t> wcnt, scnt, ecnt;      // boundaries per word of the maps
+      alloc_counts(c, wcnt, nw);
+      PFP_HIP(hipMemsetAsync(out.bmap.p + nw, 0, 8, c->stream));
+      if (want_s) { out.smap.alloc(c, nw + 1); out.spre.alloc(c, nw + 1); alloc_counts(c, scnt, nw); }
+      if (want_e) { out.emap.alloc(c, nw + 1); out.epre.alloc(c, nw + 1); alloc_counts(c, ecnt, nw); }
+      if (nw) {
+        KScope ks(c, "pfp::run_bitmap_kernel", cnt_slice + nw * (12 + (want_s ? 12 : 0) + (want_e ? 12 : 0)));
+        hipLaunchKernelGGL(run_bitmap_kernel, gdim(cdiv(cdiv64(cnt_slice, 16), 256)), gdim(256), 0, c->stream, out.d_bwt, cnt_slice,
+                           out.bmap.p, wcnt.p, out.smap.p, scnt.p, out.emap.p, ecnt.p);
+      }
+      exclusive_sum_u32_u64(c, wcnt.p, out.bpre.p, nw + 1);
+      if (want_s) exclusive_sum_u32_u64(c, scnt.p, out.spre.p, nw + 1);
+      if (want_e) exclusive_sum_u32_u64(c, ecnt.p, out.epre.p, nw + 1);
+      out.n_bound = read_scalar(c, out.bpre.p + nw);
+      if (want_s) out.n_starts = read_scalar(c, out.spre.p + nw);
+      if (want_e) out.n_ends = read_scalar(c, out.epre.p + nw);
     }
-    exclusive_sum_u32_u64(c, wcnt.p, out.bpre.p, nw + 1);
-    if (want_s) exclusive_sum_u32_u64(c, scnt.p, out.spre.p, nw + 1);
-    if (want_e) exclusive_sum_u32_u64(c, ecnt.p, out.epre.p, nw + 1);
-    out.n_bound = read_scalar(c, out.bpre.p + nw);
-    if (want_s) out.n_starts = read_scalar(c, out.spre.p + nw);
-    if (want_e) out.n_ends = read_scalar(c, out.epre.p + nw);
+    a.bmap = out.bmap.p; a.bpre = out.bpre.p;
+    if (!out.d_sa) {      // the caller keeps no SA array: values go to their rank among the boundaries
+      out.sa_c.alloc(c, out.n_bound + 1);
+      if (c->debug) PFP_HIP(hipMemsetAsync(out.sa_c.p, 0xFF, (out.n_bound + 1) * 8, c->stream));
+      a.sa_c = out.sa_c.p;
+    }
   }
-  a.bmap = out.bmap.p; a.bpre = out.bpre.p;
-  if (!out.d_sa) {      // the caller keeps no SA array: values go to their rank among the boundaries
-    out.sa_c.alloc(c, out.n_bound + 1);
-    if (c->debug) PFP_HIP(hipMemsetAsync(out.sa_c.p, 0xFF, (out.n_bound + 1) * 8, c->stream));
-    a.sa_c = out.sa_c.p;
-  }
-  a.pass = PASS_SA;
-  if (ix.wslot_lex.p && pb.P) {      // whole words: one lane per occurrence of the inverted lists
-    KScope ks(c, "pfp::word_sa_kernel", pb.P * (4 + 8 + 8 + 8));
-    hipLaunchKernelGGL(word_sa_kernel<I>, gdim(cdiv(pb.P, 256)), gdim(256), 0, c->stream, a, pb.P, ix.wslot_lex.p, so.slot_base,
-                       (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-  } else run_expand();
-  { KScope ks(c, "pfp::unit_edges_kernel", N * (1 + sizeof(I) * 2 + 4));
-    hipLaunchKernelGGL(unit_edges_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, a); }
-  if (n_mm) {
-    const uint64_t nr = n_minor;      // one record per minority occurrence, at its precomputed index (MinorMember::roff)
-    if (nr) hipLaunchKernelGGL(hard_minor_sa_kernel<I>, gdim(cdiv(nr, 256)), gdim(256), 0, c->stream, a, recs.p, nr);
-  }
-  if (n_fallback) {      // the groups the LDS kernels ranked: the same ranks again, SA values this time (queues as they stand)
-    DBuf<unsigned long long> scratch(c, 5);
-    scratch.zero();
-    KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-    hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, a, hard_list, hard_list_n, scratch.p, big.p,
-                       0u, mid.p, 0u, gpb);
+
+  // ---- 13. sparse SA, second round: SA values at the boundaries, class by class
+  void sa_round(const HeadList<I> &lds) {
+    const MergeArgsT<I> ap = with_pass(PASS_SA);
+    // whole words: one lane per occurrence of the inverted lists (every caller ranks the words - compute_lexrank or
+    // compute_lexrank_from_slots - before it merges; a parse without phrases emits nothing)
+    PFP_REQUIRE(ix.wslot_lex.p, PFP_EINVAL, "merge: the dictionary index has no whole-word slots (compute_lexrank has not run)");
+    if (pb.P) {
+      KScope ks(c, "pfp::word_sa_kernel", pb.P * (4 + 8 + 8 + 8));
+      hipLaunchKernelGGL(word_sa_kernel<I>, gdim(cdiv(pb.P, 256)), gdim(256), 0, c->stream, ap, pb.P, ix.wslot_lex.p, so.slot_base);
+    }
+    { KScope ks(c, "pfp::unit_edges_kernel", N * (1 + sizeof(I) * 2 + 4));
+      hipLaunchKernelGGL(unit_edges_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, ap); }
+    if (hg.n_mm) {
+      const uint64_t nr = hg.n_minor;      // one record per minority occurrence, at its precomputed index (MinorMember::roff)
+      if (nr) hipLaunchKernelGGL(hard_minor_sa_kernel<I>, gdim(cdiv(nr, 256)), gdim(256), 0, c->stream, ap, hg.recs.p, nr);
+    }
+    if (lds.n) {      // the groups the LDS kernels ranked: the same ranks again, SA values this time (queues as they stand)
+      DBuf<unsigned long long> scratch(c, 5);
+      scratch.zero();
+      KScope ks(c, "pfp::hard_groups_kernel", N * 5);
+      hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.n_dev, scratch.p, hg.big.p,
+                         0u, hg.mid.p, 0u, hg.gpb);
+      PFP_HIP(hipGetLastError());
+      queued_groups(PASS_SA);
+      sync(c);
+    }
     PFP_HIP(hipGetLastError());
-    run_queued();
-    sync(c);
   }
-  PFP_HIP(hipGetLastError());
-  if (c->debug && a.sa_c) {      // every boundary of the BWT must have received its value
+
+  // ---- 14. PFP_DEBUG: every boundary of the BWT must have received its value
+  void check_boundaries_set() {
+    if (!c->debug || !a.sa_c) return;
     DBuf<unsigned long long> unset(c, 1);
     unset.zero();
     // (a slice's own two edge positions are marked as boundaries whatever their neighbours in the other slices hold:
@@ -1853,160 +1656,46 @@ void merge_bwt(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const Suffi
     const uint64_t u = read_scalar(c, (const uint64_t *)unset.p);
     PFP_REQUIRE(u == 0, PFP_EHIP, "sparse SA: " + std::to_string(u) + " run boundaries of the BWT received no SA value");
   }
-  sync(c);
+
+  void run() {
+    PFP_REQUIRE(!o.flags || pb.bwsai.p, PFP_EINVAL, "SA output requested without sa info");
+    word_records();
+    {
+      DBuf<uint32_t> cnt;      // from the sort keys: occurrences per slot, until the offsets are summed
+      if (src == RecordSource::SortKeys) alloc_counts(c, cnt, N, 8);
+      alloc_slot_tables();
+      switch (src) {
+        case RecordSource::SortKeys: slot_tables_from_keys(cnt); break;
+        case RecordSource::Gathered: slot_tables_gathered(); break;
+        case RecordSource::PerSlot: slot_tables_per_slot(); break;
+      }
+      offsets_and_totals();
+    }
+    fill_args();
+    find_hard_groups();
+    const HeadList<I> lds = sa_mode != SA_DENSE && hg.n_heads ? classify() : HeadList<I>{hg.heads.p, hg.list_len.p + kAllHeads, hg.n_heads};
+    expand();
+    place_minority(lds);
+    rank_in_lds(lds);
+    lay_out_queued();
+    queued_groups(first_pass);
+    if (sa_mode == SA_SPARSE) {
+      mark_run_boundaries();
+      sa_round(lds);
+      check_boundaries_set();
+    }
+    sync(c);
+  }
+};
+
+template <class I>
+void merge_bwt(pfp_ctx *c, const Dictionary &D, const DictIndex &ix, const SuffixOrderT<I> &so, const ParseBWT &pb,
+               const uint32_t *occ_lex, const MergeOpts &o, BwtOutputs &out) {
+  Merge<I>(c, D, ix, so, pb, occ_lex, o, out).run();
 }
 template void merge_bwt<uint32_t>(pfp_ctx *, const Dictionary &, const DictIndex &, const SuffixOrderT<uint32_t> &, const ParseBWT &,
-                                  const uint32_t *, int, int, uint64_t, BwtOutputs &, uint64_t, uint64_t, uint64_t, uint64_t);
+                                  const uint32_t *, const MergeOpts &, BwtOutputs &);
 template void merge_bwt<uint64_t>(pfp_ctx *, const Dictionary &, const DictIndex &, const SuffixOrderT<uint64_t> &, const ParseBWT &,
-                                  const uint32_t *, int, int, uint64_t, BwtOutputs &, uint64_t, uint64_t, uint64_t, uint64_t);
-
-// ------------------------------------------------------------------ output packing
-
-// utils.c:112-129: low 5 bytes, little endian.  One thread per 16 OUTPUT bytes (3.2 values): it reads the
-// (up to) four values its chunk overlaps - neighbouring lanes read overlapping, consecutive values - lays
-// their 5-byte fields end to end and cuts its 16 bytes out; every store is one aligned-size 16-byte store.
-__global__ __launch_bounds__(256) void pack5_kernel(const uint64_t *__restrict__ v, uint64_t cnt, uint8_t *__restrict__ out) {
-  const uint64_t q = (uint64_t)BID * 256 + threadIdx.x;
-  const uint64_t total = cnt * 5, b0 = q * 16;
-  if (b0 >= total) return;
-  const uint64_t v0 = b0 / 5;
-  const uint32_t s = (uint32_t)(b0 - v0 * 5) * 8;
-  const uint64_t M = 0xFFFFFFFFFFull;
-  const uint64_t a = v[v0] & M, b = v0 + 1 < cnt ? v[v0 + 1] & M : 0, c2 = v0 + 2 < cnt ? v[v0 + 2] & M : 0,
-                 d = v0 + 3 < cnt ? v[v0 + 3] & M : 0;
-  const uint64_t lo = a | (b << 40), mid = (b >> 24) | (c2 << 16) | (d << 56), hi = d >> 8;
-  const uint64_t olo = s ? (lo >> s) | (mid << (64 - s)) : lo, ohi = s ? (mid >> s) | (hi << (64 - s)) : mid;
-  if (b0 + 16 <= total) st16u(out + b0, make_uint4((uint32_t)olo, (uint32_t)(olo >> 32), (uint32_t)ohi, (uint32_t)(ohi >> 32)));
-  else
-    for (uint64_t k = 0; b0 + k < total; k++) out[b0 + k] = (uint8_t)((k < 8 ? olo >> (8 * k) : ohi >> (8 * (k - 8))) & 0xff);
-}
-__global__ void unpack5_kernel(const uint8_t *__restrict__ in, uint64_t cnt, uint64_t *__restrict__ v) {
-  uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (i >= cnt) return;
-  const uint8_t *p = in + 5 * i;
-  uint64_t x = 0;
-#pragma unroll
-  for (int b = 0; b < 5; b++) x |= (uint64_t)p[b] << (8 * b);
-  v[i] = x;
-}
-void pack5_dev(pfp_ctx *c, const uint64_t *vals, uint64_t cnt, uint8_t *out5) {
-  if (!cnt) return;
-  KScope ks(c, "pfp::pack5_kernel", cnt * 13);
-  hipLaunchKernelGGL(pack5_kernel, gdim((unsigned)cdiv64(cdiv64(cnt * 5, 16), TB)), gdim(TB), 0, c->stream, vals, cnt, out5);
-  PFP_HIP(hipGetLastError());
-}
-void unpack5_dev(pfp_ctx *c, const uint8_t *in5, uint64_t cnt, uint64_t *vals) {
-  if (!cnt) return;
-  hipLaunchKernelGGL(unpack5_kernel, gdim(cdiv(cnt, TB)), gdim(TB), 0, c->stream, in5, cnt, vals);
-  PFP_HIP(hipGetLastError());
-}
-
-// run boundaries: .ssa = <j,SA[j]> for BWT[j] != BWT[j-1] incl. j=0 (pfbwt.cpp:169-174,184-189);
-//                 .esa = <j,SA[j]> for BWT[j] != BWT[j+1] incl. j=n (pfbwt.cpp:175-179,225-229)
-// Two streaming passes over the BWT bytes of a slice [pos_base, pos_base+cnt) (16 positions per thread from
-// one unaligned 16-byte load, the neighbour byte shifted in): boundaries counted per tile of 4096
-// positions, tile offsets scanned, then every thread places its pairs <position, SA value> as 10 bytes.
-// left / right: the BWT byte just outside the slice, or -1 at the ends of the whole BWT (then the
-// edge position is a boundary by definition).
-__global__ __launch_bounds__(256) void run_count_kernel(const uint8_t *__restrict__ bwt, uint64_t cnt, int left, int right,
-                                                        int run_end, uint32_t *__restrict__ tile_cnt) {
-  __shared__ uint32_t ws[4];
-  if ((uint64_t)BID * kRunTile >= cnt) return;      // a workgroup of the padded last grid row
-  const uint64_t base = (uint64_t)BID * kRunTile + (uint64_t)threadIdx.x * 16;
-  uint32_t m[4];
-  run_mask16(bwt, base, cnt, left, right, run_end, m);
-  uint32_t c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_cnt[BID] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-__global__ __launch_bounds__(256) void run_place_kernel(const uint8_t *__restrict__ bwt, SaView sa,
-                                                        uint64_t cnt, uint64_t pos_base, int left, int right, int run_end,
-                                                        const uint64_t *__restrict__ tile_off, uint8_t *__restrict__ out10) {
-  __shared__ uint32_t ws[4];
-  if ((uint64_t)BID * kRunTile >= cnt) return;      // a workgroup of the padded last grid row
-  const uint64_t base = (uint64_t)BID * kRunTile + (uint64_t)threadIdx.x * 16;
-  uint32_t m[4];
-  run_mask16(bwt, base, cnt, left, right, run_end, m);
-  const uint32_t c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
-  uint32_t inc = c;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
-  if (lane == 63) ws[wv] = inc;
-  __syncthreads();
-  if (!c) return;
-  uint64_t o = tile_off[BID] + inc - c;
-  for (int q = 0; q < wv; q++) o += ws[q];
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    if ((m[k >> 2] >> (8 * (k & 3))) & 1u) {
-      const uint64_t x = pos_base + base + k, r = base + k;
-      uint64_t v;
-      if (sa.dense) v = sa.dense[r];
-      else { const uint64_t wv = sa.bmap[r >> 6]; v = sa.sa_c[sa.bpre[r >> 6] + (uint64_t)__popcll(wv & ((1ull << (r & 63)) - 1ull))]; }
-      uint8_t *dst = out10 + 10 * o;
-      reinterpret_cast<U64u *>(dst)->v = (x & 0xFFFFFFFFFFull) | (v << 40);       // 5 bytes of x, 3 low bytes of v
-      reinterpret_cast<U16u *>(dst + 8)->v = (uint16_t)(v >> 24);                  // bytes 3, 4 of v
-      o++;
-    }
-}
-
-RunSampler::RunSampler(pfp_ctx *c_, const uint8_t *bwt_, uint64_t cnt_, int left_, int right_, bool run_end_)
-    : c(c_), bwt(bwt_), cnt(cnt_), left(left_), right(right_), run_end(run_end_) {
-  ntile = cdiv64(cnt, kRunTile);
-  tile_cnt.alloc(c, ntile + 1);
-  tile_off.alloc(c, ntile + 1);
-  PFP_HIP(hipMemsetAsync(tile_cnt.p + ntile, 0, 4, c->stream));
-  if (ntile) {
-    KScope ks(c, "pfp::run_count_kernel", cnt);
-    hipLaunchKernelGGL(run_count_kernel, gdim((unsigned)ntile), gdim(256), 0, c->stream, bwt, cnt, left, right, run_end ? 1 : 0,
-                       tile_cnt.p);
-  }
-  exclusive_sum_u32_u64(c, tile_cnt.p, tile_off.p, ntile + 1);
-  PFP_HIP(hipGetLastError());
-  pairs = read_scalar(c, tile_off.p + ntile);
-}
-void RunSampler::place(const SaView &sa, uint64_t pos_base, uint8_t *out10) {
-  if (!ntile || !pairs) return;
-  KScope ks(c, "pfp::run_place_kernel", cnt + pairs * 18);
-  hipLaunchKernelGGL(run_place_kernel, gdim((unsigned)ntile), gdim(256), 0, c->stream, bwt, sa, cnt, pos_base, left, right,
-                     run_end ? 1 : 0, tile_off.p, out10);
-  PFP_HIP(hipGetLastError());
-}
-
-uint64_t sample_runs_dev(pfp_ctx *c, const uint8_t *bwt, const SaView &sa, uint64_t n_out, bool run_end,
-                         DBuf<uint8_t> &out10) {
-  const uint64_t *map = run_end ? sa.emap : sa.smap;
-  if (map && sa.sa_c) {      // the merge left the run starts / ends as bitmaps
-    const uint64_t pairs = run_end ? sa.n_ends : sa.n_starts;
-    out10.alloc(c, pairs * 10 + 16);
-    if (sa.n_words) {
-      KScope ks(c, "pfp::bitmap_place_kernel", sa.n_words * 24 + pairs * 18);
-      hipLaunchKernelGGL(bitmap_place_kernel, gdim(cdiv(sa.n_words, 256)), gdim(256), 0, c->stream, map, run_end ? sa.epre : sa.spre, sa.bmap,
-                         sa.bpre, sa.sa_c, sa.n_words, out10.p, (uint64_t)0, 0, ~0ull);
-      PFP_HIP(hipGetLastError());
-    }
-    return pairs;
-  }
-  RunSampler rs(c, bwt, n_out, -1, -1, run_end);
-  out10.alloc(c, rs.pairs * 10 + 16);
-  rs.place(sa, 0, out10.p);
-  return rs.pairs;
-}
-
-uint64_t sample_runs_maps(pfp_ctx *c, const SaView &sa, uint64_t slice_n, bool run_end, bool drop_edge, uint64_t pos_base, uint8_t *out10) {
-  const uint64_t *map = run_end ? sa.emap : sa.smap;
-  PFP_REQUIRE(map && sa.sa_c, PFP_EINVAL, "no run maps: the merge was not run for a sampled SA without an SA array");
-  const uint64_t all = run_end ? sa.n_ends : sa.n_starts;
-  const uint64_t pairs = all - ((drop_edge && all) ? 1 : 0);
-  if (!out10 || !pairs || !sa.n_words) return pairs;
-  KScope ks(c, "pfp::bitmap_place_kernel", sa.n_words * 24 + pairs * 18);
-  hipLaunchKernelGGL(bitmap_place_kernel, gdim(cdiv(sa.n_words, 256)), gdim(256), 0, c->stream, map, run_end ? sa.epre : sa.spre, sa.bmap,
-                     sa.bpre, sa.sa_c, sa.n_words, out10, pos_base, (drop_edge && !run_end) ? 1 : 0,
-                     (drop_edge && run_end && slice_n) ? slice_n - 1 : ~0ull);
-  PFP_HIP(hipGetLastError());
-  return pairs;
-}
+                                  const uint32_t *, const MergeOpts &, BwtOutputs &);
 
 }  // namespace pfp
