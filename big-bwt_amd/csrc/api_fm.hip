@@ -2,6 +2,7 @@
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
 // of a collection (seqmap.hip).
 #include <memory>
+#include <vector>
 #include "api.hpp"
 
 using namespace pfp;
@@ -25,6 +26,15 @@ struct HostOut {
   }
   T *release() { T *q = n ? p : nullptr; if (!n) free(p); p = nullptr; return q; }
 };
+
+// `count` device values behind the n held
+template <class T>
+static void apx_take(pfp_ctx *c, HostOut<T> &out, const T *d_src, uint64_t count) {
+  if (!count) return;
+  download(c, out.grow(count), (const uint8_t *)d_src, count * sizeof(T));
+  sync(c);      // (the next download fills the same pinned buffers)
+  out.n += count;
+}
 
 extern "C" {
 
@@ -137,6 +147,153 @@ int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint6
     fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, d_pos.p);
     *pos = (uint64_t *)fetch_bytes(c, (const uint8_t *)d_pos.p, total * 8);
   }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- approximate search (fmapprox.hip)
+int pfp_fm_approx_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, int k, uint64_t *d_hit_off, uint64_t *d_sp,
+                      uint64_t *d_ep, uint64_t *d_first, uint8_t *d_dist) {
+  if (!fm || !d_hit_off || (npat && !d_pat_off)) return PFP_EINVAL;
+  const bool fill = d_sp || d_ep || d_dist;
+  if (fill && !(d_sp && d_ep && d_dist)) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_approx(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, k, d_hit_off, d_sp, d_ep, d_first, d_dist);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_approx_stats(pfp_fm *fm, uint64_t out[3]) {
+  if (!fm || !out) return PFP_EINVAL;
+  memcpy(out, fm->f.apx_stats, sizeof fm->f.apx_stats);
+  memset(fm->f.apx_stats, 0, sizeof fm->f.apx_stats);
+  return PFP_OK;
+}
+
+// host patterns on the device with their hit counts: cnt on the device (npat + 1), hcnt on the host
+struct ApxCall {
+  DBuf<uint8_t> pat;
+  DBuf<uint64_t> off, cnt;
+  std::vector<uint64_t> hcnt;
+  uint64_t budget = PFP_SEQ_BUDGET;
+  // the end of the group of consecutive entries that starts at p0: their sum stays within the budget, a larger entry goes alone
+  uint64_t group_end(const std::vector<uint64_t> &per, uint64_t p0, uint64_t end) const {
+    uint64_t p1 = p0 + 1, sum = per[p0];
+    while (p1 < end && sum + per[p1] <= budget) sum += per[p1++];
+    return p1;
+  }
+};
+static void apx_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, bool toehold, ApxCall &s) {
+  pfp_ctx *c = fm->f.c;
+  fm_approx_check(fm->f, k, toehold);
+  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
+    const uint64_t v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < s.budget) s.budget = v;
+  }
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  s.pat.alloc(c, bytes + 16);
+  s.off.alloc(c, npat + 1);
+  s.cnt.alloc(c, npat + 1);
+  s.hcnt.assign(npat + 1, 0);
+  if (bytes) h2d(c, s.pat.p, pat, bytes);
+  if (npat) h2d(c, s.off.p, pat_off, npat + 1);
+  fm_approx_count(fm->f, s.pat.p, s.off.p, npat, k, s.cnt.p);
+  d2h(c, s.hcnt.data(), s.cnt.p, npat + 1);
+  sync(c);
+}
+// the hits of patterns [p0, p1) on the device
+struct ApxHits {
+  DBuf<uint64_t> hoff, sp, ep, first;
+  DBuf<uint8_t> dist;
+  uint64_t H = 0;
+};
+static void apx_group_hits(pfp_fm *fm, const ApxCall &s, uint64_t p0, uint64_t p1, int k, bool toehold, ApxHits &h) {
+  pfp_ctx *c = fm->f.c;
+  const uint64_t np = p1 - p0;
+  h.H = 0;
+  for (uint64_t p = p0; p < p1; p++) h.H += s.hcnt[p];
+  h.hoff.alloc(c, np + 1);
+  exclusive_sum_u64(c, s.cnt.p + p0, h.hoff.p, np + 1);   // (entry np of the input does not reach the sums)
+  h.sp.alloc(c, h.H); h.ep.alloc(c, h.H); h.dist.alloc(c, h.H);
+  if (toehold) h.first.alloc(c, h.H);
+  fm_approx_fill(fm->f, s.pat.p, s.off.p + p0, np, k, h.hoff.p, h.H, h.sp.p, h.ep.p, toehold ? h.first.p : nullptr, h.dist.p);
+}
+
+int pfp_fm_approx(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *hit_off, uint64_t **sp,
+                  uint64_t **ep, uint64_t **first, uint8_t **dist) {
+  if (!fm || !hit_off || !sp || !ep || !dist || (npat && !pat_off)) return PFP_EINVAL;
+  *sp = nullptr; *ep = nullptr; *dist = nullptr;
+  if (first) *first = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  ApxCall s;
+  apx_call_begin(fm, pat, pat_off, npat, k, first != nullptr, s);
+  HostOut<uint64_t> h_sp, h_ep, h_first;
+  HostOut<uint8_t> h_dist;
+  hit_off[0] = 0;
+  for (uint64_t p = 0; p < npat; p++) hit_off[p + 1] = hit_off[p] + s.hcnt[p];
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
+    p1 = s.group_end(s.hcnt, p0, npat);
+    ApxHits h;
+    apx_group_hits(fm, s, p0, p1, k, first != nullptr, h);
+    sync(c);
+    apx_take(c, h_sp, h.sp.p, h.H);
+    apx_take(c, h_ep, h.ep.p, h.H);
+    apx_take(c, h_dist, h.dist.p, h.H);
+    if (first) apx_take(c, h_first, h.first.p, h.H);
+  }
+  *sp = h_sp.release(); *ep = h_ep.release(); *dist = h_dist.release();
+  if (first) *first = h_first.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_approx_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t max_occ, uint64_t *out_off,
+                         uint64_t **pos, uint8_t **dist) {
+  if (!fm || !out_off || !pos || !dist || (npat && !pat_off)) return PFP_EINVAL;
+  *pos = nullptr; *dist = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  ApxCall s;
+  apx_call_begin(fm, pat, pat_off, npat, k, true, s);
+  HostOut<uint64_t> h_pos;
+  HostOut<uint8_t> h_dist;
+  std::vector<uint64_t> go, per, hbase;
+  out_off[0] = 0;
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
+    p1 = s.group_end(s.hcnt, p0, npat);
+    const uint64_t np = p1 - p0;
+    ApxHits h;
+    apx_group_hits(fm, s, p0, p1, k, true, h);
+    DBuf<uint64_t> d_go(c, np + 1), cep;
+    fm_approx_clip(fm->f, np, h.hoff.p, h.H, h.sp.p, h.ep.p, h.first.p, max_occ, d_go.p, cep);
+    go.resize(np + 1);
+    d2h(c, go.data(), d_go.p, np + 1);
+    sync(c);
+    per.resize(np);
+    hbase.assign(np + 1, 0);
+    for (uint64_t i = 0; i < np; i++) {
+      out_off[p0 + i + 1] = out_off[p0] + go[i + 1];
+      per[i] = go[i + 1] - go[i];
+      hbase[i + 1] = hbase[i] + s.hcnt[p0 + i];
+    }
+    // inside the group: consecutive patterns whose positions stay within the budget
+    for (uint64_t q0 = 0, q1; q0 < np; q0 = q1) {
+      q1 = s.group_end(per, q0, np);
+      const uint64_t h0 = hbase[q0], nh = hbase[q1] - h0;
+      DBuf<uint64_t> d_pos;
+      DBuf<uint8_t> d_pd;
+      const uint64_t U = fm_approx_positions(fm->f, nh, h.sp.p + h0, cep.p + h0, h.first.p + h0, h.dist.p + h0, d_pos, d_pd);
+      if (U != go[q1] - go[q0]) throw Error(PFP_EHIP, "approximate locate: a group's positions do not add up");
+      apx_take(c, h_pos, d_pos.p, U);
+      apx_take(c, h_dist, d_pd.p, U);
+    }
+  }
+  *pos = h_pos.release();
+  *dist = h_dist.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

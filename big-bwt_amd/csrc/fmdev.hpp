@@ -1,4 +1,4 @@
-// fmdev.hpp -- what the kernels over an FmIndex share (fmsearch.hip, lcp.hip): the index as kernel arguments, rank and select
+// fmdev.hpp -- what the kernels over an FmIndex share (fmsearch.hip, fmapprox.hip, lcp.hip, seqmap.hip): the index as kernel arguments, rank and select
 // by groups of 16 lanes, the longest common extension on the text, and the record a bounded launch leaves behind.
 #pragma once
 #include "kernels.hpp"
@@ -113,6 +113,7 @@ __global__ void __launch_bounds__(kTB) bucket_dir_k(const K *__restrict__ key, u
 }
 
 constexpr uint64_t kMsWork = 16384;         // units of work per pattern and launch: one per step, one per 1024 bytes compared
+                                            // (matching statistics), one per iteration of the approximate walk (fmapprox.hip)
 struct MsRec { uint64_t t, q, pos, l; };    // the next byte to read is pat[t - 1]; SA[q] = pos; l bytes matched to the right of it
 
 // the common prefix of T[x ..) and T[y ..), at most cap bytes and never past the end of the text (x, y are clamped to n); the

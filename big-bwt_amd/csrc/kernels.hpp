@@ -333,6 +333,7 @@ struct FmIndex {
   DBuf<uint8_t> text;                    // the text, n1 - 1 bytes and 16 bytes of zero padding (whole 16-byte loads stay in bounds)
   DBuf<uint8_t> re_sa;                   // [runs] of I: SA value of run end i
   uint64_t ms_stats[3] = {0, 0, 0};      // fm_ms launches; with PFP_FM_MS_STATS=1 also steps that jumped and bytes their LCEs matched
+  uint64_t apx_stats[3] = {0, 0, 0};     // fm_approx launches and hits filled; with PFP_FM_MS_STATS=1 also (in [1]) LF pairs
   bool has_thr = false;                  // fm_lcp (keep) or fm_load_thresholds filled the array below
   DBuf<uint8_t> thr;                     // [runs] of I: the threshold row of run k (lcp.hip)
   uint64_t nseq = 0;                     // sequences of the collection (seqmap.hip); 0: no table was set
@@ -392,6 +393,26 @@ struct DocOut {
 };
 void fm_doclist(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
                 uint64_t *doc_off, DocOut &o);
+// k-mismatch search (fmapprox.hip; pfpgpu.h, "Approximate search", states the definitions).  Device pointers.  k outside 0 ..
+// PFP_FM_APPROX_MAX_K, or a toehold asked of an index without samples -> PFP_EINVAL
+void fm_approx_check(const FmIndex &f, int k, bool toehold);
+// cnt[p] = hits of pattern p, cnt[npat] = 0 (npat + 1 entries)
+void fm_approx_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *cnt);
+// the H = hit_off[npat] hits, pattern p's at hit_off[p] .. hit_off[p+1] by increasing sp (hit_off: the exclusive sums of
+// fm_approx_count's counts); first may be NULL
+void fm_approx_fill(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, const uint64_t *hit_off, uint64_t H,
+                    uint64_t *sp, uint64_t *ep, uint64_t *first, uint8_t *dist);
+// both: hit_off[0..npat] is written; sp == NULL: only that
+void fm_approx(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *hit_off, uint64_t *sp, uint64_t *ep,
+               uint64_t *first, uint8_t *dist);
+// locating fm_approx_fill's hits, at most max_occ rows per pattern (0: all): cep[h] = hit h's ep clipped to the rows its pattern
+// keeps (allocated here), out_off[0..npat] the exclusive sums of the positions per pattern
+void fm_approx_clip(FmIndex &f, uint64_t npat, const uint64_t *hit_off, uint64_t H, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
+                    uint64_t max_occ, uint64_t *out_off, DBuf<uint64_t> &cep);
+// the positions of H hits (a whole call's, or those of consecutive patterns) in hit order, rows in row order, each with its hit's
+// distance; pos / pdist are allocated here once their number, which is returned, is known
+uint64_t fm_approx_positions(FmIndex &f, uint64_t H, const uint64_t *sp, const uint64_t *cep, const uint64_t *first, const uint8_t *dist,
+                             DBuf<uint64_t> &pos, DBuf<uint8_t> &pdist);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

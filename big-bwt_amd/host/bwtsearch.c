@@ -3,6 +3,7 @@
  *   bwtsearch [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
  *   bwtsearch --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch -l --seqs[=FILE] | --docs [--seqs=FILE] ... PATTERNFILE basename        (any mode: --rc)
+ *   bwtsearch -k K [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -21,6 +22,10 @@
  * `ndocs<TAB>name:hits name:hits ...`: the sequences that hold the pattern inside them, in table order, with their numbers of
  * hits; every occurrence counts.  --rc searches every line as given and then as its reverse complement (reversed, A<->T, C<->G,
  * a<->t, c<->g, other bytes as they are): two output lines per input line, in that order, in every mode.
+ * -k K (0..3) searches with at most K substitutions (the definitions: include/pfpgpu.h, "Approximate search").  The line becomes
+ * `total<TAB>c0 c1 .. cK`: the approximate occurrences, and how many of them have exactly 0, 1, .. K mismatches; with -l
+ * `total<TAB>pos:d pos:d ...`: the positions with their mismatches, hits by increasing row range and rows in row order, at most
+ * MAXOCC of them; total stays the number of occurrences.  Not with --ms, --mems, --docs or --seqs.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -41,12 +46,16 @@
 static void usage(const char *argv0) {
   printf("usage: %s [-h] [-l] [-m MAXOCC] [--seqs[=FILE]] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --docs [--seqs=FILE] [--rc] [--device D] PATTERNFILE basename\n"
-         "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
+         "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
+         "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
          "  -l            print count<TAB>positions (in suffix order) instead of the count\n"
          "  -m MAXOCC     with -l: at most MAXOCC positions per pattern (def. 0 = all)\n"
+         "  -k K          at most K substitutions (0..3): print total<TAB>c0 c1 .. cK, the occurrences and how many of them have\n"
+         "                exactly 0, 1, .. K mismatches; with -l total<TAB>pos:d ... , at most MAXOCC positions with their\n"
+         "                mismatches (not with --ms, --mems, --docs, --seqs)\n"
          "      --ms        print the matching statistics: len:pos for every byte of the line (0:- where nothing matches);\n"
          "                  reads basename.bwt, .ssa and .esa\n"
          "      --mems L    print count<TAB>i:len:pos ... : the maximal exact matches of at least L >= 1 bytes; reads the same files\n"
@@ -59,7 +68,7 @@ static void usage(const char *argv0) {
          "                  reads basename.ssa and .esa; every occurrence counts)\n"
          "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0, argv0);
+         argv0, argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -97,7 +106,7 @@ static void revcomp(const uint8_t *in, uint64_t len, uint8_t *out) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0;
   const char *seqsfile = NULL;
   pfp_seqs tab;
   pfp_seqs_init(&tab);
@@ -109,7 +118,7 @@ int main(int argc, char **argv) {
                                {0, 0, 0, 0}};
   int c;
   char *end;
-  while ((c = getopt_long(argc, argv, "lm:h", lo, NULL)) != -1) {
+  while ((c = getopt_long(argc, argv, "lm:k:h", lo, NULL)) != -1) {
     switch (c) {
       case 'l': locate = 1; break;
       case 'm':
@@ -117,6 +126,12 @@ int main(int argc, char **argv) {
         if (!*optarg || *end || optarg[0] == '-') { usage(argv[0]); return 2; }
         have_m = 1;
         break;
+      case 'k': {
+        const long v = strtol(optarg, &end, 10);
+        if (!*optarg || *end || v < 0 || v > PFP_FM_APPROX_MAX_K) { usage(argv[0]); return 2; }
+        approx = 1;
+        kmis = (int)v;
+      } break;
       case 1002: ms = 1; break;
       case 1003:
         min_len = strtoull(optarg, &end, 10);
@@ -137,7 +152,8 @@ int main(int argc, char **argv) {
     }
   }
   if (optind + 2 != argc) { usage(argv[0]); return 2; }
-  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems) || ((ms || mems) && seqs)) {
+  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems) || ((ms || mems) && seqs) ||
+      (approx && (ms || mems || docs || seqs))) {
     usage(argv[0]);
     return 2;
   }
@@ -228,7 +244,7 @@ int main(int argc, char **argv) {
   if (env && strtoull(env, NULL, 10) > 0) batch = strtoull(env, NULL, 10);
   const uint64_t max_bytes = 64ull << 20, mult = rcomp ? 2 : 1;      /* --rc: every line gives two patterns */
   uint64_t *off = malloc((mult * batch + 1) * sizeof(uint64_t)), *oo = malloc((mult * batch + 1) * sizeof(uint64_t));
-  uint64_t *sp = malloc(mult * batch * sizeof(uint64_t)), *ep = malloc(mult * batch * sizeof(uint64_t));
+  uint64_t *sp = malloc((mult * batch + 1) * sizeof(uint64_t)), *ep = malloc(mult * batch * sizeof(uint64_t));
   uint8_t *buf = malloc(mult * max_bytes + 1), *big = NULL;
   if (!off || !oo || !sp || !ep || !buf) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
   static char obuf[1 << 20];
@@ -308,6 +324,32 @@ int main(int argc, char **argv) {
         putchar('\n');
       }
       pfp_free(doc); pfp_free(cnt);
+    } else if (approx) {
+      uint64_t *hsp = NULL, *hep = NULL, *pos = NULL;
+      uint8_t *hd = NULL, *pd = NULL;
+      rc = pfp_fm_approx(fm, pat, off, k, kmis, oo, &hsp, &hep, NULL, &hd);
+      if (!rc && locate) rc = pfp_fm_approx_locate(fm, pat, off, k, kmis, maxocc, sp, &pos, &pd);      /* (sp: the positions' offsets) */
+      if (rc) {
+        fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
+        pfp_free(hsp); pfp_free(hep); pfp_free(hd);
+        rc = 1;
+        goto done;
+      }
+      for (uint64_t i = 0; i < k; i++) {
+        uint64_t by[PFP_FM_APPROX_MAX_K + 1] = {0}, total = 0;
+        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) {
+          total += hep[j] - hsp[j];
+          if (hd[j] <= PFP_FM_APPROX_MAX_K) by[hd[j]] += hep[j] - hsp[j];
+        }
+        printf("%" PRIu64 "\t", total);
+        if (locate) {
+          for (uint64_t j = sp[i]; j < sp[i + 1]; j++) printf(j > sp[i] ? " %" PRIu64 ":%u" : "%" PRIu64 ":%u", pos[j], (unsigned)pd[j]);
+        } else {
+          for (int d = 0; d <= kmis; d++) printf(d ? " %" PRIu64 : "%" PRIu64, by[d]);
+        }
+        putchar('\n');
+      }
+      pfp_free(hsp); pfp_free(hep); pfp_free(hd); pfp_free(pos); pfp_free(pd);
     } else if (locate && seqs) {
       uint32_t *sq = NULL;
       uint64_t *so = NULL;

@@ -37,7 +37,10 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
            "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats",
            "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
-           "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist"]
+           "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
+           "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats"]
+
+FM_APPROX_MAX_K = 3
 
 LCP_LCP, LCP_THR = 1, 2
 
@@ -164,6 +167,58 @@ class FmIndex:
             positions = np.ctypeslib.as_array(pos, shape=(total,)).copy()
             self.lib.pfp_free(pos)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
+
+    def approx(self, patterns, k, toehold=False):
+        """the hits of every pattern with at most k substitutions (pfpgpu.h, "Approximate search"; k in 0..FM_APPROX_MAX_K)
+        -> (hit_off, sp, ep, dist): pattern p's hits, by increasing sp, are the row ranges [sp[i], ep[i]) with dist[i] (uint8)
+        mismatches for i in hit_off[p]:hit_off[p+1]; toehold=True: (hit_off, sp, ep, dist, SA[sp]) (needs samples)"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        hit_off = np.zeros(npat + 1, dtype=np.uint64)
+        sp, ep, first = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        dist = C.POINTER(C.c_uint8)()
+        self.ctx._check(self.lib.pfp_fm_approx(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_int(k),
+                                               _ptr(hit_off, C.c_uint64), C.byref(sp), C.byref(ep), C.byref(first) if toehold else None,
+                                               C.byref(dist)))
+        total = int(hit_off[-1])
+        out = [hit_off, _take(sp, total, np.uint64), _take(ep, total, np.uint64), _take(dist, total, np.uint8)]
+        if toehold:
+            out.append(_take(first, total, np.uint64))
+        for q in (sp, ep, first, dist):
+            if q:
+                self.lib.pfp_free(q)
+        return tuple(out)
+
+    def approx_locate(self, patterns, k, max_occ=0):
+        """-> (off, pos, dist): the positions of pattern p's occurrences with at most k substitutions are pos[off[p]:off[p+1]],
+        hits by increasing sp and rows in row order inside a hit, each with its number of mismatches in dist (uint8); at most
+        max_occ per pattern (0: all).  Needs samples."""
+        pat, poff = _patterns(patterns)
+        npat = len(poff) - 1
+        out_off = np.zeros(npat + 1, dtype=np.uint64)
+        pos, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
+        self.ctx._check(self.lib.pfp_fm_approx_locate(self._h, _ptr(pat, C.c_uint8), _ptr(poff, C.c_uint64), C.c_uint64(npat), C.c_int(k),
+                                                      C.c_uint64(max_occ), _ptr(out_off, C.c_uint64), C.byref(pos), C.byref(dist)))
+        total = int(out_off[-1])
+        res = out_off, _take(pos, total, np.uint64), _take(dist, total, np.uint8)
+        for q in (pos, dist):
+            if q:
+                self.lib.pfp_free(q)
+        return res
+
+    def approx_dev(self, d_pat, d_pat_off, npat, k, d_hit_off, d_sp=None, d_ep=None, d_dist=None, d_first=None):
+        """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_hit_off; d_sp / d_ep (uint64) and d_dist
+        (uint8), room for d_hit_off[npat] each, get the hits (all three None: offsets only), d_first their toeholds"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._check(self.lib.pfp_fm_approx_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_int(k),
+                                                   C.c_void_p(d_hit_off), vp(d_sp), vp(d_ep), vp(d_first), vp(d_dist)))
+
+    def approx_stats(self):
+        """{launches, pairs, hits} of the approximate searches since the last look; pairs (LF pairs of the walks) are collected
+        only under PFP_FM_MS_STATS=1"""
+        out = (C.c_uint64 * 3)()
+        self.ctx._check(self.lib.pfp_fm_approx_stats(self._h, out))
+        return dict(launches=int(out[0]), pairs=int(out[1]), hits=int(out[2]))
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

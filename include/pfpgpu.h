@@ -528,6 +528,50 @@ int pfp_fm_info(const pfp_fm *fm, pfp_fm_info_t *out);
 void pfp_fm_free(pfp_fm *fm);
 
 /* ------------------------------------------------------------------------------------
+ * Approximate search: the occurrences of a pattern with at most k substitutions, over the same index (csrc/fmapprox.hip).  The
+ * reference has no counterpart: the method is backtracking over the BWT, a depth-first walk that spends one of k mismatches
+ * where it steps with a byte other than the pattern's.  Conventions as in "Searching a BWT": the text T has n bytes, rows run
+ * 0..n with SA[0] = n, symbols are the bytes other than 0 that T holds.
+ * For a pattern P of m bytes and a budget k in 0..PFP_FM_APPROX_MAX_K:
+ *   occurrence: a position i in [0, n-m] with Hamming(T[i..i+m), P) <= k.  A pattern byte that is 0, or that T does not hold,
+ *     can never match: it costs one mismatch wherever the window lies.  m > n gives no occurrence.
+ *   hit: a distinct string S of m bytes that occurs in T with d = Hamming(S, P) <= k, reported as (sp, ep, first, d): [sp, ep)
+ *     is the non-empty row range of the suffixes that start with S, first = SA[sp] as pfp_fm_count_dev gives it.
+ *   order of hits: the hits of one pattern have disjoint ranges and are listed by increasing sp, the lexicographic order of the
+ *     strings S: the answer depends on the inputs only, not on the walk, the batch or the launch budget.
+ *   special cases: the empty pattern has the one hit (0, n+1, n, 0); with k = 0 the result is exactly pfp_fm_count's, one hit or
+ *     none; with m <= k every string of m bytes that occurs in T is a hit.
+ *   locating: the positions of a pattern are the SA values of its hits' rows, hits in hit order and rows in row order inside a
+ *     hit, so the whole list is in increasing row order; each position carries its hit's d.  max_occ (0: all) caps the rows per
+ *     PATTERN: it keeps the first max_occ rows in that order.
+ * PFP_FM_APPROX_MAX_K is a choice, not a measurement: the record a bounded launch leaves holds k + 1 frames, and the walk's work
+ * grows roughly as (m sigma)^k.  k outside 0..PFP_FM_APPROX_MAX_K: PFP_EINVAL.
+ * Device memory on top of the caller's buffers: 176 bytes per pattern (the record) and 8 per pattern for the counts; filling
+ * takes 25 bytes per hit for the hits in walk order (17 without toeholds), 16 for the sort's keys and values, 8 per pattern
+ * for its segment bounds, plus the library sort's scratch.  2^32 - 1 or more hits in one call: PFP_ELIMIT (the segmented
+ * sort's segment bounds are u32).
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_APPROX_MAX_K 3
+/* device pointers, patterns as in pfp_fm_count_dev.  d_hit_off (npat+1) gets the exclusive sums of the hit counts.  d_sp, d_ep
+ * and d_dist all NULL: the offsets only; otherwise all three are required, with room for d_hit_off[npat] entries, and pattern
+ * p's hits lie at d_hit_off[p] .. d_hit_off[p+1].  d_first may be NULL; it needs samples otherwise (PFP_EINVAL).  A hit is a
+ * "pattern" for pfp_fm_locate_dev: the H = d_hit_off[npat] triples (sp, ep, first) as its npat list every hit's positions. */
+int pfp_fm_approx_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, int k, uint64_t *d_hit_off, uint64_t *d_sp,
+                      uint64_t *d_ep, uint64_t *d_first, uint8_t *d_dist);
+/* host buffers (offsets that decrease: PFP_EINVAL): hit_off (npat+1) is filled; *sp, *ep, *dist and, where first is not NULL,
+ * *first are malloc'ed arrays of hit_off[npat] entries (pfp_free; NULL when there are none).  The patterns go through in
+ * consecutive groups of at most PFP_SEQ_BUDGET hits (a pattern with more goes alone; PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_approx(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *hit_off, uint64_t **sp,
+                  uint64_t **ep, uint64_t **first, uint8_t **dist);
+/* host buffers: out_off (npat+1), *pos and *dist malloc'ed arrays of out_off[npat] positions and their distances, in the order
+ * of "locating" above.  Needs samples.  The groups also hold at most PFP_SEQ_BUDGET positions (a pattern with more goes alone). */
+int pfp_fm_approx_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t max_occ,
+                         uint64_t *out_off, uint64_t **pos, uint8_t **dist);
+/* {launches, LF pairs, hits filled} of the approximate searches since the last call, which it resets; the LF pairs are
+ * collected only under PFP_FM_MS_STATS=1 (measurement: tools/approx_time.py) */
+int pfp_fm_approx_stats(pfp_fm *fm, uint64_t out[3]);
+
+/* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
  * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
  * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
