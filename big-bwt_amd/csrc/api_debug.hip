@@ -1,5 +1,6 @@
 // api_debug.hip -- micro and diagnostic entry points: a text staged once and scanned on its own (pfp_stage_text_dev,
-// pfp_scan_staged, pfp_scan_k1_enqueue), the first-round sort and the library sorts on caller data (pfp_debug_*).
+// pfp_scan_staged, pfp_scan_k1_enqueue), the first-round sort and the library sorts on caller data, the fused chain's scan with a
+// report of what it did (pfp_debug_*).
 #include "api.hpp"
 
 using namespace pfp;
@@ -142,6 +143,62 @@ int pfp_debug_lib_sort(pfp_ctx *c, int kind, void *keys, void *vals, uint64_t n,
       sync(c);
       ((uint32_t *)vals)[n] = (uint32_t)got;
     } break;
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// diagnostic: stage 1a as the fused chain runs it - scan_text_adaptive under the context's settings - or, with a plan, as a rank of
+// the multi-GPU chain runs it (pfp_dist_local_parse2: params_from_plan, the given extra hashes, scan_text); see pfpgpu.h
+int pfp_debug_scan_chain(pfp_ctx *c, const uint8_t *text, uint64_t n, int w, uint64_t p, const uint64_t *plan,
+                         const uint32_t *extra_hashes, uint32_t n_extra, uint64_t **ends, uint64_t **dense_ends, uint8_t **nominal,
+                         pfp_scan_report *rep) {
+  if (!c || (!text && n) || !ends || !rep || (n_extra && !extra_hashes)) return PFP_EINVAL;
+  *ends = nullptr;
+  if (dense_ends) *dense_ends = nullptr;
+  if (nominal) *nominal = nullptr;
+  memset(rep, 0, sizeof *rep);
+  PFP_TRY_DEV(c)
+  check_args(w, p, 0);
+  PFP_REQUIRE(n_extra <= KRParams::kMaxExtra, PFP_EINVAL, "too many extra trigger hashes");
+  StagedText tx;
+  tx.stage(c, text, false, n, w);
+  DBuf<uint64_t> d_ends;
+  uint64_t used = n, k = 0;
+  ScanReport sr;
+  if (plan) {
+    KRParams kp = params_from_plan(w, p, plan);
+    for (uint32_t q = 0; q < n_extra; q++) { kp.extra[kp.nextra++] = extra_hashes[q]; kp.bloom |= 1ull << (extra_hashes[q] & 63); }
+    k = scan_text(c, tx, n, w, p, d_ends, &used, &kp);
+    sr.first = sr.kp = kp;
+    rep->parse_density = kp.fast ? (double)kp.fdens : 1.0;
+  } else {
+    uint32_t nx = 0;
+    k = scan_text_adaptive(c, tx, n, w, p, c->max_phrase, d_ends, &used, &nx, &sr);
+    rep->parse_density = c->stats.parse_density;
+  }
+  uint64_t *h = host_alloc<uint64_t>(k);
+  if (k) d2h(c, h, d_ends.p, k);
+  sync(c);
+  *ends = h;
+  const KRParams &kp = sr.kp;
+  rep->n_used = used; rep->n_ends = k;
+  // (seed and nominal threshold are the first pass's: only the Karp-Rabin fall-back, which has neither, ever replaces them)
+  rep->fast = kp.fast; rep->fthr = kp.fthr; rep->fseed = sr.first.fseed; rep->fthr_nom = sr.first.fthr_nom;
+  rep->fauto = sr.first.fauto; rep->fthr_first = sr.first.fthr; rep->density = (double)sr.first.fdens;
+  rep->n_extra = kp.nextra;
+  for (uint32_t q = 0; q < kp.nextra; q++) rep->extra[q] = kp.extra[q];
+  rep->chose = sr.chose; rep->dense = sr.dense; rep->kr_fallback = sr.kr_fallback;
+  rep->dense_cuts = sr.dense_ends.size();
+  for (uint8_t f : sr.nominal) rep->n_nominal += f != 0;
+  rep->sampled = sr.sampled; rep->kept = sr.kept; rep->distinct = sr.distinct; rep->singles = sr.singles;
+  if (dense_ends && rep->dense_cuts) {
+    *dense_ends = host_alloc<uint64_t>(rep->dense_cuts);
+    memcpy(*dense_ends, sr.dense_ends.data(), rep->dense_cuts * 8);
+  }
+  if (nominal && rep->dense_cuts) {
+    *nominal = host_alloc<uint8_t>(rep->dense_cuts);
+    memcpy(*nominal, sr.nominal.data(), rep->dense_cuts);
   }
   return PFP_OK;
   PFP_CATCH(c)

@@ -134,20 +134,10 @@ int pfp_dist_propose_triggers(pfp_ctx *c, const void *d_text, uint64_t n, int w,
 }
 
 // ---- the collection's parse plan (round 4): which hash cuts the text, with which seed, how densely
-// plan[0] 0 = the reference's Karp-Rabin hash, 1 = the window hash of scan.hip; plan[1] its seed; plan[2] the density (a double's
-// bits: the text is cut with probability density / p); plan[3] 1 while the density is a candidate the ranks still have to decide on
-static KRParams params_from_plan(int w, uint64_t p, const uint64_t plan[4]) {
-  KRParams kp = make_kr_params(w, p);
-  if (!plan || plan[0] == 0) return kp;
-  double dens;
-  memcpy(&dens, &plan[2], 8);
-  PFP_REQUIRE(w >= 4 && w <= 17 && dens >= 0.01 && dens <= 64.0, PFP_EINVAL, "bad parse plan");
-  const double thr_nom = 4294967296.0 / (double)p, thr = thr_nom * dens;
-  kp.fast = 1; kp.fseed = (uint32_t)plan[1]; kp.fdens = (float)dens; kp.fauto = 0;
-  kp.fthr = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr;
-  kp.fthr_nom = thr_nom >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr_nom;
-  return kp;
-}
+// plan[0] 0 = the reference's Karp-Rabin hash, 1 = the window hash of scan.hip, 2 = the same at a pinned density (no nominal
+// threshold beside the scan's); plan[1] its seed; plan[2] the density (a double's bits, exactly the value the single-GPU chain
+// computes its thresholds from: the text is cut with probability density / p); plan[3] 1 while the density is a candidate the
+// ranks still have to decide on (scan.hip: params_from_plan)
 // Rank 0 (which holds the text's first bytes) makes the plan; the hosts hand it to every rank.  first_hash: the hash of the text's
 // first window under the plan (it must not become an extra trigger: SURVEY.md 2.2-Q1), ~0 when the text is shorter than a window.
 int pfp_dist_parse_plan(pfp_ctx *c, const uint8_t *first_bytes, uint64_t n_bytes, int w, uint64_t p, uint32_t ranks, uint64_t plan[4],
@@ -167,9 +157,9 @@ int pfp_dist_parse_plan(pfp_ctx *c, const uint8_t *first_bytes, uint64_t n_bytes
   //  phrases pay on one or two ranks - 42.3 -> 35.8 and 51.1 -> 42.2 ms per rank - and no longer on eight, 71.9 -> 72.3; so the
   //  density is a candidate only there, and nominal beyond)
   const double setting = c->parse_density > 0 ? c->parse_density : (ranks > 2 ? 1.0 : 0.0);
-  const KRParams kp = make_fast_params_host(have ? first_bytes : nullptr, w, p, setting);
-  const double dens = (double)kp.fdens;
-  plan[0] = 1; plan[1] = kp.fseed; memcpy(&plan[2], &dens, 8); plan[3] = kp.fauto;
+  double dens = 1.0;
+  const KRParams kp = make_fast_params_host(have ? first_bytes : nullptr, w, p, setting, &dens);
+  plan[0] = setting > 0 ? 2 : 1; plan[1] = kp.fseed; memcpy(&plan[2], &dens, 8); plan[3] = kp.fauto;
   if (have) *first_hash = window_hash_host(first_bytes, w, kp.fseed);
   return PFP_OK;
   PFP_CATCH(c)

@@ -33,13 +33,14 @@ struct KRParams {
 };
 KRParams make_kr_params(int w, uint64_t p);
 KRParams make_fast_params(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t p);
-KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, double density_setting);
+KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, double density_setting, double *density_used);
+KRParams params_from_plan(int w, uint64_t p, const uint64_t plan[4]);      // a rank's parameters under a parse plan (pfp_dist_parse_plan)
 // phrase length by repetitiveness (scan.hip): the pieces the single-GPU chain runs in one go and the multi-GPU chain with an
 // all-gather of the ranks' samples in between
-struct CutSample { DBuf<uint8_t> nominal; DBuf<uint64_t> hashes; uint64_t ns = 0; };
+struct CutSample { DBuf<uint8_t> nominal; DBuf<uint64_t> hashes; uint64_t ns = 0, counted = 0; };      // counted: sampled cuts, ns: those that found room
 void classify_cuts(pfp_ctx *c, const StagedText &tx, int w, const DBuf<uint64_t> &d_ends, uint64_t ne, const KRParams &kp, uint64_t min_end,
                    CutSample &out);
-bool sample_says_dense(pfp_ctx *c, const uint64_t *d_sorted, uint64_t ns, uint64_t p);
+bool sample_says_dense(pfp_ctx *c, const uint64_t *d_sorted, uint64_t ns, uint64_t p, uint64_t counts[2] = nullptr);
 uint64_t keep_nominal_cuts(pfp_ctx *c, DBuf<uint64_t> &d_ends, uint64_t ne, const DBuf<uint8_t> &nominal);
 uint32_t window_hash_host(const uint8_t *win, int w, uint32_t seed);      // the seeded window hash of scan.hip, on the host
 void scan_flags(pfp_ctx *c, const uint8_t *tbase, uint64_t n, int w, uint64_t p, uint16_t *flags16,
@@ -48,9 +49,17 @@ uint64_t scan_text(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t
                    uint64_t *n_used, const KRParams *kp_override = nullptr);
 uint32_t propose_extra_triggers(pfp_ctx *c, const StagedText &tx, uint64_t n_used, int w, uint64_t max_phrase,
                                 const DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp);
+// what scan_text_adaptive did, for the diagnostic entry point pfp_debug_scan_chain (host memory only; the chain passes none)
+struct ScanReport {
+  KRParams first{}, kp{};       // the parameters of the first pass and of the last one
+  bool chose = false, dense = false, kr_fallback = false;      // a density choice was made / it kept the dense cuts / no cut: Karp-Rabin
+  uint64_t sampled = 0, kept = 0, distinct = 0, singles = 0;   // the choice's sample: cuts counted, cuts that found room, contexts
+  std::vector<uint64_t> dense_ends;                            // the first pass's cuts and their "inside the nominal threshold" flags
+  std::vector<uint8_t> nominal;
+};
 // fused chain: reference triggers plus a few extra window hashes that split phrases longer than max_phrase
 uint64_t scan_text_adaptive(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t p, uint64_t max_phrase,
-                            DBuf<uint64_t> &d_ends, uint64_t *n_used, uint32_t *n_extra);
+                            DBuf<uint64_t> &d_ends, uint64_t *n_used, uint32_t *n_extra, ScanReport *rep = nullptr);
 
 // ---------------------------------------------------------------- stage 1b (phrase.hip)
 // Distinct phrases (the dictionary), most frequent first (ties: first occurrence), plus the parse as word ids.

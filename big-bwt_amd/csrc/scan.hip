@@ -387,11 +387,22 @@ KRParams make_fast_params(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, u
     PFP_HIP(hipMemcpyAsync(fw, tx.tbase(), (size_t)w, hipMemcpyDeviceToHost, c->stream));
     sync(c);
   }
-  return make_fast_params_host(have ? fw : nullptr, w, p, c->parse_density);
+  return make_fast_params_host(have ? fw : nullptr, w, p, c->parse_density, nullptr);
 }
-// the same from the window's bytes (host): what the multi-GPU hosts' rank 0 computes for everybody (pfp_dist_parse_plan)
-KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, double density_setting) {
+// the two thresholds of the window hash at `dens` times the nominal density 1 / p, in ONE place: the single-GPU chain and a rank
+// under a parse plan must cut at the same 32-bit values (keep_nominal: fthr_nom stays at 1 / p - the density is a candidate, or
+// was one; else the scan's threshold is the only one there is)
+static void set_fast_thresholds(KRParams &kp, uint64_t p, double dens, bool keep_nominal) {
+  kp.fdens = (float)dens;
+  const double thr_nom = 4294967296.0 / (double)p, thr = thr_nom * dens;
+  kp.fthr = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr;
+  kp.fthr_nom = keep_nominal ? (thr_nom >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr_nom) : kp.fthr;
+}
+// the same from the window's bytes (host): what the multi-GPU hosts' rank 0 computes for everybody (pfp_dist_parse_plan);
+// *density_used: the density as the thresholds were computed from it (a double: KRParams keeps a float for the statistics only)
+KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, double density_setting, double *density_used) {
   KRParams kp = make_kr_params(w, p);
+  if (density_used) *density_used = 1.0;
   if (w < 4 || w > 17) return kp;          // (the register path of the scan kernel; wider windows keep Karp-Rabin)
   kp.fast = 1;
   // pfp_set_parse_density: 0 (default) = the chain chooses between the nominal density 1 / p and twice that (see
@@ -401,10 +412,8 @@ KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, d
   //  times the nominal density, -p 200: 4 times)
   const double dens_auto = std::min(8.0, std::max(1.0, (double)p / 48.0));
   const double dens = auto_density ? dens_auto : density_setting;
-  kp.fdens = (float)dens;
-  const double thr_nom = 4294967296.0 / (double)p, thr = thr_nom * dens;
-  kp.fthr = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr;
-  kp.fthr_nom = auto_density ? (thr_nom >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr_nom) : kp.fthr;
+  set_fast_thresholds(kp, p, dens, auto_density);
+  if (density_used) *density_used = dens;
   kp.fauto = (auto_density && dens > 1.0) ? 1u : 0u;
   bool have_first = false, ref_first = false;
   uint8_t fw[32] = {0};
@@ -438,6 +447,19 @@ KRParams make_fast_params_host(const uint8_t *first_window, int w, uint64_t p, d
     if (!crumbs) break;
   }
   kp.fseed = best;
+  return kp;
+}
+
+// a rank's parameters under a parse plan (pfpgpu.h: pfp_dist_parse_plan): the thresholds come from the plan's density by the
+// arithmetic above, so every rank cuts where the single-GPU chain cuts with the same settings
+KRParams params_from_plan(int w, uint64_t p, const uint64_t plan[4]) {
+  KRParams kp = make_kr_params(w, p);
+  if (!plan || plan[0] == 0) return kp;
+  double dens;
+  memcpy(&dens, &plan[2], 8);
+  PFP_REQUIRE(plan[0] <= 2 && w >= 4 && w <= 17 && dens >= 0.01 && dens <= 64.0, PFP_EINVAL, "bad parse plan");
+  kp.fast = 1; kp.fseed = (uint32_t)plan[1]; kp.fauto = 0;
+  set_fast_thresholds(kp, p, dens, plan[0] == 1);
   return kp;
 }
 
@@ -717,22 +739,26 @@ void classify_cuts(pfp_ctx *c, const StagedText &tx, int w, const DBuf<uint64_t>
   std::vector<unsigned long long> hsn(kSampleSlots);
   PFP_HIP(hipMemcpyAsync(hsn.data(), sn.p, kSampleSlots * 8, hipMemcpyDeviceToHost, c->stream));
   sync(c);
-  uint64_t ns = 0;
-  for (unsigned long long v : hsn) ns += std::min<uint64_t>(v, slot_cap);
-  out.ns = ns;
+  uint64_t ns = 0, counted = 0;
+  for (unsigned long long v : hsn) { ns += std::min<uint64_t>(v, slot_cap); counted += v; }
+  out.ns = ns; out.counted = counted;
   out.hashes.alloc(c, scap);
   sort_keys_raw(c, h.p, out.hashes.p, scap, 0, 64);      // (the valid hashes first: the filler is all ones)
 }
 // a sorted sample of context hashes (a rank's own, or the ranks' samples gathered and sorted again): does it show a collection
 // whose variants outweigh its loci?
-bool sample_says_dense(pfp_ctx *c, const uint64_t *d_sorted, uint64_t ns, uint64_t p) {
-  if (ns < 1024) return false;
+// counts (diagnostic, may be null): {distinct, singles} - counted then even for a sample too small to decide by
+bool sample_says_dense(pfp_ctx *c, const uint64_t *d_sorted, uint64_t ns, uint64_t p, uint64_t counts[2]) {
+  if (counts) counts[0] = counts[1] = 0;
+  if (ns < 1024 && !(counts && ns)) return false;
   DBuf<unsigned long long> nd(c, 2);
   nd.zero();
   hipLaunchKernelGGL(count_distinct_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, d_sorted, ns, nd.p);
   PFP_HIP(hipMemcpyAsync(c->h_scalars, nd.p, 16, hipMemcpyDeviceToHost, c->stream));
   sync(c);
   const uint64_t distinct = c->h_scalars[0], singles = c->h_scalars[1], loci = distinct - singles;
+  if (counts) { counts[0] = distinct; counts[1] = singles; }
+  if (ns < 1024) return false;
   // contexts seen twice or more are the collection's loci, contexts seen once the variants around them: V / U = copies x 64 r, and
   // what shorter phrases save is the variants' share of the dictionary, c r L = (V / U) (p / 64): worth it from about 1
   // (16 copies at 10^-3: 1.5, measured -14 %; 64 copies at 10^-4: 0.6, left alone)
@@ -753,36 +779,49 @@ uint64_t keep_nominal_cuts(pfp_ctx *c, DBuf<uint64_t> &d_ends, uint64_t ne, cons
 }
 // the scan cut at kp.fthr = the dense candidate: keep that (returns ne, *dense = true) or fall back to the nominal cuts
 // (d_ends compacted, kp.fthr lowered to the nominal threshold for every later rescan)
-static uint64_t choose_parse_density(pfp_ctx *c, const StagedText &tx, int w, uint64_t p, DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp, bool *dense) {
+static uint64_t choose_parse_density(pfp_ctx *c, const StagedText &tx, int w, uint64_t p, DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp, bool *dense,
+                                     ScanReport *rep) {
   CutSample cs;
   classify_cuts(c, tx, w, d_ends, ne, kp, 0, cs);
-  *dense = sample_says_dense(c, cs.hashes.p, cs.ns, p);
+  uint64_t counts[2] = {0, 0};
+  *dense = sample_says_dense(c, cs.hashes.p, cs.ns, p, rep ? counts : nullptr);
+  if (rep) {      // (diagnostic: the first pass's cuts and their flags, before the cuts are thinned out)
+    rep->chose = true; rep->dense = *dense;
+    rep->sampled = cs.counted; rep->kept = cs.ns; rep->distinct = counts[0]; rep->singles = counts[1];
+    rep->dense_ends.resize(ne); rep->nominal.resize(ne);
+    d2h(c, rep->dense_ends.data(), d_ends.p, ne);
+    d2h(c, rep->nominal.data(), cs.nominal.p, ne);
+    sync(c);
+  }
   if (*dense) return ne;
   kp.fthr = kp.fthr_nom;
   return keep_nominal_cuts(c, d_ends, ne, cs.nominal);
 }
 
 uint64_t scan_text_adaptive(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t p, uint64_t max_phrase,
-                            DBuf<uint64_t> &d_ends, uint64_t *n_used, uint32_t *n_extra) {
+                            DBuf<uint64_t> &d_ends, uint64_t *n_used, uint32_t *n_extra, ScanReport *rep) {
   KRParams kp = c->fast_triggers ? make_fast_params(c, tx, n, w, p) : make_kr_params(w, p);
   *n_extra = 0;
+  if (rep) { *rep = ScanReport(); rep->first = kp; }
   uint64_t ne = scan_text(c, tx, n, w, p, d_ends, n_used, &kp);
   c->stats.parse_density = kp.fast ? (c->parse_density > 0 ? c->parse_density : 1.0) : 1.0;
   if (kp.fast && kp.fauto && ne > 0) {
     bool dense = false;
-    ne = choose_parse_density(c, tx, w, p, d_ends, ne, kp, &dense);
+    ne = choose_parse_density(c, tx, w, p, d_ends, ne, kp, &dense, rep);
     c->stats.parse_density = dense ? (double)kp.fdens : 1.0;
   }
   if (kp.fast && ne == 0) {      // no cut at all: the reference's own hash decides whether this text has a parse (bwtparse.c:244)
     kp = make_kr_params(w, p);
     ne = scan_text(c, tx, n, w, p, d_ends, n_used, &kp);
     c->stats.parse_density = 1.0;
+    if (rep) rep->kr_fallback = true;
   }
   for (int iter = 0; iter < 4 && max_phrase; iter++) {
     if (!propose_extra_triggers(c, tx, *n_used, w, max_phrase, d_ends, ne, kp)) break;
     ne = scan_text(c, tx, *n_used, w, p, d_ends, n_used, &kp);
   }
   *n_extra = kp.nextra;
+  if (rep) rep->kp = kp;
   return ne;
 }
 

@@ -30,7 +30,7 @@ ERRORS = {0: "PFP_OK", -1: "PFP_EINVAL", -2: "PFP_ENODEV", -3: "PFP_EHIP", -4: "
 SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_error", "pfp_strerror", "pfp_version", "pfp_ctx_stream",
            "pfp_free", "pfp_debug_check", "pfp_get_mem_stats", "pfp_get_pool_counters", "pfp_pool_trim", "pfp_scan", "pfp_parse", "pfp_parse_result_free", "pfp_sacak_int", "pfp_sacak", "pfp_gsacak", "pfp_sacak_int64", "pfp_sacak64", "pfp_gsacak64", "pfp_gsacak_lcp_da", "pfp_gsacak_lcp_da64",
            "pfp_bwtparse", "pfp_merge", "pfp_bwt_result_free", "pfp_bigbwt", "pfp_bigbwt_files", "pfp_bigbwt_dev", "pfp_bigbwt_formats_dev", "pfp_dev_free", "pfp_memcpy_d2h", "pfp_pack5_dev", "pfp_sample_runs_dev", "pfp_pwrite_dev", "pfp_get_stats",
-           "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_debug_lib_sort", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
+           "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_debug_lib_sort", "pfp_debug_scan_chain", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
            "pfp_dist_propose_triggers", "pfp_dist_local_parse", "pfp_dist_export_local", "pfp_dist_global", "pfp_dist_global_sort", "pfp_dist_global_finish", "pfp_dist_partition_words", "pfp_dist_export_partition",
            "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
            "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
@@ -415,6 +415,16 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScanReport(C.Structure):
+    _fields_ = [("n_used", C.c_uint64), ("n_ends", C.c_uint64),
+                ("fast", C.c_uint32), ("fthr", C.c_uint32), ("fseed", C.c_uint32), ("fthr_nom", C.c_uint32),
+                ("fauto", C.c_uint32), ("fthr_first", C.c_uint32), ("n_extra", C.c_uint32), ("reserved", C.c_uint32),
+                ("extra", C.c_uint32 * 32), ("density", C.c_double), ("parse_density", C.c_double),
+                ("chose", C.c_uint64), ("dense", C.c_uint64), ("kr_fallback", C.c_uint64),
+                ("dense_cuts", C.c_uint64), ("n_nominal", C.c_uint64), ("sampled", C.c_uint64), ("kept", C.c_uint64),
+                ("distinct", C.c_uint64), ("singles", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -606,6 +616,31 @@ class Context:
                                                 C.c_int(begin_bit), C.c_int(end_bit),
                                                 _ptr(seg_begin, C.c_uint32) if nseg else None, _ptr(seg_end, C.c_uint32) if nseg else None,
                                                 C.c_uint64(nseg)))
+
+    def debug_scan_chain(self, text, w=10, p=100, plan=None, extra=()):
+        """stage 1a as the fused chain runs it under the context's settings - or, with a settled plan, as a rank of the multi-GPU
+        chain runs it - and what it did (pfpgpu.h: pfp_debug_scan_chain): a dict of the report's fields plus `ends`, `extra` and,
+        where a density choice was made, `dense_ends` and `nominal` (else None)"""
+        t = _arr(text, np.uint8)
+        ends, dends, nom = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
+        rep = ScanReport()
+        pl = (C.c_uint64 * 4)(*plan) if plan is not None else None
+        ex = np.ascontiguousarray(np.array(list(extra), dtype=np.uint32))
+        rc = self.lib.pfp_debug_scan_chain(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p), pl,
+                                           _ptr(ex, C.c_uint32) if len(ex) else None, C.c_uint32(len(ex)),
+                                           C.byref(ends), C.byref(dends), C.byref(nom), C.byref(rep))
+        try:
+            self._check(rc)
+            out = {k: getattr(rep, k) for k, _ in ScanReport._fields_ if k not in ("extra", "reserved")}
+            out["extra"] = [int(rep.extra[q]) for q in range(rep.n_extra)]
+            out["ends"] = _take(ends, rep.n_ends, np.uint64)
+            out["dense_ends"] = _take(dends, rep.dense_cuts, np.uint64) if dends else None
+            out["nominal"] = _take(nom, rep.dense_cuts, np.uint8) if nom else None
+        finally:
+            self.lib.pfp_free(ends)
+            self.lib.pfp_free(dends)
+            self.lib.pfp_free(nom)
+        return out
 
     def set_parse_density(self, density):
         """fused chain, opt-in: the window hash cuts with probability density / p (outputs unchanged, see pfpgpu.h)"""

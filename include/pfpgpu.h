@@ -258,6 +258,30 @@ int pfp_debug_msd_sort(pfp_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n,
  * 9 select_index (keys: n flag bytes, vals: n + 1 u32 - the indices of the non-zero flags, their count in vals[n]). */
 int pfp_debug_lib_sort(pfp_ctx *ctx, int kind, void *keys, void *vals, uint64_t n, int begin_bit, int end_bit,
                        const uint32_t *seg_begin, const uint32_t *seg_end, uint64_t nseg);
+/* Diagnostic (tests): stage 1a exactly as the fused chain runs it on a host text - the window hash or Karp-Rabin, the choice of
+ * the phrase length, the Karp-Rabin fall-back of a text the window hash does not cut, the extra triggers that split giant phrases -
+ * under the context's current settings (pfp_set_window_hash, pfp_set_parse_density, pfp_set_max_phrase), with a report of what
+ * it did.  With plan != NULL (a settled plan of pfp_dist_parse_plan) the text is scanned as a rank of the multi-GPU chain scans
+ * its shard instead: the plan's parameters plus the n_extra given extra hashes, one pass.  ends (library-allocated, pfp_free):
+ * rep->n_ends final phrase ends.  dense_ends / nominal (optional, NULL to skip; library-allocated; NULL when no choice was made):
+ * the rep->dense_cuts cuts of the first, dense pass and for each whether it lies inside the nominal threshold. */
+typedef struct {
+  uint64_t n_used, n_ends;
+  uint32_t fast, fthr;                   /* the last pass: window hash (1) or Karp-Rabin (0), the threshold it cut at */
+  uint32_t fseed, fthr_nom;              /* the first pass (all passes but a Karp-Rabin fall-back): the seed, the nominal threshold, */
+  uint32_t fauto, fthr_first;            /* whether its density was a candidate, the threshold it cut at */
+  uint32_t n_extra, reserved;            /* extra trigger hashes of the last pass (seeded window hashes, or Karp-Rabin hashes) */
+  uint32_t extra[32];
+  double density;                        /* the density the first pass cut at (x nominal) */
+  double parse_density;                  /* pfp_stats.parse_density as the chain would report it */
+  uint64_t chose, dense, kr_fallback;    /* a density choice was made; it kept the dense cuts; the window hash made no cut: Karp-Rabin */
+  uint64_t dense_cuts, n_nominal;        /* the choice: cuts of the dense pass, those inside the nominal threshold, */
+  uint64_t sampled, kept;                /* sampled cuts counted, sampled cuts that found room on the sample lists, */
+  uint64_t distinct, singles;            /* distinct 64-byte contexts among the kept ones, contexts seen once */
+} pfp_scan_report;
+int pfp_debug_scan_chain(pfp_ctx *ctx, const uint8_t *text, uint64_t n, int w, uint64_t p, const uint64_t *plan,
+                         const uint32_t *extra_hashes, uint32_t n_extra, uint64_t **ends, uint64_t **dense_ends, uint8_t **nominal,
+                         pfp_scan_report *rep);
 void pfp_set_max_phrase(pfp_ctx *ctx, uint64_t max_phrase);
 /* Fused chain only: which function of the last w bytes cuts the text.  fast != 0 (default): a multiply-add hash of the window,
  * a third of the arithmetic of the reference's `KR_window` (newscan.cpp:168-202: mod 1999999973, then mod p) with the same 1 / p
@@ -326,8 +350,10 @@ int pfp_dist_local_parse(pfp_ctx *ctx, const void *d_text, uint64_t n, uint64_t 
                          const uint32_t *extra_hashes, uint32_t n_extra, uint64_t out_sizes[4]);
 /* Round 4: the multi-GPU chain under a PARSE PLAN - the window hash and the phrase length by repetitiveness of the fused chain
  * (pfp_set_window_hash, pfp_set_parse_density), agreed between the ranks.  plan[4]: [0] 0 = the reference's Karp-Rabin hash (what
- * the two calls above cut by), 1 = the window hash; [1] its seed; [2] the density (the bits of a double: cuts with probability
- * density / p); [3] 1 while that density is a candidate the ranks still have to decide on.
+ * the two calls above cut by), 1 = the window hash, 2 = the window hash at a pinned density (pfp_set_parse_density > 0, or more
+ * than two ranks); [1] its seed; [2] the density (the bits of a double: cuts with probability density / p - the very double the
+ * single-GPU chain computes its thresholds from, so both chains cut at the same 32-bit thresholds); [3] 1 while that density is
+ * a candidate the ranks still have to decide on.
  *   pfp_dist_parse_plan        rank 0, from the text's first bytes (host): the plan every rank gets, and the first window's hash
  *                              under it (banned as an extra trigger: SURVEY.md 2.2-Q1).  The density is a candidate (p / 48) on one
  *                              or two ranks and nominal beyond: every rank reads the whole parse, only the dictionary is shared
