@@ -1,6 +1,6 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
-// of a collection (seqmap.hip).
+// of a collection (seqmap.hip); extending seeds (fmextend.hip).
 #include <memory>
 #include <vector>
 #include "api.hpp"
@@ -531,6 +531,113 @@ int pfp_lcp_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd
   fm_lcp(f, o);
   if (o.lcp5) write_dev_file(c, b + ".lcp", 0, lcp5.p, 5 * f.n1, true);
   if (o.thr5) write_dev_file(c, b + ".thr_pos", 0, thr5.p, 5 * f.runs, true);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- extending seeds (fmextend.hip)
+int pfp_fm_extend_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_cand_pat,
+                      const int64_t *d_cand_diag, uint64_t ncand, int k, uint8_t *d_dist, uint64_t *d_start, uint64_t *d_end) {
+  if (!fm || (npat && !d_pat_off) || (ncand && (!d_cand_pat || !d_cand_diag || !d_dist || !d_start || !d_end))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_extend(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_extend(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const int64_t *cand_diag,
+                  uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end) {
+  if (!fm || (npat && !pat_off) || (ncand && (!cand_pat || !cand_diag || !dist || !start || !end))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_extend_check(fm->f, k);
+  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
+  DBuf<uint8_t> d_pat(c, bytes + 16), d_dist(c, ncand);
+  DBuf<uint64_t> d_off(c, npat + 1), d_out(c, 2 * ncand);
+  DBuf<uint32_t> d_cp(c, ncand);
+  DBuf<int64_t> d_cd(c, ncand);
+  if (bytes) h2d(c, d_pat.p, pat, bytes);
+  if (npat) h2d(c, d_off.p, pat_off, npat + 1);
+  if (ncand) { h2d(c, d_cp.p, cand_pat, ncand); h2d(c, d_cd.p, cand_diag, ncand); }
+  fm_extend(fm->f, d_pat.p, d_off.p, npat, d_cp.p, d_cd.p, ncand, k, d_dist.p, d_out.p, d_out.p + ncand);
+  if (ncand) {
+    d2h(c, dist, d_dist.p, ncand);
+    d2h(c, start, d_out.p, ncand);
+    d2h(c, end, d_out.p + ncand, ncand);
+  }
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_align_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                     int thresholds, uint64_t *d_aln_off, uint64_t *d_start, uint64_t *d_end, uint8_t *d_dist) {
+  if (!fm || !d_aln_off || (npat && !d_pat_off)) return PFP_EINVAL;
+  const bool fill = d_start || d_end || d_dist;
+  if (fill && !(d_start && d_end && d_dist)) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_align(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, max_aln, thresholds != 0, d_aln_off, d_start, d_end, d_dist);
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                 int thresholds, uint64_t *aln_off, uint64_t **start, uint64_t **end, uint8_t **dist) {
+  if (!fm || !aln_off || !start || !end || !dist || (npat && !pat_off)) return PFP_EINVAL;
+  *start = nullptr; *end = nullptr; *dist = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_extend_check(fm->f, k);
+  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
+  if (thresholds) require_thresholds(fm);
+  ApxCall s;                                            // (its budget and its grouping)
+  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
+    const uint64_t v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < s.budget) s.budget = v;
+  }
+  pattern_bytes(pat, pat_off, npat);                    // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
+  for (uint64_t p = 0; p < npat; p++)                   // (before any work: fm_extend_check_patterns' rule, on the host's copy)
+    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
+                "pattern " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+  MsOnDevice d;
+  ms_on_device(fm, pat, pat_off, npat, d, thresholds != 0);
+  aln_off[0] = 0;
+  if (!npat) return PFP_OK;
+  std::vector<uint64_t> moff(npat + 1), per(npat), goff, go;
+  {
+    DBuf<uint64_t> d_moff(c, npat + 1);
+    fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_seed, d_moff.p, nullptr);
+    d2h(c, moff.data(), d_moff.p, npat + 1);
+    sync(c);
+  }
+  for (uint64_t p = 0; p < npat; p++) per[p] = moff[p + 1] - moff[p];
+  HostOut<uint64_t> h_start, h_end;
+  HostOut<uint8_t> h_dist;
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns whose seeds stay within the budget
+    p1 = s.group_end(per, p0, npat);
+    const uint64_t np = p1 - p0;
+    goff.resize(np + 1);                                // the group's MEM offsets: the call's, counted from its first pattern
+    for (uint64_t i = 0; i <= np; i++) goff[i] = moff[p0 + i] - moff[p0];
+    DBuf<uint64_t> g_moff(c, np + 1), g_off(c, np + 1);
+    h2d(c, g_moff.p, goff.data(), np + 1);
+    AlnKeys keys;
+    fm_align_seeds(fm->f, d.pat.p, d.off.p + p0, np, min_seed, k, max_aln, d.len.p, d.pos.p, g_moff.p, goff[np], g_off.p, keys);
+    DBuf<uint64_t> g_start(c, keys.total), g_end(c, keys.total);
+    DBuf<uint8_t> g_dist(c, keys.total);
+    fm_align_write(fm->f, keys, g_start.p, g_end.p, g_dist.p);
+    go.resize(np + 1);
+    d2h(c, go.data(), g_off.p, np + 1);
+    sync(c);
+    for (uint64_t i = 0; i < np; i++) aln_off[p0 + i + 1] = aln_off[p0] + go[i + 1];
+    apx_take(c, h_start, g_start.p, keys.total);
+    apx_take(c, h_end, g_end.p, keys.total);
+    apx_take(c, h_dist, g_dist.p, keys.total);
+  }
+  *start = h_start.release(); *end = h_end.release(); *dist = h_dist.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

@@ -193,17 +193,6 @@ __global__ void __launch_bounds__(kTB) apx_rows_k(uint64_t H, const uint64_t *__
   rows[h] = h < H && ep[h] > sp[h] ? ep[h] - sp[h] : 0;
 }
 
-// the last index i in [0, count) with off[i] <= x (off[0] <= x; count >= 1)
-__device__ __forceinline__ uint64_t last_le(const uint64_t *__restrict__ off, uint64_t count, uint64_t x) {
-  uint64_t lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= x) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // cep[h] = the end of hit h's rows among the first max_occ rows of its pattern (rsum: exclusive sums of the hits' rows)
 __global__ void __launch_bounds__(kTB) apx_clip_k(uint64_t H, const uint64_t *__restrict__ hit_off, uint64_t npat, const uint64_t *__restrict__ rsum,
                                                   const uint64_t *__restrict__ sp, uint64_t max_occ, uint64_t *__restrict__ cep) {

@@ -1,4 +1,4 @@
-// fmdev.hpp -- what the kernels over an FmIndex share (fmsearch.hip, fmapprox.hip, lcp.hip, seqmap.hip): the index as kernel arguments, rank and select
+// fmdev.hpp -- what the kernels over an FmIndex share (fmsearch.hip, fmapprox.hip, fmextend.hip, lcp.hip, seqmap.hip): the index as kernel arguments, rank and select
 // by groups of 16 lanes, the longest common extension on the text, and the record a bounded launch leaves behind.
 #pragma once
 #include "kernels.hpp"
@@ -110,6 +110,17 @@ __global__ void __launch_bounds__(kTB) bucket_dir_k(const K *__restrict__ key, u
     else hi = mid;
   }
   dir[b] = (D)lo;
+}
+
+// the last index i in [0, count) with off[i] <= x (off[0] <= x; count >= 1)
+__device__ __forceinline__ uint64_t last_le(const uint64_t *__restrict__ off, uint64_t count, uint64_t x) {
+  uint64_t lo = 0, hi = count - 1;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
 }
 
 constexpr uint64_t kMsWork = 16384;         // units of work per pattern and launch: one per step, one per 1024 bytes compared

@@ -589,6 +589,17 @@ void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t 
   }
 }
 
+void fm_mem_triples(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
+                    const uint64_t *mem_off, uint64_t *mem) {
+  pfp_ctx *c = f.c;
+  require_text(f, "maximal exact matches");
+  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
+  if (!npat) return;
+  KScope ks(c, "fm_mems", 0);
+  fm_mem_gather<<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(pat_off, npat, len, pos, min_len, mem_off, mem);
+  PFP_HIP(hipGetLastError());
+}
+
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
   pfp_ctx *c = f.c;
   PFP_REQUIRE(!first || f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");

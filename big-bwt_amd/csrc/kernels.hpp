@@ -365,6 +365,9 @@ void fm_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npa
 // maximal exact matches from fm_ms's outputs: mem_off[0..npat] exclusive sums of the counts; mem == NULL: only those
 void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
              uint64_t *mem_off, uint64_t *mem);
+// the triples alone, at offsets a call above gave for the same patterns
+void fm_mem_triples(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
+                    const uint64_t *mem_off, uint64_t *mem);
 // the LCP array and thresholds of an index with text (lcp.hip; pfpgpu.h states the definitions).  Device outputs, each may be
 // NULL: lcp64 n1 values, thr64 runs values, lcp5 / thr5 the same as 5-byte ints; keep: the index keeps the thresholds (fm_ms_thr)
 struct LcpOut {
@@ -422,6 +425,30 @@ void fm_approx_clip(FmIndex &f, uint64_t npat, const uint64_t *hit_off, uint64_t
 // distance; pos / pdist are allocated here once their number, which is returned, is known
 uint64_t fm_approx_positions(FmIndex &f, uint64_t H, const uint64_t *sp, const uint64_t *cep, const uint64_t *first, const uint8_t *dist,
                              DBuf<uint64_t> &pos, DBuf<uint8_t> &pdist);
+
+// extending seeds (fmextend.hip; pfpgpu.h, "Extending seeds", states the definitions).  Device pointers.  k outside 0 ..
+// PFP_FM_EXTEND_MAX_K or an index without text -> PFP_EINVAL; a pattern longer than PFP_FM_EXTEND_MAX_M -> PFP_ELIMIT
+void fm_extend_check(const FmIndex &f, int k);
+// candidate i = (cand_pat[i], cand_diag[i]) -> (dist[i], start[i], end[i]); 0xFF and UINT64_MAX twice where nothing aligns
+void fm_extend(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const int64_t *cand_diag,
+               uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end);
+// a pattern of the call longer than PFP_FM_EXTEND_MAX_M -> PFP_ELIMIT (one pass over the offsets, one scalar read back)
+void fm_extend_check_patterns(FmIndex &f, const uint64_t *pat_off, uint64_t npat);
+// what fm_align_seeds leaves for fm_align_write: the C candidates' sorted keys, the flags of the kept ones and their exclusive sums
+struct AlnKeys {
+  DBuf<uint64_t> skey, flag, idx;
+  uint64_t C = 0, total = 0;               // total: the alignments kept, which is what the outputs must hold
+};
+// the alignments of every pattern from its matching statistics (len / pos as fm_ms or fm_ms_thr gave them) and its MEM offsets
+// (mem_off[0..npat] as fm_mems gave them for the same patterns, M = mem_off[npat]): aln_off[0..npat] the exclusive sums of their
+// numbers, at most max_aln per pattern (0: all).  The callers have checked the patterns' lengths (fm_extend_check_patterns)
+void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                    const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, uint64_t *aln_off, AlnKeys &out);
+// the kept alignments, each pattern's ordered by (d, start, end): room for keys.total entries each
+void fm_align_write(FmIndex &f, const AlnKeys &keys, uint64_t *start, uint64_t *end, uint8_t *dist);
+// matching statistics (thresholds: by fm_ms_thr), MEMs, fm_align_seeds and, where start is given, fm_align_write
+void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
+              uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

@@ -4,6 +4,7 @@
  *   bwtsearch --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch -l --seqs[=FILE] | --docs [--seqs=FILE] ... PATTERNFILE basename        (any mode: --rc)
  *   bwtsearch -k K [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
+ *   bwtsearch --align K [--seed L] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -26,6 +27,11 @@
  * `total<TAB>c0 c1 .. cK`: the approximate occurrences, and how many of them have exactly 0, 1, .. K mismatches; with -l
  * `total<TAB>pos:d pos:d ...`: the positions with their mismatches, hits by increasing row range and rows in row order, at most
  * MAXOCC of them; total stays the number of occurrences.  Not with --ms, --mems, --docs or --seqs.
+ * --align K (0..32) is seed-and-extend (the definitions: include/pfpgpu.h, "Extending seeds"): every maximal exact match of at
+ * least L bytes (--seed, default 20: a choice) is extended along its diagonal with at most K edits (substitutions, insertions and
+ * deletions).  The line becomes `count<TAB>start:end:d start:end:d ...`: the distinct alignments T[start..end) with their edit
+ * distances, ordered by (d, start, end), at most MAXALN of them (0: all); count stays their number before the cap.  It reads the
+ * files --mems reads and takes --text and --thresholds as --mems does.  Not with -l, -k, --ms, --mems, --docs or --seqs.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -47,7 +53,8 @@ static void usage(const char *argv0) {
   printf("usage: %s [-h] [-l] [-m MAXOCC] [--seqs[=FILE]] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --docs [--seqs=FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
-         "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n\n"
+         "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n"
+         "       %s --align K [--seed L] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -59,8 +66,12 @@ static void usage(const char *argv0) {
          "      --ms        print the matching statistics: len:pos for every byte of the line (0:- where nothing matches);\n"
          "                  reads basename.bwt, .ssa and .esa\n"
          "      --mems L    print count<TAB>i:len:pos ... : the maximal exact matches of at least L >= 1 bytes; reads the same files\n"
-         "      --text FILE with --ms / --mems: the text (def. inverted from basename.bwt)\n"
-         "      --thresholds with --ms / --mems: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
+         "      --align K   seed-and-extend with at most K edits (0..32; substitutions, insertions, deletions): print\n"
+         "                  count<TAB>start:end:d ... : the distinct alignments T[start..end) by (d, start, end), at most MAXALN (-m)\n"
+         "                  of them; reads the files --mems reads (not with -l, -k, --ms, --mems, --docs, --seqs)\n"
+         "      --seed L    with --align: the seeds are the maximal exact matches of at least L >= 1 bytes (def. 20, a choice)\n"
+         "      --text FILE with --ms / --mems / --align: the text (def. inverted from basename.bwt)\n"
+         "      --thresholds with --ms / --mems / --align: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
          "                  count<TAB>name:offset ... : the hits inside one sequence among the at most MAXOCC rows examined;\n"
          "                  count stays the number of rows, matches that span two sequences included\n"
@@ -68,7 +79,7 @@ static void usage(const char *argv0) {
          "                  reads basename.ssa and .esa; every occurrence counts)\n"
          "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0, argv0, argv0);
+         argv0, argv0, argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -106,15 +117,16 @@ static void revcomp(const uint8_t *in, uint64_t len, uint8_t *out) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0;
   const char *seqsfile = NULL;
   pfp_seqs tab;
   pfp_seqs_init(&tab);
-  uint64_t maxocc = 0, min_len = 0;
+  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
                                {"seqs", optional_argument, 0, 1006}, {"docs", no_argument, 0, 1007}, {"rc", no_argument, 0, 1008},
+                               {"align", required_argument, 0, 1009}, {"seed", required_argument, 0, 1010},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -143,6 +155,17 @@ int main(int argc, char **argv) {
       case 1006: seqs = 1; if (optarg) seqsfile = optarg; break;
       case 1007: docs = seqs = 1; break;
       case 1008: rcomp = 1; break;
+      case 1009: {
+        const long v = strtol(optarg, &end, 10);
+        if (!*optarg || *end || v < 0 || v > PFP_FM_EXTEND_MAX_K) { usage(argv[0]); return 2; }
+        align = 1;
+        kedit = (int)v;
+      } break;
+      case 1010:
+        seed = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-' || seed < 1) { usage(argv[0]); return 2; }
+        have_seed = 1;
+        break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -152,8 +175,9 @@ int main(int argc, char **argv) {
     }
   }
   if (optind + 2 != argc) { usage(argv[0]); return 2; }
-  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems) || ((ms || mems) && seqs) ||
-      (approx && (ms || mems || docs || seqs))) {
+  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems && !align) ||
+      ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) || (align && (locate || approx || ms || mems || docs || seqs)) ||
+      (have_seed && !align)) {
     usage(argv[0]);
     return 2;
   }
@@ -185,7 +209,7 @@ int main(int argc, char **argv) {
     return 1;
   }
   pfp_fm *fm = NULL;
-  if (ms || mems) {
+  if (ms || mems || align) {
     int fd = -1;
     uint64_t n = 0;
     if (textfile) {
@@ -313,6 +337,19 @@ int main(int argc, char **argv) {
         putchar('\n');
       }
       pfp_free(m);
+    } else if (align) {
+      uint64_t *as = NULL, *ae = NULL;
+      uint8_t *ad = NULL;
+      rc = pfp_fm_align(fm, pat, off, k, seed, kedit, 0, thresholds, oo, &as, &ae, &ad);
+      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
+      for (uint64_t i = 0; i < k; i++) {
+        const uint64_t cnt = oo[i + 1] - oo[i], shown = maxocc && maxocc < cnt ? maxocc : cnt;
+        printf("%" PRIu64 "\t", cnt);
+        for (uint64_t j = oo[i]; j < oo[i] + shown; j++)
+          printf(j > oo[i] ? " %" PRIu64 ":%" PRIu64 ":%u" : "%" PRIu64 ":%" PRIu64 ":%u", as[j], ae[j], (unsigned)ad[j]);
+        putchar('\n');
+      }
+      pfp_free(as); pfp_free(ae); pfp_free(ad);
     } else if (docs) {
       uint32_t *doc = NULL;
       uint64_t *cnt = NULL;

@@ -38,9 +38,11 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats",
            "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
            "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
-           "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats"]
+           "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats",
+           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align"]
 
 FM_APPROX_MAX_K = 3
+FM_EXTEND_MAX_K, FM_EXTEND_MAX_M = 32, 65535
 
 LCP_LCP, LCP_THR = 1, 2
 
@@ -219,6 +221,58 @@ class FmIndex:
         out = (C.c_uint64 * 3)()
         self.ctx._check(self.lib.pfp_fm_approx_stats(self._h, out))
         return dict(launches=int(out[0]), pairs=int(out[1]), hits=int(out[2]))
+
+    def extend(self, patterns, cand_pat, cand_diag, k):
+        """the best alignment of a whole pattern near a diagonal under unit-cost edit distance (pfpgpu.h, "Extending seeds"; k in
+        0..FM_EXTEND_MAX_K, an index with text).  Candidate i is pattern cand_pat[i] with pattern byte 0 at text position
+        cand_diag[i] (signed) -> (dist, start, end): dist[i] (uint8) edits align the pattern to T[start[i]:end[i]); 0xFF and
+        2^64 - 1 twice where nothing within k edits lies in the window"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        cp = np.ascontiguousarray(cand_pat, dtype=np.uint32)
+        cd = np.ascontiguousarray(cand_diag, dtype=np.int64)
+        if cp.shape != cd.shape or cp.ndim != 1:
+            raise ValueError("cand_pat and cand_diag: two 1-D arrays of one length")
+        nc = len(cp)
+        dist, start, end = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
+        self.ctx._check(self.lib.pfp_fm_extend(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(cp, C.c_uint32),
+                                               _ptr(cd, C.c_int64), C.c_uint64(nc), C.c_int(k), _ptr(dist, C.c_uint8),
+                                               _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
+        return dist, start, end
+
+    def extend_dev(self, d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end):
+        """device pointers: pattern bytes, npat+1 uint64 offsets, ncand uint32 pattern indices and int64 diagonals -> ncand uint8
+        d_dist and uint64 d_start / d_end"""
+        self.ctx._check(self.lib.pfp_fm_extend_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_cand_pat),
+                                                   C.c_void_p(d_cand_diag), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
+                                                   C.c_void_p(d_start), C.c_void_p(d_end)))
+
+    def align(self, patterns, k, min_seed, max_aln=0, thresholds=False):
+        """seed-and-extend: every maximal exact match of at least min_seed bytes (as mems lists them; thresholds as there) is
+        extended along its diagonal with at most k edits -> (aln_off, start, end, dist): pattern p's distinct alignments are
+        T[start[i]:end[i]) with dist[i] (uint8) edits for i in aln_off[p]:aln_off[p+1], ordered by (dist, start, end), at most
+        max_aln of them (0: all).  A heuristic: a MEM carries one position of its string"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        aln_off = np.zeros(npat + 1, dtype=np.uint64)
+        start, end, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
+        self.ctx._check(self.lib.pfp_fm_align(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_seed),
+                                              C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), _ptr(aln_off, C.c_uint64),
+                                              C.byref(start), C.byref(end), C.byref(dist)))
+        total = int(aln_off[-1])
+        res = aln_off, _take(start, total, np.uint64), _take(end, total, np.uint64), _take(dist, total, np.uint8)
+        for q in (start, end, dist):
+            if q:
+                self.lib.pfp_free(q)
+        return res
+
+    def align_dev(self, d_pat, d_pat_off, npat, k, min_seed, d_aln_off, d_start=None, d_end=None, d_dist=None, max_aln=0, thresholds=False):
+        """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_aln_off; d_start / d_end (uint64) and d_dist
+        (uint8), room for d_aln_off[npat] each, get the alignments (all three None: offsets only)"""
+        vp = lambda x: C.c_void_p(x) if x else None
+        self.ctx._check(self.lib.pfp_fm_align_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
+                                                  C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), C.c_void_p(d_aln_off),
+                                                  vp(d_start), vp(d_end), vp(d_dist)))
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

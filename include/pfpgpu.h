@@ -598,6 +598,63 @@ int pfp_fm_approx_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off
 int pfp_fm_approx_stats(pfp_fm *fm, uint64_t out[3]);
 
 /* ------------------------------------------------------------------------------------
+ * Extending seeds: edit-distance alignment of a whole pattern to the text near a diagonal, and the seed-and-extend call that takes
+ * a pattern's MEMs as its diagonals (csrc/fmextend.hip).  The reference has no counterpart: the method is the banded form of
+ * Sellers' dynamic programme (Sellers, "The theory and computation of evolutionary distances: pattern recognition", 1980; the band
+ * is Ukkonen's, "Algorithms for approximate string matching", 1985) under unit costs.  Conventions as in "Searching a BWT"; the
+ * index is one built with text (pfp_fm_build_ms_*), an index without text: PFP_EINVAL.  The text T has n bytes.
+ * For a pattern P of m bytes and a budget k in 0..PFP_FM_EXTEND_MAX_K:
+ *   candidate: a pair (p, delta) of a pattern index and a signed 64-bit diagonal, the text position that pattern byte 0 would have.
+ *     A MEM (i, len, pos) of pattern p gives delta = pos - i.  delta may be negative, or >= n.
+ *   window, in signed arithmetic: lo = min(max(delta - k, 0), n), hi = min(max(delta + m + k, 0), n).
+ *   d(s, e) = Levenshtein(P, T[s..e)) for lo <= s <= e <= hi: a substitution, an insertion and a deletion cost 1 each.  A pattern
+ *     byte that is 0, or that T does not hold, equals no text byte.  d* = the minimum over all such pairs (s, e).
+ *   result (d, s, e): if d* > k there is no alignment: d = 0xFF and s = e = UINT64_MAX.  Otherwise d = d*, e is the smallest e with
+ *     min over s of d(s, e) = d*, and s the largest s with d(s, e) = d*: the shortest span that ends first.  The empty pattern
+ *     gives (0, lo, lo).  The result is a function of (P, T, delta, k) alone - not of the batch, the launch shape or the schedule.
+ *   A candidate whose pattern index is >= npat, or whose pattern's offsets decrease, gets "no alignment".  Nothing is read outside
+ *     the index or the pattern buffer.
+ *   alignments of a pattern (the composite call): the MEMs of P of at least min_seed bytes, by PHONI or by thresholds, exactly as
+ *     pfp_fm_mems / pfp_fm_mems_thr list them, each give the candidate delta = pos - i.  The alignments of P are the distinct
+ *     triples (s, e, d) with d <= k among the results, ordered by (d, s, e); with max_aln > 0 only the first max_aln per pattern
+ *     are kept.  min_seed = 0: PFP_EINVAL.  A MEM carries ONE position of its string, so this is a heuristic, as in every
+ *     seed-and-extend mapper: a better alignment elsewhere in T - at another occurrence of a seed, or where no seed of min_seed
+ *     bytes survives the edits - can be missed.
+ * PFP_FM_EXTEND_MAX_K and PFP_FM_EXTEND_MAX_M are choices, not measurements: the band holds 5k + 1 diagonals, which at k = 32 is
+ * 11 cells per lane of a group of 16, and a span of at most m + 2k bytes is packed in 17 bits of a sort key.  k outside
+ * 0..PFP_FM_EXTEND_MAX_K: PFP_EINVAL.  A pattern of the call longer than PFP_FM_EXTEND_MAX_M: PFP_ELIMIT.
+ * Bounds: every loop of the kernel is bounded by m and k: a candidate costs at most two passes of m rows over a band of 16
+ * ceil((5k + 1) / 16) cells, about 2 m (5k + 1) cell updates, 2.1e7 at the limits.  So a launch is not cut into bounded pieces and
+ * no record is kept (PFP_FM_MS_STEPS bounds the matching statistics of the composite call as it bounds pfp_fm_ms*).
+ * Device memory on top of the caller's buffers: pfp_fm_extend_dev takes 8 bytes.  pfp_fm_align_dev takes 12 bytes per pattern
+ * byte (the matching statistics) and 16 per pattern; per seed (MEM) 24 for the triples, then - those released - 44 for the
+ * diagonals, their sort and the scan; per distinct diagonal 12 for the candidate and 17 for its result, then 32 for the keys,
+ * their sort and the scan, plus the library sort's scratch.  2^32 - 1 or more seeds in one call: PFP_ELIMIT (the segmented
+ * sort's segment bounds are u32).
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_EXTEND_MAX_K 32
+#define PFP_FM_EXTEND_MAX_M 65535
+/* device pointers, patterns as in pfp_fm_count_dev.  Candidate i is (d_cand_pat[i], d_cand_diag[i]); d_dist (uint8), d_start and
+ * d_end (ncand entries each) get its result. */
+int pfp_fm_extend_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_cand_pat,
+                      const int64_t *d_cand_diag, uint64_t ncand, int k, uint8_t *d_dist, uint64_t *d_start, uint64_t *d_end);
+/* the same with host buffers (offsets that decrease: PFP_EINVAL) */
+int pfp_fm_extend(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat,
+                  const int64_t *cand_diag, uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end);
+/* device pointers.  thresholds != 0: the seeds are pfp_fm_mems_thr's (an index without thresholds: PFP_EINVAL), else pfp_fm_mems's.
+ * d_aln_off (npat+1) gets the exclusive sums of the patterns' numbers of alignments.  d_start, d_end and d_dist all NULL: the offsets
+ * only; otherwise all three are required (PFP_EINVAL), with room for d_aln_off[npat] entries, and pattern p's alignments lie at
+ * d_aln_off[p] .. d_aln_off[p+1]. */
+int pfp_fm_align_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                     int thresholds, uint64_t *d_aln_off, uint64_t *d_start, uint64_t *d_end, uint8_t *d_dist);
+/* host buffers (offsets that decrease: PFP_EINVAL): aln_off (npat+1) is filled; *start, *end and *dist are malloc'ed arrays of
+ * aln_off[npat] entries (pfp_free; NULL when there are none).  The matching statistics are computed for the whole call; the
+ * patterns then go through in consecutive groups of at most PFP_SEQ_BUDGET seeds (a pattern with more goes alone;
+ * PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                 int thresholds, uint64_t *aln_off, uint64_t **start, uint64_t **end, uint8_t **dist);
+
+/* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
  * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
  * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
