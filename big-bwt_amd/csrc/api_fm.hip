@@ -1,6 +1,10 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
 // of a collection (seqmap.hip); extending seeds (fmextend.hip).
+// What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
+// budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
+// (HostOut::take, fetch_group_offsets).
+#include <algorithm>
 #include <memory>
 #include <vector>
 #include "api.hpp"
@@ -10,6 +14,74 @@ using namespace pfp;
 struct pfp_fm {
   pfp::FmIndex f;
 };
+
+namespace {
+
+// the body of an entry point over device pointers: body(), then a wait for the stream (api.hpp: between PFP_TRY_DEV and PFP_CATCH)
+template <class F>
+int dev_call(pfp_fm *fm, F &&body, bool wait = true) {
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  body();
+  if (wait) sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// the body of an entry point that makes an index: build(the new index's FmIndex); *out gets the index once it stands
+template <class F>
+int build_call(pfp_ctx *c, pfp_fm **out, F &&build) {
+  *out = nullptr;
+  PFP_TRY_DEV(c)
+  auto fm = std::make_unique<pfp_fm>();
+  build(fm->f);
+  *out = fm.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// host patterns: the bytes to copy (pat_off[npat]), once the offsets are known to be non-decreasing (no kernel reads past them)
+uint64_t pattern_bytes(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat) {
+  if (!npat) return 0;
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p] <= pat_off[p + 1], PFP_EINVAL, "pattern offsets decrease at pattern " + std::to_string(p));
+  PFP_REQUIRE(pat || !pat_off[npat], PFP_EINVAL, "no pattern bytes");
+  return pat_off[npat];
+}
+
+// the device copy of a call's host patterns: pat (the bytes and 16 more) and off (npat + 1), filled by upload(), which checks
+// the host arrays first (pattern_bytes).  pat can go before off does
+struct HostPatterns {
+  DBuf<uint8_t> pat;
+  DBuf<uint64_t> off;
+  uint64_t npat = 0, bytes = 0;
+  void upload(pfp_ctx *c, const uint8_t *h_pat, const uint64_t *h_off, uint64_t n) {
+    bytes = pattern_bytes(h_pat, h_off, n);
+    npat = n;
+    pat.alloc(c, bytes + 16);
+    off.alloc(c, npat + 1);
+    if (bytes) h2d(c, pat.p, h_pat, bytes);
+    if (npat) h2d(c, off.p, h_off, npat + 1);
+  }
+};
+
+// What one group of a call may hold: positions, hits or seeds (PFP_FM_SEQ_BUDGET lowers it: tests cut a small call into groups)
+uint64_t seq_budget() {
+  uint64_t budget = PFP_SEQ_BUDGET;
+  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {
+    const uint64_t v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < budget) budget = v;
+  }
+  return budget;
+}
+// The grouping rule of every call that works group by group.  off: exclusive sums of what each pattern brings.  The group that
+// starts at p0 is the longest run of consecutive patterns before `end` whose total stays within the budget; a pattern that
+// brings more goes alone.  -> the group's end
+uint64_t group_end(const uint64_t *off, uint64_t p0, uint64_t end, uint64_t budget) {
+  uint64_t p1 = p0 + 1;
+  while (p1 < end && off[p1 + 1] - off[p0] <= budget) p1++;
+  return p1;
+}
 
 // a malloc'ed result array that grows group by group
 template <class T>
@@ -24,82 +96,227 @@ struct HostOut {
     p = q;
     return p + n;
   }
+  // `count` device values behind the n held
+  void take(pfp_ctx *c, const T *d_src, uint64_t count) {
+    if (!count) return;
+    download(c, grow(count), (const uint8_t *)d_src, count * sizeof(T));
+    sync(c);      // (the next download fills the same pinned buffers)
+    n += count;
+  }
   T *release() { T *q = n ? p : nullptr; if (!n) free(p); p = nullptr; return q; }
 };
 
-// `count` device values behind the n held
-template <class T>
-static void apx_take(pfp_ctx *c, HostOut<T> &out, const T *d_src, uint64_t count) {
-  if (!count) return;
-  download(c, out.grow(count), (const uint8_t *)d_src, count * sizeof(T));
-  sync(c);      // (the next download fills the same pinned buffers)
-  out.n += count;
+// a group's np + 1 offsets, counted from its first pattern, come to the host (go) and go behind the call's: out[0] is the
+// call's offset of the group's first pattern, out[1 .. np] are written
+void fetch_group_offsets(pfp_ctx *c, const uint64_t *d_go, uint64_t np, std::vector<uint64_t> &go, uint64_t *out) {
+  go.resize(np + 1);
+  d2h(c, go.data(), d_go, np + 1);
+  sync(c);
+  for (uint64_t i = 1; i <= np; i++) out[i] = out[0] + go[i];
 }
+
+void require_samples(const pfp_fm *fm) {
+  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+}
+// what: "matching statistics need", ...
+void require_text(const pfp_fm *fm, const char *what) {
+  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, std::string(what) + " the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
+                                                              "pfp_fm_build_ms_files");
+}
+void require_thresholds(const pfp_fm *fm) {
+  PFP_REQUIRE(fm->f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
+}
+
+// f = an index with text from base.bwt / .ssa / .esa; the text: n bytes given in memory or in a file, else inverted from the BWT
+void load_ms_index(pfp_ctx *c, const std::string &b, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, FmIndex &f) {
+  DBuf<uint8_t> d_bwt, d_ssa, d_esa;
+  const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
+  check_bwt_rows(n1);
+  const bool given = text || text_fd >= 0;
+  PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
+                                                     " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
+  const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+  if (given) {
+    f.text.alloc(c, n + 16);
+    upload_text(c, f.text.p, text, text_fd, text_offset, n);
+    sync(c);
+  }
+  fm_build_ms(c, f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? f.text.p : nullptr);
+}
+
+// ---------------------------------------------------------------- approximate search (fmapprox.hip)
+// host patterns on the device with their hit counts: cnt on the device (npat + 1), hit_off their exclusive sums on the host
+struct ApxCall {
+  HostPatterns in;
+  DBuf<uint64_t> cnt;
+  std::vector<uint64_t> hit_off;
+};
+void apx_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, bool toehold, ApxCall &s) {
+  pfp_ctx *c = fm->f.c;
+  fm_approx_check(fm->f, k, toehold);
+  s.in.upload(c, pat, pat_off, npat);
+  s.cnt.alloc(c, npat + 1);
+  s.hit_off.assign(npat + 1, 0);
+  fm_approx_count(fm->f, s.in.pat.p, s.in.off.p, npat, k, s.cnt.p);
+  d2h(c, s.hit_off.data(), s.cnt.p, npat + 1);
+  sync(c);
+  uint64_t sum = 0;      // the counts become their sums (entry npat of the counts does not reach them)
+  for (uint64_t p = 0; p <= npat; p++) { const uint64_t n = s.hit_off[p]; s.hit_off[p] = sum; sum += n; }
+}
+// the hits of patterns [p0, p1) on the device
+struct ApxHits {
+  DBuf<uint64_t> hoff, sp, ep, first;
+  DBuf<uint8_t> dist;
+  uint64_t H = 0;
+};
+void apx_group_hits(pfp_fm *fm, const ApxCall &s, uint64_t p0, uint64_t p1, int k, bool toehold, ApxHits &h) {
+  pfp_ctx *c = fm->f.c;
+  const uint64_t np = p1 - p0;
+  h.H = s.hit_off[p1] - s.hit_off[p0];
+  h.hoff.alloc(c, np + 1);
+  exclusive_sum_u64(c, s.cnt.p + p0, h.hoff.p, np + 1);   // (entry np of the input does not reach the sums)
+  h.sp.alloc(c, h.H); h.ep.alloc(c, h.H); h.dist.alloc(c, h.H);
+  if (toehold) h.first.alloc(c, h.H);
+  fm_approx_fill(fm->f, s.in.pat.p, s.in.off.p + p0, np, k, h.hoff.p, h.H, h.sp.p, h.ep.p, toehold ? h.first.p : nullptr, h.dist.p);
+}
+
+// ---------------------------------------------------------------- matching statistics and MEMs (fmsearch.hip: PHONI)
+// host patterns -> device patterns, lengths and positions (entry t of the device arrays belongs to pattern byte t)
+struct MsOnDevice {
+  const uint8_t *h_pat;
+  const uint64_t *h_off;
+  uint64_t npat, bytes, first, total;
+  HostPatterns in;
+  DBuf<uint32_t> len;
+  DBuf<uint64_t> pos;
+  // (the host arrays are checked here: a caller may look at the lengths before anything is uploaded)
+  MsOnDevice(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat_)
+      : h_pat(pat), h_off(pat_off), npat(npat_), bytes(pattern_bytes(pat, pat_off, npat_)), first(npat_ ? pat_off[0] : 0), total(bytes - first) {}
+  void run(pfp_fm *fm, bool thr) {
+    pfp_ctx *c = fm->f.c;
+    in.upload(c, h_pat, h_off, npat);
+    len.alloc(c, bytes + 1);
+    pos.alloc(c, bytes + 1);
+    (thr ? fm_ms_thr : fm_ms)(fm->f, in.pat.p, in.off.p, npat, len.p, pos.p);
+  }
+};
+
+int ms_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos, bool thr) {
+  if (!fm || (npat && (!pat_off || !len))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  require_text(fm, "matching statistics need");
+  if (thr) require_thresholds(fm);
+  if (!npat) return PFP_OK;
+  MsOnDevice d(pat, pat_off, npat);
+  d.run(fm, thr);
+  if (d.total) {
+    download(c, len, (const uint8_t *)(d.len.p + d.first), d.total * 4);
+    sync(c);      // (the next download fills the same pinned buffers)
+    if (pos) download(c, pos, (const uint8_t *)(d.pos.p + d.first), d.total * 8);
+  }
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int mems_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems,
+              bool thr) {
+  if (!fm || !mem_off || !mems || (npat && !pat_off)) return PFP_EINVAL;
+  *mems = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  require_text(fm, "maximal exact matches need");
+  if (thr) require_thresholds(fm);
+  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
+  MsOnDevice d(pat, pat_off, npat);
+  d.run(fm, thr);
+  d.in.pat.release();
+  DBuf<uint64_t> d_mem_off(c, npat + 1);
+  fm_mems(fm->f, d.in.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
+  d2h(c, mem_off, d_mem_off.p, npat + 1);
+  sync(c);
+  const uint64_t total = mem_off[npat];
+  if (total) {
+    DBuf<uint64_t> d_mem(c, 3 * total);
+    fm_mems(fm->f, d.in.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, d_mem.p);
+    *mems = (uint64_t *)fetch_bytes(c, (const uint8_t *)d_mem.p, total * 24);
+  }
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos, bool thr) {
+  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
+  return dev_call(fm, [&] { (thr ? fm_ms_thr : fm_ms)(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos); });
+}
+
+// ---------------------------------------------------------------- sequences of a collection (seqmap.hip)
+// host patterns counted on the device, and what plain locate would list for them: uoff = its npat + 1 offsets, on the host
+struct SeqCall {
+  HostPatterns in;      // (its bytes go once the patterns are counted; off stays for the groups)
+  DBuf<uint64_t> rng;
+  std::vector<uint64_t> uoff;
+  // pattern p's entry of the ranges: which = 0 sp, 1 ep, 2 the toehold
+  const uint64_t *range(uint64_t p, int which) const { return rng.p + which * in.npat + p; }
+};
+void seq_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
+                    SeqCall &s) {
+  pfp_ctx *c = fm->f.c;
+  require_samples(fm);
+  PFP_REQUIRE(fm->f.nseq, PFP_EINVAL, "this index has no sequence table: give it one with pfp_fm_set_seqs (bigbwt -f --seqs writes it)");
+  s.in.upload(c, pat, pat_off, npat);
+  DBuf<uint64_t> d_uoff(c, npat + 1);
+  s.rng.alloc(c, 3 * npat + 1);
+  s.uoff.assign(npat + 1, 0);
+  fm_count(fm->f, s.in.pat.p, s.in.off.p, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat);
+  fm_locate(fm->f, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat, max_occ, d_uoff.p, nullptr);
+  d2h(c, s.uoff.data(), d_uoff.p, npat + 1);
+  if (sp) d2h(c, sp, s.rng.p, npat);
+  if (ep) d2h(c, ep, s.rng.p + npat, npat);
+  sync(c);
+  s.in.pat.release();
+}
+
+}  // namespace
 
 extern "C" {
-
-// host patterns: the bytes to copy (pat_off[npat]), once the offsets are known to be non-decreasing (no kernel reads past them)
-static uint64_t pattern_bytes(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat) {
-  if (!npat) return 0;
-  for (uint64_t p = 0; p < npat; p++)
-    PFP_REQUIRE(pat_off[p] <= pat_off[p + 1], PFP_EINVAL, "pattern offsets decrease at pattern " + std::to_string(p));
-  PFP_REQUIRE(pat || !pat_off[npat], PFP_EINVAL, "no pattern bytes");
-  return pat_off[npat];
-}
 
 int pfp_fm_build_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
                      uint64_t esa_bytes, pfp_fm **out) {
   if (!c || !d_bwt || !out) return PFP_EINVAL;
-  *out = nullptr;
-  PFP_TRY_DEV(c)
-  auto fm = std::make_unique<pfp_fm>();
-  fm_build(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes);
-  *out = fm.release();
-  return PFP_OK;
-  PFP_CATCH(c)
+  return build_call(c, out, [&](FmIndex &f) {
+    fm_build(c, f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes);
+  });
 }
 
 int pfp_fm_build_files(pfp_ctx *c, const char *base, int flags, pfp_fm **out) {
   if (!c || !base || !out) return PFP_EINVAL;
-  *out = nullptr;
-  PFP_TRY_DEV(c)
-  const std::string b(base);
-  const int samp = flags & (PFP_FLAG_SSA | PFP_FLAG_ESA);
-  PFP_REQUIRE(samp == 0 || samp == (PFP_FLAG_SSA | PFP_FLAG_ESA), PFP_EINVAL, "the run samples come as a pair: .ssa and .esa, or neither");
-  auto fm = std::make_unique<pfp_fm>();
-  // (the index adopts the buffer the file is read into: it has the room fm_build wants behind the rows)
-  const uint64_t n1 = file_to_dev(c, b + ".bwt", fm->f.bwt, [](uint64_t rows) { check_bwt_rows(rows); return fm_bwt_bytes(rows); });
-  DBuf<uint8_t> d_ssa, d_esa;
-  uint64_t ssa_bytes = 0, esa_bytes = 0;
-  if (samp) {
-    ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa);
-    esa_bytes = file_to_dev(c, b + ".esa", d_esa);
-  }
-  fm_build(c, fm->f, fm->f.bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes);
-  *out = fm.release();
-  return PFP_OK;
-  PFP_CATCH(c)
+  return build_call(c, out, [&](FmIndex &f) {
+    const std::string b(base);
+    const int samp = flags & (PFP_FLAG_SSA | PFP_FLAG_ESA);
+    PFP_REQUIRE(samp == 0 || samp == (PFP_FLAG_SSA | PFP_FLAG_ESA), PFP_EINVAL, "the run samples come as a pair: .ssa and .esa, or neither");
+    // (the index adopts the buffer the file is read into: it has the room fm_build wants behind the rows)
+    const uint64_t n1 = file_to_dev(c, b + ".bwt", f.bwt, [](uint64_t rows) { check_bwt_rows(rows); return fm_bwt_bytes(rows); });
+    DBuf<uint8_t> d_ssa, d_esa;
+    uint64_t ssa_bytes = 0, esa_bytes = 0;
+    if (samp) {
+      ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa);
+      esa_bytes = file_to_dev(c, b + ".esa", d_esa);
+    }
+    fm_build(c, f, f.bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes);
+  });
 }
 
 int pfp_fm_count_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t *d_sp, uint64_t *d_ep, uint64_t *d_first) {
   if (!fm || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_count(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_sp, d_ep, d_first);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_count(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_sp, d_ep, d_first); });
 }
 
 int pfp_fm_locate_dev(pfp_fm *fm, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep, const uint64_t *d_first, uint64_t max_occ,
                       uint64_t *d_out_off, uint64_t *d_pos) {
   if (!fm || !d_out_off || (npat && (!d_sp || !d_ep))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_locate(fm->f, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_locate(fm->f, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos); });
 }
 
 int pfp_fm_count(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
@@ -108,12 +325,10 @@ int pfp_fm_count(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
   PFP_TRY_DEV(c)
   PFP_REQUIRE(!first || fm->f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
   if (!npat) return PFP_OK;
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  DBuf<uint8_t> d_pat(c, bytes + 16);
-  DBuf<uint64_t> d_off(c, npat + 1), d_out(c, 3 * npat);
-  if (bytes) h2d(c, d_pat.p, pat, bytes);
-  h2d(c, d_off.p, pat_off, npat + 1);
-  fm_count(fm->f, d_pat.p, d_off.p, npat, d_out.p, d_out.p + npat, first ? d_out.p + 2 * npat : nullptr);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint64_t> d_out(c, 3 * npat);
+  fm_count(fm->f, in.pat.p, in.off.p, npat, d_out.p, d_out.p + npat, first ? d_out.p + 2 * npat : nullptr);
   d2h(c, sp, d_out.p, npat);
   d2h(c, ep, d_out.p + npat, npat);
   if (first) d2h(c, first, d_out.p + 2 * npat, npat);
@@ -128,14 +343,12 @@ int pfp_fm_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint6
   *pos = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
-  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  DBuf<uint8_t> d_pat(c, bytes + 16);
-  DBuf<uint64_t> d_off(c, npat + 1), d_rng(c, 3 * npat + 1), d_out_off(c, npat + 1);
-  if (bytes) h2d(c, d_pat.p, pat, bytes);
-  if (npat) h2d(c, d_off.p, pat_off, npat + 1);
-  fm_count(fm->f, d_pat.p, d_off.p, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat);
-  d_pat.release();
+  require_samples(fm);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint64_t> d_rng(c, 3 * npat + 1), d_out_off(c, npat + 1);
+  fm_count(fm->f, in.pat.p, in.off.p, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat);
+  in.pat.release();
   fm_locate(fm->f, npat, d_rng.p, d_rng.p + npat, d_rng.p + 2 * npat, max_occ, d_out_off.p, nullptr);
   d2h(c, out_off, d_out_off.p, npat + 1);
   if (sp) d2h(c, sp, d_rng.p, npat);
@@ -157,12 +370,7 @@ int pfp_fm_approx_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, 
   if (!fm || !d_hit_off || (npat && !d_pat_off)) return PFP_EINVAL;
   const bool fill = d_sp || d_ep || d_dist;
   if (fill && !(d_sp && d_ep && d_dist)) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_approx(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, k, d_hit_off, d_sp, d_ep, d_first, d_dist);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_approx(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, k, d_hit_off, d_sp, d_ep, d_first, d_dist); });
 }
 
 int pfp_fm_approx_stats(pfp_fm *fm, uint64_t out[3]) {
@@ -172,55 +380,6 @@ int pfp_fm_approx_stats(pfp_fm *fm, uint64_t out[3]) {
   return PFP_OK;
 }
 
-// host patterns on the device with their hit counts: cnt on the device (npat + 1), hcnt on the host
-struct ApxCall {
-  DBuf<uint8_t> pat;
-  DBuf<uint64_t> off, cnt;
-  std::vector<uint64_t> hcnt;
-  uint64_t budget = PFP_SEQ_BUDGET;
-  // the end of the group of consecutive entries that starts at p0: their sum stays within the budget, a larger entry goes alone
-  uint64_t group_end(const std::vector<uint64_t> &per, uint64_t p0, uint64_t end) const {
-    uint64_t p1 = p0 + 1, sum = per[p0];
-    while (p1 < end && sum + per[p1] <= budget) sum += per[p1++];
-    return p1;
-  }
-};
-static void apx_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, bool toehold, ApxCall &s) {
-  pfp_ctx *c = fm->f.c;
-  fm_approx_check(fm->f, k, toehold);
-  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < s.budget) s.budget = v;
-  }
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  s.pat.alloc(c, bytes + 16);
-  s.off.alloc(c, npat + 1);
-  s.cnt.alloc(c, npat + 1);
-  s.hcnt.assign(npat + 1, 0);
-  if (bytes) h2d(c, s.pat.p, pat, bytes);
-  if (npat) h2d(c, s.off.p, pat_off, npat + 1);
-  fm_approx_count(fm->f, s.pat.p, s.off.p, npat, k, s.cnt.p);
-  d2h(c, s.hcnt.data(), s.cnt.p, npat + 1);
-  sync(c);
-}
-// the hits of patterns [p0, p1) on the device
-struct ApxHits {
-  DBuf<uint64_t> hoff, sp, ep, first;
-  DBuf<uint8_t> dist;
-  uint64_t H = 0;
-};
-static void apx_group_hits(pfp_fm *fm, const ApxCall &s, uint64_t p0, uint64_t p1, int k, bool toehold, ApxHits &h) {
-  pfp_ctx *c = fm->f.c;
-  const uint64_t np = p1 - p0;
-  h.H = 0;
-  for (uint64_t p = p0; p < p1; p++) h.H += s.hcnt[p];
-  h.hoff.alloc(c, np + 1);
-  exclusive_sum_u64(c, s.cnt.p + p0, h.hoff.p, np + 1);   // (entry np of the input does not reach the sums)
-  h.sp.alloc(c, h.H); h.ep.alloc(c, h.H); h.dist.alloc(c, h.H);
-  if (toehold) h.first.alloc(c, h.H);
-  fm_approx_fill(fm->f, s.pat.p, s.off.p + p0, np, k, h.hoff.p, h.H, h.sp.p, h.ep.p, toehold ? h.first.p : nullptr, h.dist.p);
-}
-
 int pfp_fm_approx(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *hit_off, uint64_t **sp,
                   uint64_t **ep, uint64_t **first, uint8_t **dist) {
   if (!fm || !hit_off || !sp || !ep || !dist || (npat && !pat_off)) return PFP_EINVAL;
@@ -228,21 +387,21 @@ int pfp_fm_approx(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint6
   if (first) *first = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
+  const uint64_t budget = seq_budget();
   ApxCall s;
   apx_call_begin(fm, pat, pat_off, npat, k, first != nullptr, s);
   HostOut<uint64_t> h_sp, h_ep, h_first;
   HostOut<uint8_t> h_dist;
-  hit_off[0] = 0;
-  for (uint64_t p = 0; p < npat; p++) hit_off[p + 1] = hit_off[p] + s.hcnt[p];
-  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
-    p1 = s.group_end(s.hcnt, p0, npat);
+  std::copy(s.hit_off.begin(), s.hit_off.end(), hit_off);
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns whose hits stay within the budget (group_end)
+    p1 = group_end(hit_off, p0, npat, budget);
     ApxHits h;
     apx_group_hits(fm, s, p0, p1, k, first != nullptr, h);
     sync(c);
-    apx_take(c, h_sp, h.sp.p, h.H);
-    apx_take(c, h_ep, h.ep.p, h.H);
-    apx_take(c, h_dist, h.dist.p, h.H);
-    if (first) apx_take(c, h_first, h.first.p, h.H);
+    h_sp.take(c, h.sp.p, h.H);
+    h_ep.take(c, h.ep.p, h.H);
+    h_dist.take(c, h.dist.p, h.H);
+    if (first) h_first.take(c, h.first.p, h.H);
   }
   *sp = h_sp.release(); *ep = h_ep.release(); *dist = h_dist.release();
   if (first) *first = h_first.release();
@@ -256,40 +415,32 @@ int pfp_fm_approx_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off
   *pos = nullptr; *dist = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
-  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  require_samples(fm);
+  const uint64_t budget = seq_budget();
   ApxCall s;
   apx_call_begin(fm, pat, pat_off, npat, k, true, s);
   HostOut<uint64_t> h_pos;
   HostOut<uint8_t> h_dist;
-  std::vector<uint64_t> go, per, hbase;
+  std::vector<uint64_t> go;
   out_off[0] = 0;
-  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
-    p1 = s.group_end(s.hcnt, p0, npat);
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns whose hits stay within the budget
+    p1 = group_end(s.hit_off.data(), p0, npat, budget);
     const uint64_t np = p1 - p0;
     ApxHits h;
     apx_group_hits(fm, s, p0, p1, k, true, h);
     DBuf<uint64_t> d_go(c, np + 1), cep;
     fm_approx_clip(fm->f, np, h.hoff.p, h.H, h.sp.p, h.ep.p, h.first.p, max_occ, d_go.p, cep);
-    go.resize(np + 1);
-    d2h(c, go.data(), d_go.p, np + 1);
-    sync(c);
-    per.resize(np);
-    hbase.assign(np + 1, 0);
-    for (uint64_t i = 0; i < np; i++) {
-      out_off[p0 + i + 1] = out_off[p0] + go[i + 1];
-      per[i] = go[i + 1] - go[i];
-      hbase[i + 1] = hbase[i] + s.hcnt[p0 + i];
-    }
+    fetch_group_offsets(c, d_go.p, np, go, out_off + p0);
     // inside the group: consecutive patterns whose positions stay within the budget
     for (uint64_t q0 = 0, q1; q0 < np; q0 = q1) {
-      q1 = s.group_end(per, q0, np);
-      const uint64_t h0 = hbase[q0], nh = hbase[q1] - h0;
+      q1 = group_end(go.data(), q0, np, budget);
+      const uint64_t h0 = s.hit_off[p0 + q0] - s.hit_off[p0], nh = s.hit_off[p0 + q1] - s.hit_off[p0 + q0];
       DBuf<uint64_t> d_pos;
       DBuf<uint8_t> d_pd;
       const uint64_t U = fm_approx_positions(fm->f, nh, h.sp.p + h0, cep.p + h0, h.first.p + h0, h.dist.p + h0, d_pos, d_pd);
       if (U != go[q1] - go[q0]) throw Error(PFP_EHIP, "approximate locate: a group's positions do not add up");
-      apx_take(c, h_pos, d_pos.p, U);
-      apx_take(c, h_dist, d_pd.p, U);
+      h_pos.take(c, d_pos.p, U);
+      h_dist.take(c, d_pd.p, U);
     }
   }
   *pos = h_pos.release();
@@ -302,79 +453,28 @@ int pfp_fm_approx_locate(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off
 int pfp_fm_build_ms_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10,
                         uint64_t esa_bytes, const void *d_text, pfp_fm **out) {
   if (!c || !d_bwt || !out) return PFP_EINVAL;
-  *out = nullptr;
-  PFP_TRY_DEV(c)
-  auto fm = std::make_unique<pfp_fm>();
-  fm_build_ms(c, fm->f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes,
-              (const uint8_t *)d_text);
-  *out = fm.release();
-  return PFP_OK;
-  PFP_CATCH(c)
+  return build_call(c, out, [&](FmIndex &f) {
+    fm_build_ms(c, f, (const uint8_t *)d_bwt, n_plus_1, (const uint8_t *)d_ssa10, ssa_bytes, (const uint8_t *)d_esa10, esa_bytes,
+                (const uint8_t *)d_text);
+  });
 }
 
 int pfp_fm_build_ms_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd, uint64_t text_offset, uint64_t n, pfp_fm **out) {
   if (!c || !base || !out) return PFP_EINVAL;
-  *out = nullptr;
-  PFP_TRY_DEV(c)
-  const std::string b(base);
-  auto fm = std::make_unique<pfp_fm>();
-  DBuf<uint8_t> d_bwt, d_ssa, d_esa;
-  const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
-  check_bwt_rows(n1);
-  const bool given = text || text_fd >= 0;
-  PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
-                                                     " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
-  const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
-  if (given) {
-    fm->f.text.alloc(c, n + 16);
-    upload_text(c, fm->f.text.p, text, text_fd, text_offset, n);
-    sync(c);
-  }
-  fm_build_ms(c, fm->f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? fm->f.text.p : nullptr);
-  *out = fm.release();
-  return PFP_OK;
-  PFP_CATCH(c)
+  return build_call(c, out, [&](FmIndex &f) { load_ms_index(c, base, text, text_fd, text_offset, n, f); });
 }
 
 int pfp_fm_ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
-  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_ms(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return ms_dev(fm, d_pat, d_pat_off, npat, d_len, d_pos, false);
+}
+int pfp_fm_ms_thr_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
+  return ms_dev(fm, d_pat, d_pat_off, npat, d_len, d_pos, true);
 }
 
 int pfp_fm_mems_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_len, const uint64_t *d_pos, uint64_t min_len,
                     uint64_t *d_mem_off, uint64_t *d_mem) {
   if (!fm || !d_mem_off || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_mems(fm->f, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
-}
-
-// host patterns -> device patterns, lengths and positions (entry t of the device arrays belongs to pattern byte t)
-struct MsOnDevice {
-  DBuf<uint8_t> pat; DBuf<uint64_t> off, pos; DBuf<uint32_t> len;
-  uint64_t first = 0, total = 0;
-};
-static void ms_on_device(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MsOnDevice &d, bool thr = false) {
-  pfp_ctx *c = fm->f.c;
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  d.first = npat ? pat_off[0] : 0;
-  d.total = bytes - d.first;
-  d.pat.alloc(c, bytes + 16);
-  d.off.alloc(c, npat + 1);
-  d.len.alloc(c, bytes + 1);
-  d.pos.alloc(c, bytes + 1);
-  if (bytes) h2d(c, d.pat.p, pat, bytes);
-  if (npat) h2d(c, d.off.p, pat_off, npat + 1);
-  if (thr) fm_ms_thr(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
-  else fm_ms(fm->f, d.pat.p, d.off.p, npat, d.len.p, d.pos.p);
+  return dev_call(fm, [&] { fm_mems(fm->f, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem); });
 }
 
 int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
@@ -384,62 +484,11 @@ int pfp_fm_ms_stats(pfp_fm *fm, uint64_t out[3]) {
   return PFP_OK;
 }
 
-static void require_thresholds(const pfp_fm *fm) {
-  PFP_REQUIRE(fm->f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
-}
-
-static int ms_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos, bool thr) {
-  if (!fm || (npat && (!pat_off || !len))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "matching statistics need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
-                                          "pfp_fm_build_ms_files");
-  if (thr) require_thresholds(fm);
-  if (!npat) return PFP_OK;
-  MsOnDevice d;
-  ms_on_device(fm, pat, pat_off, npat, d, thr);
-  if (d.total) {
-    download(c, len, (const uint8_t *)(d.len.p + d.first), d.total * 4);
-    sync(c);      // (the next download fills the same pinned buffers)
-    if (pos) download(c, pos, (const uint8_t *)(d.pos.p + d.first), d.total * 8);
-  }
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
-}
-
 int pfp_fm_ms(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
   return ms_host(fm, pat, pat_off, npat, len, pos, false);
 }
 int pfp_fm_ms_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
   return ms_host(fm, pat, pat_off, npat, len, pos, true);
-}
-
-static int mems_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems,
-                     bool thr) {
-  if (!fm || !mem_off || !mems || (npat && !pat_off)) return PFP_EINVAL;
-  *mems = nullptr;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "maximal exact matches need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
-                                          "pfp_fm_build_ms_files");
-  if (thr) require_thresholds(fm);
-  PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
-  MsOnDevice d;
-  ms_on_device(fm, pat, pat_off, npat, d, thr);
-  d.pat.release();
-  DBuf<uint64_t> d_mem_off(c, npat + 1);
-  fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
-  d2h(c, mem_off, d_mem_off.p, npat + 1);
-  sync(c);
-  const uint64_t total = mem_off[npat];
-  if (total) {
-    DBuf<uint64_t> d_mem(c, 3 * total);
-    fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, d_mem.p);
-    *mems = (uint64_t *)fetch_bytes(c, (const uint8_t *)d_mem.p, total * 24);
-  }
-  return PFP_OK;
-  PFP_CATCH(c)
 }
 
 int pfp_fm_mems(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_len, uint64_t *mem_off, uint64_t **mems) {
@@ -449,43 +498,28 @@ int pfp_fm_mems_thr(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uin
   return mems_host(fm, pat, pat_off, npat, min_len, mem_off, mems, true);
 }
 
-int pfp_fm_ms_thr_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos) {
-  if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_ms_thr(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
-}
-
 // ---------------------------------------------------------------- the LCP array and thresholds (lcp.hip)
 int pfp_fm_thresholds_dev(pfp_fm *fm, const void *d_thr5, uint64_t bytes) {
   if (!fm) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  if (d_thr5) {
-    fm_load_thresholds(fm->f, (const uint8_t *)d_thr5, bytes);
-  } else {
-    LcpOut o;
-    o.keep = true;
-    fm_lcp(fm->f, o);
-  }
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] {
+    if (d_thr5) {
+      fm_load_thresholds(fm->f, (const uint8_t *)d_thr5, bytes);
+    } else {
+      LcpOut o;
+      o.keep = true;
+      fm_lcp(fm->f, o);
+    }
+  }, false);
 }
 
 int pfp_fm_thresholds_files(pfp_fm *fm, const char *base) {
   if (!fm || !base) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  PFP_REQUIRE(fm->f.has_text, PFP_EINVAL, "thresholds need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
-                                          "pfp_fm_build_ms_files");
-  DBuf<uint8_t> d_thr;
-  const uint64_t bytes = file_to_dev(c, std::string(base) + ".thr_pos", d_thr);
-  fm_load_thresholds(fm->f, d_thr.p, bytes);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] {
+    require_text(fm, "thresholds need");
+    DBuf<uint8_t> d_thr;
+    const uint64_t bytes = file_to_dev(fm->f.c, std::string(base) + ".thr_pos", d_thr);
+    fm_load_thresholds(fm->f, d_thr.p, bytes);
+  }, false);
 }
 
 int pfp_lcp_dev(pfp_ctx *c, const void *d_bwt, uint64_t n_plus_1, const void *d_ssa10, uint64_t ssa_bytes, const void *d_esa10, uint64_t esa_bytes,
@@ -509,21 +543,7 @@ int pfp_lcp_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd
   PFP_REQUIRE(what && !(what & ~(PFP_LCP_LCP | PFP_LCP_THR)), PFP_EINVAL, "what: PFP_LCP_LCP, PFP_LCP_THR or both");
   const std::string b(base);
   FmIndex f;
-  {
-    DBuf<uint8_t> d_bwt, d_ssa, d_esa;
-    const uint64_t n1 = file_to_dev(c, b + ".bwt", d_bwt);
-    check_bwt_rows(n1);
-    const bool given = text || text_fd >= 0;
-    PFP_REQUIRE(!given || n + 1 == n1, PFP_EINVAL, "the text holds " + std::to_string(n) + " bytes; " + b + ".bwt holds " + std::to_string(n1) +
-                                                       " rows, so its text holds " + std::to_string(n1 ? n1 - 1 : 0));
-    const uint64_t ssa_bytes = file_to_dev(c, b + ".ssa", d_ssa), esa_bytes = file_to_dev(c, b + ".esa", d_esa);
-    if (given) {
-      f.text.alloc(c, n + 16);
-      upload_text(c, f.text.p, text, text_fd, text_offset, n);
-      sync(c);
-    }
-    fm_build_ms(c, f, d_bwt.p, n1, d_ssa.p, ssa_bytes, d_esa.p, esa_bytes, given ? f.text.p : nullptr);
-  }
+  load_ms_index(c, b, text, text_fd, text_offset, n, f);
   DBuf<uint8_t> lcp5, thr5;
   LcpOut o;
   if (what & PFP_LCP_LCP) { lcp5.alloc(c, 5 * f.n1 + 16); o.lcp5 = lcp5.p; }
@@ -539,12 +559,7 @@ int pfp_lcp_files(pfp_ctx *c, const char *base, const uint8_t *text, int text_fd
 int pfp_fm_extend_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_cand_pat,
                       const int64_t *d_cand_diag, uint64_t ncand, int k, uint8_t *d_dist, uint64_t *d_start, uint64_t *d_end) {
   if (!fm || (npat && !d_pat_off) || (ncand && (!d_cand_pat || !d_cand_diag || !d_dist || !d_start || !d_end))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_extend(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_extend(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end); });
 }
 
 int pfp_fm_extend(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const int64_t *cand_diag,
@@ -553,15 +568,14 @@ int pfp_fm_extend(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint6
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
   fm_extend_check(fm->f, k);
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  DBuf<uint8_t> d_pat(c, bytes + 16), d_dist(c, ncand);
-  DBuf<uint64_t> d_off(c, npat + 1), d_out(c, 2 * ncand);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint8_t> d_dist(c, ncand);
+  DBuf<uint64_t> d_out(c, 2 * ncand);
   DBuf<uint32_t> d_cp(c, ncand);
   DBuf<int64_t> d_cd(c, ncand);
-  if (bytes) h2d(c, d_pat.p, pat, bytes);
-  if (npat) h2d(c, d_off.p, pat_off, npat + 1);
   if (ncand) { h2d(c, d_cp.p, cand_pat, ncand); h2d(c, d_cd.p, cand_diag, ncand); }
-  fm_extend(fm->f, d_pat.p, d_off.p, npat, d_cp.p, d_cd.p, ncand, k, d_dist.p, d_out.p, d_out.p + ncand);
+  fm_extend(fm->f, in.pat.p, in.off.p, npat, d_cp.p, d_cd.p, ncand, k, d_dist.p, d_out.p, d_out.p + ncand);
   if (ncand) {
     d2h(c, dist, d_dist.p, ncand);
     d2h(c, start, d_out.p, ncand);
@@ -577,12 +591,9 @@ int pfp_fm_align_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, u
   if (!fm || !d_aln_off || (npat && !d_pat_off)) return PFP_EINVAL;
   const bool fill = d_start || d_end || d_dist;
   if (fill && !(d_start && d_end && d_dist)) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_align(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, max_aln, thresholds != 0, d_aln_off, d_start, d_end, d_dist);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] {
+    fm_align(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, max_aln, thresholds != 0, d_aln_off, d_start, d_end, d_dist);
+  });
 }
 
 int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
@@ -594,48 +605,39 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
   fm_extend_check(fm->f, k);
   PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
   if (thresholds) require_thresholds(fm);
-  ApxCall s;                                            // (its budget and its grouping)
-  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < s.budget) s.budget = v;
-  }
-  pattern_bytes(pat, pat_off, npat);                    // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
+  const uint64_t budget = seq_budget();
+  MsOnDevice d(pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
   for (uint64_t p = 0; p < npat; p++)                   // (before any work: fm_extend_check_patterns' rule, on the host's copy)
     PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
                 "pattern " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
-  MsOnDevice d;
-  ms_on_device(fm, pat, pat_off, npat, d, thresholds != 0);
+  d.run(fm, thresholds != 0);
   aln_off[0] = 0;
   if (!npat) return PFP_OK;
-  std::vector<uint64_t> moff(npat + 1), per(npat), goff, go;
+  std::vector<uint64_t> moff(npat + 1), goff, go;
   {
     DBuf<uint64_t> d_moff(c, npat + 1);
-    fm_mems(fm->f, d.off.p, npat, d.len.p, d.pos.p, min_seed, d_moff.p, nullptr);
+    fm_mems(fm->f, d.in.off.p, npat, d.len.p, d.pos.p, min_seed, d_moff.p, nullptr);
     d2h(c, moff.data(), d_moff.p, npat + 1);
     sync(c);
   }
-  for (uint64_t p = 0; p < npat; p++) per[p] = moff[p + 1] - moff[p];
   HostOut<uint64_t> h_start, h_end;
   HostOut<uint8_t> h_dist;
   for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns whose seeds stay within the budget
-    p1 = s.group_end(per, p0, npat);
+    p1 = group_end(moff.data(), p0, npat, budget);
     const uint64_t np = p1 - p0;
     goff.resize(np + 1);                                // the group's MEM offsets: the call's, counted from its first pattern
     for (uint64_t i = 0; i <= np; i++) goff[i] = moff[p0 + i] - moff[p0];
     DBuf<uint64_t> g_moff(c, np + 1), g_off(c, np + 1);
     h2d(c, g_moff.p, goff.data(), np + 1);
     AlnKeys keys;
-    fm_align_seeds(fm->f, d.pat.p, d.off.p + p0, np, min_seed, k, max_aln, d.len.p, d.pos.p, g_moff.p, goff[np], g_off.p, keys);
+    fm_align_seeds(fm->f, d.in.pat.p, d.in.off.p + p0, np, min_seed, k, max_aln, d.len.p, d.pos.p, g_moff.p, goff[np], g_off.p, keys);
     DBuf<uint64_t> g_start(c, keys.total), g_end(c, keys.total);
     DBuf<uint8_t> g_dist(c, keys.total);
     fm_align_write(fm->f, keys, g_start.p, g_end.p, g_dist.p);
-    go.resize(np + 1);
-    d2h(c, go.data(), g_off.p, np + 1);
-    sync(c);
-    for (uint64_t i = 0; i < np; i++) aln_off[p0 + i + 1] = aln_off[p0] + go[i + 1];
-    apx_take(c, h_start, g_start.p, keys.total);
-    apx_take(c, h_end, g_end.p, keys.total);
-    apx_take(c, h_dist, g_dist.p, keys.total);
+    fetch_group_offsets(c, g_off.p, np, go, aln_off + p0);
+    h_start.take(c, g_start.p, keys.total);
+    h_end.take(c, g_end.p, keys.total);
+    h_dist.take(c, g_dist.p, keys.total);
   }
   *start = h_start.release(); *end = h_end.release(); *dist = h_dist.release();
   return PFP_OK;
@@ -645,115 +647,52 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
 // ---------------------------------------------------------------- sequences of a collection (seqmap.hip)
 int pfp_fm_set_seqs(pfp_fm *fm, const uint64_t *starts, uint64_t nseq) {
   if (!fm) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_set_seqs(fm->f, starts, nseq);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_set_seqs(fm->f, starts, nseq); }, false);
 }
 
 int pfp_fm_seqmap_dev(pfp_fm *fm, const uint64_t *d_pos, uint64_t count, uint32_t *d_seq, uint64_t *d_off) {
   if (!fm || (count && !d_pos)) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_seqmap(fm->f, d_pos, count, d_seq, d_off);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_seqmap(fm->f, d_pos, count, d_seq, d_off); });
 }
 
 int pfp_fm_locate_seqs_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
                            const uint64_t *d_first, uint64_t max_occ, uint64_t *d_out_off, uint32_t *d_seq, uint64_t *d_off) {
   if (!fm || !d_out_off || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  fm_locate_seqs(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq, d_off);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] { fm_locate_seqs(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq, d_off); });
 }
 
 int pfp_fm_doclist_dev(pfp_fm *fm, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_sp, const uint64_t *d_ep,
                        const uint64_t *d_first, uint64_t *d_doc_off, uint32_t *d_doc, uint64_t *d_cnt) {
   if (!fm || !d_doc_off || (npat && (!d_pat_off || !d_sp || !d_ep))) return PFP_EINVAL;
-  pfp_ctx *c = fm->f.c;
-  PFP_TRY_DEV(c)
-  DocOut o;
-  o.doc = d_doc; o.cnt = d_cnt;
-  fm_doclist(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, o);
-  sync(c);
-  return PFP_OK;
-  PFP_CATCH(c)
+  return dev_call(fm, [&] {
+    DocOut o;
+    o.doc = d_doc; o.cnt = d_cnt;
+    fm_doclist(fm->f, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, o);
+  });
 }
 
-// host patterns counted on the device, and what plain locate would list for them: uoff = its npat + 1 offsets, on the host
-struct SeqCall {
-  DBuf<uint64_t> off, rng;
-  std::vector<uint64_t> uoff;
-  uint64_t budget = PFP_SEQ_BUDGET;
-  // pattern p's entry of the ranges: which = 0 sp, 1 ep, 2 the toehold
-  const uint64_t *range(uint64_t p, uint64_t npat, int which) const { return rng.p + which * npat + p; }
-  // the end of the group of consecutive patterns that starts at p0: at most `budget` positions, a pattern with more goes alone
-  uint64_t group_end(uint64_t p0, uint64_t npat) const {
-    uint64_t p1 = p0 + 1;
-    while (p1 < npat && uoff[p1 + 1] - uoff[p0] <= budget) p1++;
-    return p1;
-  }
-};
-static void seq_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp, uint64_t *ep,
-                           SeqCall &s) {
-  pfp_ctx *c = fm->f.c;
-  PFP_REQUIRE(fm->f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
-  PFP_REQUIRE(fm->f.nseq, PFP_EINVAL, "this index has no sequence table: give it one with pfp_fm_set_seqs (bigbwt -f --seqs writes it)");
-  if (const char *e = getenv("PFP_FM_SEQ_BUDGET")) {    // (tests: a small budget cuts a small call into groups)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < s.budget) s.budget = v;
-  }
-  const uint64_t bytes = pattern_bytes(pat, pat_off, npat);
-  DBuf<uint8_t> d_pat(c, bytes + 16);
-  DBuf<uint64_t> d_uoff(c, npat + 1);
-  s.off.alloc(c, npat + 1);
-  s.rng.alloc(c, 3 * npat + 1);
-  s.uoff.assign(npat + 1, 0);
-  if (bytes) h2d(c, d_pat.p, pat, bytes);
-  if (npat) h2d(c, s.off.p, pat_off, npat + 1);
-  fm_count(fm->f, d_pat.p, s.off.p, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat);
-  fm_locate(fm->f, npat, s.rng.p, s.rng.p + npat, s.rng.p + 2 * npat, max_occ, d_uoff.p, nullptr);
-  d2h(c, s.uoff.data(), d_uoff.p, npat + 1);
-  if (sp) d2h(c, sp, s.rng.p, npat);
-  if (ep) d2h(c, ep, s.rng.p + npat, npat);
-  sync(c);
-}
 int pfp_fm_locate_seqs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t max_occ, uint64_t *sp,
                        uint64_t *ep, uint64_t *out_off, uint32_t **seq, uint64_t **off) {
   if (!fm || !out_off || !seq || !off || (npat && !pat_off)) return PFP_EINVAL;
   *seq = nullptr; *off = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
+  const uint64_t budget = seq_budget();
   SeqCall s;
   seq_call_begin(fm, pat, pat_off, npat, max_occ, sp, ep, s);
   HostOut<uint32_t> h_seq;
   HostOut<uint64_t> h_off;
   std::vector<uint64_t> go;
   out_off[0] = 0;
-  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
-    p1 = s.group_end(p0, npat);
+  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns with at most `budget` positions to look at
+    p1 = group_end(s.uoff.data(), p0, npat, budget);
     const uint64_t k = p1 - p0, U = s.uoff[p1] - s.uoff[p0];
     DBuf<uint64_t> d_go(c, k + 1), d_o(c, U);
     DBuf<uint32_t> d_s(c, U);
-    fm_locate_seqs(fm->f, s.off.p + p0, k, s.range(p0, npat, 0), s.range(p0, npat, 1), s.range(p0, npat, 2), max_occ, d_go.p, d_s.p, d_o.p);
-    go.resize(k + 1);
-    d2h(c, go.data(), d_go.p, k + 1);
-    sync(c);
-    for (uint64_t i = 1; i <= k; i++) out_off[p0 + i] = out_off[p0] + go[i];
-    const uint64_t kept = go[k];
-    if (kept) {
-      download(c, h_seq.grow(kept), (const uint8_t *)d_s.p, kept * 4);
-      sync(c);      // (the next download fills the same pinned buffers)
-      download(c, h_off.grow(kept), (const uint8_t *)d_o.p, kept * 8);
-      sync(c);
-      h_seq.n += kept; h_off.n += kept;
-    }
+    fm_locate_seqs(fm->f, s.in.off.p + p0, k, s.range(p0, 0), s.range(p0, 1), s.range(p0, 2), max_occ, d_go.p, d_s.p, d_o.p);
+    fetch_group_offsets(c, d_go.p, k, go, out_off + p0);
+    h_seq.take(c, d_s.p, go[k]);
+    h_off.take(c, d_o.p, go[k]);
   }
   *seq = h_seq.release();
   *off = h_off.release();
@@ -767,6 +706,7 @@ int pfp_fm_doclist(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint
   *doc = nullptr; *cnt = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
+  const uint64_t budget = seq_budget();
   SeqCall s;
   seq_call_begin(fm, pat, pat_off, npat, 0, nullptr, nullptr, s);
   HostOut<uint32_t> h_doc;
@@ -774,25 +714,16 @@ int pfp_fm_doclist(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint
   std::vector<uint64_t> go;
   doc_off[0] = 0;
   for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {
-    p1 = s.group_end(p0, npat);
+    p1 = group_end(s.uoff.data(), p0, npat, budget);
     const uint64_t k = p1 - p0;
     DBuf<uint64_t> d_go(c, k + 1), d_c;
     DBuf<uint32_t> d_d;
     DocOut o;
     o.own_doc = &d_d; o.own_cnt = &d_c;      // (sized inside, once the group's total is known: nothing is listed twice)
-    fm_doclist(fm->f, s.off.p + p0, k, s.range(p0, npat, 0), s.range(p0, npat, 1), s.range(p0, npat, 2), d_go.p, o);
-    go.resize(k + 1);
-    d2h(c, go.data(), d_go.p, k + 1);
-    sync(c);
-    for (uint64_t i = 1; i <= k; i++) doc_off[p0 + i] = doc_off[p0] + go[i];
-    const uint64_t docs = go[k];
-    if (docs) {
-      download(c, h_doc.grow(docs), (const uint8_t *)d_d.p, docs * 4);
-      sync(c);
-      download(c, h_cnt.grow(docs), (const uint8_t *)d_c.p, docs * 8);
-      sync(c);
-      h_doc.n += docs; h_cnt.n += docs;
-    }
+    fm_doclist(fm->f, s.in.off.p + p0, k, s.range(p0, 0), s.range(p0, 1), s.range(p0, 2), d_go.p, o);
+    fetch_group_offsets(c, d_go.p, k, go, doc_off + p0);
+    h_doc.take(c, d_d.p, go[k]);
+    h_cnt.take(c, d_c.p, go[k]);
   }
   *doc = h_doc.release();
   *cnt = h_cnt.release();

@@ -116,6 +116,130 @@ static void revcomp(const uint8_t *in, uint64_t len, uint8_t *out) {
   for (uint64_t i = 0; i < len; i++) out[i] = map[in[len - 1 - i]];
 }
 
+/* one batch of k patterns, the index, the options, and main's scratch arrays (room for k + 1 entries each; ep: k) */
+typedef struct {
+  pfp_ctx *ctx; pfp_fm *fm; const char *base; const pfp_seqs *tab;
+  const uint8_t *pat; const uint64_t *off; uint64_t k, *oo, *sp, *ep;
+  uint64_t maxocc, min_len, seed;
+  int thresholds, locate, kmis, kedit;
+} batch_t;
+
+static int fail(const char *what, int rc, pfp_ctx *ctx) {
+  fprintf(stderr, "%s: %s: %s\n", what, pfp_strerror(rc), pfp_last_error(ctx));
+  return 1;
+}
+
+/* the space between the items of a line: before every item j but the line's first */
+static void sep(uint64_t j, uint64_t first) { if (j > first) putchar(' '); }
+
+/* Every mode answers one batch, a line per pattern: 0, or 1 after the error went to stderr. */
+static int mode_ms(const batch_t *b) {
+  const uint64_t total = b->off[b->k];
+  uint32_t *len = malloc((total + 1) * sizeof(uint32_t));
+  uint64_t *pos = malloc((total + 1) * sizeof(uint64_t));
+  int rc = 1;
+  if (!len || !pos) fprintf(stderr, "out of memory\n");
+  else if ((rc = (b->thresholds ? pfp_fm_ms_thr : pfp_fm_ms)(b->fm, b->pat, b->off, b->k, len, pos)) != 0) rc = fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; !rc && i < b->k; i++) {
+    for (uint64_t j = b->off[i]; j < b->off[i + 1]; j++) {
+      sep(j, b->off[i]);
+      if (len[j]) printf("%" PRIu32 ":%" PRIu64, len[j], pos[j]);
+      else fputs("0:-", stdout);
+    }
+    putchar('\n');
+  }
+  free(len); free(pos);
+  return rc;
+}
+
+static int mode_mems(const batch_t *b) {
+  uint64_t *m = NULL, *oo = b->oo;
+  const int rc = (b->thresholds ? pfp_fm_mems_thr : pfp_fm_mems)(b->fm, b->pat, b->off, b->k, b->min_len, oo, &m);
+  if (rc) return fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; i < b->k; i++) {
+    printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);
+    for (uint64_t j = oo[i]; j < oo[i + 1]; j++) { sep(j, oo[i]); printf("%" PRIu64 ":%" PRIu64 ":%" PRIu64, m[3 * j], m[3 * j + 1], m[3 * j + 2]); }
+    putchar('\n');
+  }
+  pfp_free(m);
+  return 0;
+}
+
+static int mode_align(const batch_t *b) {
+  uint64_t *as = NULL, *ae = NULL, *oo = b->oo;
+  uint8_t *ad = NULL;
+  const int rc = pfp_fm_align(b->fm, b->pat, b->off, b->k, b->seed, b->kedit, 0, b->thresholds, oo, &as, &ae, &ad);
+  if (rc) return fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; i < b->k; i++) {
+    const uint64_t cnt = oo[i + 1] - oo[i], shown = b->maxocc && b->maxocc < cnt ? b->maxocc : cnt;
+    printf("%" PRIu64 "\t", cnt);
+    for (uint64_t j = oo[i]; j < oo[i] + shown; j++) { sep(j, oo[i]); printf("%" PRIu64 ":%" PRIu64 ":%u", as[j], ae[j], (unsigned)ad[j]); }
+    putchar('\n');
+  }
+  pfp_free(as); pfp_free(ae); pfp_free(ad);
+  return 0;
+}
+
+/* -l, -l --seqs and --docs after their call: the lines count<TAB>[name:]value ..., count = ep - sp (rows) or the number of items,
+ * the names by id (NULL: values alone); the arrays go back */
+static int item_lines(const batch_t *b, int rc, int rows, uint32_t *id, uint64_t *val) {
+  const uint64_t *oo = b->oo;
+  if (rc) return fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; i < b->k; i++) {
+    printf("%" PRIu64 "\t", rows ? b->ep[i] - b->sp[i] : oo[i + 1] - oo[i]);
+    for (uint64_t j = oo[i]; j < oo[i + 1]; j++) { sep(j, oo[i]); if (id) printf("%s:", b->tab->name[id[j]]); printf("%" PRIu64, val[j]); }
+    putchar('\n');
+  }
+  pfp_free(id); pfp_free(val);
+  return 0;
+}
+static int mode_docs(const batch_t *b) {
+  uint32_t *doc = NULL;
+  uint64_t *cnt = NULL;
+  const int rc = pfp_fm_doclist(b->fm, b->pat, b->off, b->k, b->oo, &doc, &cnt);
+  return item_lines(b, rc, 0, doc, cnt);
+}
+static int mode_locate_seqs(const batch_t *b) {
+  uint32_t *sq = NULL;
+  uint64_t *so = NULL;
+  const int rc = pfp_fm_locate_seqs(b->fm, b->pat, b->off, b->k, b->maxocc, b->sp, b->ep, b->oo, &sq, &so);
+  return item_lines(b, rc, 1, sq, so);
+}
+static int mode_locate(const batch_t *b) {
+  uint64_t *pos = NULL;
+  const int rc = pfp_fm_locate(b->fm, b->pat, b->off, b->k, b->maxocc, b->sp, b->ep, b->oo, &pos);
+  return item_lines(b, rc, 1, NULL, pos);
+}
+
+/* -k K, and its -l form */
+static int mode_approx(const batch_t *b) {
+  uint64_t *hsp = NULL, *hep = NULL, *pos = NULL, *oo = b->oo, *po = b->sp;      /* (po: the positions' offsets) */
+  uint8_t *hd = NULL, *pd = NULL;
+  int rc = pfp_fm_approx(b->fm, b->pat, b->off, b->k, b->kmis, oo, &hsp, &hep, NULL, &hd);
+  if (!rc && b->locate) rc = pfp_fm_approx_locate(b->fm, b->pat, b->off, b->k, b->kmis, b->maxocc, po, &pos, &pd);
+  if (rc) rc = fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; !rc && i < b->k; i++) {
+    uint64_t by[PFP_FM_APPROX_MAX_K + 1] = {0}, total = 0;
+    for (uint64_t j = oo[i]; j < oo[i + 1]; j++) {
+      total += hep[j] - hsp[j];
+      if (hd[j] <= PFP_FM_APPROX_MAX_K) by[hd[j]] += hep[j] - hsp[j];
+    }
+    printf("%" PRIu64 "\t", total);
+    if (b->locate) for (uint64_t j = po[i]; j < po[i + 1]; j++) { sep(j, po[i]); printf("%" PRIu64 ":%u", pos[j], (unsigned)pd[j]); }
+    else for (int d = 0; d <= b->kmis; d++) { sep(d, 0); printf("%" PRIu64, by[d]); }
+    putchar('\n');
+  }
+  pfp_free(hsp); pfp_free(hep); pfp_free(hd); pfp_free(pos); pfp_free(pd);
+  return rc;
+}
+
+static int mode_count(const batch_t *b) {
+  const int rc = pfp_fm_count(b->fm, b->pat, b->off, b->k, b->sp, b->ep, NULL);
+  if (rc) return fail(b->base, rc, b->ctx);
+  for (uint64_t i = 0; i < b->k; i++) printf("%" PRIu64 "\n", b->ep[i] - b->sp[i]);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0;
   const char *seqsfile = NULL;
@@ -174,24 +298,25 @@ int main(int argc, char **argv) {
       default: usage(argv[0]); return 2;
     }
   }
-  if (optind + 2 != argc) { usage(argv[0]); return 2; }
-  if (ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) || ((textfile || thresholds) && !ms && !mems && !align) ||
-      ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) || (align && (locate || approx || ms || mems || docs || seqs)) ||
-      (have_seed && !align)) {
+  if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
+      ((textfile || thresholds) && !ms && !mems && !align) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
+      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align)) {
     usage(argv[0]);
     return 2;
   }
   const char *patfile = argv[optind], *base = argv[optind + 1];
-
-  uint8_t *pats = NULL;
-  uint64_t plen = 0;
-  if (read_file(patfile, &pats, &plen)) { perror(patfile); return 1; }
+  /* (everything `done` releases, before the first jump there) */
+  uint8_t *pats = NULL, *buf = NULL, *big = NULL;
+  uint64_t plen = 0, npat = 0, *lstart = NULL, *off = NULL, *oo = NULL, *sp = NULL, *ep = NULL;
+  pfp_ctx *ctx = NULL;
+  pfp_fm *fm = NULL;
+  int rc = 1;
+  if (read_file(patfile, &pats, &plen)) { perror(patfile); goto done; }
   /* npat lines; line k = [lstart[k], lstart[k + 1] - 1) */
-  uint64_t npat = 0;
   for (uint64_t i = 0; i < plen; i++) npat += pats[i] == '\n';
   if (plen && pats[plen - 1] != '\n') npat++;
-  uint64_t *lstart = malloc((npat + 1) * sizeof(uint64_t));
-  if (!lstart) { fprintf(stderr, "out of memory\n"); free(pats); return 1; }
+  lstart = malloc((npat + 1) * sizeof(uint64_t));
+  if (!lstart) { fprintf(stderr, "out of memory\n"); goto done; }
   {
     uint64_t k = 0, s = 0;
     for (uint64_t i = 0; i < plen; i++)
@@ -201,14 +326,8 @@ int main(int argc, char **argv) {
     lstart[npat] = plen && pats[plen - 1] == '\n' ? plen : plen + 1;
   }
 
-  pfp_ctx *ctx = NULL;
-  int rc = pfp_ctx_create(&ctx, device);
-  if (rc) {
-    fprintf(stderr, "Cannot initialise the GPU (%s): this tool has no CPU path\n", pfp_strerror(rc));
-    free(pats); free(lstart);
-    return 1;
-  }
-  pfp_fm *fm = NULL;
+  rc = pfp_ctx_create(&ctx, device);
+  if (rc) { fprintf(stderr, "Cannot initialise the GPU (%s): this tool has no CPU path\n", pfp_strerror(rc)); rc = 1; goto done; }
   if (ms || mems || align) {
     int fd = -1;
     uint64_t n = 0;
@@ -218,9 +337,7 @@ int main(int argc, char **argv) {
       if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
         perror(textfile);
         if (fd >= 0) close(fd);
-        pfp_ctx_destroy(ctx);
-        free(pats); free(lstart);
-        return 1;
+        rc = 1; goto done;
       }
       n = (uint64_t)sb.st_size;
     }
@@ -231,48 +348,33 @@ int main(int argc, char **argv) {
       char thrname[4096];
       snprintf(thrname, sizeof thrname, "%s.thr_pos", base);
       rc = access(thrname, R_OK) == 0 ? pfp_fm_thresholds_files(fm, base) : pfp_fm_thresholds_dev(fm, NULL, 0);
-      if (rc) { pfp_fm_free(fm); fm = NULL; }
     }
   } else {
     rc = pfp_fm_build_files(ctx, base, locate || docs ? (PFP_FLAG_SSA | PFP_FLAG_ESA) : 0, &fm);
   }
-  if (rc) {
-    fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
-    pfp_ctx_destroy(ctx);
-    free(pats); free(lstart);
-    return 1;
-  }
+  if (rc) { rc = fail(base, rc, ctx); goto done; }
 
   if (seqs) {
     char name[4096 + 8], err[1024];
     pfp_fm_info_t inf;
     if (!seqsfile) { snprintf(name, sizeof name, "%s.seqs", base); seqsfile = name; }
     pfp_fm_info(fm, &inf);
-    if (pfp_seqs_read(seqsfile, inf.n, &tab, err, sizeof err)) {
-      fprintf(stderr, "%s\n", err);
-      rc = 1;
-    } else if ((rc = pfp_fm_set_seqs(fm, tab.start, tab.nseq)) != 0) {
-      fprintf(stderr, "%s: %s: %s\n", seqsfile, pfp_strerror(rc), pfp_last_error(ctx));
-    }
-    if (rc) {
-      pfp_seqs_free(&tab);
-      pfp_fm_free(fm);
-      pfp_ctx_destroy(ctx);
-      free(pats); free(lstart);
-      return 1;
-    }
+    if (pfp_seqs_read(seqsfile, inf.n, &tab, err, sizeof err)) { fprintf(stderr, "%s\n", err); rc = 1; goto done; }
+    if ((rc = pfp_fm_set_seqs(fm, tab.start, tab.nseq)) != 0) { rc = fail(seqsfile, rc, ctx); goto done; }
   }
 
   uint64_t batch = 1 << 20;
   const char *env = getenv("PFP_FM_BATCH");
   if (env && strtoull(env, NULL, 10) > 0) batch = strtoull(env, NULL, 10);
   const uint64_t max_bytes = 64ull << 20, mult = rcomp ? 2 : 1;      /* --rc: every line gives two patterns */
-  uint64_t *off = malloc((mult * batch + 1) * sizeof(uint64_t)), *oo = malloc((mult * batch + 1) * sizeof(uint64_t));
-  uint64_t *sp = malloc((mult * batch + 1) * sizeof(uint64_t)), *ep = malloc(mult * batch * sizeof(uint64_t));
-  uint8_t *buf = malloc(mult * max_bytes + 1), *big = NULL;
+  off = malloc((mult * batch + 1) * sizeof(uint64_t)), oo = malloc((mult * batch + 1) * sizeof(uint64_t));
+  sp = malloc((mult * batch + 1) * sizeof(uint64_t)), ep = malloc(mult * batch * sizeof(uint64_t));
+  buf = malloc(mult * max_bytes + 1);
   if (!off || !oo || !sp || !ep || !buf) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
   static char obuf[1 << 20];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+  int (*const mode)(const batch_t *) = ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
+                                     : locate && seqs ? mode_locate_seqs : locate ? mode_locate : mode_count;
   for (uint64_t p0 = 0; p0 < npat;) {
     /* a batch: at most `batch` patterns and max_bytes bytes (a single longer line goes alone, from the file buffer) */
     uint64_t k = 0, bytes = 0;
@@ -282,8 +384,7 @@ int main(int argc, char **argv) {
       bytes += len;
       k++;
     }
-    const uint8_t *src = pats + lstart[p0];
-    const uint8_t *pat = src;
+    const uint8_t *pat = pats + lstart[p0];
     const uint64_t lines = k;
     if (bytes <= max_bytes || rcomp) {
       /* the lines without their '\n' (--rc: each followed by its reverse complement) */
@@ -310,109 +411,8 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    if (ms) {
-      const uint64_t total = off[k];
-      uint32_t *len = malloc((total + 1) * sizeof(uint32_t));
-      uint64_t *pos = malloc((total + 1) * sizeof(uint64_t));
-      if (!len || !pos) { fprintf(stderr, "out of memory\n"); free(len); free(pos); rc = 1; goto done; }
-      rc = thresholds ? pfp_fm_ms_thr(fm, pat, off, k, len, pos) : pfp_fm_ms(fm, pat, off, k, len, pos);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); free(len); free(pos); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        for (uint64_t j = off[i]; j < off[i + 1]; j++) {
-          if (j > off[i]) putchar(' ');
-          if (len[j]) printf("%" PRIu32 ":%" PRIu64, len[j], pos[j]);
-          else fputs("0:-", stdout);
-        }
-        putchar('\n');
-      }
-      free(len); free(pos);
-    } else if (mems) {
-      uint64_t *m = NULL;
-      rc = thresholds ? pfp_fm_mems_thr(fm, pat, off, k, min_len, oo, &m) : pfp_fm_mems(fm, pat, off, k, min_len, oo, &m);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);
-        for (uint64_t j = oo[i]; j < oo[i + 1]; j++)
-          printf(j > oo[i] ? " %" PRIu64 ":%" PRIu64 ":%" PRIu64 : "%" PRIu64 ":%" PRIu64 ":%" PRIu64, m[3 * j], m[3 * j + 1], m[3 * j + 2]);
-        putchar('\n');
-      }
-      pfp_free(m);
-    } else if (align) {
-      uint64_t *as = NULL, *ae = NULL;
-      uint8_t *ad = NULL;
-      rc = pfp_fm_align(fm, pat, off, k, seed, kedit, 0, thresholds, oo, &as, &ae, &ad);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        const uint64_t cnt = oo[i + 1] - oo[i], shown = maxocc && maxocc < cnt ? maxocc : cnt;
-        printf("%" PRIu64 "\t", cnt);
-        for (uint64_t j = oo[i]; j < oo[i] + shown; j++)
-          printf(j > oo[i] ? " %" PRIu64 ":%" PRIu64 ":%u" : "%" PRIu64 ":%" PRIu64 ":%u", as[j], ae[j], (unsigned)ad[j]);
-        putchar('\n');
-      }
-      pfp_free(as); pfp_free(ae); pfp_free(ad);
-    } else if (docs) {
-      uint32_t *doc = NULL;
-      uint64_t *cnt = NULL;
-      rc = pfp_fm_doclist(fm, pat, off, k, oo, &doc, &cnt);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        printf("%" PRIu64 "\t", oo[i + 1] - oo[i]);
-        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %s:%" PRIu64 : "%s:%" PRIu64, tab.name[doc[j]], cnt[j]);
-        putchar('\n');
-      }
-      pfp_free(doc); pfp_free(cnt);
-    } else if (approx) {
-      uint64_t *hsp = NULL, *hep = NULL, *pos = NULL;
-      uint8_t *hd = NULL, *pd = NULL;
-      rc = pfp_fm_approx(fm, pat, off, k, kmis, oo, &hsp, &hep, NULL, &hd);
-      if (!rc && locate) rc = pfp_fm_approx_locate(fm, pat, off, k, kmis, maxocc, sp, &pos, &pd);      /* (sp: the positions' offsets) */
-      if (rc) {
-        fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx));
-        pfp_free(hsp); pfp_free(hep); pfp_free(hd);
-        rc = 1;
-        goto done;
-      }
-      for (uint64_t i = 0; i < k; i++) {
-        uint64_t by[PFP_FM_APPROX_MAX_K + 1] = {0}, total = 0;
-        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) {
-          total += hep[j] - hsp[j];
-          if (hd[j] <= PFP_FM_APPROX_MAX_K) by[hd[j]] += hep[j] - hsp[j];
-        }
-        printf("%" PRIu64 "\t", total);
-        if (locate) {
-          for (uint64_t j = sp[i]; j < sp[i + 1]; j++) printf(j > sp[i] ? " %" PRIu64 ":%u" : "%" PRIu64 ":%u", pos[j], (unsigned)pd[j]);
-        } else {
-          for (int d = 0; d <= kmis; d++) printf(d ? " %" PRIu64 : "%" PRIu64, by[d]);
-        }
-        putchar('\n');
-      }
-      pfp_free(hsp); pfp_free(hep); pfp_free(hd); pfp_free(pos); pfp_free(pd);
-    } else if (locate && seqs) {
-      uint32_t *sq = NULL;
-      uint64_t *so = NULL;
-      rc = pfp_fm_locate_seqs(fm, pat, off, k, maxocc, sp, ep, oo, &sq, &so);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        printf("%" PRIu64 "\t", ep[i] - sp[i]);
-        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %s:%" PRIu64 : "%s:%" PRIu64, tab.name[sq[j]], so[j]);
-        putchar('\n');
-      }
-      pfp_free(sq); pfp_free(so);
-    } else if (locate) {
-      uint64_t *pos = NULL;
-      rc = pfp_fm_locate(fm, pat, off, k, maxocc, sp, ep, oo, &pos);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) {
-        printf("%" PRIu64 "\t", ep[i] - sp[i]);
-        for (uint64_t j = oo[i]; j < oo[i + 1]; j++) printf(j > oo[i] ? " %" PRIu64 : "%" PRIu64, pos[j]);
-        putchar('\n');
-      }
-      pfp_free(pos);
-    } else {
-      rc = pfp_fm_count(fm, pat, off, k, sp, ep, NULL);
-      if (rc) { fprintf(stderr, "%s: %s: %s\n", base, pfp_strerror(rc), pfp_last_error(ctx)); rc = 1; goto done; }
-      for (uint64_t i = 0; i < k; i++) printf("%" PRIu64 "\n", ep[i] - sp[i]);
-    }
+    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit};
+    if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }
   rc = 0;

@@ -111,6 +111,11 @@ def _patterns(patterns):
     return np.frombuffer(b"".join(parts) + b"\0", dtype=np.uint8), off
 
 
+def _vp(x):
+    """a device address as an argument; None (NULL) for an array that is not given"""
+    return C.c_void_p(x) if x else None
+
+
 class FmIndex:
     """Count and locate over a BWT and its run samples (pfp_fm, csrc/fmsearch.hip; the r-index of Gagie, Navarro and Prezza).
     Made by Context.fm_index / fm_index_files; holds device memory of its context until close()."""
@@ -136,6 +141,19 @@ class FmIndex:
         except Exception:
             pass
 
+    @staticmethod
+    def _host_patterns(patterns):
+        """-> (npat, the npat+1 offsets, the three leading arguments of a call over host patterns)"""
+        pat, off = _patterns(patterns)
+        npat = len(off) - 1
+        return npat, off, (_ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat))
+
+    def _take_free(self, ptr, n, dtype):
+        """a copy of the n entries of a result array of the library, which goes back to it (pfp_free takes NULL)"""
+        out = _take(ptr, n, dtype)
+        self.lib.pfp_free(ptr)
+        return out
+
     def info(self):
         r = _FmInfo()
         self.ctx._check(self.lib.pfp_fm_info(self._h, C.byref(r)))
@@ -143,77 +161,55 @@ class FmIndex:
 
     def count(self, patterns, toehold=False):
         """-> (sp, ep) uint64 arrays, the row range [sp, ep) of each pattern; toehold=True: (sp, ep, SA[sp]) (needs samples)"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        npat, _, args = self._host_patterns(patterns)
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         first = np.zeros(npat, dtype=np.uint64) if toehold else None
         u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_count(self._h, _ptr(pat, C.c_uint8), u64(off), C.c_uint64(npat), u64(sp), u64(ep),
-                                              u64(first) if toehold else None))
+        self.ctx._check(self.lib.pfp_fm_count(self._h, *args, u64(sp), u64(ep), u64(first) if toehold else None))
         return (sp, ep, first) if toehold else (sp, ep)
 
     def locate(self, patterns, max_occ=0, ranges=False):
         """-> (offsets, positions): pattern p's positions, in row order, are positions[offsets[p]:offsets[p+1]], at most max_occ
         of them (0: all); ranges=True: (offsets, positions, sp, ep)"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        npat, _, args = self._host_patterns(patterns)
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         pos = C.POINTER(C.c_uint64)()
         u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_locate(self._h, _ptr(pat, C.c_uint8), u64(off), C.c_uint64(npat), C.c_uint64(max_occ), u64(sp),
-                                               u64(ep), u64(out_off), C.byref(pos)))
-        total = int(out_off[-1])
-        positions = np.zeros(0, dtype=np.uint64)
-        if total and pos:
-            positions = np.ctypeslib.as_array(pos, shape=(total,)).copy()
-            self.lib.pfp_free(pos)
+        self.ctx._check(self.lib.pfp_fm_locate(self._h, *args, C.c_uint64(max_occ), u64(sp), u64(ep), u64(out_off), C.byref(pos)))
+        positions = self._take_free(pos, out_off[-1], np.uint64)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
 
     def approx(self, patterns, k, toehold=False):
         """the hits of every pattern with at most k substitutions (pfpgpu.h, "Approximate search"; k in 0..FM_APPROX_MAX_K)
         -> (hit_off, sp, ep, dist): pattern p's hits, by increasing sp, are the row ranges [sp[i], ep[i]) with dist[i] (uint8)
         mismatches for i in hit_off[p]:hit_off[p+1]; toehold=True: (hit_off, sp, ep, dist, SA[sp]) (needs samples)"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        npat, _, args = self._host_patterns(patterns)
         hit_off = np.zeros(npat + 1, dtype=np.uint64)
         sp, ep, first = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
         dist = C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_approx(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_int(k),
-                                               _ptr(hit_off, C.c_uint64), C.byref(sp), C.byref(ep), C.byref(first) if toehold else None,
-                                               C.byref(dist)))
-        total = int(hit_off[-1])
-        out = [hit_off, _take(sp, total, np.uint64), _take(ep, total, np.uint64), _take(dist, total, np.uint8)]
-        if toehold:
-            out.append(_take(first, total, np.uint64))
-        for q in (sp, ep, first, dist):
-            if q:
-                self.lib.pfp_free(q)
-        return tuple(out)
+        self.ctx._check(self.lib.pfp_fm_approx(self._h, *args, C.c_int(k), _ptr(hit_off, C.c_uint64), C.byref(sp), C.byref(ep),
+                                               C.byref(first) if toehold else None, C.byref(dist)))
+        total = hit_off[-1]
+        out = hit_off, self._take_free(sp, total, np.uint64), self._take_free(ep, total, np.uint64), self._take_free(dist, total, np.uint8)
+        return out + (self._take_free(first, total, np.uint64),) if toehold else out
 
     def approx_locate(self, patterns, k, max_occ=0):
         """-> (off, pos, dist): the positions of pattern p's occurrences with at most k substitutions are pos[off[p]:off[p+1]],
         hits by increasing sp and rows in row order inside a hit, each with its number of mismatches in dist (uint8); at most
         max_occ per pattern (0: all).  Needs samples."""
-        pat, poff = _patterns(patterns)
-        npat = len(poff) - 1
+        npat, _, args = self._host_patterns(patterns)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         pos, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_approx_locate(self._h, _ptr(pat, C.c_uint8), _ptr(poff, C.c_uint64), C.c_uint64(npat), C.c_int(k),
-                                                      C.c_uint64(max_occ), _ptr(out_off, C.c_uint64), C.byref(pos), C.byref(dist)))
-        total = int(out_off[-1])
-        res = out_off, _take(pos, total, np.uint64), _take(dist, total, np.uint8)
-        for q in (pos, dist):
-            if q:
-                self.lib.pfp_free(q)
-        return res
+        self.ctx._check(self.lib.pfp_fm_approx_locate(self._h, *args, C.c_int(k), C.c_uint64(max_occ), _ptr(out_off, C.c_uint64),
+                                                      C.byref(pos), C.byref(dist)))
+        return out_off, self._take_free(pos, out_off[-1], np.uint64), self._take_free(dist, out_off[-1], np.uint8)
 
     def approx_dev(self, d_pat, d_pat_off, npat, k, d_hit_off, d_sp=None, d_ep=None, d_dist=None, d_first=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_hit_off; d_sp / d_ep (uint64) and d_dist
         (uint8), room for d_hit_off[npat] each, get the hits (all three None: offsets only), d_first their toeholds"""
-        vp = lambda x: C.c_void_p(x) if x else None
         self.ctx._check(self.lib.pfp_fm_approx_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_int(k),
-                                                   C.c_void_p(d_hit_off), vp(d_sp), vp(d_ep), vp(d_first), vp(d_dist)))
+                                                   C.c_void_p(d_hit_off), _vp(d_sp), _vp(d_ep), _vp(d_first), _vp(d_dist)))
 
     def approx_stats(self):
         """{launches, pairs, hits} of the approximate searches since the last look; pairs (LF pairs of the walks) are collected
@@ -227,17 +223,15 @@ class FmIndex:
         0..FM_EXTEND_MAX_K, an index with text).  Candidate i is pattern cand_pat[i] with pattern byte 0 at text position
         cand_diag[i] (signed) -> (dist, start, end): dist[i] (uint8) edits align the pattern to T[start[i]:end[i]); 0xFF and
         2^64 - 1 twice where nothing within k edits lies in the window"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        _, _, args = self._host_patterns(patterns)
         cp = np.ascontiguousarray(cand_pat, dtype=np.uint32)
         cd = np.ascontiguousarray(cand_diag, dtype=np.int64)
         if cp.shape != cd.shape or cp.ndim != 1:
             raise ValueError("cand_pat and cand_diag: two 1-D arrays of one length")
         nc = len(cp)
         dist, start, end = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
-        self.ctx._check(self.lib.pfp_fm_extend(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(cp, C.c_uint32),
-                                               _ptr(cd, C.c_int64), C.c_uint64(nc), C.c_int(k), _ptr(dist, C.c_uint8),
-                                               _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
+        self.ctx._check(self.lib.pfp_fm_extend(self._h, *args, _ptr(cp, C.c_uint32), _ptr(cd, C.c_int64), C.c_uint64(nc), C.c_int(k),
+                                               _ptr(dist, C.c_uint8), _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
         return dist, start, end
 
     def extend_dev(self, d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end):
@@ -252,27 +246,21 @@ class FmIndex:
         extended along its diagonal with at most k edits -> (aln_off, start, end, dist): pattern p's distinct alignments are
         T[start[i]:end[i]) with dist[i] (uint8) edits for i in aln_off[p]:aln_off[p+1], ordered by (dist, start, end), at most
         max_aln of them (0: all).  A heuristic: a MEM carries one position of its string"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        npat, _, args = self._host_patterns(patterns)
         aln_off = np.zeros(npat + 1, dtype=np.uint64)
         start, end, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_align(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_seed),
-                                              C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), _ptr(aln_off, C.c_uint64),
-                                              C.byref(start), C.byref(end), C.byref(dist)))
-        total = int(aln_off[-1])
-        res = aln_off, _take(start, total, np.uint64), _take(end, total, np.uint64), _take(dist, total, np.uint8)
-        for q in (start, end, dist):
-            if q:
-                self.lib.pfp_free(q)
-        return res
+        self.ctx._check(self.lib.pfp_fm_align(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_uint64(max_aln),
+                                              C.c_int(1 if thresholds else 0), _ptr(aln_off, C.c_uint64), C.byref(start), C.byref(end),
+                                              C.byref(dist)))
+        total = aln_off[-1]
+        return aln_off, self._take_free(start, total, np.uint64), self._take_free(end, total, np.uint64), self._take_free(dist, total, np.uint8)
 
     def align_dev(self, d_pat, d_pat_off, npat, k, min_seed, d_aln_off, d_start=None, d_end=None, d_dist=None, max_aln=0, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_aln_off; d_start / d_end (uint64) and d_dist
         (uint8), room for d_aln_off[npat] each, get the alignments (all three None: offsets only)"""
-        vp = lambda x: C.c_void_p(x) if x else None
         self.ctx._check(self.lib.pfp_fm_align_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
                                                   C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), C.c_void_p(d_aln_off),
-                                                  vp(d_start), vp(d_end), vp(d_dist)))
+                                                  _vp(d_start), _vp(d_end), _vp(d_dist)))
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the
@@ -302,53 +290,41 @@ class FmIndex:
     def locate_seqs(self, patterns, max_occ=0, ranges=False):
         """-> (off, seq, offset): the hits of pattern p that lie inside one sequence, among the at most max_occ rows locate() would
         list (0: all), in row order, are (seq[i], offset[i]) for i in off[p]:off[p+1]; ranges=True: (off, seq, offset, sp, ep)"""
-        pat, poff = _patterns(patterns)
-        npat = len(poff) - 1
+        npat, _, args = self._host_patterns(patterns)
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         seq, off = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
         u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_locate_seqs(self._h, _ptr(pat, C.c_uint8), u64(poff), C.c_uint64(npat), C.c_uint64(max_occ), u64(sp),
-                                                    u64(ep), u64(out_off), C.byref(seq), C.byref(off)))
-        total = int(out_off[-1])
-        seqs, offs = _take(seq, total, np.uint32), _take(off, total, np.uint64)
-        self.lib.pfp_free(seq)
-        self.lib.pfp_free(off)
+        self.ctx._check(self.lib.pfp_fm_locate_seqs(self._h, *args, C.c_uint64(max_occ), u64(sp), u64(ep), u64(out_off), C.byref(seq),
+                                                    C.byref(off)))
+        seqs, offs = self._take_free(seq, out_off[-1], np.uint32), self._take_free(off, out_off[-1], np.uint64)
         return (out_off, seqs, offs, sp, ep) if ranges else (out_off, seqs, offs)
 
     def doclist(self, patterns):
         """-> (off, doc, cnt): the distinct sequences that hold a hit of pattern p inside one sequence are doc[off[p]:off[p+1]]
         (uint32, ascending) and cnt (uint64) their numbers of such hits; every occurrence counts"""
-        pat, poff = _patterns(patterns)
-        npat = len(poff) - 1
+        npat, _, args = self._host_patterns(patterns)
         doc_off = np.zeros(npat + 1, dtype=np.uint64)
         doc, cnt = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
-        self.ctx._check(self.lib.pfp_fm_doclist(self._h, _ptr(pat, C.c_uint8), _ptr(poff, C.c_uint64), C.c_uint64(npat),
-                                                _ptr(doc_off, C.c_uint64), C.byref(doc), C.byref(cnt)))
-        total = int(doc_off[-1])
-        docs, cnts = _take(doc, total, np.uint32), _take(cnt, total, np.uint64)
-        self.lib.pfp_free(doc)
-        self.lib.pfp_free(cnt)
-        return doc_off, docs, cnts
+        self.ctx._check(self.lib.pfp_fm_doclist(self._h, *args, _ptr(doc_off, C.c_uint64), C.byref(doc), C.byref(cnt)))
+        return doc_off, self._take_free(doc, doc_off[-1], np.uint32), self._take_free(cnt, doc_off[-1], np.uint64)
 
     def seqmap_dev(self, d_pos, count, d_seq=None, d_off=None):
         """device pointers: count uint64 positions -> uint32 d_seq / uint64 d_off (either may be None)"""
-        self.ctx._check(self.lib.pfp_fm_seqmap_dev(self._h, C.c_void_p(d_pos), C.c_uint64(count), C.c_void_p(d_seq) if d_seq else None,
-                                                   C.c_void_p(d_off) if d_off else None))
+        self.ctx._check(self.lib.pfp_fm_seqmap_dev(self._h, C.c_void_p(d_pos), C.c_uint64(count), _vp(d_seq), _vp(d_off)))
 
     def locate_seqs_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq=None, d_off=None):
         """device pointers from count_dev -> npat+1 offsets of the kept hits; d_seq (uint32) / d_off (uint64), each with room for
         what locate_dev's offsets-only call reports, get them (both None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_locate_seqs_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
-                                                        C.c_void_p(d_first) if d_first else None, C.c_uint64(max_occ), C.c_void_p(d_out_off),
-                                                        C.c_void_p(d_seq) if d_seq else None, C.c_void_p(d_off) if d_off else None))
+        self.ctx._check(self.lib.pfp_fm_locate_seqs_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp),
+                                                        C.c_void_p(d_ep), _vp(d_first), C.c_uint64(max_occ), C.c_void_p(d_out_off),
+                                                        _vp(d_seq), _vp(d_off)))
 
     def doclist_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, d_doc=None, d_cnt=None):
         """device pointers from count_dev -> npat+1 offsets of the documents; d_doc (uint32) / d_cnt (uint64), room for
         offsets[npat] each, get them (both None: offsets only)"""
         self.ctx._check(self.lib.pfp_fm_doclist_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
-                                                    C.c_void_p(d_first) if d_first else None, C.c_void_p(d_doc_off),
-                                                    C.c_void_p(d_doc) if d_doc else None, C.c_void_p(d_cnt) if d_cnt else None))
+                                                    _vp(d_first), C.c_void_p(d_doc_off), _vp(d_doc), _vp(d_cnt)))
 
     def add_thresholds(self, thr=None):
         """give the index its thresholds (pfpgpu.h, "The LCP array and thresholds"): thr=None computes them on the GPU, else the
@@ -377,32 +353,23 @@ class FmIndex:
         patterns[p][i:] that occurs in the text and pos[off[p] + i] (uint64) one place where it occurs (2**64 - 1 where the
         length is 0).  Needs an index with text (Context.fm_index_ms*).  thresholds=True: the two passes with thresholds
         (add_thresholds first): the same len, pos by their own rule."""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        _, off, args = self._host_patterns(patterns)
         total = int(off[-1])
         ln, pos = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint64)
         call = self.lib.pfp_fm_ms_thr if thresholds else self.lib.pfp_fm_ms
-        self.ctx._check(call(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), _ptr(ln, C.c_uint32),
-                             _ptr(pos, C.c_uint64)))
+        self.ctx._check(call(self._h, *args, _ptr(ln, C.c_uint32), _ptr(pos, C.c_uint64)))
         return off, ln, pos
 
     def mems(self, patterns, min_len=1, thresholds=False):
         """-> (mem_off, mems): the maximal exact matches of pattern p of at least min_len bytes are the rows
         mems[mem_off[p]:mem_off[p+1]] of a (k, 3) uint64 array, each (i, len, pos), by increasing i; thresholds as in
         matching_statistics"""
-        pat, off = _patterns(patterns)
-        npat = len(off) - 1
+        npat, _, args = self._host_patterns(patterns)
         mem_off = np.zeros(npat + 1, dtype=np.uint64)
         out = C.POINTER(C.c_uint64)()
         call = self.lib.pfp_fm_mems_thr if thresholds else self.lib.pfp_fm_mems
-        self.ctx._check(call(self._h, _ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat), C.c_uint64(min_len),
-                             _ptr(mem_off, C.c_uint64), C.byref(out)))
-        total = int(mem_off[-1])
-        mems = np.zeros((0, 3), dtype=np.uint64)
-        if total and out:
-            mems = np.ctypeslib.as_array(out, shape=(3 * total,)).copy().reshape(total, 3)
-            self.lib.pfp_free(out)
-        return mem_off, mems
+        self.ctx._check(call(self._h, *args, C.c_uint64(min_len), _ptr(mem_off, C.c_uint64), C.byref(out)))
+        return mem_off, self._take_free(out, 3 * int(mem_off[-1]), np.uint64).reshape(-1, 3)
 
     def ms_stats(self):
         """{launches, jumps, matched} of the matching-statistics calls (and add_thresholds) since the last look; jumps (steps
@@ -414,26 +381,23 @@ class FmIndex:
     def matching_statistics_dev(self, d_pat, d_pat_off, npat, d_len, d_pos=None, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> uint32 d_len / uint64 d_pos, entry t for pattern byte d_pat[t]"""
         call = self.lib.pfp_fm_ms_thr_dev if thresholds else self.lib.pfp_fm_ms_dev
-        self.ctx._check(call(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
-                             C.c_void_p(d_pos) if d_pos else None))
+        self.ctx._check(call(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len), _vp(d_pos)))
 
     def mems_dev(self, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem=None):
         """device pointers from matching_statistics_dev -> npat+1 offsets; d_mem (room for 3 * offsets[npat] uint64) gets the
         triples (None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_mems_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len),
-                                                 C.c_void_p(d_pos) if d_pos else None, C.c_uint64(min_len), C.c_void_p(d_mem_off),
-                                                 C.c_void_p(d_mem) if d_mem else None))
+        self.ctx._check(self.lib.pfp_fm_mems_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len), _vp(d_pos),
+                                                 C.c_uint64(min_len), C.c_void_p(d_mem_off), _vp(d_mem)))
 
     def count_dev(self, d_pat, d_pat_off, npat, d_sp, d_ep, d_first=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat uint64 sp / ep (and SA[sp] where d_first is given)"""
         self.ctx._check(self.lib.pfp_fm_count_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp),
-                                                  C.c_void_p(d_ep), C.c_void_p(d_first) if d_first else None))
+                                                  C.c_void_p(d_ep), _vp(d_first)))
 
     def locate_dev(self, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos=None):
         """device pointers from count_dev -> npat+1 offsets; d_pos (room for offsets[npat]) gets the positions (None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_locate_dev(self._h, C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
-                                                   C.c_void_p(d_first) if d_first else None, C.c_uint64(max_occ), C.c_void_p(d_out_off),
-                                                   C.c_void_p(d_pos) if d_pos else None))
+        self.ctx._check(self.lib.pfp_fm_locate_dev(self._h, C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep), _vp(d_first),
+                                                   C.c_uint64(max_occ), C.c_void_p(d_out_off), _vp(d_pos)))
 
 
 class _ParseResult(C.Structure):
