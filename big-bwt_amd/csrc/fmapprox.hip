@@ -24,7 +24,6 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
-#include <cstdlib>
 
 namespace pfp {
 
@@ -48,13 +47,11 @@ __global__ void __launch_bounds__(kTB) fm_approx_k(FmArgs<I> a, const uint8_t *_
                                                    unsigned long long *__restrict__ ctr, int stats) {
   __shared__ uint8_t code[256], sym[256];
   __shared__ ApxFrame stack[kTB / 16][kApxFrames];
-  code[threadIdx.x] = a.codes[threadIdx.x];
-  sym[threadIdx.x] = a.codes[256 + threadIdx.x];
-  __syncthreads();
-  const int gl = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const uint64_t p = BID * (kTB / 16) + g;
-  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
-  const uint64_t o0 = off[p], o1 = off[p + 1], sigma = (uint64_t)a.sigma;
+  sym[threadIdx.x] = a.codes[256 + threadIdx.x];       // (pat_group's barrier covers it)
+  PatGroup pg;
+  if (!pat_group(code, a.codes, off, npat, pg)) return;
+  const int gl = pg.gl, g = threadIdx.x >> 4;
+  const uint64_t p = pg.p, o0 = pg.o0, o1 = pg.o1, sigma = (uint64_t)a.sigma;
   const uint64_t slot0 = o_sp ? hit_off[p] : 0, slot1 = o_sp ? hit_off[p + 1] : 0;
   const bool toehold = o_first != nullptr;
   ApxFrame cur;
@@ -117,16 +114,7 @@ __global__ void __launch_bounds__(kTB) fm_approx_k(FmArgs<I> a, const uint8_t *_
       const uint64_t nsp = lf_at(a, cur.sp, c4, (uint32_t)c, gl), nep = lf_at(a, cur.ep, c4, (uint32_t)c, gl);
       pairs++;
       if (nep > nsp) {
-        uint64_t first = 0;
-        if (toehold) {
-          if (a.bwt[cur.sp] == b) {
-            first = cur.first - 1;
-          } else {
-            const uint64_t j = select_first(a, cur.sp, cur.ep, nsp, c4, (uint32_t)c, gl);
-            const uint64_t q = j < a.n1 ? bit_rank(a.rbits, a.rdir, j) : a.runs;
-            first = q < a.runs ? (uint64_t)a.rs_sa[q] - 1 : ~0ull;
-          }
-        }
+        const uint64_t first = toehold ? toehold_step(a, cur.sp, cur.ep, nsp, cur.first, b, c4, (uint32_t)c, gl) : 0;
         const ApxFrame nf{cur.t - 1, nsp, nep, first, 0};
         if (nf.t == o0) {
           emit(nf, d + child);
@@ -163,14 +151,6 @@ __global__ void __launch_bounds__(kTB) fm_approx_k(FmArgs<I> a, const uint8_t *_
     }
     if (stats) atomicAdd(&ctr[1], (unsigned long long)pairs);
   }
-}
-
-// segment p of the sort = pattern p's hits; val[h] = h
-__global__ void __launch_bounds__(kTB) apx_segs_k(const uint64_t *__restrict__ hit_off, uint64_t npat, uint64_t H, uint32_t *__restrict__ sb,
-                                                  uint32_t *__restrict__ se, uint32_t *__restrict__ val) {
-  const uint64_t i = BID * kTB + threadIdx.x;
-  if (i < npat) { sb[i] = (uint32_t)hit_off[i]; se[i] = (uint32_t)hit_off[i + 1]; }
-  if (i < H) val[i] = (uint32_t)i;
 }
 
 // the hits from walk order to sp order: place[i] = where hit i of the sorted order stood
@@ -214,50 +194,25 @@ __global__ void __launch_bounds__(kTB) apx_pdist_k(uint64_t U, const uint64_t *_
   if (i < U) pdist[i] = dist[last_le(loc_off, H, i)];
 }
 
-// out_off[p] = loc_off[hit_off[p]], p = 0..npat: the positions before pattern p's first hit
-__global__ void __launch_bounds__(kTB) apx_outoff_k(const uint64_t *__restrict__ hit_off, uint64_t npat, uint64_t H, const uint64_t *__restrict__ loc_off,
-                                                    uint64_t *__restrict__ out_off) {
-  const uint64_t p = BID * kTB + threadIdx.x;
-  if (p > npat) return;
-  const uint64_t h = hit_off[p];
-  out_off[p] = loc_off[h < H ? h : H];
-}
-
 struct ApxOut { uint64_t *sp, *ep, *first; uint8_t *dist; };
 
 // the walk of every pattern, launch after launch; fill: the hits go to o at hit_off, else cnt[p] = their number
 template <class I>
 void walk_t(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, const uint64_t *hit_off, uint64_t *cnt, const ApxOut &o) {
   pfp_ctx *c = f.c;
-  uint64_t budget = kMsWork;
-  if (const char *e = getenv("PFP_FM_MS_STEPS")) {      // (tests: a small budget reaches the resume path with small inputs)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < budget) budget = v;
-  }
-  const char *se = getenv("PFP_FM_MS_STATS");           // (measurement: tools/approx_time.py reads the sums through pfp_fm_approx_stats)
-  const int stats = se && *se && *se != '0';
+  const uint64_t budget = budget_from_env(kMsWork);
+  const int stats = stats_from_env();
   const FmArgs<I> a = args_of<I>(f);
   DBuf<ApxRec> rec(c, npat);
   DBuf<uint64_t> ctr(c, 2);
-  for (int first = 1;; first = 0) {                     // every launch finishes at least one iteration of every unfinished pattern
-    ctr.zero();
-    {
-      KScope ks(c, "fm_approx", 0);
-      fm_approx_k<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, pat, pat_off, npat, k, rec.p, first, budget, hit_off, cnt, o.sp, o.ep, o.first,
-                                                                        o.dist, (unsigned long long *)ctr.p, stats);
-      PFP_HIP(hipGetLastError());
-    }
-    uint64_t h[2];
-    d2h(c, h, ctr.p, 2);
-    sync(c);
-    f.apx_stats[0] += 1; f.apx_stats[1] += h[1];
-    if (!h[0]) break;
-  }
+  bounded_launches(c, "fm_approx", ctr, [&](int first, unsigned long long *d_ctr) {
+    fm_approx_k<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, pat, pat_off, npat, k, rec.p, first, budget, hit_off, cnt, o.sp, o.ep, o.first,
+                                                                      o.dist, d_ctr, stats);
+  }, [&](const uint64_t *h) { f.apx_stats[0] += 1; f.apx_stats[1] += h[1]; });
 }
 
 void walk(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, const uint64_t *hit_off, uint64_t *cnt, const ApxOut &o) {
-  if (f.wide) walk_t<uint64_t>(f, pat, pat_off, npat, k, hit_off, cnt, o);
-  else walk_t<uint32_t>(f, pat, pat_off, npat, k, hit_off, cnt, o);
+  by_width(f, [&](auto w) { walk_t<decltype(w)>(f, pat, pat_off, npat, k, hit_off, cnt, o); });
 }
 
 }  // namespace
@@ -265,7 +220,7 @@ void walk(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat
 void fm_approx_check(const FmIndex &f, int k, bool toehold) {
   PFP_REQUIRE(k >= 0 && k <= PFP_FM_APPROX_MAX_K, PFP_EINVAL, "k = " + std::to_string(k) + ": the mismatch budget is 0 .. " +
                                                                    std::to_string(PFP_FM_APPROX_MAX_K) + " (PFP_FM_APPROX_MAX_K)");
-  PFP_REQUIRE(!toehold || f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
+  require_toehold(f, toehold);
 }
 
 void fm_approx_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, int k, uint64_t *cnt) {
@@ -278,8 +233,7 @@ void fm_approx_fill(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
                     uint64_t *sp, uint64_t *ep, uint64_t *first, uint8_t *dist) {
   pfp_ctx *c = f.c;
   fm_approx_check(f, k, first != nullptr);
-  PFP_REQUIRE(H < 0xFFFFFFFFull, PFP_ELIMIT, std::to_string(H) + " hits in one call: the limit is 2^32 - 2 (the segmented sort's bounds are 32 bits; "
-                                                                 "fewer patterns per call)");
+  require_sortable(H, "hits");
   f.apx_stats[2] += H;
   if (!H || !npat) return;
   if (k == 0) {                                         // (at most one hit per pattern: walk order is sp order)
@@ -290,7 +244,7 @@ void fm_approx_fill(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
   DBuf<uint8_t> w_dist(c, H);
   walk(f, pat, pat_off, npat, k, hit_off, nullptr, ApxOut{w_sp.p, w_ep.p, first ? w_first.p : nullptr, w_dist.p});
   DBuf<uint32_t> sb(c, npat), se(c, npat), val(c, H), place(c, H);
-  apx_segs_k<<<gdim(cdiv(std::max(npat, H), kTB)), kTB, 0, c->stream>>>(hit_off, npat, H, sb.p, se.p, val.p);
+  seg_bounds_k<uint32_t><<<gdim(cdiv(std::max(npat, H), kTB)), kTB, 0, c->stream>>>(hit_off, npat, nullptr, sb.p, se.p, nullptr, val.p, H);
   PFP_HIP(hipGetLastError());
   segsort_pairs_u64_u32(c, w_sp.p, sorted.p, val.p, place.p, H, npat, sb.p, se.p, 0, bits_for(f.n1));
   KScope ks(c, "fm_approx_gather", H * (4 + 2 * (first ? 25 : 17)));
@@ -309,15 +263,14 @@ void fm_approx(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t
     exclusive_sum_u64(c, cnt.p, hit_off, npat + 1);
   }
   const uint64_t H = read_scalar(c, hit_off + npat);
-  PFP_REQUIRE(H < 0xFFFFFFFFull, PFP_ELIMIT, std::to_string(H) + " hits in one call: the limit is 2^32 - 2 (the segmented sort's bounds are 32 bits; "
-                                                                 "fewer patterns per call)");
+  require_sortable(H, "hits");
   if (sp) fm_approx_fill(f, pat, pat_off, npat, k, hit_off, H, sp, ep, first, dist);
 }
 
 void fm_approx_clip(FmIndex &f, uint64_t npat, const uint64_t *hit_off, uint64_t H, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
                     uint64_t max_occ, uint64_t *out_off, DBuf<uint64_t> &cep) {
   pfp_ctx *c = f.c;
-  PFP_REQUIRE(f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  require_samples(f);
   cep.alloc(c, H);
   if (!H || !npat) {
     PFP_HIP(hipMemsetAsync(out_off, 0, (npat + 1) * sizeof(uint64_t), c->stream));
@@ -330,7 +283,7 @@ void fm_approx_clip(FmIndex &f, uint64_t npat, const uint64_t *hit_off, uint64_t
   apx_clip_k<<<gdim(cdiv(H, kTB)), kTB, 0, c->stream>>>(H, hit_off, npat, rsum.p, sp, max_occ, cep.p);
   PFP_HIP(hipGetLastError());
   fm_locate(f, H, sp, cep.p, first, 0, loc_off.p, nullptr);
-  apx_outoff_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(hit_off, npat, H, loc_off.p, out_off);
+  gather_off_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(hit_off, npat, loc_off.p, H, out_off);
   PFP_HIP(hipGetLastError());
   sync(c);                                              // (the sums go back when this returns)
 }

@@ -68,12 +68,8 @@ __device__ __forceinline__ bool band_pass(const uint8_t *__restrict__ text, cons
   auto scan = [&](int (&v)[CPL]) {
 #pragma unroll
     for (int q = 1; q < CPL; q++) v[q] = min(v[q], v[q - 1] + 1);
-    int z = v[CPL - 1] - base - (CPL - 1);              // this lane's last cell, as seen from column 0
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const int o = __shfl_up(z, d, 16);
-      if (gl >= d) z = min(z, o);
-    }
+    // the last cells of this lane and those before it, as seen from column 0
+    const int z = gscan16(v[CPL - 1] - base - (CPL - 1), gl, [](int x, int y) { return min(x, y); });
     int carry = __shfl_up(z, 1, 16);                    // the lanes before this one
     carry = gl ? carry + base : (1 << 20);
 #pragma unroll
@@ -209,15 +205,6 @@ __global__ void __launch_bounds__(kTB) aln_cand_k(uint64_t M, const uint64_t *__
   key[j] = mem[3 * j + 2] - mem[3 * j] + kDiagBias;
 }
 
-// segment p of a sort = the entries of pattern p: [at[off[p]], at[off[p + 1]]), or the offsets themselves (at NULL)
-__global__ void __launch_bounds__(kTB) aln_segs_k(const uint64_t *__restrict__ off, uint64_t npat, const uint64_t *__restrict__ at,
-                                                  uint32_t *__restrict__ sb, uint32_t *__restrict__ se) {
-  const uint64_t p = BID * kTB + threadIdx.x;
-  if (p >= npat) return;
-  sb[p] = (uint32_t)(at ? at[off[p]] : off[p]);
-  se[p] = (uint32_t)(at ? at[off[p + 1]] : off[p + 1]);
-}
-
 // flag[j] = entry j of the sorted keys is the first of its value in its pattern, and not `none`; flag[count] = 0
 __global__ void __launch_bounds__(kTB) aln_mark_k(uint64_t count, const uint64_t *__restrict__ key, const uint32_t *__restrict__ cpat, uint64_t none,
                                                   uint64_t *__restrict__ flag) {
@@ -256,7 +243,8 @@ __global__ void __launch_bounds__(kTB) aln_cap_k(uint64_t C, const uint64_t *__r
   if (idx[j] - idx[b < C ? b : C] >= max_aln) flag[j] = 0;
 }
 
-// aln_off[p] = kept entries before pattern p's first, p = 0 .. npat
+// aln_off[p] = kept entries before pattern p's first, p = 0 .. npat.  (Not gather_off_k: the place comes from the sort's 32-bit
+// bounds, which have no entry npat.)
 __global__ void __launch_bounds__(kTB) aln_off_k(uint64_t npat, const uint32_t *__restrict__ sb, uint64_t C, const uint64_t *__restrict__ idx,
                                                  uint64_t *__restrict__ aln_off) {
   const uint64_t p = BID * kTB + threadIdx.x;
@@ -348,8 +336,7 @@ void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
   pfp_ctx *c = f.c;
   fm_extend_check(f, k);
   PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
-  PFP_REQUIRE(M < 0xFFFFFFFFull, PFP_ELIMIT, std::to_string(M) + " seeds in one call: the limit is 2^32 - 2 (the segmented sort's bounds are 32 bits; "
-                                                                 "fewer patterns per call)");
+  require_sortable(M, "seeds");
   out.C = out.total = 0;
   if (!M || !npat) {
     PFP_HIP(hipMemsetAsync(aln_off, 0, (npat + 1) * sizeof(uint64_t), c->stream));
@@ -368,7 +355,7 @@ void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
     aln_cand_k<<<gdim(cdiv(M, kTB)), kTB, 0, c->stream>>>(M, mem_off, npat, mem.p, cpat.p, key.p);
     PFP_HIP(hipGetLastError());
     mem.release();
-    aln_segs_k<<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(mem_off, npat, nullptr, sb.p, se.p);
+    seg_bounds_k<uint32_t><<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(mem_off, npat, nullptr, sb.p, se.p, nullptr, nullptr, 0);
     PFP_HIP(hipGetLastError());
     sort_and_mark(c, key.p, cpat.p, M, npat, sb.p, se.p, bits_for(f.n1 + 2 * kDiagBias), ~0ull, skey, flag, idx);
     C = read_scalar(c, idx.p + M);
@@ -376,7 +363,7 @@ void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
     udiag.alloc(c, C);
     aln_uniq_k<<<gdim(cdiv(M, kTB)), kTB, 0, c->stream>>>(M, flag.p, idx.p, skey.p, cpat.p, C, upat.p, udiag.p);
     PFP_HIP(hipGetLastError());
-    aln_segs_k<<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(mem_off, npat, idx.p, sb.p, se.p);
+    seg_bounds_k<uint32_t><<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(mem_off, npat, idx.p, sb.p, se.p, nullptr, nullptr, 0);
     PFP_HIP(hipGetLastError());
     sync(c);                                            // (the seeds' arrays go back when this block ends)
   }

@@ -32,7 +32,6 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
-#include <cstdlib>
 
 namespace pfp {
 
@@ -143,12 +142,10 @@ template <class I>
 __global__ void __launch_bounds__(kTB) fm_count_k(FmArgs<I> a, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
                                                   uint64_t *__restrict__ sp_out, uint64_t *__restrict__ ep_out, uint64_t *__restrict__ first_out) {
   __shared__ uint8_t code[256];
-  code[threadIdx.x] = a.codes[threadIdx.x];
-  __syncthreads();
-  const int gl = threadIdx.x & 15;
-  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
-  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
-  const uint64_t o0 = off[p], o1 = off[p + 1];
+  PatGroup g;
+  if (!pat_group(code, a.codes, off, npat, g)) return;
+  const int gl = g.gl;
+  const uint64_t p = g.p, o0 = g.o0, o1 = g.o1;
   uint64_t sp = 0, ep = o1 < o0 ? 0 : a.n1, first = a.n1 - 1;      // (decreasing offsets: no pattern, no occurrence)
   for (uint64_t t = o1; t > o0 && sp < ep;) {           // at most m = o1 - o0 steps
     t--;
@@ -156,15 +153,7 @@ __global__ void __launch_bounds__(kTB) fm_count_k(FmArgs<I> a, const uint8_t *__
     if (k == kAbsent) { ep = sp; break; }               // (byte 0 has no code: a pattern holding it has no occurrence)
     const uint32_t c4 = c * 0x01010101u;
     const uint64_t nsp = lf_at(a, sp, c4, k, gl), nep = lf_at(a, ep, c4, k, gl);
-    if (first_out && nep > nsp) {
-      if (a.bwt[sp] == c) {
-        first -= 1;
-      } else {
-        const uint64_t j = select_first(a, sp, ep, nsp, c4, k, gl);
-        const uint64_t q = j < a.n1 ? bit_rank(a.rbits, a.rdir, j) : a.runs;
-        first = q < a.runs ? (uint64_t)a.rs_sa[q] - 1 : ~0ull;
-      }
-    }
+    if (first_out && nep > nsp) first = toehold_step(a, sp, ep, nsp, first, c, c4, k, gl);
     sp = nsp; ep = nep;
   }
   if (ep <= sp) { sp = ep = 0; first = ~0ull; }
@@ -208,13 +197,7 @@ __global__ void __launch_bounds__(kTB) fm_expand(FmArgs<I> a, uint64_t npat, uin
                                                  Seg *__restrict__ seg, uint64_t *__restrict__ maxlen) {
   const uint64_t g = BID * kTB + threadIdx.x;
   if (g >= S) return;
-  uint64_t lo = 0, hi = npat - 1;                      // the last pattern p with seg_off[p] <= g
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (seg_off[mid] <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  const uint64_t p = lo, k = g - seg_off[p], s = sp[p];
+  const uint64_t p = last_le(seg_off, npat, g), k = g - seg_off[p], s = sp[p];
   uint64_t row = s, x = first[p];
   if (k) { row = a.rs_row[q0[p] + k - 1]; x = a.rs_sa[q0[p] + k - 1]; }
   const uint64_t end = k + 1 < nseg[p] ? (uint64_t)a.rs_row[q0[p] + k] : s + npos[p];
@@ -263,22 +246,11 @@ __global__ void __launch_bounds__(kTB) fm_ms_k(FmArgs<I> a, const uint8_t *__res
                                                MsRec *__restrict__ rec, int first, uint64_t budget, uint32_t *__restrict__ len_out,
                                                uint64_t *__restrict__ pos_out, unsigned long long *__restrict__ ctr, int stats) {
   __shared__ uint8_t code[256];
-  code[threadIdx.x] = a.codes[threadIdx.x];
-  __syncthreads();
-  const int gl = threadIdx.x & 15;
-  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
-  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
-  const uint64_t o0 = off[p], o1 = off[p + 1], n = a.n1 - 1;
-  MsRec s;
-  if (first) {
-    s = MsRec{o1 > o0 ? o1 : o0, 0, n, 0};              // (decreasing offsets: no pattern)
-    if (o1 > o0 && o1 - o0 >= 0xFFFFFFFFull) {
-      s.t = o0;
-      if (gl == 0) atomicAdd(&ctr[1], 1ull);
-    }
-  } else {
-    s = rec[p];
-  }
+  PatGroup g;
+  if (!pat_group(code, a.codes, off, npat, g)) return;
+  const int gl = g.gl;
+  const uint64_t p = g.p, o0 = g.o0, o1 = g.o1, n = a.n1 - 1;
+  MsRec s = ms_start(first, rec + p, o0, o1, n, ctr, gl);
   uint64_t work = 0, jumps = 0, matched = 0;
   while (s.t > o0 && work < budget) {                   // at least one step per launch, at most budget + what the last one compares
     s.t--;
@@ -293,22 +265,15 @@ __global__ void __launch_bounds__(kTB) fm_ms_k(FmArgs<I> a, const uint8_t *__res
       if (a.bwt[s.q] == c) {
         s.q = target; s.pos -= 1; s.l += 1;
       } else {
-        // the last c before q ends a run, the first c after q starts one (BWT[q] != c): both SA values are samples
-        const uint64_t qp = s.q ? select_first(a, 0, s.q, target - 1, c4, k, gl) : ~0ull;
-        const uint64_t qs = s.q + 1 < a.n1 ? select_first(a, s.q + 1, a.n1, target, c4, k, gl) : ~0ull;
+        const MsNeighbours nb = ms_neighbours(a, s.q, target, c4, k, gl);
         int64_t lp = -1, ls = -1;                        // (a side that does not exist loses)
         uint64_t sap = 0, sas = 0;
-        if (qp != ~0ull) {
-          uint64_t r = bit_rank(a.rbits, a.rdir, qp + 1);            // run starts in [0, qp]: qp lies in run r - 1
-          r = r ? r - 1 : 0;
-          if (r >= a.runs) r = a.runs - 1;
-          sap = (uint64_t)re_sa[r];
+        if (nb.qp != ~0ull) {
+          sap = (uint64_t)re_sa[run_ending_at(a, nb.qp)];
           lp = s.l ? (int64_t)lce16(text, n, sap, s.pos, s.l, gl, work) : 0;
         }
-        if (qs != ~0ull && lp < (int64_t)s.l) {        // (lp = l: the predecessor wins whatever the successor has)
-          uint64_t r = bit_rank(a.rbits, a.rdir, qs);
-          if (r >= a.runs) r = a.runs - 1;
-          sas = (uint64_t)a.rs_sa[r];
+        if (nb.qs != ~0ull && lp < (int64_t)s.l) {     // (lp = l: the predecessor wins whatever the successor has)
+          sas = (uint64_t)a.rs_sa[run_starting_at(a, nb.qs)];
           ls = s.l ? (int64_t)lce16(text, n, sas, s.pos, s.l, gl, work) : 0;
         }
         jumps++;
@@ -367,12 +332,7 @@ __global__ void __launch_bounds__(kTB) fm_mem_gather(const uint64_t *__restrict_
   for (uint64_t base = o0; base < o1; base += 16) {     // (base, o1 and slot are the same in all 16 lanes)
     const uint64_t t = base + gl;
     const uint32_t f = t < o1 && is_mem(len, t, o0, min_len);
-    uint32_t incl = f;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d, 16);
-      if (gl >= d) incl += o;
-    }
+    const uint32_t incl = gscan16_incl(f, gl);
     const uint64_t mine = slot + incl - f;
     if (f) {
       mem[3 * mine] = t - o0; mem[3 * mine + 1] = len[t]; mem[3 * mine + 2] = pos ? pos[t] : ~0ull;
@@ -403,7 +363,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
     {
       KScope ks(c, "fm_pairs", 20 * r + 4 * r * sizeof(I));
       fm_pairs<I><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(ssa10, esa10, r, n1, f.rs.bits.p, f.rs.dir.p, re.bits.p, re.dir.p,
-                                                              (I *)f.rs_row.p, (I *)f.rs_sa.p, key.p, val.p, (I *)f.re_sa.p, bad.p);
+                                                              as<I>(f.rs_row), as<I>(f.rs_sa), key.p, val.p, as<I>(f.re_sa), bad.p);
       PFP_HIP(hipGetLastError());
     }
     uint64_t h[2];
@@ -417,7 +377,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
   f.phi_val.alloc(c, std::max<uint64_t>(f.nphi, 1) * sizeof(I));
   if (f.nphi) {
     SortTag tag("phi^-1 table");
-    sort_pairs<I, I>(c, key.p, (I *)f.phi_key.p, val.p, (I *)f.phi_val.p, f.nphi, 0, kb);
+    sort_pairs<I, I>(c, key.p, as<I>(f.phi_key), val.p, as<I>(f.phi_val), f.nphi, 0, kb);
   } else {                                              // (one run: the table is never read; one entry keeps the search in bounds)
     PFP_HIP(hipMemsetAsync(f.phi_key.p, 0, sizeof(I), c->stream));
     PFP_HIP(hipMemsetAsync(f.phi_val.p, 0, sizeof(I), c->stream));
@@ -429,7 +389,7 @@ void build_samples(pfp_ctx *c, FmIndex &f, const uint8_t *ssa10, uint64_t ssa_by
   f.phi_dir.alloc(c, (f.nbk + 1) * sizeof(I));
   {
     KScope ks(c, "fm_phidir", (f.nbk + 1) * sizeof(I) * 8);
-    bucket_dir_k<I, I><<<gdim(cdiv(f.nbk + 1, kTB)), kTB, 0, c->stream>>>((const I *)f.phi_key.p, f.nphi, f.nbk, f.shift, (I *)f.phi_dir.p);
+    bucket_dir_k<I, I><<<gdim(cdiv(f.nbk + 1, kTB)), kTB, 0, c->stream>>>(as<I>(f.phi_key), f.nphi, f.nbk, f.shift, as<I>(f.phi_dir));
     PFP_HIP(hipGetLastError());
   }
   f.samples = true;
@@ -501,10 +461,7 @@ void fm_build(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const uin
     fm_sbc<<<gdim(cdiv(ns * sigma, kTB)), kTB, 0, c->stream>>>(base.p, ns, sigma, f.sbc.p);
     PFP_HIP(hipGetLastError());
   }
-  if (ssa10) {
-    if (f.wide) build_samples<uint64_t>(c, f, ssa10, ssa_bytes, esa10, esa_bytes);
-    else build_samples<uint32_t>(c, f, ssa10, ssa_bytes, esa10, esa_bytes);
-  }
+  if (ssa10) by_width(f, [&](auto w) { build_samples<decltype(w)>(c, f, ssa10, ssa_bytes, esa10, esa_bytes); });
   sync(c);
 }
 
@@ -532,43 +489,21 @@ void fm_build_ms(pfp_ctx *c, FmIndex &f, const uint8_t *bwt, uint64_t n1, const 
 template <class I>
 static void ms_t(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
   pfp_ctx *c = f.c;
-  uint64_t budget = kMsWork;
-  if (const char *e = getenv("PFP_FM_MS_STEPS")) {      // (tests: a small budget reaches the resume path with small inputs)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < budget) budget = v;
-  }
+  const uint64_t budget = budget_from_env(kMsWork);
+  const int stats = stats_from_env();
   const FmArgs<I> a = args_of<I>(f);
   DBuf<MsRec> rec(c, npat);
   DBuf<uint64_t> ctr(c, 4);
-  const char *se = getenv("PFP_FM_MS_STATS");           // (measurement: tools/ms_time.py reads the sums through pfp_fm_ms_stats)
-  const int stats = se && *se && *se != '0';
-  for (int first = 1;; first = 0) {                     // every launch finishes at least one step of every unfinished pattern
-    ctr.zero();
-    {
-      KScope ks(c, "fm_ms", 0);
-      fm_ms_k<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, f.text.p, (const I *)f.re_sa.p, pat, pat_off, npat, rec.p, first, budget, len,
-                                                                    pos, (unsigned long long *)ctr.p, stats);
-      PFP_HIP(hipGetLastError());
-    }
-    uint64_t h[4];
-    d2h(c, h, ctr.p, 4);
-    sync(c);
-    f.ms_stats[0] += 1; f.ms_stats[1] += h[2]; f.ms_stats[2] += h[3];
-    PFP_REQUIRE(!h[1], PFP_ELIMIT, std::to_string(h[1]) + " patterns of 2^32 - 1 bytes or more: the lengths of matching statistics are 32 bits");
-    if (!h[0]) break;
-  }
-}
-
-static void require_text(const FmIndex &f, const char *what) {
-  PFP_REQUIRE(f.has_text, PFP_EINVAL, std::string(what) + " need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
-                                      "pfp_fm_build_ms_files");
+  bounded_launches(c, "fm_ms", ctr, [&](int first, unsigned long long *d_ctr) {
+    fm_ms_k<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, f.text.p, as<I>(f.re_sa), pat, pat_off, npat, rec.p, first, budget, len, pos,
+                                                                  d_ctr, stats);
+  }, [&](const uint64_t *h) { ms_launch_counted(f, h); });
 }
 
 void fm_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
   require_text(f, "matching statistics");
   if (!npat) return;
-  if (f.wide) ms_t<uint64_t>(f, pat, pat_off, npat, len, pos);
-  else ms_t<uint32_t>(f, pat, pat_off, npat, len, pos);
+  by_width(f, [&](auto w) { ms_t<decltype(w)>(f, pat, pat_off, npat, len, pos); });
 }
 
 void fm_mems(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint32_t *len, const uint64_t *pos, uint64_t min_len,
@@ -602,11 +537,12 @@ void fm_mem_triples(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const ui
 
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
   pfp_ctx *c = f.c;
-  PFP_REQUIRE(!first || f.samples, PFP_EINVAL, "the toehold SA[sp] needs the run samples: this index was built without .ssa / .esa");
+  require_toehold(f, first != nullptr);
   if (!npat) return;
   KScope ks(c, "fm_count", 0);
-  if (f.wide) fm_count_k<uint64_t><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<uint64_t>(f), pat, pat_off, npat, sp, ep, first);
-  else fm_count_k<uint32_t><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<uint32_t>(f), pat, pat_off, npat, sp, ep, first);
+  by_width(f, [&](auto w) {
+    fm_count_k<decltype(w)><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<decltype(w)>(f), pat, pat_off, npat, sp, ep, first);
+  });
   PFP_HIP(hipGetLastError());
 }
 
@@ -642,10 +578,9 @@ static void locate_t(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64
 
 void fm_locate(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
                uint64_t *out_off, uint64_t *pos) {
-  PFP_REQUIRE(f.samples, PFP_EINVAL, "locate needs the run samples: this index was built without .ssa / .esa (bigbwt -s -e writes them)");
+  require_samples(f);
   PFP_REQUIRE(!pos || first, PFP_EINVAL, "locate needs the toehold SA[sp] of every pattern (count with first)");
-  if (f.wide) locate_t<uint64_t>(f, npat, sp, ep, first, max_occ, out_off, pos);
-  else locate_t<uint32_t>(f, npat, sp, ep, first, max_occ, out_off, pos);
+  by_width(f, [&](auto w) { locate_t<decltype(w)>(f, npat, sp, ep, first, max_occ, out_off, pos); });
 }
 
 }  // namespace pfp

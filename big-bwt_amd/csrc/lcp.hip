@@ -23,7 +23,6 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
-#include <cstdlib>
 
 namespace pfp {
 
@@ -87,16 +86,7 @@ __global__ void __launch_bounds__(kTB) lcp_irr_block(const uint8_t *__restrict__
       u[j] = v[j] = make_uint4(0, 0, 0, 0);
       if (o < cap) { u[j] = ld16u(text + x + o); v[j] = ld16u(text + y + o); }      // (below text + n + 16: the copy's padding)
     }
-    uint64_t mine = cap;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-      const uint64_t o = base + 4096 * j + 16 * (uint64_t)threadIdx.x;
-      const uint32_t w[4] = {u[j].x ^ v[j].x, u[j].y ^ v[j].y, u[j].z ^ v[j].z, u[j].w ^ v[j].w};
-#pragma unroll
-      for (int q = 3; q >= 0; q--)
-        if (w[q]) mine = o + 4 * q + (__ffs(w[q]) - 1) / 8;
-    }
-    if (mine > cap) mine = cap;
+    uint64_t mine = first_diff_rows<4096>(u, v, base + 16 * (uint64_t)threadIdx.x, cap);
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint64_t o = __shfl_xor(mine, d, 64); mine = o < mine ? o : mine; }
     if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = mine;
@@ -255,14 +245,6 @@ __global__ void __launch_bounds__(kTB) lcp_thr_load(const uint8_t *__restrict__ 
   thr[k] = (I)(v > n1 ? n1 : v);
 }
 
-uint64_t budget_from_env(uint64_t budget) {
-  if (const char *e = getenv("PFP_FM_MS_STEPS")) {      // (tests: a small budget reaches the resume paths with small inputs)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < budget) budget = v;
-  }
-  return budget;
-}
-
 // I values -> 5-byte ints, through a chunk of u64 (pack5_dev reads those)
 template <class I>
 void pack5_from(pfp_ctx *c, const I *in, uint64_t cnt, uint8_t *out5) {
@@ -280,7 +262,7 @@ template <class I>
 void lcp_t(FmIndex &f, const LcpOut &o) {
   pfp_ctx *c = f.c;
   const uint64_t n1 = f.n1, n = n1 - 1, r = f.runs;
-  const I *rs_sa = (const I *)f.rs_sa.p, *re_sa = (const I *)f.re_sa.p, *rs_row = (const I *)f.rs_row.p;
+  const I *rs_sa = as<I>(f.rs_sa), *re_sa = as<I>(f.re_sa), *rs_row = as<I>(f.rs_row);
   // 1. irreducible values
   DBuf<uint64_t> irr(c, r);
   {
@@ -296,6 +278,7 @@ void lcp_t(FmIndex &f, const LcpOut &o) {
     f.ms_stats[0] += 1;
     const uint64_t listed = read_scalar(c, ctr.p);
     const uint64_t budget = budget_from_env(kIrrBlock);
+    // (not bounded_launches: no launch at all where nothing is listed, only ctr[1] is zeroed, and the count comes by read_scalar)
     for (uint64_t left = listed; left;) {               // every launch matches at least kBlockBytes more of every listed run
       PFP_HIP(hipMemsetAsync(ctr.p + 1, 0, 8, c->stream));
       {
@@ -368,7 +351,7 @@ void lcp_t(FmIndex &f, const LcpOut &o) {
     uint64_t *t64 = o.thr64 ? o.thr64 : thr64.p;
     {
       KScope ks(c, "lcp_thr", r * (4 * sizeof(I) + 16 + 8));
-      lcp_thr<I><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(sk.p, sv.p, r, runmin.p, runarg.p, tab.p, nb, rs_row, lcp.p, n1, (I *)thr.p, t64);
+      lcp_thr<I><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(sk.p, sv.p, r, runmin.p, runarg.p, tab.p, nb, rs_row, lcp.p, n1, as<I>(thr), t64);
       PFP_HIP(hipGetLastError());
     }
     if (o.thr5) pack5_dev(c, t64, r, o.thr5);
@@ -399,18 +382,8 @@ __device__ __forceinline__ uint64_t lce16_pat(const uint8_t *__restrict__ p, con
         else { u[j] = ld_tail(p + o, (int)(cap - o)); v[j] = keep_bytes16(v[j], (int)(cap - o)); }
       }
     }
-    uint64_t mine = cap;
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-      const uint64_t o = done + 256 * j + 16 * (uint64_t)gl;
-      const uint32_t w[4] = {u[j].x ^ v[j].x, u[j].y ^ v[j].y, u[j].z ^ v[j].z, u[j].w ^ v[j].w};
-#pragma unroll
-      for (int q = 3; q >= 0; q--)
-        if (w[q]) mine = o + 4 * q + (__ffs(w[q]) - 1) / 8;
-    }
-    if (mine > cap) mine = cap;
     work++;
-    const uint64_t m = gmin16(mine);
+    const uint64_t m = first_diff_1024(u, v, done, cap, gl);
     if (m < cap) return m;
   }
   return cap;
@@ -423,22 +396,11 @@ __global__ void __launch_bounds__(kTB) fm_ms_thr1(FmArgs<I> a, const I *__restri
                                                   const uint64_t *__restrict__ off, uint64_t npat, MsRec *__restrict__ rec, int first, uint64_t budget,
                                                   uint64_t *__restrict__ pos_out, unsigned long long *__restrict__ ctr, int stats) {
   __shared__ uint8_t code[256];
-  code[threadIdx.x] = a.codes[threadIdx.x];
-  __syncthreads();
-  const int gl = threadIdx.x & 15;
-  const uint64_t p = BID * (kTB / 16) + (threadIdx.x >> 4);
-  if (p >= npat) return;                               // (whole groups leave together: the shuffles stay inside groups)
-  const uint64_t o0 = off[p], o1 = off[p + 1], n = a.n1 - 1;
-  MsRec s;
-  if (first) {
-    s = MsRec{o1 > o0 ? o1 : o0, 0, n, 0};
-    if (o1 > o0 && o1 - o0 >= 0xFFFFFFFFull) {
-      s.t = o0;
-      if (gl == 0) atomicAdd(&ctr[1], 1ull);
-    }
-  } else {
-    s = rec[p];
-  }
+  PatGroup g;
+  if (!pat_group(code, a.codes, off, npat, g)) return;
+  const int gl = g.gl;
+  const uint64_t p = g.p, o0 = g.o0, o1 = g.o1;
+  MsRec s = ms_start(first, rec + p, o0, o1, a.n1 - 1, ctr, gl);
   uint64_t work = 0, jumps = 0;
   while (s.t > o0 && work < budget) {
     s.t--;
@@ -452,21 +414,16 @@ __global__ void __launch_bounds__(kTB) fm_ms_thr1(FmArgs<I> a, const I *__restri
         s.q = target; s.pos -= 1;
         out = s.pos;
       } else {
-        const uint64_t qp = s.q ? select_first(a, 0, s.q, target - 1, c4, k, gl) : ~0ull;
-        const uint64_t qs = s.q + 1 < a.n1 ? select_first(a, s.q + 1, a.n1, target, c4, k, gl) : ~0ull;
-        if (qp != ~0ull || qs != ~0ull) {              // (no c at all: only for a directory that is not this BWT's; the state stays)
+        const MsNeighbours nb = ms_neighbours(a, s.q, target, c4, k, gl);
+        if (nb.qp != ~0ull || nb.qs != ~0ull) {        // (no c at all: only for a directory that is not this BWT's; the state stays)
           uint64_t rs = 0;
-          bool up = qs == ~0ull;
+          bool up = nb.qs == ~0ull;
           if (!up) {
-            rs = bit_rank(a.rbits, a.rdir, qs);        // q_s starts run rs
-            if (rs >= a.runs) rs = a.runs - 1;
-            up = qp != ~0ull && s.q < (uint64_t)thr[rs];
+            rs = run_starting_at(a, nb.qs);
+            up = nb.qp != ~0ull && s.q < (uint64_t)thr[rs];
           }
           if (up) {
-            uint64_t r = bit_rank(a.rbits, a.rdir, qp + 1);          // run starts in [0, qp]: qp ends run r - 1
-            r = r ? r - 1 : 0;
-            if (r >= a.runs) r = a.runs - 1;
-            s.q = target - 1; s.pos = (uint64_t)re_sa[r] - 1;
+            s.q = target - 1; s.pos = (uint64_t)re_sa[run_ending_at(a, nb.qp)] - 1;
           } else {
             s.q = target; s.pos = (uint64_t)a.rs_sa[rs] - 1;
           }
@@ -543,53 +500,33 @@ void ms_thr_t(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
     own.alloc(c, read_scalar(c, pat_off + npat) + 1);
     pos = own.p;
   }
-  const char *se = getenv("PFP_FM_MS_STATS");
-  const int stats = se && *se && *se != '0';
-  for (int pass = 1; pass <= 2; pass++)
-    for (int first = 1;; first = 0) {                   // every launch finishes at least one step, or 1024 bytes, of every unfinished pattern
-      ctr.zero();
-      {
-        KScope ks(c, pass == 1 ? "fm_ms_thr1" : "fm_ms_thr2", 0);
-        if (pass == 1)
-          fm_ms_thr1<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, (const I *)f.re_sa.p, (const I *)f.thr.p, pat, pat_off, npat, rec.p, first,
-                                                                           budget, pos, (unsigned long long *)ctr.p, stats);
-        else
-          fm_ms_thr2<<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(f.text.p, f.n1 - 1, pat, pat_off, npat, rec.p, first, budget, len, pos,
-                                                                        (unsigned long long *)ctr.p, stats);
-        PFP_HIP(hipGetLastError());
-      }
-      uint64_t h[4];
-      d2h(c, h, ctr.p, 4);
-      sync(c);
-      f.ms_stats[0] += 1; f.ms_stats[1] += h[2]; f.ms_stats[2] += h[3];
-      PFP_REQUIRE(!h[1], PFP_ELIMIT, std::to_string(h[1]) + " patterns of 2^32 - 1 bytes or more: the lengths of matching statistics are 32 bits");
-      if (!h[0]) break;
-    }
-}
-
-void require_ms_index(const FmIndex &f, const char *what) {
-  PFP_REQUIRE(f.has_text, PFP_EINVAL, std::string(what) + " need the text and the run-end values: build the index with pfp_fm_build_ms_dev / "
-                                      "pfp_fm_build_ms_files");
+  const int stats = stats_from_env();
+  const auto counted = [&](const uint64_t *h) { ms_launch_counted(f, h); };
+  bounded_launches(c, "fm_ms_thr1", ctr, [&](int first, unsigned long long *d_ctr) {
+    fm_ms_thr1<I><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(a, as<I>(f.re_sa), as<I>(f.thr), pat, pat_off, npat, rec.p, first, budget, pos,
+                                                                     d_ctr, stats);
+  }, counted);
+  bounded_launches(c, "fm_ms_thr2", ctr, [&](int first, unsigned long long *d_ctr) {      // (a unit of its work: a step, or 1024 bytes)
+    fm_ms_thr2<<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(f.text.p, f.n1 - 1, pat, pat_off, npat, rec.p, first, budget, len, pos, d_ctr, stats);
+  }, counted);
 }
 
 }  // namespace
 
 void fm_lcp(FmIndex &f, const LcpOut &o) {
-  require_ms_index(f, "the LCP array and thresholds");
-  if (f.wide) lcp_t<uint64_t>(f, o);
-  else lcp_t<uint32_t>(f, o);
+  require_text(f, "the LCP array and thresholds");
+  by_width(f, [&](auto w) { lcp_t<decltype(w)>(f, o); });
   sync(f.c);
 }
 
 void fm_load_thresholds(FmIndex &f, const uint8_t *thr5, uint64_t bytes) {
   pfp_ctx *c = f.c;
-  require_ms_index(f, "thresholds");
+  require_text(f, "thresholds");
   const uint64_t r = f.runs;
   PFP_REQUIRE(bytes == 5 * r, PFP_EFORMAT, ".thr_pos holds " + std::to_string(bytes) + " bytes; the BWT has " + std::to_string(r) +
                                                " runs, so its .thr_pos holds " + std::to_string(5 * r));
   DBuf<uint8_t> thr(c, r * (f.wide ? 8 : 4));
-  if (f.wide) lcp_thr_load<uint64_t><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(thr5, r, f.n1, (uint64_t *)thr.p);
-  else lcp_thr_load<uint32_t><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(thr5, r, f.n1, (uint32_t *)thr.p);
+  by_width(f, [&](auto w) { lcp_thr_load<decltype(w)><<<gdim(cdiv(r, kTB)), kTB, 0, c->stream>>>(thr5, r, f.n1, as<decltype(w)>(thr)); });
   PFP_HIP(hipGetLastError());
   sync(c);
   f.thr = std::move(thr);
@@ -597,11 +534,10 @@ void fm_load_thresholds(FmIndex &f, const uint8_t *thr5, uint64_t bytes) {
 }
 
 void fm_ms_thr(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint32_t *len, uint64_t *pos) {
-  require_ms_index(f, "matching statistics");
+  require_text(f, "matching statistics");
   PFP_REQUIRE(f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
   if (!npat) return;
-  if (f.wide) ms_thr_t<uint64_t>(f, pat, pat_off, npat, len, pos);
-  else ms_thr_t<uint32_t>(f, pat, pat_off, npat, len, pos);
+  by_width(f, [&](auto w) { ms_thr_t<decltype(w)>(f, pat, pat_off, npat, len, pos); });
 }
 
 }  // namespace pfp

@@ -22,7 +22,6 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
-#include <cstdlib>
 
 namespace pfp {
 
@@ -38,7 +37,7 @@ struct SeqArgs {
 };
 template <class I>
 SeqArgs<I> seq_args(const FmIndex &f) {
-  return SeqArgs<I>{(const I *)f.seq_start.p, f.seq_dir.p, f.nseq, f.n1 - 1, f.seq_shift};
+  return SeqArgs<I>{as<I>(f.seq_start), f.seq_dir.p, f.nseq, f.n1 - 1, f.seq_shift};
 }
 
 // the sequence that holds text position x < n: the first start above x, searched in x's bucket, is the next sequence's
@@ -78,24 +77,12 @@ __global__ void __launch_bounds__(kTB) seq_flag_k(SeqArgs<I> s, const uint64_t *
   uint32_t k = kNoSeq;
   const uint64_t x = i < U ? pos[i] : ~0ull;
   if (x < s.n) {
-    uint64_t lo = 0, hi = npat - 1;                     // the last pattern p with uoff[p] <= i
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) >> 1;
-      if (uoff[mid] <= i) lo = mid;
-      else hi = mid - 1;
-    }
-    const uint64_t o0 = pat_off[lo], o1 = pat_off[lo + 1], m = o1 > o0 ? o1 - o0 : 0;
+    const uint64_t p = last_le(uoff, npat, i);          // the position's pattern
+    const uint64_t o0 = pat_off[p], o1 = pat_off[p + 1], m = o1 > o0 ? o1 - o0 : 0;
     const uint32_t q = seq_of(s, x);
     if (m <= (uint64_t)s.start[q + 1] - x) k = q;       // x + m <= starts[q + 1], without the sum
   }
   tmp[i] = k;
-}
-
-// out[p] = slot[at[p]], p = 0..npat: what was counted before a pattern's first entry
-__global__ void __launch_bounds__(kTB) seq_outoff_k(const uint64_t *__restrict__ at, uint64_t npat, const uint64_t *__restrict__ slot,
-                                                    uint64_t *__restrict__ out) {
-  const uint64_t p = BID * kTB + threadIdx.x;
-  if (p <= npat) out[p] = slot[at[p]];
 }
 
 // the kept hits to their slots, in row order
@@ -166,13 +153,8 @@ __global__ void __launch_bounds__(kTB) doc_hist_k(const uint32_t *__restrict__ s
   __shared__ uint32_t wsum[kTB / 64];
   const uint64_t b = BID;
   if (b >= C) return;                                   // (the whole workgroup)
-  uint64_t lo = 0, hi = npat - 1;                       // the last pattern p with chunk_off[p] <= b: it has a chunk b
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (chunk_off[mid] <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  const uint64_t p = lo, k = b - chunk_off[p], nchunks = chunk_off[p + 1] - chunk_off[p];
+  const uint64_t p = last_le(chunk_off, npat, b);       // the last pattern with chunk_off[p] <= b: it has a chunk b
+  const uint64_t k = b - chunk_off[p], nchunks = chunk_off[p + 1] - chunk_off[p];
   if (EMIT && nchunks > 1) return;                      // (written from its row)
   const uint64_t i0 = hoff[p] + k * chunk, end = hoff[p + 1], i1 = i0 + chunk < end ? i0 + chunk : end;
   for (uint64_t t = threadIdx.x; t < nseq; t += kTB) h[t] = 0;
@@ -204,14 +186,6 @@ __global__ void __launch_bounds__(kTB) doc_rows_k(const unsigned long long *__re
 }
 
 // ---------------------------------------------------------------- document listing: the sort regime
-__global__ void __launch_bounds__(kTB) doc_segs_k(const uint64_t *__restrict__ hoff, uint64_t npat, uint32_t *__restrict__ sb, uint32_t *__restrict__ se,
-                                                  uint32_t *__restrict__ head) {
-  const uint64_t p = BID * kTB + threadIdx.x;
-  if (p >= npat) return;
-  const uint64_t a = hoff[p], b = hoff[p + 1];
-  sb[p] = (uint32_t)a; se[p] = (uint32_t)b;
-  if (b > a) head[a] = 1;                               // a pattern's first hit starts a run
-}
 __global__ void __launch_bounds__(kTB) doc_heads_k(const uint32_t *__restrict__ sorted, uint64_t K, uint32_t *__restrict__ head) {
   const uint64_t i = BID * kTB + threadIdx.x;
   if (i >= 1 && i < K && sorted[i] != sorted[i - 1]) head[i] = 1;
@@ -262,7 +236,7 @@ void keep_hits(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64_
     PFP_HIP(hipGetLastError());
   }
   exclusive_count_ne_u32(c, k.tmp.p, kNoSeq, k.slot.p, U + 1);
-  seq_outoff_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(k.uoff.p, npat, k.slot.p, out_off);
+  gather_off_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(k.uoff.p, npat, k.slot.p, U, out_off);
   PFP_HIP(hipGetLastError());
 }
 
@@ -290,12 +264,7 @@ void doc_out_ready(pfp_ctx *c, DocOut &o, uint64_t D) {
 // sq: the K kept hits' sequence numbers, pattern p's at hoff[p] .. hoff[p+1]
 void doc_hist(FmIndex &f, const uint32_t *sq, const uint64_t *hoff, uint64_t npat, uint64_t *doc_off, DocOut &o) {
   pfp_ctx *c = f.c;
-  uint64_t chunk = kDocChunk;
-  if (const char *e = getenv("PFP_FM_MS_STEPS")) {      // (tests: a small bound splits the patterns of small inputs)
-    const uint64_t v = strtoull(e, nullptr, 10);
-    if (v >= 1 && v < chunk) chunk = v;
-  }
-  const uint64_t nseq = f.nseq;
+  const uint64_t chunk = budget_from_env(kDocChunk), nseq = f.nseq;   // (tests: a small bound splits the patterns of small inputs)
   DBuf<uint64_t> nchunk(c, npat + 1), isrow(c, npat + 1), chunk_off(c, npat + 1), row_of(c, npat + 1), ndoc(c, npat + 1);
   doc_plan_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(hoff, npat, chunk, nchunk.p, isrow.p);
   PFP_HIP(hipGetLastError());
@@ -340,7 +309,7 @@ void doc_sort(FmIndex &f, DBuf<uint32_t> &sq, uint64_t K, const uint64_t *hoff, 
                                                  std::to_string(K) + " of them, the limit is 2^32 - 2 (fewer patterns per call)");
   DBuf<uint32_t> sorted(c, K), sb(c, npat), se(c, npat), head(c, K + 1);
   head.zero();
-  doc_segs_k<<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(hoff, npat, sb.p, se.p, head.p);
+  seg_bounds_k<uint32_t><<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(hoff, npat, nullptr, sb.p, se.p, head.p, nullptr, 0);   // (head: a first hit starts a run)
   PFP_HIP(hipGetLastError());
   segsort_keys_u32(c, sq.p, sorted.p, K, npat, sb.p, se.p, 0, bits_for(f.nseq - 1));
   sq.release(); sb.release(); se.release();
@@ -348,7 +317,7 @@ void doc_sort(FmIndex &f, DBuf<uint32_t> &sq, uint64_t K, const uint64_t *hoff, 
   PFP_HIP(hipGetLastError());
   DBuf<uint64_t> hs(c, K + 1);
   exclusive_sum_u32_u64(c, head.p, hs.p, K + 1);
-  seq_outoff_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(hoff, npat, hs.p, doc_off);
+  gather_off_k<<<gdim(cdiv(npat + 1, kTB)), kTB, 0, c->stream>>>(hoff, npat, hs.p, K, doc_off);
   PFP_HIP(hipGetLastError());
   if (!o.doc && !o.own_doc) return;
   const uint64_t D = read_scalar(c, hs.p + K);
@@ -393,14 +362,14 @@ void set_seqs_t(FmIndex &f, const uint64_t *starts, uint64_t nseq) {
   std::vector<I> h(nseq + 1);
   for (uint64_t k = 0; k <= nseq; k++) h[k] = (I)starts[k];
   DBuf<uint8_t> d_start(c, (nseq + 1) * sizeof(I));
-  h2d(c, (I *)d_start.p, h.data(), nseq + 1);
+  h2d(c, as<I>(d_start), h.data(), nseq + 1);
   // about one start per bucket
   const int shift = std::max(0, bits_for(f.n1) - bits_for(nseq + 1));
   const uint64_t nbk = (n >> shift) + 1;
   DBuf<uint32_t> d_dir(c, nbk + 1);
   {
     KScope ks(c, "seq_dir", (nbk + 1) * 4 * 8);
-    bucket_dir_k<I, uint32_t><<<gdim(cdiv(nbk + 1, kTB)), kTB, 0, c->stream>>>((const I *)d_start.p, nseq + 1, nbk, shift, d_dir.p);
+    bucket_dir_k<I, uint32_t><<<gdim(cdiv(nbk + 1, kTB)), kTB, 0, c->stream>>>(as<I>(d_start), nseq + 1, nbk, shift, d_dir.p);
     PFP_HIP(hipGetLastError());
   }
   sync(c);                                              // (h is read until here; a failure above leaves the old table in place)
@@ -421,8 +390,7 @@ void fm_set_seqs(FmIndex &f, const uint64_t *starts, uint64_t nseq) {
                                                             ", below entry " + std::to_string(k - 1) + ": the starts do not decrease");
   PFP_REQUIRE(starts[nseq] == n, PFP_EINVAL, "sequence table entry " + std::to_string(nseq) + " (the last) is " + std::to_string(starts[nseq]) +
                                                  ": it is the text's length, " + std::to_string(n));
-  if (f.wide) set_seqs_t<uint64_t>(f, starts, nseq);
-  else set_seqs_t<uint32_t>(f, starts, nseq);
+  by_width(f, [&](auto w) { set_seqs_t<decltype(w)>(f, starts, nseq); });
 }
 
 void fm_seqmap(FmIndex &f, const uint64_t *pos, uint64_t count, uint32_t *seq, uint64_t *off) {
@@ -430,8 +398,7 @@ void fm_seqmap(FmIndex &f, const uint64_t *pos, uint64_t count, uint32_t *seq, u
   require_seqs(f);
   if (!count || (!seq && !off)) return;
   KScope ks(c, "seq_map", count * 20);
-  if (f.wide) seq_map_k<uint64_t><<<gdim(cdiv(count, kTB)), kTB, 0, c->stream>>>(seq_args<uint64_t>(f), pos, count, seq, off);
-  else seq_map_k<uint32_t><<<gdim(cdiv(count, kTB)), kTB, 0, c->stream>>>(seq_args<uint32_t>(f), pos, count, seq, off);
+  by_width(f, [&](auto w) { seq_map_k<decltype(w)><<<gdim(cdiv(count, kTB)), kTB, 0, c->stream>>>(seq_args<decltype(w)>(f), pos, count, seq, off); });
   PFP_HIP(hipGetLastError());
 }
 
@@ -444,13 +411,10 @@ void fm_locate_seqs(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const ui
     return;
   }
   Kept k;
-  if (f.wide) {
-    keep_hits<uint64_t>(f, pat_off, npat, sp, ep, first, max_occ, out_off, k);
-    if (seq) scatter_hits<uint64_t>(f, k, seq, off);
-  } else {
-    keep_hits<uint32_t>(f, pat_off, npat, sp, ep, first, max_occ, out_off, k);
-    if (seq) scatter_hits<uint32_t>(f, k, seq, off);
-  }
+  by_width(f, [&](auto w) {
+    keep_hits<decltype(w)>(f, pat_off, npat, sp, ep, first, max_occ, out_off, k);
+    if (seq) scatter_hits<decltype(w)>(f, k, seq, off);
+  });
 }
 
 void fm_doclist(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first,
@@ -462,8 +426,7 @@ void fm_doclist(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const uint64
     doc_out_ready(f.c, o, 0);
     return;
   }
-  if (f.wide) doclist_t<uint64_t>(f, pat_off, npat, sp, ep, first, doc_off, o);
-  else doclist_t<uint32_t>(f, pat_off, npat, sp, ep, first, doc_off, o);
+  by_width(f, [&](auto w) { doclist_t<decltype(w)>(f, pat_off, npat, sp, ep, first, doc_off, o); });
 }
 
 }  // namespace pfp
