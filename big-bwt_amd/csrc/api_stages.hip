@@ -100,7 +100,7 @@ __global__ void lcp_da_kernel(const uint8_t *__restrict__ s, uint64_t n, const I
   uint64_t l = 0;
   for (; l < kLcpCap; l += 8) {
     const uint64_t x = ld8u(s + a + l), y = ld8u(s + b + l);
-    const uint64_t end = (x - 0x0202020202020202ull) & ~x & 0x8080808080808080ull;      // bytes < 2 of x (lowest flag exact)
+    const uint64_t end = lt2_flags64(x);
     const uint64_t diff = x ^ y;
     if (diff | end) {
       const int fd = diff ? (__builtin_ctzll(diff) >> 3) : 8, fe = end ? (__builtin_ctzll(end) >> 3) : 8;
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64) void lcp_long_kernel(const uint8_t *__restrict_
       int ev = 16;
 #pragma unroll
       for (int q = 3; q >= 0; q--) {
-        const uint32_t end = (xs[q] - 0x02020202u) & ~xs[q] & 0x80808080u, diff = xs[q] ^ ys[q];
+        const uint32_t end = lt2_flags32(xs[q]), diff = xs[q] ^ ys[q];
         if (diff | end) {
           const int fd = diff ? (__builtin_ctz(diff) >> 3) : 4, fe = end ? (__builtin_ctz(end) >> 3) : 4;
           ev = 4 * q + (fd < fe ? fd : fe);

@@ -20,6 +20,21 @@ __device__ __forceinline__ void st16u(uint8_t *p, uint4 v) {
 }
 __device__ __forceinline__ uint64_t ld8u(const uint8_t *p) { return reinterpret_cast<const U64u *>(p)->v; }
 
+// Terminated strings (dictionary words: bytes >= 2, ended by one < 2).  Bit 7 of every byte of x that is below 2; lowest flag exact.
+__device__ __forceinline__ uint32_t lt2_flags32(uint32_t x) { return (x - 0x02020202u) & ~x & 0x80808080u; }
+__device__ __forceinline__ uint64_t lt2_flags64(uint64_t x) { return (x - 0x0202020202020202ull) & ~x & 0x8080808080808080ull; }
+// One 8-byte step of comparing two terminated strings that are equal so far, x and y their next 8 bytes (little-endian):
+// -1 / +1 = x's string is the smaller / larger, 0 = the same string (both end before they differ), kCmpOn = neither yet.
+constexpr int kCmpOn = 2;
+__device__ __forceinline__ int cmp_term8(uint64_t x, uint64_t y) {
+  const uint64_t diff = x ^ y, term = lt2_flags64(x);
+  if (!(diff | term)) return kCmpOn;
+  const int fd = diff ? (__builtin_ctzll(diff) >> 3) : 8, ft = term ? (__builtin_ctzll(term) >> 3) : 8;
+  if (ft < fd) return 0;                                    // both end before they differ: the same string
+  const uint32_t bx = (uint32_t)(x >> (8 * fd)) & 0xffu, by = (uint32_t)(y >> (8 * fd)) & 0xffu;
+  return bx < by ? -1 : 1;
+}
+
 // zero the bytes at index >= keep (0..16) of a little-endian 16-byte register block
 __device__ __forceinline__ uint4 keep_bytes16(uint4 v, int keep) {
   uint32_t r[4] = {v.x, v.y, v.z, v.w};

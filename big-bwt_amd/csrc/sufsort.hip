@@ -772,10 +772,8 @@ __global__ void build_keys_pivot_kernel(const uint8_t *__restrict__ s, uint64_t 
       xa0 = ld16u(pa + off); xa1 = ld16u(pa + off + 16); xp0 = ld16u(pp + off); xp1 = ld16u(pp + off + 16);
       const uint32_t diff = (xa0.x ^ xp0.x) | (xa0.y ^ xp0.y) | (xa0.z ^ xp0.z) | (xa0.w ^ xp0.w) | (xa1.x ^ xp1.x) |
                             (xa1.y ^ xp1.y) | (xa1.z ^ xp1.z) | (xa1.w ^ xp1.w);
-#define PFP_LT2(v) (((v) - 0x02020202u) & ~(v) & 0x80808080u)
-      const uint32_t term = PFP_LT2(xa0.x) | PFP_LT2(xa0.y) | PFP_LT2(xa0.z) | PFP_LT2(xa0.w) | PFP_LT2(xa1.x) | PFP_LT2(xa1.y) |
-                            PFP_LT2(xa1.z) | PFP_LT2(xa1.w);
-#undef PFP_LT2
+      const uint32_t term = lt2_flags32(xa0.x) | lt2_flags32(xa0.y) | lt2_flags32(xa0.z) | lt2_flags32(xa0.w) | lt2_flags32(xa1.x) |
+                            lt2_flags32(xa1.y) | lt2_flags32(xa1.z) | lt2_flags32(xa1.w);
       if (diff | term) { hit = true; break; }
     }
     if (hit) {
@@ -786,7 +784,7 @@ __global__ void build_keys_pivot_kernel(const uint8_t *__restrict__ s, uint64_t 
       bool done = false;
 #pragma unroll
       for (int q = 0; q < 4 && !done; q++) {
-        const uint64_t tb = (x[q] - 0x0202020202020202ull) & ~x[q] & 0x8080808080808080ull;   // bytes < 2; lowest flag exact
+        const uint64_t tb = lt2_flags64(x[q]);
         if (x[q] == y[q]) { if (tb) { settled = finbit; done = true; } continue; }
         const int fd = __builtin_ctzll(x[q] ^ y[q]) >> 3;
         const int ft = tb ? (__builtin_ctzll(tb) >> 3) : 8;
@@ -905,14 +903,8 @@ constexpr int kFinishGrp = 64;
 constexpr uint32_t kFinishCmp = 8192;
 __device__ __forceinline__ int finish_cmp_dict(const uint8_t *__restrict__ s, uint64_t i, uint64_t j, uint32_t *ovf) {
   for (uint32_t k = 0; k < kFinishCmp; k += 8) {
-    const uint64_t x = ld8u(s + i + k), y = ld8u(s + j + k);
-    const uint64_t tb = (x - 0x0202020202020202ull) & ~x & 0x8080808080808080ull;   // bytes < 2 of x; lowest flag exact
-    if (x == y) { if (tb) return 0; continue; }
-    const int fd = __builtin_ctzll(x ^ y) >> 3;
-    const int ft = tb ? (__builtin_ctzll(tb) >> 3) : 8;
-    if (ft < fd) return 0;       // both end before they differ
-    const uint32_t bx = (uint32_t)(x >> (8 * fd)) & 0xffu, by = (uint32_t)(y >> (8 * fd)) & 0xffu;
-    return bx < by ? -1 : 1;
+    const int r = cmp_term8(ld8u(s + i + k), ld8u(s + j + k));
+    if (r != kCmpOn) return r;
   }
   *ovf = 1;
   return 0;
@@ -1588,6 +1580,8 @@ void gather_ranks(pfp_ctx *c, const SuffixOrderT<I> &so, const uint64_t *d_pos, 
 template void gather_ranks<uint32_t>(pfp_ctx *, const SuffixOrderT<uint32_t> &, const uint64_t *, uint64_t, uint32_t *);
 template void gather_ranks<uint64_t>(pfp_ctx *, const SuffixOrderT<uint64_t> &, const uint64_t *, uint64_t, uint64_t *);
 
+// ---- whole-array entry points: first-round keys for all N positions, then doubling()
+
 static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, double rep_hint = 0) {
   DBuf<unsigned long long> hist(c, 256);
   hist.zero();
@@ -1616,10 +1610,31 @@ static int keysonly_bits(uint64_t N, double rep_hint, KeyCode &kc) {
 }
 
 template <class I>
-void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, SuffixOrderT<I> &out,
-                        const SlotPayloadSrc *pay) {
+static void require_dict_size(uint64_t N) {
   PFP_REQUIRE(N >= 1 && (sizeof(I) == 8 ? N < (1ull << 40) : N < 0xFFFFFFF0ull), PFP_ELIMIT,
               sizeof(I) == 8 ? "dictionary of 2^40 bytes or more" : "dictionary too large for 32-bit suffix indices");
+}
+static uint64_t dict_keymask(const KeyCode &kc) { return kc.kbits + 1 >= 64 ? ~0ull : ((1ull << (kc.kbits + 1)) - 1); }
+
+// what follows the first-round keys of a dictionary, of all its positions or of a list of them (list_len): what the merge reads
+// of the key code, then the rounds
+template <class I>
+static void dict_rounds(pfp_ctx *c, const SufGeom &g, const uint8_t *bytes, const KeyCode &kc, int idx_bits, std::optional<uint64_t> list_len,
+                        DBuf<uint64_t> &key, DBuf<I> &val, SuffixOrderT<I> &out) {
+  out.keymask = dict_keymask(kc);
+  out.lut.alloc(c, 256);
+  PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
+  sync(c);      // kc may be a stack object of the caller
+  out.bytes = bytes; out.kbits = kc.kbits;
+  DoublingOpts o;
+  o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = list_len, o.idx_bits = idx_bits;
+  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
+}
+
+template <class I>
+void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, SuffixOrderT<I> &out,
+                        const SlotPayloadSrc *pay) {
+  require_dict_size<I>(N);
   SufGeom g{MODE_DICT, N, wv};
   KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint);
   // Keys-only first round.  A dictionary of a repetitive collection (text / dictionary >= 2) is mostly families of
@@ -1632,30 +1647,191 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
   DBuf<I> val;
   if (!idx_bits) val.alloc(c, N);
   out.paybits = (pay && !idx_bits && kc.kbits + 1 <= 48) ? 16 : 0;
-  out.keymask = kc.kbits + 1 >= 64 ? ~0ull : ((1ull << (kc.kbits + 1)) - 1);
   { KScope ks(c, "pfp::init_keys_packed_kernel", N * (9 + (idx_bits ? 0 : sizeof(I)) + (out.paybits ? 9 : 0)));
     hipLaunchKernelGGL(init_keys_packed_kernel<I>, gdim((unsigned)cdiv64(N, kKeyPos)), gdim(256), 0, c->stream, bytes, N, kc,
                        pay ? *pay : SlotPayloadSrc{}, out.paybits, key.p, val.p, idx_bits); }
   if (c->debug) {
     DBuf<unsigned long long> bad(c, 1);
     bad.zero();
-    hipLaunchKernelGGL(check_keys_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, kc, key.p, out.keymask, bad.p, idx_bits);
+    hipLaunchKernelGGL(check_keys_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, kc, key.p, dict_keymask(kc), bad.p, idx_bits);
     PFP_HIP(hipMemcpyAsync(c->h_scalars, bad.p, 8, hipMemcpyDeviceToHost, c->stream));
     sync(c);
     PFP_REQUIRE(c->h_scalars[0] == 0, PFP_EHIP, "bit-stream keys differ from packed_key_at at " + std::to_string(c->h_scalars[0]) + " positions");
   }
-  out.lut.alloc(c, 256);
-  PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
-  sync(c);      // kc is a stack object
-  out.bytes = bytes; out.kbits = kc.kbits;
-  DoublingOpts o;
-  o.key_bits = kc.kbits + 1, o.dict = true, o.idx_bits = idx_bits;
-  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
+  dict_rounds<I>(c, g, bytes, kc, idx_bits, std::nullopt, key, val, out);
 }
 template void sort_dict_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint32_t> &, const SlotPayloadSrc *);
 template void sort_dict_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint64_t> &, const SlotPayloadSrc *);
 
-// ---- key-range sharded variant (multi-GPU)
+// (Tried in round 3 and removed: "grouped order without sorting duplicates".  Equal suffixes of a dictionary of variants can be
+//  read off the WORDS: sort the d words by their reversed strings, keep the longest common suffix lcs[r] of neighbours; the
+//  suffix of length L of the word at rank r duplicates its left neighbour's iff lcs[r] >= L, so only one representative per
+//  distinct string (71 M of 129 M suffixes on the 64-copy workload) is suffix-sorted - as a list - and every sorted
+//  representative is expanded into its run of words.  Bit-exact on all goldens, half the peak memory (12.6 GB input: 165 ->
+//  90 GB) - and slower: the dictionary sort went 20.0 -> 22.2 ms (64 copies) and 354 -> 434 ms (1024 copies).  The first
+//  round shrinks (radix 3.8 -> 2.2 ms, pivot 6.8 -> 4.9 ms), but with the identical strings gone every remaining tie is a real
+//  difference: 7 rounds instead of 5 (23 pivot launches instead of 7 on 1024 copies), and finding the runs and laying out
+//  the slots costs 4.5 ms / 87 ms.  It would pay if the MERGE worked on the 71 M groups instead of 129 M slots (sums over
+//  a run from prefix sums, "all chars equal" from a range minimum over lcs[]): DESIGN.md 7b.)
+
+template <class I>
+void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrderT<I> &out) {
+  PFP_REQUIRE(N >= 1 && (sizeof(I) == 8 ? N < (1ull << 40) : N < 0xFFFFFFF0ull), PFP_ELIMIT, "text too large for the suffix index width");
+  SufGeom g{MODE_PLAIN, N, WordView{}};
+  DBuf<uint64_t> key(c, N);
+  DBuf<I> val(c, N);
+  { KScope ks(c, "pfp::init_keys_bytes_kernel", N * (16 + sizeof(I)));
+    hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p); }
+  doubling<I>(c, g, key, val, 8, out, DoublingOpts{});
+}
+template void sort_byte_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint32_t> &);
+template void sort_byte_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint64_t> &);
+
+// First-round keys of an integer string, for both integer sorters: the symbol-width check, g.dist for the pivot rounds where the
+// caller wants it, key[] and val[] for all N positions.  The caller holds the IntKeys while it sorts and names the trace scopes
+// that differ between the entry points, so that each one's rows stay its own (dist_scope null: none).  What the caller has
+// allocated itself is not allocated here: each entry point keeps the order of its requests to the pool, which hands out its cached
+// blocks by that order - the buffers of a sort lie where they lay when each sorter had its own setup.
+struct IntKeys {
+  DBuf<uint32_t> mx, dist, val;      // (mx: the largest symbol; held with the rest, as it always has been: the pool's peak counts it)
+  DBuf<uint64_t> key;
+};
+static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t N, uint32_t max_sym, const uint32_t *occ, uint32_t n_sym,
+                           bool want_dist, const char *dist_scope, const char *plain_scope, uint64_t plain_bytes, IntKeys &k) {
+  // the symbol width is measured, not taken on trust (max_sym is only an upper bound for the check)
+  auto need = [&](auto &b) { if (!b.p) b.alloc(c, N); };
+  k.mx.alloc(c, 1);
+  k.mx.zero();
+  hipLaunchKernelGGL(max_u32_kernel, gdim((int)std::min<uint64_t>(cdiv64(N, 256), 1024)), gdim(256), 0, c->stream, sym, N, k.mx.p);
+  const uint32_t real_max = read_scalar(c, k.mx.p);
+  PFP_REQUIRE(real_max <= max_sym, PFP_EFORMAT, "integer string holds a symbol above its alphabet size");
+  const int sb = bits_for(real_max);
+  g.sym = sym;
+  std::optional<KScope> ks;
+  // occ[x - 1] = occurrences of symbol x (the parse: the words' counts): rare = fewer than the mean; dist[] for the pivot rounds
+  if (want_dist) {
+    if (dist_scope) ks.emplace(c, dist_scope, N * 24);      // (+ rare_marks_kernel and the running maximum between them)
+    DBuf<uint32_t> mk(c, N), pm(c, N);
+    need(k.dist);
+    const uint32_t below = (uint32_t)std::max<uint64_t>(2, N / n_sym);
+    hipLaunchKernelGGL(rare_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, occ, n_sym, below, mk.p);
+    inclusive_max_u32(c, mk.p, pm.p, N);
+    hipLaunchKernelGGL(rare_dist_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, (uint32_t)N, pm.p, k.dist.p);
+    g.dist = k.dist.p;
+    ks.reset();
+  }
+  need(k.key);
+  need(k.val);
+  if (64 - 2 * sb >= 6) {
+    ks.emplace(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
+    DBuf<uint32_t> v(c, N), pm(c, N);
+    hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
+    inclusive_max_u32(c, v.p, pm.p, N);
+    hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, k.key.p,
+                       k.val.p);
+  } else {
+    ks.emplace(c, plain_scope, plain_bytes);
+    hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, k.key.p, k.val.p);
+  }
+}
+
+void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder &out, uint32_t max_sym, const uint32_t *occ,
+                       uint32_t n_sym) {
+  PFP_REQUIRE(N >= 1 && N < 0xFFFFFFF0ull, PFP_ELIMIT, "parse too large for 32-bit suffix indices");
+  SufGeom g{MODE_PLAIN, N, WordView{}};
+  IntKeys k;
+  k.key.alloc(c, N);
+  k.val.alloc(c, N);
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, occ && n_sym && N >= parse_pivot_min(), nullptr, "pfp::init_keys_int_kernel", N * (8 + 8 + 4), k);
+  doubling<uint32_t>(c, g, k.key, k.val, 2, out, DoublingOpts{});
+}
+
+// ---- one rank's share of a suffix array (multi-GPU chain): the suffixes of one key range out of `parts`.  First what the two share
+// sorters have in common (share_splitters, select_share), then the dictionary's kernels and sorter with gather_slots_range, then the parse's.
+// The splitters: every stride-th suffix's first-round key, sorted; the same on every rank.  `sample(stride, ns, key, val)`
+// launches the caller's kernel, which writes the ns sample keys and val[k] = k.  Part q starts at the sample q ns / parts.
+struct Splitters {
+  std::vector<uint64_t> hs;          // the sample keys, ascending
+  std::vector<uint32_t> hv;          // the sample each of them came from (where the caller asked for that)
+  uint64_t klo = 0, khi = ~0ull;     // this part's keys: [klo, khi), no upper bound where khi_open
+  int khi_open = 1;
+};
+template <class Sample>
+static Splitters share_splitters(pfp_ctx *c, uint64_t N, uint32_t part, uint32_t parts, bool want_idx, Sample &&sample) {
+  Splitters sp;
+  sp.khi_open = part + 1 == parts ? 1 : 0;
+  if (parts <= 1) return sp;
+  const uint32_t ns = (uint32_t)std::min<uint64_t>(N, 1u << 16);
+  DBuf<uint64_t> sk(c, ns), sko(c, ns);
+  DBuf<uint32_t> sv(c, ns), svo(c, ns);
+  sample(N / ns, ns, sk.p, sv.p);
+  sort_pairs_u64_u32(c, sk.p, sko.p, sv.p, svo.p, ns, 0, 64);
+  sp.hs.resize(ns);
+  PFP_HIP(hipMemcpyAsync(sp.hs.data(), sko.p, (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
+  if (want_idx) {
+    sp.hv.resize(ns);
+    PFP_HIP(hipMemcpyAsync(sp.hv.data(), svo.p, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  sync(c);
+  if (part > 0) sp.klo = sp.hs[(uint64_t)part * ns / parts];
+  if (part + 1 < parts) sp.khi = sp.hs[(uint64_t)(part + 1) * ns / parts];
+  return sp;
+}
+
+__global__ __launch_bounds__(256) void sum2_u64_kernel(const unsigned long long *__restrict__ a, const unsigned long long *__restrict__ b,
+                                                       uint64_t n, unsigned long long *__restrict__ out) {
+  __shared__ unsigned long long ws[2][4];
+  unsigned long long x = 0, y = 0;
+  for (uint64_t i = (uint64_t)BID * 256 + threadIdx.x; i < n; i += (uint64_t)GDIM * 256) { x += a[i]; y += b[i]; }
+  for (int o = 32; o > 0; o >>= 1) { x += __shfl_down(x, o, 64); y += __shfl_down(y, o, 64); }
+  if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = x; ws[1][threadIdx.x >> 6] = y; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(out, ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3]);
+    atomicAdd(out + 1, ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3]);
+  }
+}
+// the end of a flag pass: its per-tile sums added up, sums[0] += a[0..n), sums[1] += b[0..n).  The pass calls it itself, inside its
+// own trace scope and while it holds the tile sums (the dictionary's go back to the pool before the flags are counted).
+static void sum_tiles(pfp_ctx *c, const unsigned long long *a, const unsigned long long *b, uint64_t n, unsigned long long *sums) {
+  hipLaunchKernelGGL(sum2_u64_kernel, gdim((int)std::min<uint64_t>(cdiv64(n, 256), 256)), gdim(256), 0, c->stream, a, b, n, sums);
+}
+
+// The share's positions.  `flag_pass(flag, sums)` is the caller's: it sets flag[i] = 1 for the positions of the share and 0 for the
+// others, all N of them, has sum_tiles add the number of positions below the share into sums[0], and returns whether sums[1] then
+// holds the number of BWT positions the share emits.  The caller holds the ShareList while it sorts.
+template <class I>
+struct ShareList {
+  DBuf<I> idx;                       // the positions, ascending
+  uint64_t n = 0, slot_base = 0, range_emits = 0;
+  DBuf<unsigned long long> sums;     // the device scalars behind them: held until the sorter returns, as they always have been
+  DBuf<uint64_t> cnt_d;              // (1 KiB that the pool's peak counts)
+};
+// flag_pad: bytes behind the N flags, zeroed.  Nothing reads them (flag_count_kernel and flag_place_kernel stop at N); the parse's
+// sorter has always asked for 16, and N + 16 bytes are another request to the pool than N where N mod 512 is 0 or above 496.
+template <class I, class FlagPass>
+static void select_share(pfp_ctx *c, uint64_t N, size_t flag_pad, FlagPass &&flag_pass, ShareList<I> &sh) {
+  DBuf<uint8_t> flag(c, N + flag_pad);
+  if (flag_pad) PFP_HIP(hipMemsetAsync(flag.p + N, 0, flag_pad, c->stream));
+  sh.sums.alloc(c, 2);
+  sh.sums.zero();
+  const bool counted = flag_pass(flag.p, sh.sums.p);
+  sh.n = count_flags(c, flag.p, N);      // the share's size first: its index list is then exactly that long
+  PFP_REQUIRE(sizeof(I) == 8 || sh.n < 0xFFFFFFF0ull, PFP_ELIMIT, "a share of the suffix array too large for 32-bit slots");
+  sh.idx.alloc(c, std::max<uint64_t>(sh.n, 1));
+  sh.cnt_d.alloc(c, 1);
+  select_index<I>(c, flag.p, sh.idx.p, sh.cnt_d.p, N);
+  PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, sh.sums.p, 16, hipMemcpyDeviceToHost, c->stream));
+  sync(c);
+  sh.slot_base = c->h_scalars[1];
+  sh.range_emits = counted ? c->h_scalars[2] : 0;
+}
+template <class I>
+static void set_share(SuffixOrderT<I> &out, const Splitters &sp, const ShareList<I> &sh) {
+  out.slot_base = sh.slot_base; out.klo = sp.klo; out.khi = sp.khi_open ? ~0ull : sp.khi; out.range_emits = sh.range_emits;
+}
+
+// -- the dictionary's share
 __global__ void sample_keys_kernel(const uint8_t *__restrict__ s, uint64_t N, uint64_t stride, uint32_t ns, KeyCode kp,
                                    uint64_t *__restrict__ key, uint32_t *__restrict__ val) {
   __shared__ uint32_t lut[256];
@@ -1679,56 +1855,21 @@ __device__ __forceinline__ int cmp_suffix_boundary(const uint8_t *__restrict__ s
   if (i == b) return 0;
 #pragma unroll 1
   for (int q = 0; q < kRangeCmp / 16; q++) {
-    const uint4 xv = ld16u(s + i + 16 * q), yv = ld16u(s + b + 16 * q);
-    const uint32_t x[4] = {xv.x, xv.y, xv.z, xv.w}, y[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t diff = x[k] ^ y[k];
-      const uint32_t term = (x[k] - 0x02020202u) & ~x[k] & 0x80808080u;      // bytes < 2 of x (lowest flag exact)
-      if (diff | term) {
-        const int fd = diff ? (__builtin_ctz(diff) >> 3) : 4, ft = term ? (__builtin_ctz(term) >> 3) : 4;
-        if (ft < fd) return 0;                                    // both end before they differ: the same string
-        const uint32_t bx = (x[k] >> (8 * fd)) & 0xffu, by = (y[k] >> (8 * fd)) & 0xffu;
-        return bx < by ? -1 : 1;
-      }
-    }
+    const uint4 x = ld16u(s + i + 16 * q), y = ld16u(s + b + 16 * q);
+    int r = cmp_term8((uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)y.x | ((uint64_t)y.y << 32));
+    if (r == kCmpOn) r = cmp_term8((uint64_t)x.z | ((uint64_t)x.w << 32), (uint64_t)y.z | ((uint64_t)y.w << 32));
+    if (r != kCmpOn) return r;
   }
   return 0;      // equal for kRangeCmp bytes: upper side
-}
-// the first 16 bytes of both suffixes in registers (two 64-bit words each); the full compare only where they do not decide
-__device__ __forceinline__ int cmp_head16(const uint4 xv, const uint4 yv, const uint8_t *__restrict__ s, uint64_t i, uint64_t b) {
-  const uint64_t x[2] = {(uint64_t)xv.x | ((uint64_t)xv.y << 32), (uint64_t)xv.z | ((uint64_t)xv.w << 32)};
-  const uint64_t y[2] = {(uint64_t)yv.x | ((uint64_t)yv.y << 32), (uint64_t)yv.z | ((uint64_t)yv.w << 32)};
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const uint64_t diff = x[k] ^ y[k];
-    const uint64_t term = (x[k] - 0x0202020202020202ull) & ~x[k] & 0x8080808080808080ull;      // bytes < 2 of x (lowest flag exact)
-    if (diff | term) {
-      const int fd = diff ? (__builtin_ctzll(diff) >> 3) : 8, ft = term ? (__builtin_ctzll(term) >> 3) : 8;
-      if (ft < fd) return 0;
-      const uint32_t bx = (uint32_t)(x[k] >> (8 * fd)) & 0xffu, by = (uint32_t)(y[k] >> (8 * fd)) & 0xffu;
-      return bx < by ? -1 : 1;
-    }
-  }
-  return cmp_suffix_boundary(s, i, b);      // (16 equal bytes: rare)
 }
 // the same with four consecutive positions per thread: their heads come out of five ALIGNED dwords (byte shifts) instead of four
 // unaligned 16-byte loads and four byte loads, the four flags leave as one dword - the one-position form is bound by its byte-wide
 // memory instructions, not by the compares.  1024 positions per workgroup.
+// (cmp_words16: the first 16 bytes of both suffixes in registers, two 64-bit words each; the full compare only where they do not decide)
 __device__ __forceinline__ int cmp_words16(uint64_t x0, uint64_t x1, uint64_t y0, uint64_t y1, const uint8_t *__restrict__ s, uint64_t i, uint64_t b) {
-  const uint64_t x[2] = {x0, x1}, y[2] = {y0, y1};
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const uint64_t diff = x[k] ^ y[k];
-    const uint64_t term = (x[k] - 0x0202020202020202ull) & ~x[k] & 0x8080808080808080ull;
-    if (diff | term) {
-      const int fd = diff ? (__builtin_ctzll(diff) >> 3) : 8, ft = term ? (__builtin_ctzll(term) >> 3) : 8;
-      if (ft < fd) return 0;
-      const uint32_t bx = (uint32_t)(x[k] >> (8 * fd)) & 0xffu, by = (uint32_t)(y[k] >> (8 * fd)) & 0xffu;
-      return bx < by ? -1 : 1;
-    }
-  }
-  return i == b ? 0 : cmp_suffix_boundary(s, i, b);
+  int r = cmp_term8(x0, y0);
+  if (r == kCmpOn) r = cmp_term8(x1, y1);
+  return r != kCmpOn ? r : i == b ? 0 : cmp_suffix_boundary(s, i, b);      // (16 equal bytes: rare)
 }
 __global__ __launch_bounds__(256) void range_flags_cmp4_kernel(const uint8_t *__restrict__ s, uint64_t N, uint64_t b_lo, int has_lo,
                                                                uint64_t b_hi, int has_hi, SlotPayloadSrc count, int want_count,
@@ -1794,19 +1935,6 @@ __global__ __launch_bounds__(256) void range_flags_cmp4_kernel(const uint8_t *__
     tile_emits[BID] = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
   }
 }
-__global__ __launch_bounds__(256) void sum2_u64_kernel(const unsigned long long *__restrict__ a, const unsigned long long *__restrict__ b,
-                                                       uint64_t n, unsigned long long *__restrict__ out) {
-  __shared__ unsigned long long ws[2][4];
-  unsigned long long x = 0, y = 0;
-  for (uint64_t i = (uint64_t)BID * 256 + threadIdx.x; i < n; i += (uint64_t)GDIM * 256) { x += a[i]; y += b[i]; }
-  for (int o = 32; o > 0; o >>= 1) { x += __shfl_down(x, o, 64); y += __shfl_down(y, o, 64); }
-  if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = x; ws[1][threadIdx.x >> 6] = y; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicAdd(out, ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3]);
-    atomicAdd(out + 1, ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3]);
-  }
-}
 template <class I>
 __global__ __launch_bounds__(256) void init_keys_list_kernel(const uint8_t *__restrict__ s, uint64_t n, KeyCode kp,
                                                              const I *__restrict__ idx,
@@ -1822,36 +1950,10 @@ __global__ __launch_bounds__(256) void init_keys_list_kernel(const uint8_t *__re
   key[a] = k; val[a] = i;
 }
 
-// the suffixes of a LIST of positions (ascending) sorted among themselves: first-round keys position by position, then the
-// rounds of doubling() in its range mode (no rank per dictionary position; out.complete == false where only a doubling
-// round - ranks of suffixes outside the list - could go on).  Releases idx.
-template <class I>
-static void sort_suffix_list(pfp_ctx *c, const SufGeom &g, const KeyCode &kc, int idx_bits, DBuf<I> &idx, uint64_t n, SuffixOrderT<I> &out) {
-  DBuf<uint64_t> key(c, std::max<uint64_t>(n, 1));
-  DBuf<I> val;
-  if (!idx_bits) val.alloc(c, std::max<uint64_t>(n, 1));
-  out.paybits = 0;
-  out.keymask = kc.kbits + 1 >= 64 ? ~0ull : ((1ull << (kc.kbits + 1)) - 1);
-  if (n) {
-    KScope ks(c, "pfp::init_keys_list_kernel", (uint64_t)n * 17);
-    hipLaunchKernelGGL(init_keys_list_kernel<I>, gdim(cdiv(n, 256)), gdim(256), 0, c->stream, g.wv.bytes, (uint64_t)n, kc, idx.p, key.p, val.p,
-                       idx_bits);
-  }
-  idx.release();
-  out.lut.alloc(c, 256);
-  PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
-  sync(c);      // kc may be a stack object of the caller
-  out.bytes = g.wv.bytes; out.kbits = kc.kbits;
-  DoublingOpts o;
-  o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = n, o.idx_bits = idx_bits;
-  doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
-}
-
 template <class I>
 void sort_dict_suffixes_range(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, uint32_t part,
                               uint32_t parts, SuffixOrderT<I> &out, const SlotPayloadSrc *pay, const SlotPayloadSrc *count) {
-  PFP_REQUIRE(N >= 1 && (sizeof(I) == 8 ? N < (1ull << 40) : N < 0xFFFFFFF0ull), PFP_ELIMIT,
-              sizeof(I) == 8 ? "dictionary of 2^40 bytes or more" : "dictionary too large for 32-bit suffix indices");
+  require_dict_size<I>(N);
   PFP_REQUIRE(parts >= 1 && part < parts, PFP_EINVAL, "bad key-range share");
   SufGeom g{MODE_DICT, N, wv};
   KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint);
@@ -1859,61 +1961,47 @@ void sort_dict_suffixes_range(pfp_ctx *c, const uint8_t *bytes, uint64_t N, cons
   // splitters: every stride-th suffix's key, sorted; the same on every rank.  The share is cut by comparing every suffix with the
   // boundary SUFFIXES (range_flags_cmp4_kernel) - boundaries with distinct keys, so that they stand in the order they are used in
   // (the two earlier forms - a first-round key per position, one position per thread - went with round 4)
-  uint64_t klo = 0, khi = ~0ull, b_lo = 0, b_hi = 0;
-  bool has_lo = false, has_hi = false;
-  if (parts > 1) {
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(N, 1u << 16);
-    const uint64_t stride = N / ns;
-    DBuf<uint64_t> sk(c, ns), sko(c, ns);
-    DBuf<uint32_t> sv(c, ns), svo(c, ns);
-    hipLaunchKernelGGL(sample_keys_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, bytes, N, stride, ns, kc, sk.p, sv.p);
-    sort_pairs_u64_u32(c, sk.p, sko.p, sv.p, svo.p, ns, 0, 64);
-    std::vector<uint64_t> hs(ns);
-    std::vector<uint32_t> hv(ns);
-    PFP_HIP(hipMemcpyAsync(hs.data(), sko.p, (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(hipMemcpyAsync(hv.data(), svo.p, (size_t)ns * 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    if (part > 0) klo = hs[(uint64_t)part * ns / parts];
-    if (part + 1 < parts) khi = hs[(uint64_t)(part + 1) * ns / parts];
-    // boundary of part q (q >= 1): the sample at q ns / parts - or the boundary before it, if that sample's key is no larger
-    // (equal keys do not say which suffix is the smaller: such a part holds nothing)
-    auto boundary = [&](uint32_t q, uint64_t &pos) {
-      uint64_t prev_key = 0; bool have = false;
-      for (uint32_t t = 1; t <= q; t++) {
-        const uint64_t at = (uint64_t)t * ns / parts;
-        if (!have || hs[at] > prev_key) { pos = (uint64_t)hv[at] * stride; prev_key = hs[at]; have = true; }
-      }
-      return have;
-    };
-    if (part > 0) has_lo = boundary(part, b_lo);
-    if (part + 1 < parts) has_hi = boundary(part + 1, b_hi);
-  }
-  const int khi_open = part + 1 == parts ? 1 : 0;
-  DBuf<uint8_t> flag(c, N);
-  DBuf<unsigned long long> below(c, 2);
-  below.zero();
-  {
+  const Splitters sp = share_splitters(c, N, part, parts, true, [&](uint64_t stride, uint32_t ns, uint64_t *sk, uint32_t *sv) {
+    hipLaunchKernelGGL(sample_keys_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, bytes, N, stride, ns, kc, sk, sv);
+  });
+  // boundary of part q (q >= 1): the sample at q ns / parts - or the boundary before it, if that sample's key is no larger
+  // (equal keys do not say which suffix is the smaller: such a part holds nothing)
+  auto boundary = [&](uint32_t q, uint64_t &pos) {
+    uint64_t prev_key = 0; bool have = false;
+    for (uint32_t t = 1; t <= q; t++) {
+      const uint64_t ns = sp.hs.size(), at = (uint64_t)t * ns / parts;
+      if (!have || sp.hs[at] > prev_key) { pos = (uint64_t)sp.hv[at] * (N / ns); prev_key = sp.hs[at]; have = true; }
+    }
+    return have;
+  };
+  uint64_t b_lo = 0, b_hi = 0;
+  const bool has_lo = part > 0 && boundary(part, b_lo), has_hi = part + 1 < parts && boundary(part + 1, b_hi);
+  ShareList<I> sh;
+  select_share<I>(c, N, 0, [&](uint8_t *flag, unsigned long long *sums) {
     const uint64_t nblk = cdiv64(N, 1024);
     DBuf<unsigned long long> tb(c, nblk), te(c, nblk);
     KScope ks(c, "pfp::range_flags_cmp4_kernel", N * 2);
     hipLaunchKernelGGL(range_flags_cmp4_kernel, gdim((unsigned)nblk), gdim(256), 0, c->stream, bytes, N, b_lo, has_lo ? 1 : 0, b_hi,
-                       has_hi ? 1 : 0, count ? *count : SlotPayloadSrc{}, count ? 1 : 0, flag.p, tb.p, te.p);
-    hipLaunchKernelGGL(sum2_u64_kernel, gdim((int)std::min<uint64_t>(cdiv64(nblk, 256), 256)), gdim(256), 0, c->stream, tb.p, te.p, nblk,
-                       below.p);
+                       has_hi ? 1 : 0, count ? *count : SlotPayloadSrc{}, count ? 1 : 0, flag, tb.p, te.p);
+    sum_tiles(c, tb.p, te.p, nblk, sums);
+    return true;      // (zeros where no count was asked for)
+  }, sh);
+  // the suffixes of a LIST of positions (ascending) sorted among themselves: first-round keys position by position, then the
+  // rounds of doubling() in its range mode (no rank per dictionary position; out.complete == false where only a doubling
+  // round - ranks of suffixes outside the list - could go on).
+  const uint64_t n = sh.n;
+  DBuf<uint64_t> key(c, std::max<uint64_t>(n, 1));
+  DBuf<I> val;
+  if (!idx_bits) val.alloc(c, std::max<uint64_t>(n, 1));
+  out.paybits = 0;
+  if (n) {
+    KScope ks(c, "pfp::init_keys_list_kernel", (uint64_t)n * 17);
+    hipLaunchKernelGGL(init_keys_list_kernel<I>, gdim(cdiv(n, 256)), gdim(256), 0, c->stream, g.wv.bytes, n, kc, sh.idx.p, key.p, val.p, idx_bits);
   }
-  const uint64_t n_mine = count_flags(c, flag.p, N);      // the share's size first: its index list is then exactly that long
-  PFP_REQUIRE(sizeof(I) == 8 || n_mine < 0xFFFFFFF0ull, PFP_ELIMIT, "a share of the suffix array too large for 32-bit slots");
-  DBuf<I> idx(c, std::max<uint64_t>(n_mine, 1));
-  DBuf<uint64_t> cnt_d(c, 1);
-  select_index<I>(c, flag.p, idx.p, cnt_d.p, N);
-  PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, below.p, 16, hipMemcpyDeviceToHost, c->stream));
-  sync(c);
-  const uint64_t slot_base = c->h_scalars[1];
-  const uint64_t range_emits = c->h_scalars[2];
-  flag.release();
-  sort_suffix_list<I>(c, g, kc, idx_bits, idx, n_mine, out);
+  sh.idx.release();
+  dict_rounds<I>(c, g, g.wv.bytes, kc, idx_bits, n, key, val, out);
   (void)pay;      // (no merge records in the keys of a share: its positions are a scattered list, every record would be a word lookup)
-  out.slot_base = slot_base; out.klo = klo; out.khi = khi_open ? ~0ull : khi; out.range_emits = range_emits;
+  set_share(out, sp, sh);
 }
 template void sort_dict_suffixes_range<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, uint32_t, uint32_t,
                                                  SuffixOrderT<uint32_t> &, const SlotPayloadSrc *, const SlotPayloadSrc *);
@@ -1942,70 +2030,7 @@ void gather_slots_range(pfp_ctx *c, const SuffixOrderT<I> &so, const WordView &w
 template void gather_slots_range<uint32_t>(pfp_ctx *, const SuffixOrderT<uint32_t> &, const WordView &, uint64_t, uint64_t *);
 template void gather_slots_range<uint64_t>(pfp_ctx *, const SuffixOrderT<uint64_t> &, const WordView &, uint64_t, uint64_t *);
 
-// (Tried in round 3 and removed: "grouped order without sorting duplicates".  Equal suffixes of a dictionary of variants can be
-//  read off the WORDS: sort the d words by their reversed strings, keep the longest common suffix lcs[r] of neighbours; the
-//  suffix of length L of the word at rank r duplicates its left neighbour's iff lcs[r] >= L, so only one representative per
-//  distinct string (71 M of 129 M suffixes on the 64-copy workload) is suffix-sorted - as a list - and every sorted
-//  representative is expanded into its run of words.  Bit-exact on all goldens, half the peak memory (12.6 GB input: 165 ->
-//  90 GB) - and slower: the dictionary sort went 20.0 -> 22.2 ms (64 copies) and 354 -> 434 ms (1024 copies).  The first
-//  round shrinks (radix 3.8 -> 2.2 ms, pivot 6.8 -> 4.9 ms), but with the identical strings gone every remaining tie is a real
-//  difference: 7 rounds instead of 5 (23 pivot launches instead of 7 on 1024 copies), and finding the runs and laying out
-//  the slots costs 4.5 ms / 87 ms.  It would pay if the MERGE worked on the 71 M groups instead of 129 M slots (sums over
-//  a run from prefix sums, "all chars equal" from a range minimum over lcs[]): DESIGN.md 7b.)
-
-template <class I>
-void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrderT<I> &out) {
-  PFP_REQUIRE(N >= 1 && (sizeof(I) == 8 ? N < (1ull << 40) : N < 0xFFFFFFF0ull), PFP_ELIMIT, "text too large for the suffix index width");
-  SufGeom g{MODE_PLAIN, N, WordView{}};
-  DBuf<uint64_t> key(c, N);
-  DBuf<I> val(c, N);
-  { KScope ks(c, "pfp::init_keys_bytes_kernel", N * (16 + sizeof(I)));
-    hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p); }
-  doubling<I>(c, g, key, val, 8, out, DoublingOpts{});
-}
-template void sort_byte_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint32_t> &);
-template void sort_byte_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint64_t> &);
-
-void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder &out, uint32_t max_sym, const uint32_t *occ,
-                       uint32_t n_sym) {
-  PFP_REQUIRE(N >= 1 && N < 0xFFFFFFF0ull, PFP_ELIMIT, "parse too large for 32-bit suffix indices");
-  SufGeom g{MODE_PLAIN, N, WordView{}};
-  DBuf<uint64_t> key(c, N);
-  DBuf<uint32_t> val(c, N);
-  // the symbol width is measured, not taken on trust (max_sym is only an upper bound for the check)
-  DBuf<uint32_t> mx(c, 1);
-  mx.zero();
-  hipLaunchKernelGGL(max_u32_kernel, gdim((int)std::min<uint64_t>(cdiv64(N, 256), 1024)), gdim(256), 0, c->stream, sym, N, mx.p);
-  const uint32_t real_max = read_scalar(c, mx.p);
-  PFP_REQUIRE(real_max <= max_sym, PFP_EFORMAT, "integer string holds a symbol above its alphabet size");
-  const int sb = bits_for(real_max);
-  g.sym = sym;
-  // occ[x - 1] = occurrences of symbol x (the parse: the words' counts): rare = fewer than the mean; dist[] for the pivot rounds
-  DBuf<uint32_t> dist;
-  if (occ && n_sym && N >= parse_pivot_min()) {
-    DBuf<uint32_t> mk(c, N), pm(c, N);
-    dist.alloc(c, N);
-    const uint32_t below = (uint32_t)std::max<uint64_t>(2, N / n_sym);
-    hipLaunchKernelGGL(rare_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, occ, n_sym, below, mk.p);
-    inclusive_max_u32(c, mk.p, pm.p, N);
-    hipLaunchKernelGGL(rare_dist_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, (uint32_t)N, pm.p, dist.p);
-    g.dist = dist.p;
-  }
-  if (64 - 2 * sb >= 6) {
-    DBuf<uint32_t> v(c, N), pm(c, N);
-    KScope ks(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
-    hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
-    inclusive_max_u32(c, v.p, pm.p, N);
-    hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, key.p,
-                       val.p);
-  } else {
-    KScope ks(c, "pfp::init_keys_int_kernel", N * (8 + 8 + 4));
-    hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, key.p, val.p);
-  }
-  doubling<uint32_t>(c, g, key, val, 2, out, DoublingOpts{});
-}
-
-// ---- one rank's share of the parse's suffix array (multi-GPU chain).  The parse is replicated, its suffix array was too; with the
+// -- one rank's share of the parse's suffix array.  The parse is replicated, its suffix array was too; with the
 // pivot round above a rank can sort the suffixes whose first-round key falls in its range without anybody's ranks, exactly as it
 // sorts its share of the dictionary: the same keys for all N positions (a streaming pass), splitters from a deterministic sample
 // (identical on every rank), the range's positions as a list, first sort + pivot round + comparison finisher on the list.
@@ -2040,76 +2065,35 @@ void sort_int_suffixes_range(pfp_ctx *c, const uint32_t *sym, uint64_t N, uint32
   PFP_REQUIRE(N >= 1 && N < 0xFFFFFFF0ull, PFP_ELIMIT, "parse too large for 32-bit suffix indices");
   PFP_REQUIRE(parts >= 1 && part < parts && occ && n_sym, PFP_EINVAL, "bad share of the parse's suffix array");
   SufGeom g{MODE_PLAIN, N, WordView{}};
-  DBuf<uint32_t> mx(c, 1);
-  mx.zero();
-  hipLaunchKernelGGL(max_u32_kernel, gdim((int)std::min<uint64_t>(cdiv64(N, 256), 1024)), gdim(256), 0, c->stream, sym, N, mx.p);
-  const uint32_t real_max = read_scalar(c, mx.p);
-  PFP_REQUIRE(real_max <= max_sym, PFP_EFORMAT, "integer string holds a symbol above its alphabet size");
-  const int sb = bits_for(real_max);
-  g.sym = sym;
-  DBuf<uint32_t> dist(c, N);
-  {
-    KScope ks(c, "pfp::rare_dist_kernel", N * 24);      // (+ rare_marks_kernel and the running maximum between them)
-    DBuf<uint32_t> mk(c, N), pm(c, N);
-    const uint32_t below = (uint32_t)std::max<uint64_t>(2, N / n_sym);
-    hipLaunchKernelGGL(rare_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, occ, n_sym, below, mk.p);
-    inclusive_max_u32(c, mk.p, pm.p, N);
-    hipLaunchKernelGGL(rare_dist_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, (uint32_t)N, pm.p, dist.p);
-    g.dist = dist.p;
-  }
-  DBuf<uint64_t> key(c, N);
-  {
-    KScope ks(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
-    DBuf<uint32_t> val(c, N);
-    if (64 - 2 * sb >= 6) {
-      DBuf<uint32_t> v(c, N), pm(c, N);
-      hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
-      inclusive_max_u32(c, v.p, pm.p, N);
-      hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, key.p, val.p);
-    } else {
-      hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, key.p, val.p);
-    }
-  }
-  uint64_t klo = 0, khi = ~0ull;
-  if (parts > 1) {
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(N, 1u << 16);
-    const uint64_t stride = N / ns;
-    DBuf<uint64_t> sk(c, ns), sko(c, ns);
-    DBuf<uint32_t> sv(c, ns), svo(c, ns);
-    hipLaunchKernelGGL(sample_u64_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, key.p, stride, ns, sk.p, sv.p);
-    sort_pairs_u64_u32(c, sk.p, sko.p, sv.p, svo.p, ns, 0, 64);
-    std::vector<uint64_t> hs(ns);
-    PFP_HIP(hipMemcpyAsync(hs.data(), sko.p, (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    if (part > 0) klo = hs[(uint64_t)part * ns / parts];
-    if (part + 1 < parts) khi = hs[(uint64_t)(part + 1) * ns / parts];
-  }
-  const int khi_open = part + 1 == parts ? 1 : 0;
+  IntKeys k;
+  k.dist.alloc(c, N);
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, true, "pfp::rare_dist_kernel", "pfp::init_keys_int_run_kernel", N * 28, k);
+  k.val.release();      // unread: the list's values are gathered from the positions
+  const Splitters sp = share_splitters(c, N, part, parts, false, [&](uint64_t stride, uint32_t ns, uint64_t *sk, uint32_t *sv) {
+    hipLaunchKernelGGL(sample_u64_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, k.key.p, stride, ns, sk, sv);
+  });
   std::optional<KScope> ks_sel;      // (ended before the list is sorted)
   ks_sel.emplace(c, "pfp::range_flags_u64_kernel", N * 10);      // (+ the flag count and the index selection)
-  DBuf<uint8_t> flag(c, N + 16);
-  PFP_HIP(hipMemsetAsync(flag.p + N, 0, 16, c->stream));
-  const uint64_t nblk = cdiv64(N, 256);
-  DBuf<unsigned long long> below(c, 2), tb(c, nblk);
-  below.zero();
-  hipLaunchKernelGGL(range_flags_u64_kernel, gdim(nblk), gdim(256), 0, c->stream, key.p, N, klo, khi, khi_open, flag.p, tb.p);
-  hipLaunchKernelGGL(sum2_u64_kernel, gdim((int)std::min<uint64_t>(cdiv64(nblk, 256), 256)), gdim(256), 0, c->stream, tb.p, tb.p, nblk, below.p);
-  const uint64_t n_mine = count_flags(c, flag.p, N);
-  DBuf<uint32_t> idx(c, std::max<uint64_t>(n_mine, 1));
-  DBuf<uint64_t> cnt_d(c, 1);
-  select_index<uint32_t>(c, flag.p, idx.p, cnt_d.p, N);
-  const uint64_t slot_base = read_scalar(c, (const uint64_t *)below.p);
-  flag.release();
-  DBuf<uint64_t> lkey(c, std::max<uint64_t>(n_mine, 1));
-  DBuf<uint32_t> lval(c, std::max<uint64_t>(n_mine, 1));
-  if (n_mine) hipLaunchKernelGGL(gather_list_keys_kernel, gdim(cdiv(n_mine, 256)), gdim(256), 0, c->stream, n_mine, idx.p, key.p, lkey.p, lval.p);
+  DBuf<unsigned long long> tb;       // (one sum per tile of 256 keys; held until the sorter returns, as it always has been)
+  ShareList<uint32_t> sh;
+  select_share<uint32_t>(c, N, 16, [&](uint8_t *flag, unsigned long long *sums) {
+    const uint64_t nblk = cdiv64(N, 256);
+    tb.alloc(c, nblk);
+    hipLaunchKernelGGL(range_flags_u64_kernel, gdim(nblk), gdim(256), 0, c->stream, k.key.p, N, sp.klo, sp.khi, sp.khi_open, flag, tb.p);
+    sum_tiles(c, tb.p, tb.p, nblk, sums);
+    return false;
+  }, sh);
+  DBuf<uint64_t> lkey(c, std::max<uint64_t>(sh.n, 1));
+  DBuf<uint32_t> lval(c, std::max<uint64_t>(sh.n, 1));
+  if (sh.n) hipLaunchKernelGGL(gather_list_keys_kernel, gdim(cdiv(sh.n, 256)), gdim(256), 0, c->stream, sh.n, sh.idx.p, k.key.p, lkey.p, lval.p);
   PFP_HIP(hipGetLastError());
-  key.release(); idx.release();
+  k.key.release(); sh.idx.release();
   ks_sel.reset();
   DoublingOpts o;
-  o.list_len = n_mine;
+  o.list_len = sh.n;
   doubling<uint32_t>(c, g, lkey, lval, 2, out, o);
-  out.slot_base = slot_base; out.klo = klo; out.khi = khi_open ? ~0ull : khi;
+  set_share(out, sp, sh);
 }
 
 }  // namespace pfp
+
