@@ -1,6 +1,6 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
-// of a collection (seqmap.hip); extending seeds (fmextend.hip).
+// of a collection (seqmap.hip); extending seeds (fmextend.hip) and their edit scripts (fmcigar.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
 // (HostOut::take, fetch_group_offsets).
@@ -640,6 +640,43 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
     h_dist.take(c, g_dist.p, keys.total);
   }
   *start = h_start.release(); *end = h_end.release(); *dist = h_dist.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- edit scripts (fmcigar.hip)
+int pfp_fm_cigar_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_aln_pat,
+                     const uint64_t *d_start, const uint64_t *d_end, uint64_t naln, int k, uint8_t *d_dist, uint64_t *d_cig_off,
+                     uint32_t *d_cig) {
+  if (!fm || !d_cig_off || (npat && !d_pat_off) || (naln && (!d_aln_pat || !d_start || !d_end || !d_dist))) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    fm_cigar(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_aln_pat, d_start, d_end, naln, k, d_dist, d_cig_off, d_cig);
+  });
+}
+
+int pfp_fm_cigar(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *aln_pat, const uint64_t *start,
+                 const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, uint32_t **cig) {
+  if (!fm || !cig_off || !cig || (npat && !pat_off) || (naln && (!aln_pat || !start || !end || !dist))) return PFP_EINVAL;
+  *cig = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_extend_check(fm->f, k);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint32_t> d_ap(c, naln);
+  DBuf<uint64_t> d_span(c, 2 * naln), d_off(c, naln + 1);
+  DBuf<uint8_t> d_dist(c, naln);
+  if (naln) { h2d(c, d_ap.p, aln_pat, naln); h2d(c, d_span.p, start, naln); h2d(c, d_span.p + naln, end, naln); }
+  CigRuns runs;                                         // (every script is computed once: the runs wait in their slots for their place)
+  fm_cigar_runs(fm->f, in.pat.p, in.off.p, npat, d_ap.p, d_span.p, d_span.p + naln, naln, k, d_dist.p, d_off.p, runs);
+  DBuf<uint32_t> d_cig(c, runs.total);
+  fm_cigar_write(fm->f, runs, d_off.p, d_cig.p);
+  if (naln) d2h(c, dist, d_dist.p, naln);
+  d2h(c, cig_off, d_off.p, naln + 1);
+  sync(c);
+  HostOut<uint32_t> h_cig;
+  h_cig.take(c, d_cig.p, runs.total);
+  *cig = h_cig.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

@@ -1,4 +1,4 @@
-// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, lcp.hip, seqmap.hip).  Device side:
+// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, fmcigar.hip, lcp.hip, seqmap.hip).  Device side:
 // the index as kernel arguments, rank and select by groups of 16 lanes, the start of a group-per-pattern kernel, the steps the walks
 // share (toehold, matching-statistics start and neighbours), the 1024-byte compare, and the tiny kernels every segmented sort needs.
 // Host side: the environment's budget and stats switch, the index width as a type, the requirement checks, and the one loop that
@@ -56,6 +56,8 @@ __device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t c4) {
   const uint32_t x = w ^ c4;
   return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
 }
+// bit 7 of a byte of w set where that byte is 0
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t w) { return (w - 0x01010101u) & ~w & 0x80808080u; }
 
 // C[c] + rank_c(i) for 0 <= i <= n1; gl = this lane's place in its group of 16 (all 16 call it with the same arguments)
 template <class I>

@@ -158,9 +158,6 @@ __global__ void __launch_bounds__(kTB) fm_extend_k(const uint8_t *__restrict__ t
   if (gl == 0) { dist[ci] = (uint8_t)d; start[ci] = s; end[ci] = e; }
 }
 
-// bit 7 of a byte of w set where that byte is 0
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t w) { return (w - 0x01010101u) & ~w & 0x80808080u; }
-
 // k = 0: the pattern at its diagonal or nothing.  One group per candidate, 16 bytes per lane and step
 __global__ void __launch_bounds__(kTB) fm_extend0_k(const uint8_t *__restrict__ text, uint64_t n, const uint8_t *__restrict__ pat,
                                                     const uint64_t *__restrict__ off, uint64_t npat, const uint32_t *__restrict__ cand_pat,

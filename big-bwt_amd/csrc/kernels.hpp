@@ -450,6 +450,21 @@ void fm_align_write(FmIndex &f, const AlnKeys &keys, uint64_t *start, uint64_t *
 void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
               uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist);
 
+// edit scripts (fmcigar.hip; pfpgpu.h, "Edit scripts", states the definitions).  Device pointers; the checks are fm_extend's.
+// what fm_cigar_runs leaves for fm_cigar_write: every alignment's runs, last first, in a slot of S = 2k + 1 words
+struct CigRuns {
+  DBuf<uint32_t> slot;
+  uint64_t naln = 0, S = 0, total = 0;     // total: the runs of all alignments, which is what the output must hold
+};
+// alignment i = (aln_pat[i], start[i], end[i]) -> dist[i] (0xFF: no script) and cig_off[0..naln], the exclusive sums of the run counts
+void fm_cigar_runs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *aln_pat, const uint64_t *start,
+                   const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, CigRuns &out);
+// the runs in order, alignment i's at cig_off[i] .. cig_off[i + 1]: room for runs.total entries
+void fm_cigar_write(FmIndex &f, const CigRuns &runs, const uint64_t *cig_off, uint32_t *cig);
+// fm_cigar_runs and, where cig is given, fm_cigar_write
+void fm_cigar(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *aln_pat, const uint64_t *start,
+              const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, uint32_t *cig);
+
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);
 void validate_dictionary(pfp_ctx *c, const Dictionary &D, int w);

@@ -4,7 +4,7 @@
  *   bwtsearch --ms | --mems L [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch -l --seqs[=FILE] | --docs [--seqs=FILE] ... PATTERNFILE basename        (any mode: --rc)
  *   bwtsearch -k K [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
- *   bwtsearch --align K [--seed L] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
+ *   bwtsearch --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -32,6 +32,9 @@
  * deletions).  The line becomes `count<TAB>start:end:d start:end:d ...`: the distinct alignments T[start..end) with their edit
  * distances, ordered by (d, start, end), at most MAXALN of them (0: all); count stays their number before the cap.  It reads the
  * files --mems reads and takes --text and --thresholds as --mems does.  Not with -l, -k, --ms, --mems, --docs or --seqs.
+ * --cigar (with --align only) adds every alignment's edit script (the definitions: include/pfpgpu.h, "Edit scripts"): the items
+ * become `start:end:d:CIGAR`, the runs as length and operation, `=` a match, `X` a substitution, `I` a pattern byte without a text
+ * byte, `D` a text byte without a pattern byte, e.g. 57=1X20=1I72=; `*` for the empty script.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -54,7 +57,7 @@ static void usage(const char *argv0) {
          "       %s --docs [--seqs=FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n"
-         "       %s --align K [--seed L] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
+         "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -70,6 +73,8 @@ static void usage(const char *argv0) {
          "                  count<TAB>start:end:d ... : the distinct alignments T[start..end) by (d, start, end), at most MAXALN (-m)\n"
          "                  of them; reads the files --mems reads (not with -l, -k, --ms, --mems, --docs, --seqs)\n"
          "      --seed L    with --align: the seeds are the maximal exact matches of at least L >= 1 bytes (def. 20, a choice)\n"
+         "      --cigar     with --align: print count<TAB>start:end:d:CIGAR ... : every alignment with its edit script, runs of\n"
+         "                  = (match), X (substitution), I (pattern byte alone), D (text byte alone); * for the empty script\n"
          "      --text FILE with --ms / --mems / --align: the text (def. inverted from basename.bwt)\n"
          "      --thresholds with --ms / --mems / --align: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
@@ -121,7 +126,7 @@ typedef struct {
   pfp_ctx *ctx; pfp_fm *fm; const char *base; const pfp_seqs *tab;
   const uint8_t *pat; const uint64_t *off; uint64_t k, *oo, *sp, *ep;
   uint64_t maxocc, min_len, seed;
-  int thresholds, locate, kmis, kedit;
+  int thresholds, locate, kmis, kedit, cigar;
 } batch_t;
 
 static int fail(const char *what, int rc, pfp_ctx *ctx) {
@@ -165,19 +170,48 @@ static int mode_mems(const batch_t *b) {
   return 0;
 }
 
+/* --cigar: the edit scripts of a batch's alignments, alignment j = (its pattern by oo, as[j], ae[j]): *coff (their number + 1
+ * offsets) and *cig (the runs); 0, or 1 after the error went to stderr */
+static int align_scripts(const batch_t *b, const uint64_t *as, const uint64_t *ae, uint64_t **coff, uint32_t **cig) {
+  const uint64_t *oo = b->oo, total = oo[b->k];
+  uint32_t *ap = malloc((total + 1) * sizeof(uint32_t));
+  uint8_t *cd = malloc(total + 1);
+  *coff = malloc((total + 1) * sizeof(uint64_t));
+  int rc = 1;
+  if (!ap || !cd || !*coff) fprintf(stderr, "out of memory\n");
+  else {
+    for (uint64_t i = 0; i < b->k; i++)
+      for (uint64_t j = oo[i]; j < oo[i + 1]; j++) ap[j] = (uint32_t)i;
+    if ((rc = pfp_fm_cigar(b->fm, b->pat, b->off, b->k, ap, as, ae, total, b->kedit, cd, *coff, cig)) != 0) rc = fail(b->base, rc, b->ctx);
+  }
+  free(ap); free(cd);
+  return rc;
+}
+
+static void print_script(const uint32_t *run, uint64_t nrun) {
+  if (!nrun) putchar('*');
+  for (uint64_t r = 0; r < nrun; r++) printf("%" PRIu32 "%c", run[r] >> 4, "MIDNSHP=X???????"[run[r] & 15]);
+}
+
 static int mode_align(const batch_t *b) {
-  uint64_t *as = NULL, *ae = NULL, *oo = b->oo;
+  uint64_t *as = NULL, *ae = NULL, *oo = b->oo, *coff = NULL;
   uint8_t *ad = NULL;
-  const int rc = pfp_fm_align(b->fm, b->pat, b->off, b->k, b->seed, b->kedit, 0, b->thresholds, oo, &as, &ae, &ad);
+  uint32_t *cig = NULL;
+  int rc = pfp_fm_align(b->fm, b->pat, b->off, b->k, b->seed, b->kedit, 0, b->thresholds, oo, &as, &ae, &ad);
   if (rc) return fail(b->base, rc, b->ctx);
-  for (uint64_t i = 0; i < b->k; i++) {
+  if (b->cigar) rc = align_scripts(b, as, ae, &coff, &cig);
+  for (uint64_t i = 0; !rc && i < b->k; i++) {
     const uint64_t cnt = oo[i + 1] - oo[i], shown = b->maxocc && b->maxocc < cnt ? b->maxocc : cnt;
     printf("%" PRIu64 "\t", cnt);
-    for (uint64_t j = oo[i]; j < oo[i] + shown; j++) { sep(j, oo[i]); printf("%" PRIu64 ":%" PRIu64 ":%u", as[j], ae[j], (unsigned)ad[j]); }
+    for (uint64_t j = oo[i]; j < oo[i] + shown; j++) {
+      sep(j, oo[i]);
+      printf("%" PRIu64 ":%" PRIu64 ":%u", as[j], ae[j], (unsigned)ad[j]);
+      if (b->cigar) { putchar(':'); print_script(cig + coff[j], coff[j + 1] - coff[j]); }
+    }
     putchar('\n');
   }
-  pfp_free(as); pfp_free(ae); pfp_free(ad);
-  return 0;
+  pfp_free(as); pfp_free(ae); pfp_free(ad); pfp_free(cig); free(coff);
+  return rc;
 }
 
 /* -l, -l --seqs and --docs after their call: the lines count<TAB>[name:]value ..., count = ep - sp (rows) or the number of items,
@@ -241,7 +275,7 @@ static int mode_count(const batch_t *b) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0;
   const char *seqsfile = NULL;
   pfp_seqs tab;
   pfp_seqs_init(&tab);
@@ -251,6 +285,7 @@ int main(int argc, char **argv) {
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
                                {"seqs", optional_argument, 0, 1006}, {"docs", no_argument, 0, 1007}, {"rc", no_argument, 0, 1008},
                                {"align", required_argument, 0, 1009}, {"seed", required_argument, 0, 1010},
+                               {"cigar", no_argument, 0, 1011},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -290,6 +325,7 @@ int main(int argc, char **argv) {
         if (!*optarg || *end || optarg[0] == '-' || seed < 1) { usage(argv[0]); return 2; }
         have_seed = 1;
         break;
+      case 1011: cigar = 1; break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -300,7 +336,7 @@ int main(int argc, char **argv) {
   }
   if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
       ((textfile || thresholds) && !ms && !mems && !align) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
-      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align)) {
+      (align && (locate || approx || ms || mems || docs || seqs)) || ((have_seed || cigar) && !align)) {
     usage(argv[0]);
     return 2;
   }
@@ -411,7 +447,7 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit};
+    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar};
     if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }

@@ -39,10 +39,11 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
            "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
            "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats",
-           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align"]
+           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar"]
 
 FM_APPROX_MAX_K = 3
 FM_EXTEND_MAX_K, FM_EXTEND_MAX_M = 32, 65535
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}    # the BAM codes of the operations an edit script holds
 
 LCP_LCP, LCP_THR = 1, 2
 
@@ -99,6 +100,11 @@ def read_seqs_file(path, n):
     finally:
         host.pfp_seqs_free(C.byref(t))
     return names, starts
+
+
+def cigar_string(runs):
+    """the runs of one edit script (uint32: length << 4 | op) as text, e.g. "57=1X20=1I72="; "*" for no runs"""
+    return "".join("%d%s" % (int(r) >> 4, CIGAR_OPS[int(r) & 15]) for r in runs) or "*"
 
 
 def _patterns(patterns):
@@ -241,11 +247,12 @@ class FmIndex:
                                                    C.c_void_p(d_cand_diag), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
                                                    C.c_void_p(d_start), C.c_void_p(d_end)))
 
-    def align(self, patterns, k, min_seed, max_aln=0, thresholds=False):
+    def align(self, patterns, k, min_seed, max_aln=0, thresholds=False, cigar=False):
         """seed-and-extend: every maximal exact match of at least min_seed bytes (as mems lists them; thresholds as there) is
         extended along its diagonal with at most k edits -> (aln_off, start, end, dist): pattern p's distinct alignments are
         T[start[i]:end[i]) with dist[i] (uint8) edits for i in aln_off[p]:aln_off[p+1], ordered by (dist, start, end), at most
-        max_aln of them (0: all).  A heuristic: a MEM carries one position of its string"""
+        max_aln of them (0: all).  A heuristic: a MEM carries one position of its string.  cigar=True: (aln_off, start, end,
+        dist, cig_off, cig), the alignments' edit scripts as cigar() returns them"""
         npat, _, args = self._host_patterns(patterns)
         aln_off = np.zeros(npat + 1, dtype=np.uint64)
         start, end, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
@@ -253,7 +260,35 @@ class FmIndex:
                                               C.c_int(1 if thresholds else 0), _ptr(aln_off, C.c_uint64), C.byref(start), C.byref(end),
                                               C.byref(dist)))
         total = aln_off[-1]
-        return aln_off, self._take_free(start, total, np.uint64), self._take_free(end, total, np.uint64), self._take_free(dist, total, np.uint8)
+        out = aln_off, self._take_free(start, total, np.uint64), self._take_free(end, total, np.uint64), self._take_free(dist, total, np.uint8)
+        if not cigar:
+            return out
+        aln_pat = np.repeat(np.arange(npat, dtype=np.uint32), np.diff(aln_off).astype(np.int64))
+        return out + self.cigar(patterns, aln_pat, out[1], out[2], k)[1:]
+
+    def cigar(self, patterns, aln_pat, start, end, k):
+        """the edit scripts of alignments that extend or align found, or of any spans (pfpgpu.h, "Edit scripts"; k as there).
+        Alignment i is pattern aln_pat[i] against T[start[i]:end[i]) -> (dist, cig_off, cig): dist[i] (uint8) edits, and the runs
+        cig[cig_off[i]:cig_off[i+1]] (uint32: length << 4 | op; cigar_string writes them out); 0xFF and no runs where the span
+        is not one of the text or the pattern is more than k edits from it"""
+        _, _, args = self._host_patterns(patterns)
+        ap = np.ascontiguousarray(aln_pat, dtype=np.uint32)
+        st, en = np.ascontiguousarray(start, dtype=np.uint64), np.ascontiguousarray(end, dtype=np.uint64)
+        if not (ap.shape == st.shape == en.shape) or ap.ndim != 1:
+            raise ValueError("aln_pat, start and end: three 1-D arrays of one length")
+        na = len(ap)
+        dist, cig_off = np.zeros(na, dtype=np.uint8), np.zeros(na + 1, dtype=np.uint64)
+        cig = C.POINTER(C.c_uint32)()
+        self.ctx._check(self.lib.pfp_fm_cigar(self._h, *args, _ptr(ap, C.c_uint32), _ptr(st, C.c_uint64), _ptr(en, C.c_uint64), C.c_uint64(na),
+                                              C.c_int(k), _ptr(dist, C.c_uint8), _ptr(cig_off, C.c_uint64), C.byref(cig)))
+        return dist, cig_off, self._take_free(cig, cig_off[-1], np.uint32)
+
+    def cigar_dev(self, d_pat, d_pat_off, npat, d_aln_pat, d_start, d_end, naln, k, d_dist, d_cig_off, d_cig=None):
+        """device pointers: pattern bytes, npat+1 uint64 offsets, naln uint32 pattern indices and uint64 starts and ends -> naln
+        uint8 d_dist and naln+1 uint64 d_cig_off; d_cig (uint32, room for d_cig_off[naln]) gets the runs (None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_cigar_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_aln_pat),
+                                                  C.c_void_p(d_start), C.c_void_p(d_end), C.c_uint64(naln), C.c_int(k), C.c_void_p(d_dist),
+                                                  C.c_void_p(d_cig_off), _vp(d_cig)))
 
     def align_dev(self, d_pat, d_pat_off, npat, k, min_seed, d_aln_off, d_start=None, d_end=None, d_dist=None, max_aln=0, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_aln_off; d_start / d_end (uint64) and d_dist

@@ -655,6 +655,48 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
                  int thresholds, uint64_t *aln_off, uint64_t **start, uint64_t **end, uint8_t **dist);
 
 /* ------------------------------------------------------------------------------------
+ * Edit scripts (CIGAR): which edits align a pattern to a span of the text that pfp_fm_extend* or pfp_fm_align* found - or to any
+ * other span (csrc/fmcigar.hip).  A separate call: one more banded pass over exactly P against T[s..e), which records the
+ * operation of every cell, and a walk back along the records (Ukkonen's band again; the traceback is Needleman and Wunsch's).
+ * The reference has no counterpart.  Conventions and the index as in "Extending seeds".
+ * For a pattern P of m bytes, a span 0 <= s <= e <= n of T with L = e - s, and a budget k in 0..PFP_FM_EXTEND_MAX_K:
+ *   D[i][j] = Levenshtein(P[0..i), T[s..s+j)) with unit costs; as in "Extending seeds", a pattern byte 0 equals no text byte.
+ *   operations, with the BAM codes: I = 1, D = 2, '=' = 7, X = 8.  '=' is a pattern byte that equals its text byte, X a
+ *     substitution, I a pattern byte with no text byte, D a text byte with no pattern byte.
+ *   the script of (P, s, e) is read backwards from (i, j) = (m, L) with c = D[i][j], until (0, 0):
+ *     1. i > 0, j > 0 and P[i-1] = T[s+j-1] (and not byte 0): '=', go to (i-1, j-1);
+ *     2. else i > 0, j > 0 and D[i-1][j-1] = c - 1: X, go to (i-1, j-1);
+ *     3. else i > 0 and D[i-1][j] = c - 1: I, go to (i-1, j);
+ *     4. else: D, go to (i, j-1).
+ *     Listed from the pattern's first byte this is the optimal script whose reversed operation string is the smallest under
+ *     '=' < X < I < D (tests/test_cigar_reference.py checks that against a brute force over all scripts).
+ *   The script is returned run-length encoded, one uint32 per run: length << 4 | op.  A script of cost d has at most 2d + 1 runs,
+ *     and the bound is attained.
+ *   result: dist = D[m][L] and the runs - a function of (P, T, s, e, k) alone, not of the batch, the chunks or the schedule.
+ *   no script: dist = 0xFF and no runs, where the pattern index is >= npat, the pattern's offsets decrease, s > e, e > n,
+ *     |L - m| > k, or D[m][L] > k.  The empty pattern with s = e gives dist = 0 and no runs.
+ *   For a result (d, s, e) of pfp_fm_extend* or pfp_fm_align* at the same k: dist = d, and the script neither begins nor ends
+ *     with D, because s is the largest start and e the smallest end.
+ * k outside 0..PFP_FM_EXTEND_MAX_K or an index without text: PFP_EINVAL.  A pattern of the call longer than PFP_FM_EXTEND_MAX_M:
+ * PFP_ELIMIT.  Nothing is read outside T[s..e) or the pattern's offsets.
+ * Bounds: every cell of an optimal path has |j - i| <= D[i][j] <= k, so the band is the 2k + 1 diagonals -k..k: an alignment
+ * costs m rows over a band of 16 ceil((2k + 1) / 16) cells and a walk of at most m + L steps by one lane.
+ * Device memory on top of the caller's buffers: 4 (2k + 1) bytes per alignment for its runs and 24 for the counts and the plan;
+ * the records of the pass take 4 ceil((2k + 1) / 16) bytes per pattern byte (5 above k = 23; whole blocks of 16 rows: 1.3 MB at
+ * the limits) and live only during a launch: alignments go through in consecutive chunks whose records fit 1 GiB - a choice,
+ * not a measurement; PFP_FM_CIGAR_SCRATCH=BYTES, read per call, lowers it - and one that needs more goes alone.  So the peak is
+ * min(1 GiB, all records) + 4 (2k + 1) naln + 24 naln, or one alignment's 1.3 MB where that is more.
+ * ------------------------------------------------------------------------------------ */
+/* device pointers; alignment i is (d_aln_pat[i], d_start[i], d_end[i]).  d_dist (naln, uint8) and d_cig_off (naln + 1, exclusive
+ * sums of the run counts) are filled; d_cig NULL: those only, else room for d_cig_off[naln] uint32 */
+int pfp_fm_cigar_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_aln_pat,
+                     const uint64_t *d_start, const uint64_t *d_end, uint64_t naln, int k, uint8_t *d_dist, uint64_t *d_cig_off,
+                     uint32_t *d_cig);
+/* host buffers (offsets that decrease: PFP_EINVAL); *cig is a malloc'ed array of cig_off[naln] entries (pfp_free; NULL when none) */
+int pfp_fm_cigar(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *aln_pat,
+                 const uint64_t *start, const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, uint32_t **cig);
+
+/* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
  * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
  * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
