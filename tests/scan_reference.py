@@ -100,6 +100,17 @@ def kr_cuts(text, w, p, extras=()):
     return _cuts(mask, w)
 
 
+def zero_hash_window(w):
+    """w bytes, all >= 3, whose Karp-Rabin hash is 0: the big-endian digits of a multiple of 1999999973 - the only windows a
+    modulus of 2^31 or more ever cuts"""
+    m = 1
+    while True:
+        b = (m * KR_PRIME).to_bytes(w, "big")
+        if min(b) >= 3:
+            return np.frombuffer(b, dtype=np.uint8)
+        m += 1
+
+
 def seed_contract_violations(first_window, w, p, seed, fthr, fthr_nom):
     """The contract of the window hash's seed; returns the list of violated clauses (empty: the seed is right).
       1. the first window lies inside the NOMINAL threshold exactly when the reference's Karp-Rabin hash of it is 0 mod p,

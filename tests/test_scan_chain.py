@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import scan_reference as R
+from scan_reference import zero_hash_window
 
 pytestmark = pytest.mark.gpu
 
@@ -418,17 +419,6 @@ def test_plan_sample_counts_cuts_after_the_halo(O, ctx, coll):
 
 
 # ---------------------------------------------------------------- the exact (Karp-Rabin) scan: pfp_scan against the oracle
-
-def zero_hash_window(w):
-    """w bytes, all >= 3, whose Karp-Rabin hash is 0: the big-endian digits of a multiple of 1999999973 - the only windows a
-    modulus of 2^31 or more ever cuts"""
-    m = 1
-    while True:
-        b = (m * R.KR_PRIME).to_bytes(w, "big")
-        if min(b) >= 3:
-            return np.frombuffer(b, dtype=np.uint8)
-        m += 1
-
 
 KR_MODULI = [10, 11, 64, 1 << 20, (1 << 31) - 1, 1 << 31, (1 << 32) + 1]
 
