@@ -1,6 +1,6 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
-// of a collection (seqmap.hip); extending seeds (fmextend.hip) and their edit scripts (fmcigar.hip).
+// of a collection (seqmap.hip); extending seeds (fmextend.hip), their edit scripts (fmcigar.hip) and mapping reads (fmmap.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
 // (HostOut::take, fetch_group_offsets).
@@ -677,6 +677,116 @@ int pfp_fm_cigar(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
   HostOut<uint32_t> h_cig;
   h_cig.take(c, d_cig.p, runs.total);
   *cig = h_cig.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- mapping reads (fmmap.hip)
+int pfp_fm_map_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec,
+                   int thresholds, uint64_t *d_hit_off, uint8_t *d_mapq, uint64_t *d_nhits, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                   uint64_t *d_start, uint8_t *d_dist, uint64_t *d_cig_off, uint32_t **d_cig, uint64_t *d_md_off, uint8_t **d_md) {
+  if (!fm || !d_hit_off || (npat && (!d_pat_off || !d_mapq || !d_nhits))) return PFP_EINVAL;
+  const bool fill = d_strand || d_seq || d_off || d_start || d_dist || d_cig_off || d_cig || d_md_off || d_md;
+  if (fill && !(d_strand && d_seq && d_off && d_start && d_dist && d_cig_off && d_cig && d_md_off && d_md)) return PFP_EINVAL;
+  if (fill) { *d_cig = nullptr; *d_md = nullptr; }
+  return dev_call(fm, [&] {
+    DBuf<uint32_t> cig;
+    DBuf<uint8_t> md;
+    fm_map(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, max_sec, thresholds != 0, d_hit_off, d_mapq, d_nhits, d_strand, d_seq, d_off,
+           d_start, d_dist, d_cig_off, cig, d_md_off, md);
+    if (fill) {                                         // the two buffers leave the call: blocks of the pool, as pfp_dev_free takes them
+      *d_cig = cig.p; cig.p = nullptr;
+      *d_md = md.p; md.p = nullptr;
+    }
+  });
+}
+
+int pfp_fm_map(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, int thresholds,
+               uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **start,
+               uint8_t **dist, uint64_t **cig_off, uint32_t **cig, uint64_t **md_off, uint8_t **md) {
+  if (!fm || !hit_off || !strand || !seq || !off || !start || !dist || !cig_off || !cig || !md_off || !md ||
+      (npat && (!pat_off || !mapq || !nhits)))
+    return PFP_EINVAL;
+  *strand = nullptr; *seq = nullptr; *off = nullptr; *start = nullptr; *dist = nullptr;
+  *cig_off = nullptr; *cig = nullptr; *md_off = nullptr; *md = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  FmIndex &f = fm->f;
+  fm_map_check(f, k, min_seed, thresholds != 0);
+  const uint64_t budget = seq_budget();
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
+                "read " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+  HostOut<uint8_t> h_strand, h_dist, h_md;
+  HostOut<uint32_t> h_seq, h_cig;
+  HostOut<uint64_t> h_off, h_start, h_cig_off, h_md_off;
+  hit_off[0] = 0;
+  *h_cig_off.grow(1) = 0; h_cig_off.n = 1;
+  *h_md_off.grow(1) = 0; h_md_off.n = 1;
+  if (npat) {
+    // both strands of every read, their matching statistics for the whole call, and the seeds of every pattern
+    MapReads rd;
+    fm_map_strands(f, in.pat.p, in.off.p, npat, rd);
+    in.pat.release();
+    const uint64_t bytes2 = 2 * (pat_off[npat] - pat_off[0]);
+    DBuf<uint32_t> len(c, bytes2 + 1);
+    DBuf<uint64_t> pos(c, bytes2 + 1);
+    (thresholds ? fm_ms_thr : fm_ms)(f, rd.pat.p, rd.off.p, 2 * npat, len.p, pos.p);
+    std::vector<uint64_t> moff(2 * npat + 1), roff(npat + 1), goff, go;
+    {
+      DBuf<uint64_t> d_moff(c, 2 * npat + 1);
+      fm_mems(f, rd.off.p, 2 * npat, len.p, pos.p, min_seed, d_moff.p, nullptr);
+      d2h(c, moff.data(), d_moff.p, 2 * npat + 1);
+      sync(c);
+    }
+    for (uint64_t p = 0; p <= npat; p++) roff[p] = moff[2 * p];       // a read brings the seeds of both its strands
+    for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {     // consecutive reads whose seeds stay within the budget
+      p1 = group_end(roff.data(), p0, npat, budget);
+      const uint64_t np = p1 - p0;
+      goff.resize(2 * np + 1);
+      for (uint64_t i = 0; i <= 2 * np; i++) goff[i] = moff[2 * p0 + i] - moff[2 * p0];
+      DBuf<uint64_t> g_moff(c, 2 * np + 1), g_aoff(c, 2 * np + 1), g_start, g_end;
+      DBuf<uint8_t> g_dist;
+      h2d(c, g_moff.p, goff.data(), 2 * np + 1);
+      uint64_t A = 0;
+      {
+        AlnKeys keys;
+        fm_align_seeds(f, rd.pat.p, rd.off.p + 2 * p0, 2 * np, min_seed, k, 0, len.p, pos.p, g_moff.p, goff[2 * np], g_aoff.p, keys);
+        A = keys.total;
+        g_start.alloc(c, A); g_end.alloc(c, A); g_dist.alloc(c, A);
+        fm_align_write(f, keys, g_start.p, g_end.p, g_dist.p);
+        sync(c);
+      }
+      DBuf<uint64_t> d_hoff(c, np + 1), d_nh(c, np);
+      DBuf<uint8_t> d_mapq(c, np);
+      MapSel sel;
+      fm_map_select(f, rd.off.p + 2 * p0, np, k, max_sec, g_aoff.p, g_start.p, g_end.p, g_dist.p, A, d_hoff.p, d_mapq.p, d_nh.p, sel);
+      g_start.release(); g_end.release(); g_dist.release();
+      fetch_group_offsets(c, d_hoff.p, np, go, hit_off + p0);
+      d2h(c, mapq + p0, d_mapq.p, np);
+      d2h(c, nhits + p0, d_nh.p, np);
+      sync(c);
+      const uint64_t H = sel.H;
+      DBuf<uint8_t> d_strand(c, H), d_dist(c, H), d_md;
+      DBuf<uint32_t> d_seq(c, H), d_cig;
+      DBuf<uint64_t> d_off(c, H), d_start(c, H), d_coff(c, H + 1), d_moff(c, H + 1);
+      fm_map_fill(f, rd.pat.p, rd.off.p + 2 * p0, np, k, g_aoff.p, d_hoff.p, sel, d_strand.p, d_seq.p, d_off.p, d_start.p, d_dist.p, d_coff.p, d_cig,
+                  d_moff.p, d_md);
+      h_strand.take(c, d_strand.p, H); h_seq.take(c, d_seq.p, H); h_off.take(c, d_off.p, H);
+      h_start.take(c, d_start.p, H); h_dist.take(c, d_dist.p, H);
+      // the group's script and MD offsets go behind the call's, counted from the call's first run and byte
+      const uint64_t c0 = h_cig_off.p[h_cig_off.n - 1], m0 = h_md_off.p[h_md_off.n - 1];
+      h_cig_off.take(c, d_coff.p + 1, H);
+      h_md_off.take(c, d_moff.p + 1, H);
+      for (uint64_t i = 1; i <= H; i++) { h_cig_off.p[h_cig_off.n - i] += c0; h_md_off.p[h_md_off.n - i] += m0; }
+      h_cig.take(c, d_cig.p, h_cig_off.p[h_cig_off.n - 1] - c0);
+      h_md.take(c, d_md.p, h_md_off.p[h_md_off.n - 1] - m0);
+    }
+  }
+  *strand = h_strand.release(); *seq = h_seq.release(); *off = h_off.release(); *start = h_start.release(); *dist = h_dist.release();
+  *cig_off = h_cig_off.release(); *cig = h_cig.release(); *md_off = h_md_off.release(); *md = h_md.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

@@ -1,4 +1,4 @@
-// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, fmcigar.hip, lcp.hip, seqmap.hip).  Device side:
+// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, fmcigar.hip, fmmap.hip, lcp.hip, seqmap.hip).  Device side:
 // the index as kernel arguments, rank and select by groups of 16 lanes, the start of a group-per-pattern kernel, the steps the walks
 // share (toehold, matching-statistics start and neighbours), the 1024-byte compare, and the tiny kernels every segmented sort needs.
 // Host side: the environment's budget and stats switch, the index width as a type, the requirement checks, and the one loop that
@@ -268,6 +268,28 @@ __global__ void __launch_bounds__(kTB) gather_off_k(const uint64_t *__restrict__
   out[p] = sums[h < last ? h : last];
 }
 
+// ---------------------------------------------------------------- the sequences of a collection (seqmap.hip, fmmap.hip)
+// the table as kernel arguments: start[0 .. nseq] and its bucket directory over text positions
+constexpr uint32_t kNoSeq = 0xFFFFFFFFu;
+template <class I>
+struct SeqArgs {
+  const I *start; const uint32_t *dir; uint64_t nseq, n; int shift;
+};
+// the sequence that holds text position x < n: the first start above x, searched in x's bucket, is the next sequence's
+template <class I>
+__device__ __forceinline__ uint32_t seq_of(const SeqArgs<I> &s, uint64_t x) {
+  const uint64_t b = x >> s.shift;
+  uint64_t lo = s.dir[b], hi = s.dir[b + 1];            // starts [lo, hi) lie in the bucket; those before lo are <= x
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)s.start[mid] <= x) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo < 1) lo = 1;                                   // (starts[0] = 0 <= x < n = starts[nseq]: checked when the table was set)
+  if (lo > s.nseq) lo = s.nseq;
+  return (uint32_t)(lo - 1);
+}
+
 // ---------------------------------------------------------------- host side
 // the index's arrays "of I" (DBuf<uint8_t>: their element is u32 or u64 by f.wide) as I
 template <class I>
@@ -291,6 +313,11 @@ FmArgs<I> args_of(const FmIndex &f) {
     a.nphi = f.nphi; a.nbk = f.nbk; a.shift = f.shift;
   }
   return a;
+}
+
+template <class I>
+SeqArgs<I> seq_args(const FmIndex &f) {
+  return SeqArgs<I>{as<I>(f.seq_start), f.seq_dir.p, f.nseq, f.n1 - 1, f.seq_shift};
 }
 
 // PFP_FM_MS_STEPS: a bound below the default (tests: a small one reaches the resume paths with small inputs)

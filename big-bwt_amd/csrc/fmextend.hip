@@ -391,8 +391,8 @@ void fm_align_write(FmIndex &f, const AlnKeys &keys, uint64_t *start, uint64_t *
   PFP_HIP(hipGetLastError());
 }
 
-void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
-              uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist) {
+void fm_align_keys(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
+                   uint64_t *aln_off, AlnKeys &keys) {
   pfp_ctx *c = f.c;
   fm_extend_check(f, k);
   PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
@@ -405,10 +405,15 @@ void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
   else fm_ms(f, pat, pat_off, npat, len.p, pos.p);
   fm_mems(f, pat_off, npat, len.p, pos.p, min_seed, mem_off.p, nullptr);
   const uint64_t M = read_scalar(c, mem_off.p + npat);
-  AlnKeys keys;
   fm_align_seeds(f, pat, pat_off, npat, min_seed, k, max_aln, len.p, pos.p, mem_off.p, M, aln_off, keys);
+}
+
+void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
+              uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist) {
+  AlnKeys keys;
+  fm_align_keys(f, pat, pat_off, npat, min_seed, k, max_aln, thresholds, aln_off, keys);
   if (start) fm_align_write(f, keys, start, end, dist);
-  sync(c);                                              // (the keys go back when this returns)
+  sync(f.c);                                            // (the keys go back when this returns)
 }
 
 }  // namespace pfp

@@ -446,7 +446,10 @@ void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
                     const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, uint64_t *aln_off, AlnKeys &out);
 // the kept alignments, each pattern's ordered by (d, start, end): room for keys.total entries each
 void fm_align_write(FmIndex &f, const AlnKeys &keys, uint64_t *start, uint64_t *end, uint8_t *dist);
-// matching statistics (thresholds: by fm_ms_thr), MEMs, fm_align_seeds and, where start is given, fm_align_write
+// matching statistics (thresholds: by fm_ms_thr), MEMs and fm_align_seeds: the checks of fm_align and everything but the writing
+void fm_align_keys(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
+                   uint64_t *aln_off, AlnKeys &keys);
+// fm_align_keys and, where start is given, fm_align_write
 void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
               uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist);
 
@@ -464,6 +467,37 @@ void fm_cigar_write(FmIndex &f, const CigRuns &runs, const uint64_t *cig_off, ui
 // fm_cigar_runs and, where cig is given, fm_cigar_write
 void fm_cigar(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *aln_pat, const uint64_t *start,
               const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, uint32_t *cig);
+
+// mapping reads (fmmap.hip; pfpgpu.h, "Mapping reads", states the definitions).  Device pointers.  An index without text or
+// without a sequence table -> PFP_EINVAL
+void fm_map_check(const FmIndex &f, int k, uint64_t min_seed, bool thresholds);
+// the 2 npat patterns of a call's reads: pattern 2p = read p, 2p + 1 = its reverse complement; off holds 2 npat + 1 offsets into
+// pat, which has 16 bytes of padding behind the last pattern
+struct MapReads {
+  DBuf<uint8_t> pat;
+  DBuf<uint64_t> off;
+};
+void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out);
+// what fm_map_select leaves for fm_map_fill: the candidates' keys (d, strand, s, e - s), sorted inside every read's segment with
+// the hits first, and the number of hits returned
+struct MapSel {
+  DBuf<uint64_t> key;
+  uint64_t H = 0;
+};
+// from the alignments of the 2 npat patterns (aln_off[0 .. 2 npat] and the A = aln_off[2 npat] triples, as fm_align gave them):
+// inside, shadowing, order and cap -> hit_off[0 .. npat], mapq[npat], nhits[npat]
+void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, uint64_t max_sec, const uint64_t *aln_off, const uint64_t *start,
+                   const uint64_t *end, const uint8_t *dist, uint64_t A, uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, MapSel &sel);
+// the sel.H returned hits: strand, seq, off, start, dist (room for sel.H each), cig_off / md_off (sel.H + 1 each); cig and md are
+// allocated here once their sizes are known
+void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat, int k, const uint64_t *aln_off, const uint64_t *hit_off,
+                 const MapSel &sel, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist, uint64_t *cig_off,
+                 DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
+// all of it over device patterns: fm_map_strands, fm_align_keys on the 2 npat patterns, fm_map_select and, where strand is given,
+// fm_map_fill
+void fm_map(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, bool thresholds,
+            uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist,
+            uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

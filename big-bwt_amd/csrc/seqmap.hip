@@ -27,33 +27,8 @@ namespace pfp {
 
 namespace {
 
-constexpr uint32_t kNoSeq = 0xFFFFFFFFu;
 constexpr uint64_t kDocLds = 4096;          // sequences whose counters (u64) fit in LDS: 32 KiB per workgroup, five workgroups per CU
 constexpr uint64_t kDocChunk = 32768;       // hits a workgroup counts
-
-template <class I>
-struct SeqArgs {
-  const I *start; const uint32_t *dir; uint64_t nseq, n; int shift;
-};
-template <class I>
-SeqArgs<I> seq_args(const FmIndex &f) {
-  return SeqArgs<I>{as<I>(f.seq_start), f.seq_dir.p, f.nseq, f.n1 - 1, f.seq_shift};
-}
-
-// the sequence that holds text position x < n: the first start above x, searched in x's bucket, is the next sequence's
-template <class I>
-__device__ __forceinline__ uint32_t seq_of(const SeqArgs<I> &s, uint64_t x) {
-  const uint64_t b = x >> s.shift;
-  uint64_t lo = s.dir[b], hi = s.dir[b + 1];            // starts [lo, hi) lie in the bucket; those before lo are <= x
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if ((uint64_t)s.start[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  if (lo < 1) lo = 1;                                   // (starts[0] = 0 <= x < n = starts[nseq]: checked when the table was set)
-  if (lo > s.nseq) lo = s.nseq;
-  return (uint32_t)(lo - 1);
-}
 
 template <class I>
 __global__ void __launch_bounds__(kTB) seq_map_k(SeqArgs<I> s, const uint64_t *__restrict__ pos, uint64_t count, uint32_t *__restrict__ seq,

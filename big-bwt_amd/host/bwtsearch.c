@@ -5,6 +5,7 @@
  *   bwtsearch -l --seqs[=FILE] | --docs [--seqs=FILE] ... PATTERNFILE basename        (any mode: --rc)
  *   bwtsearch -k K [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
  *   bwtsearch --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
+ *   bwtsearch --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -35,6 +36,17 @@
  * --cigar (with --align only) adds every alignment's edit script (the definitions: include/pfpgpu.h, "Edit scripts"): the items
  * become `start:end:d:CIGAR`, the runs as length and operation, `=` a match, `X` a substitution, `I` a pattern byte without a text
  * byte, `D` a text byte without a pattern byte, e.g. 57=1X20=1I72=; `*` for the empty script.
+ * --sam K (0..32) maps reads to a collection and prints SAM (the definitions: include/pfpgpu.h, "Mapping reads"): both strands of
+ * every read go through --align's seed-and-extend (--seed, --thresholds and --text as there), the alignments that lie inside one
+ * record are kept, one per locus, and ordered by (edits, strand, position).  It needs the sequence table (--seqs=FILE, default
+ * basename.seqs, which bigbwt -f --seqs writes).  READS: a file whose first byte is > or @ is FASTA / FASTQ, plain or
+ * gzip-compressed, read as bigbwt -f reads it - names up to the first white space, bases upper-cased, qualities not kept (QUAL is
+ * *); any other file holds one read per line, named by its 1-based line number.  Output: @HD VN:1.6 SO:unsorted, one @SQ SN:name
+ * LN:length per record that is not empty, @PG ID:bwtsearch, then per read its primary line `QNAME FLAG RNAME POS MAPQ CIGAR * 0 0
+ * SEQ * NM:i:edits MD:Z:... NH:i:hits` (tab-separated; FLAG 0, or 16 where the reverse complement aligns, and SEQ is then the
+ * reverse complement; POS counts from 1 inside the record; CIGAR with = and X; MAPQ 0..60 is a choice, not a probability) and up
+ * to N (--secondary, default 0) further hits with FLAG | 256 and MAPQ 0; a read without hits prints `QNAME 4 * 0 0 * * 0 0 SEQ *`.
+ * Not with -l, -k, -m, --ms, --mems, --docs, --align, --cigar or --rc.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -50,6 +62,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include "pfpgpu.h"
+#include "fasta.h"
 #include "seqs.h"
 
 static void usage(const char *argv0) {
@@ -57,7 +70,8 @@ static void usage(const char *argv0) {
          "       %s --docs [--seqs=FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n"
-         "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n\n"
+         "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
+         "       %s --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -75,8 +89,17 @@ static void usage(const char *argv0) {
          "      --seed L    with --align: the seeds are the maximal exact matches of at least L >= 1 bytes (def. 20, a choice)\n"
          "      --cigar     with --align: print count<TAB>start:end:d:CIGAR ... : every alignment with its edit script, runs of\n"
          "                  = (match), X (substitution), I (pattern byte alone), D (text byte alone); * for the empty script\n"
-         "      --text FILE with --ms / --mems / --align: the text (def. inverted from basename.bwt)\n"
-         "      --thresholds with --ms / --mems / --align: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
+         "      --sam K     map the reads of READS to the records of a collection with at most K edits (0..32) and print SAM: both\n"
+         "                  strands through --align's seed-and-extend (--seed, --thresholds, --text as there), the alignments inside\n"
+         "                  one record, one per locus; per read the best hit (FLAG 0 / 16, POS from 1 in its record, MAPQ 0..60 - a\n"
+         "                  choice, not a probability -, CIGAR with = and X, NM, MD, NH), `QNAME 4 * 0 0 * * 0 0 SEQ *` for a read\n"
+         "                  without hits.  Needs the sequence table (--seqs=FILE, def. basename.seqs: bigbwt -f --seqs writes it).\n"
+         "                  READS: first byte > or @: FASTA / FASTQ, plain or gzip, bases upper-cased, qualities not kept (QUAL is *);\n"
+         "                  else one read per line, named by its line number (not with -l, -k, -m, --ms, --mems, --docs, --align,\n"
+         "                  --cigar, --rc)\n"
+         "      --secondary N with --sam: also print up to N further hits of a read, with FLAG | 256 and MAPQ 0 (def. 0)\n"
+         "      --text FILE with --ms / --mems / --align / --sam: the text (def. inverted from basename.bwt)\n"
+         "      --thresholds with --ms / --mems / --align / --sam: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
          "                  count<TAB>name:offset ... : the hits inside one sequence among the at most MAXOCC rows examined;\n"
          "                  count stays the number of rows, matches that span two sequences included\n"
@@ -84,7 +107,7 @@ static void usage(const char *argv0) {
          "                  reads basename.ssa and .esa; every occurrence counts)\n"
          "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0, argv0, argv0, argv0);
+         argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -127,6 +150,7 @@ typedef struct {
   const uint8_t *pat; const uint64_t *off; uint64_t k, *oo, *sp, *ep;
   uint64_t maxocc, min_len, seed;
   int thresholds, locate, kmis, kedit, cigar;
+  uint64_t maxsec, first; char *const *qname;      /* --sam: the batch's first read, and the reads' names (NULL: their numbers) */
 } batch_t;
 
 static int fail(const char *what, int rc, pfp_ctx *ctx) {
@@ -214,6 +238,75 @@ static int mode_align(const batch_t *b) {
   return rc;
 }
 
+/* --sam: the header, once */
+static void sam_header(const pfp_seqs *tab) {
+  puts("@HD\tVN:1.6\tSO:unsorted");
+  for (uint64_t k = 0; k < tab->nseq; k++)
+    if (tab->start[k + 1] > tab->start[k]) printf("@SQ\tSN:%s\tLN:%" PRIu64 "\n", tab->name[k], tab->start[k + 1] - tab->start[k]);
+  puts("@PG\tID:bwtsearch");
+}
+
+/* --sam: one record per read and up to maxsec further hits (the definitions: include/pfpgpu.h, "Mapping reads") */
+static int mode_sam(const batch_t *b) {
+  uint64_t *oo = b->oo, *nhits = b->sp, *off = NULL, *start = NULL, *coff = NULL, *moff = NULL, longest = 0;
+  uint8_t *strand = NULL, *dist = NULL, *md = NULL, *mapq = malloc(b->k + 1), *rc = NULL;
+  uint32_t *seq = NULL, *cig = NULL;
+  for (uint64_t i = 0; i < b->k; i++)
+    if (b->off[i + 1] - b->off[i] > longest) longest = b->off[i + 1] - b->off[i];
+  rc = malloc(longest + 1);
+  int r = 1;
+  if (!mapq || !rc) fprintf(stderr, "out of memory\n");
+  else if ((r = pfp_fm_map(b->fm, b->pat, b->off, b->k, b->seed, b->kedit, b->maxsec, b->thresholds, oo, mapq, nhits, &strand, &seq, &off, &start,
+                           &dist, &coff, &cig, &moff, &md)) != 0)
+    r = fail(b->base, r, b->ctx);
+  for (uint64_t i = 0; !r && i < b->k; i++) {
+    const uint8_t *read = b->pat + b->off[i];
+    const uint64_t m = b->off[i + 1] - b->off[i];
+    char num[24];
+    snprintf(num, sizeof num, "%" PRIu64, b->first + i + 1);
+    const char *qn = b->qname ? b->qname[b->first + i] : num;
+    if (oo[i + 1] == oo[i]) {
+      printf("%s\t4\t*\t0\t0\t*\t*\t0\t0\t", qn);
+      if (m) fwrite(read, 1, m, stdout); else putchar('*');
+      fputs("\t*\n", stdout);
+    }
+    for (uint64_t j = oo[i]; j < oo[i + 1]; j++) {
+      const int second = j > oo[i];
+      printf("%s\t%d\t%s\t%" PRIu64 "\t%u\t", qn, (strand[j] ? 16 : 0) | (second ? 256 : 0), b->tab->name[seq[j]], off[j] + 1,
+             second ? 0u : (unsigned)mapq[i]);
+      print_script(cig + coff[j], coff[j + 1] - coff[j]);
+      fputs("\t*\t0\t0\t", stdout);
+      if (strand[j]) revcomp(read, m, rc);
+      if (m) fwrite(strand[j] ? rc : read, 1, m, stdout); else putchar('*');
+      printf("\t*\tNM:i:%u\tMD:Z:", (unsigned)dist[j]);
+      fwrite(md + moff[j], 1, moff[j + 1] - moff[j], stdout);
+      printf("\tNH:i:%" PRIu64 "\n", nhits[i]);
+    }
+  }
+  pfp_free(strand); pfp_free(seq); pfp_free(off); pfp_free(start); pfp_free(dist); pfp_free(coff); pfp_free(cig); pfp_free(moff); pfp_free(md);
+  free(mapq); free(rc);
+  return r;
+}
+
+/* --sam with a FASTA / FASTQ file: *buf (n bytes, malloc'ed) becomes the reads one per line, as a line file holds them; tab gets
+ * their names.  0, or -1 when memory runs out */
+static int reads_to_lines(uint8_t **buf, uint64_t *n, pfp_seqs *tab) {
+  uint8_t *text = malloc(*n + 1);
+  if (!text) return -1;
+  const size_t len = pfp_fasta_text_seqs(*buf, *n, text, tab);
+  uint8_t *lines = len == (size_t)-1 ? NULL : malloc(len + tab->nseq + 1);
+  if (!lines) { free(text); return -1; }
+  uint64_t at = 0;
+  for (uint64_t r = 0; r < tab->nseq; r++) {
+    memcpy(lines + at, text + tab->start[r], tab->start[r + 1] - tab->start[r]);
+    at += tab->start[r + 1] - tab->start[r];
+    lines[at++] = '\n';
+  }
+  free(text); free(*buf);
+  *buf = lines; *n = at;
+  return 0;
+}
+
 /* -l, -l --seqs and --docs after their call: the lines count<TAB>[name:]value ..., count = ep - sp (rows) or the number of items,
  * the names by id (NULL: values alone); the arrays go back */
 static int item_lines(const batch_t *b, int rc, int rows, uint32_t *id, uint64_t *val) {
@@ -275,17 +368,18 @@ static int mode_count(const batch_t *b) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0;
   const char *seqsfile = NULL;
-  pfp_seqs tab;
+  pfp_seqs tab, rtab;      /* the collection's table, and with --sam the names of a FASTA / FASTQ file's reads */
   pfp_seqs_init(&tab);
-  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0;
+  pfp_seqs_init(&rtab);
+  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
                                {"seqs", optional_argument, 0, 1006}, {"docs", no_argument, 0, 1007}, {"rc", no_argument, 0, 1008},
                                {"align", required_argument, 0, 1009}, {"seed", required_argument, 0, 1010},
-                               {"cigar", no_argument, 0, 1011},
+                               {"cigar", no_argument, 0, 1011}, {"sam", required_argument, 0, 1012}, {"secondary", required_argument, 0, 1013},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -326,6 +420,17 @@ int main(int argc, char **argv) {
         have_seed = 1;
         break;
       case 1011: cigar = 1; break;
+      case 1012: {
+        const long v = strtol(optarg, &end, 10);
+        if (!*optarg || *end || v < 0 || v > PFP_FM_EXTEND_MAX_K) { usage(argv[0]); return 2; }
+        sam = 1;
+        kedit = (int)v;
+      } break;
+      case 1013:
+        maxsec = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-') { usage(argv[0]); return 2; }
+        have_sec = 1;
+        break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -334,20 +439,36 @@ int main(int argc, char **argv) {
       default: usage(argv[0]); return 2;
     }
   }
+  if (sam && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp)) {
+    fprintf(stderr, "--sam does not combine with -l, -k, -m, --ms, --mems, --docs, --align, --cigar or --rc (both strands are always searched)\n");
+    return 2;
+  }
   if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
-      ((textfile || thresholds) && !ms && !mems && !align) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
-      (align && (locate || approx || ms || mems || docs || seqs)) || ((have_seed || cigar) && !align)) {
+      ((textfile || thresholds) && !ms && !mems && !align && !sam) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
+      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align && !sam) || (cigar && !align) ||
+      (have_sec && !sam)) {
     usage(argv[0]);
     return 2;
   }
+  if (sam) seqs = 1;
   const char *patfile = argv[optind], *base = argv[optind + 1];
   /* (everything `done` releases, before the first jump there) */
   uint8_t *pats = NULL, *buf = NULL, *big = NULL;
   uint64_t plen = 0, npat = 0, *lstart = NULL, *off = NULL, *oo = NULL, *sp = NULL, *ep = NULL;
+  char *const *qname = NULL;
   pfp_ctx *ctx = NULL;
   pfp_fm *fm = NULL;
   int rc = 1;
-  if (read_file(patfile, &pats, &plen)) { perror(patfile); goto done; }
+  if (sam) {      /* plain or gzip-compressed; FASTA / FASTQ becomes one read per line */
+    size_t n = 0;
+    pats = pfp_read_maybe_gz(patfile, &n);
+    if (!pats) { perror(patfile); goto done; }
+    plen = n;
+    if (plen && (pats[0] == '>' || pats[0] == '@')) {
+      if (reads_to_lines(&pats, &plen, &rtab)) { fprintf(stderr, "out of memory\n"); goto done; }
+      qname = rtab.name;
+    }
+  } else if (read_file(patfile, &pats, &plen)) { perror(patfile); goto done; }
   /* npat lines; line k = [lstart[k], lstart[k + 1] - 1) */
   for (uint64_t i = 0; i < plen; i++) npat += pats[i] == '\n';
   if (plen && pats[plen - 1] != '\n') npat++;
@@ -364,7 +485,7 @@ int main(int argc, char **argv) {
 
   rc = pfp_ctx_create(&ctx, device);
   if (rc) { fprintf(stderr, "Cannot initialise the GPU (%s): this tool has no CPU path\n", pfp_strerror(rc)); rc = 1; goto done; }
-  if (ms || mems || align) {
+  if (ms || mems || align || sam) {
     int fd = -1;
     uint64_t n = 0;
     if (textfile) {
@@ -395,7 +516,12 @@ int main(int argc, char **argv) {
     pfp_fm_info_t inf;
     if (!seqsfile) { snprintf(name, sizeof name, "%s.seqs", base); seqsfile = name; }
     pfp_fm_info(fm, &inf);
-    if (pfp_seqs_read(seqsfile, inf.n, &tab, err, sizeof err)) { fprintf(stderr, "%s\n", err); rc = 1; goto done; }
+    const int bad = pfp_seqs_read(seqsfile, inf.n, &tab, err, sizeof err);
+    if (bad) {
+      fprintf(stderr, "%s\n", err);
+      if (sam && bad == -1) fprintf(stderr, "--sam needs the sequence table of the collection: bigbwt -f --seqs writes it\n");
+      rc = 1; goto done;
+    }
     if ((rc = pfp_fm_set_seqs(fm, tab.start, tab.nseq)) != 0) { rc = fail(seqsfile, rc, ctx); goto done; }
   }
 
@@ -409,7 +535,8 @@ int main(int argc, char **argv) {
   if (!off || !oo || !sp || !ep || !buf) { fprintf(stderr, "out of memory\n"); rc = 1; goto done; }
   static char obuf[1 << 20];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
-  int (*const mode)(const batch_t *) = ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
+  if (sam) sam_header(&tab);
+  int (*const mode)(const batch_t *) = sam ? mode_sam : ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
                                      : locate && seqs ? mode_locate_seqs : locate ? mode_locate : mode_count;
   for (uint64_t p0 = 0; p0 < npat;) {
     /* a batch: at most `batch` patterns and max_bytes bytes (a single longer line goes alone, from the file buffer) */
@@ -447,7 +574,7 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar};
+    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, maxsec, p0, qname};
     if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }
@@ -457,6 +584,7 @@ done:
   pfp_fm_free(fm);
   pfp_ctx_destroy(ctx);
   pfp_seqs_free(&tab);
+  pfp_seqs_free(&rtab);
   free(off); free(oo); free(sp); free(ep); free(buf); free(big); free(pats); free(lstart);
   return rc;
 }

@@ -39,7 +39,7 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
            "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
            "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats",
-           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar"]
+           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar", "pfp_fm_map_dev", "pfp_fm_map"]
 
 FM_APPROX_MAX_K = 3
 FM_EXTEND_MAX_K, FM_EXTEND_MAX_M = 32, 65535
@@ -105,6 +105,12 @@ def read_seqs_file(path, n):
 def cigar_string(runs):
     """the runs of one edit script (uint32: length << 4 | op) as text, e.g. "57=1X20=1I72="; "*" for no runs"""
     return "".join("%d%s" % (int(r) >> 4, CIGAR_OPS[int(r) & 15]) for r in runs) or "*"
+
+
+def md_string(md, md_off, i):
+    """the MD string of hit i of FmIndex.map_reads, as bytes: matched lengths in decimal, a text byte per substitution, ^ and the
+    text bytes of a deletion, e.g. b"57T20^AC72" (text bytes are kept as they are)"""
+    return bytes(md[int(md_off[i]):int(md_off[i + 1])])
 
 
 def _patterns(patterns):
@@ -296,6 +302,45 @@ class FmIndex:
         self.ctx._check(self.lib.pfp_fm_align_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
                                                   C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), C.c_void_p(d_aln_off),
                                                   _vp(d_start), _vp(d_end), _vp(d_dist)))
+
+    def map_reads(self, patterns, k, min_seed, max_sec=0, thresholds=False):
+        """one answer per read over a collection (pfpgpu.h, "Mapping reads"; an index with text and a sequence table): both
+        strands through seed-and-extend, the alignments inside one record, one hit per locus, ordered by (dist, strand, start, end)
+        -> (hit_off, mapq, nhits, strand, seq, off, start, dist, cig_off, cig, md_off, md): read p has nhits[p] hits and mapping
+        quality mapq[p] (uint8; a choice, not a probability); the first 1 + max_sec of them are i in hit_off[p]:hit_off[p+1], the
+        first the primary: strand[i] (uint8; 1: the reverse complement aligns), record seq[i] (uint32) at offset off[i], text
+        position start[i], dist[i] (uint8) edits, the runs cig[cig_off[i]:cig_off[i+1]] as cigar() gives them and the MD string
+        md[md_off[i]:md_off[i+1]] (uint8; md_string reads it)"""
+        npat, _, args = self._host_patterns(patterns)
+        hit_off, mapq, nhits = np.zeros(npat + 1, dtype=np.uint64), np.zeros(npat, dtype=np.uint8), np.zeros(npat, dtype=np.uint64)
+        p8, p32, p64 = (lambda: C.POINTER(C.c_uint8)()), (lambda: C.POINTER(C.c_uint32)()), (lambda: C.POINTER(C.c_uint64)())
+        strand, seq, off, start, dist, cig_off, cig, md_off, md = p8(), p32(), p64(), p64(), p8(), p64(), p32(), p64(), p8()
+        self.ctx._check(self.lib.pfp_fm_map(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_uint64(max_sec),
+                                            C.c_int(1 if thresholds else 0), _ptr(hit_off, C.c_uint64), _ptr(mapq, C.c_uint8),
+                                            _ptr(nhits, C.c_uint64), C.byref(strand), C.byref(seq), C.byref(off), C.byref(start),
+                                            C.byref(dist), C.byref(cig_off), C.byref(cig), C.byref(md_off), C.byref(md)))
+        H = int(hit_off[-1])
+        t = self._take_free
+        co, mo = t(cig_off, H + 1, np.uint64), t(md_off, H + 1, np.uint64)
+        return (hit_off, mapq, nhits, t(strand, H, np.uint8), t(seq, H, np.uint32), t(off, H, np.uint64), t(start, H, np.uint64),
+                t(dist, H, np.uint8), co, t(cig, co[-1], np.uint32), mo, t(md, mo[-1], np.uint8))
+
+    def map_reads_dev(self, d_pat, d_pat_off, npat, k, min_seed, d_hit_off, d_mapq, d_nhits, d_strand=None, d_seq=None, d_off=None,
+                      d_start=None, d_dist=None, d_cig_off=None, d_md_off=None, max_sec=0, thresholds=False):
+        """device pointers: read bytes, npat+1 uint64 offsets -> npat+1 uint64 d_hit_off, npat uint8 d_mapq and uint64 d_nhits.
+        The per-hit outputs all None: those only.  Otherwise d_strand (uint8), d_seq (uint32), d_off, d_start (uint64) and d_dist
+        (uint8) with room for d_hit_off[npat] entries and d_cig_off, d_md_off (uint64) for one more are filled, and the call
+        returns (d_cig, d_md): the addresses of the runs (uint32) and the MD bytes, device buffers of the library that go back
+        with Context.dev_free (None where there is no hit)"""
+        per_hit = (d_strand, d_seq, d_off, d_start, d_dist, d_cig_off, d_md_off)
+        fill = any(x for x in per_hit)
+        d_cig, d_md = C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.lib.pfp_fm_map_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
+                                                C.c_int(k), C.c_uint64(max_sec), C.c_int(1 if thresholds else 0), C.c_void_p(d_hit_off),
+                                                _vp(d_mapq), _vp(d_nhits), _vp(d_strand), _vp(d_seq), _vp(d_off), _vp(d_start), _vp(d_dist),
+                                                _vp(d_cig_off), C.byref(d_cig) if fill else None, _vp(d_md_off),
+                                                C.byref(d_md) if fill else None))
+        return (d_cig.value, d_md.value) if fill else None
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

@@ -697,6 +697,71 @@ int pfp_fm_cigar(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
                  const uint64_t *start, const uint64_t *end, uint64_t naln, int k, uint8_t *dist, uint64_t *cig_off, uint32_t **cig);
 
 /* ------------------------------------------------------------------------------------
+ * Mapping reads: one answer per read over a collection - where it maps, on which strand, how confidently, with its edit script
+ * and its MD string (csrc/fmmap.hip).  The layer over "Extending seeds", "Edit scripts" and "Sequences of a collection" that a
+ * read mapper needs; the reference has no counterpart.  Conventions as in those sections.  The index carries the text
+ * (pfp_fm_build_ms_*) and a sequence table (pfp_fm_set_seqs): either one missing is PFP_EINVAL.  starts[0..nseq], seq(x) and
+ * off(x) are as in "Sequences of a collection".  Arguments: k in 0..PFP_FM_EXTEND_MAX_K, min_seed >= 1, thresholds as in
+ * pfp_fm_align, and max_sec, the cap on the secondary hits returned per read (0: none).
+ * For a read P:
+ *   strands: strand 0 is P, strand 1 is rc(P): P reversed with A<->T, C<->G, a<->t, c<->g swapped and every other byte as it is
+ *     (what `bwtsearch --rc` searches).  The candidates of P are the alignments (s, e, d) that pfp_fm_align lists for P (strand
+ *     0) and for rc(P) (strand 1) with the same min_seed, k and thresholds and max_aln = 0.
+ *   inside: a candidate with s < e and e <= starts[seq(s) + 1]: its whole span lies in one record.  All others are discarded -
+ *     the empty spans that appear when m <= k included.
+ *   key: (d, strand, s, e), compared in that order.
+ *   shadowed: an inside candidate a for which some inside candidate b of the same read - on either strand, shadowed itself or
+ *     not - has key(b) < key(a) and max(s_a, s_b) < min(e_a, e_b): b is better and their spans intersect.  This folds the
+ *     neighbouring triples of one locus, and the second copy of a read that equals its own reverse complement, into one hit.  It
+ *     is NOT the greedy, transitive rule (a shadowed b would no longer shadow): this one is decided per candidate from its
+ *     neighbours alone, whatever the order they are looked at.
+ *   hits: the inside candidates that are not shadowed, in key order.  nhits is their number, the first is the primary.  At most
+ *     1 + max_sec of them are returned; nhits stays the full number.
+ *   MAPQ: a choice, as every mapper's is, not a calibrated probability.  With d1 the primary's distance: 0 if another hit has
+ *     distance d1; 60 if the primary is the only hit; otherwise min(60, 10 (d2 - d1)) with d2 the smallest distance above d1
+ *     among the hits.  A read without hits (unmapped): 0.  It says how far the next best place found is - and seed-and-extend
+ *     finds only places a seed leads to.
+ *   per returned hit: strand (uint8); seq (uint32) and off (uint64, 0-based in the record) of s; start = s (uint64, in the
+ *     text); dist = d (uint8); the edit script of the strand's pattern against T[s..e) exactly as pfp_fm_cigar returns it
+ *     (length << 4 | op); and the MD string.
+ *   MD: walk the script from the pattern's first byte with a text cursor j = s and a counter run = 0.  A '=' run of length L:
+ *     run += L, j += L.  An X run: for each of its bytes emit run in decimal (a 0 included), emit T[j], run = 0, j += 1.  An I
+ *     run: nothing.  A D run of length L: emit run, '^', T[j..j+L), run = 0, j += L.  At the end emit run.  Text bytes are emitted
+ *     as they are.  (So T[s..e) can be rebuilt from the strand's pattern, the script and the MD string alone.)
+ *   An empty read has no hits.  The result is a function of (P, index, table, arguments) alone - not of the batch, its order,
+ *   the groups of the host call, the chunks of the edit scripts or the launch shape.
+ * Errors follow pfp_fm_align and pfp_fm_cigar: k out of range or min_seed = 0: PFP_EINVAL; thresholds asked of an index without
+ * them: PFP_EINVAL; a read longer than PFP_FM_EXTEND_MAX_M: PFP_ELIMIT; 2^32 - 1 or more candidates in one call: PFP_ELIMIT.
+ * Bounds: on top of pfp_fm_align and pfp_fm_cigar, a candidate costs one predecessor search in the table's directory, two places
+ * in the library's segmented sort (by s, then by key) and one scan of its neighbours: a span holds at most m + k bytes, so the
+ * scan looks left while s_b > s_a - (m + k) and right while s_b < e_a, and visits only the candidates of its read that start
+ * within m + 2k bytes of it.  A returned hit costs one walk over its at most 2k + 1 runs and 2k text bytes, twice.
+ * Device memory on top of the caller's buffers and of what pfp_fm_align_dev (on 2 npat patterns) and pfp_fm_cigar_dev (on the
+ * returned hits) take: 2 bytes per read byte and 32 per read for the two strands and their offsets; 17 per candidate for the
+ * triples and 32 for the keys, their sorts and the reads' numbers, plus the library sort's scratch; 16 per read for the segments
+ * and counts; per returned hit 21 for the plan of the scripts and the MD lengths, plus the scripts and the MD strings themselves.
+ * ------------------------------------------------------------------------------------ */
+/* device pointers, reads as patterns in pfp_fm_count_dev.  d_hit_off (npat + 1) gets the exclusive sums of the numbers of hits
+ * returned, d_mapq (uint8) and d_nhits (uint64) npat entries each.  The nine outputs behind them all NULL: those three only;
+ * otherwise all nine are required (PFP_EINVAL).  d_strand, d_seq, d_off, d_start and d_dist need room for d_hit_off[npat] entries -
+ * which the offsets-only call reports, and npat (1 + max_sec) bounds - and d_cig_off, d_md_off for one more: read p's hits lie at
+ * d_hit_off[p] .. d_hit_off[p+1], hit h's runs at (*d_cig)[d_cig_off[h] .. d_cig_off[h+1]), its MD string at (*d_md)[d_md_off[h] ..
+ * d_md_off[h+1]) (no terminator).  The runs and the MD bytes are sized inside the call: *d_cig and *d_md are device buffers the
+ * LIBRARY allocates, blocks of the context's pool as pfp_bigbwt_formats_dev hands out; the caller releases each with pfp_dev_free
+ * (NULL where there is no hit). */
+int pfp_fm_map_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec,
+                   int thresholds, uint64_t *d_hit_off, uint8_t *d_mapq, uint64_t *d_nhits, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                   uint64_t *d_start, uint8_t *d_dist, uint64_t *d_cig_off, uint32_t **d_cig, uint64_t *d_md_off, uint8_t **d_md);
+/* host buffers (offsets that decrease: PFP_EINVAL): hit_off (npat + 1), mapq and nhits (npat each) are filled; *strand, *seq, *off,
+ * *start and *dist are malloc'ed arrays of hit_off[npat] entries, *cig_off and *md_off of hit_off[npat] + 1, *cig of the runs and
+ * *md of the MD bytes (pfp_free each; NULL for an array without entries).  The matching statistics of both strands are computed
+ * for the whole call; the reads then go through in consecutive groups of at most PFP_SEQ_BUDGET seeds, both strands counted (a read
+ * with more goes alone; PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_map(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, int thresholds,
+               uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **start,
+               uint8_t **dist, uint64_t **cig_off, uint32_t **cig, uint64_t **md_off, uint8_t **md);
+
+/* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
  * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
  * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
