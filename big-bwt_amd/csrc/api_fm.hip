@@ -1,6 +1,7 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
-// of a collection (seqmap.hip); extending seeds (fmextend.hip), their edit scripts (fmcigar.hip) and mapping reads (fmmap.hip).
+// of a collection (seqmap.hip); extending seeds (fmextend.hip), aligning in a window (fmwindow.hip), edit scripts (fmcigar.hip) and
+// mapping reads (fmmap.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
 // (HostOut::take, fetch_group_offsets).
@@ -644,6 +645,36 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
   PFP_CATCH(c)
 }
 
+// ---------------------------------------------------------------- aligning in a window (fmwindow.hip)
+int pfp_fm_window_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_cand_pat, const uint64_t *d_lo,
+                      const uint64_t *d_hi, uint64_t ncand, int k, uint8_t *d_dist, uint64_t *d_start, uint64_t *d_end) {
+  if (!fm || (npat && !d_pat_off) || (ncand && (!d_cand_pat || !d_lo || !d_hi || !d_dist || !d_start || !d_end))) return PFP_EINVAL;
+  return dev_call(fm, [&] { fm_window(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_cand_pat, d_lo, d_hi, ncand, k, d_dist, d_start, d_end); });
+}
+
+int pfp_fm_window(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const uint64_t *lo,
+                  const uint64_t *hi, uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end) {
+  if (!fm || (npat && !pat_off) || (ncand && (!cand_pat || !lo || !hi || !dist || !start || !end))) return PFP_EINVAL;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_extend_check(fm->f, k);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint8_t> d_dist(c, ncand);
+  DBuf<uint64_t> d_win(c, 2 * ncand), d_out(c, 2 * ncand);
+  DBuf<uint32_t> d_cp(c, ncand);
+  if (ncand) { h2d(c, d_cp.p, cand_pat, ncand); h2d(c, d_win.p, lo, ncand); h2d(c, d_win.p + ncand, hi, ncand); }
+  fm_window(fm->f, in.pat.p, in.off.p, npat, d_cp.p, d_win.p, d_win.p + ncand, ncand, k, d_dist.p, d_out.p, d_out.p + ncand);
+  if (ncand) {
+    d2h(c, dist, d_dist.p, ncand);
+    d2h(c, start, d_out.p, ncand);
+    d2h(c, end, d_out.p + ncand, ncand);
+  }
+  sync(c);
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
 // ---------------------------------------------------------------- edit scripts (fmcigar.hip)
 int pfp_fm_cigar_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_aln_pat,
                      const uint64_t *d_start, const uint64_t *d_end, uint64_t naln, int k, uint8_t *d_dist, uint64_t *d_cig_off,
@@ -787,6 +818,113 @@ int pfp_fm_map(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t
   }
   *strand = h_strand.release(); *seq = h_seq.release(); *off = h_off.release(); *start = h_start.release(); *dist = h_dist.release();
   *cig_off = h_cig_off.release(); *cig = h_cig.release(); *md_off = h_md_off.release(); *md = h_md.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- mapping read pairs (fmpair.hip)
+int pfp_fm_map_pairs_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, int thresholds,
+                         uint64_t min_ins, uint64_t max_ins, uint64_t anchors, uint8_t *d_proper, uint64_t *d_npairs, uint8_t *d_mapped,
+                         uint8_t *d_rescued, uint8_t *d_mapq, uint64_t *d_nhits, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                         uint64_t *d_start, uint8_t *d_dist, int64_t *d_tlen, uint64_t *d_cig_off, uint32_t **d_cig, uint64_t *d_md_off,
+                         uint8_t **d_md) {
+  if (!fm || !d_cig_off || !d_cig || !d_md_off || !d_md ||
+      (npat && (!d_pat_off || !d_proper || !d_npairs || !d_mapped || !d_rescued || !d_mapq || !d_nhits || !d_strand || !d_seq || !d_off || !d_start ||
+                !d_dist || !d_tlen)))
+    return PFP_EINVAL;
+  *d_cig = nullptr; *d_md = nullptr;
+  return dev_call(fm, [&] {
+    DBuf<uint32_t> cig;
+    DBuf<uint8_t> md;
+    const PairOut out{d_proper, d_npairs, d_mapped, d_rescued, d_mapq, d_strand, d_seq, d_off, d_start, d_dist, d_tlen, d_cig_off, d_md_off};
+    fm_map_pairs(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, thresholds != 0, min_ins, max_ins, anchors, d_nhits, out, cig, md);
+    *d_cig = cig.p; cig.p = nullptr;                    // the two buffers leave the call: blocks of the pool, as pfp_dev_free takes them
+    *d_md = md.p; md.p = nullptr;
+  });
+}
+
+int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, int thresholds,
+                     uint64_t min_ins, uint64_t max_ins, uint64_t anchors, uint8_t *proper, uint64_t *npairs, uint8_t *mapped, uint8_t *rescued,
+                     uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist, int64_t *tlen,
+                     uint64_t *cig_off, uint32_t **cig, uint64_t *md_off, uint8_t **md) {
+  if (!fm || !cig_off || !cig || !md_off || !md ||
+      (npat && (!pat_off || !proper || !npairs || !mapped || !rescued || !mapq || !nhits || !strand || !seq || !off || !start || !dist || !tlen)))
+    return PFP_EINVAL;
+  *cig = nullptr; *md = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  FmIndex &f = fm->f;
+  fm_pair_check(f, npat, k, min_seed, thresholds != 0, min_ins, max_ins, anchors);
+  const uint64_t budget = seq_budget();
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
+                "read " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+  HostOut<uint32_t> h_cig;
+  HostOut<uint8_t> h_md;
+  cig_off[0] = 0; md_off[0] = 0;
+  if (npat) {
+    // both strands of every read, their matching statistics for the whole call, and the seeds of every pattern
+    MapReads rd;
+    fm_map_strands(f, in.pat.p, in.off.p, npat, rd);
+    in.pat.release();
+    const uint64_t bytes2 = 2 * (pat_off[npat] - pat_off[0]), npair = npat / 2;
+    DBuf<uint32_t> len(c, bytes2 + 1);
+    DBuf<uint64_t> pos(c, bytes2 + 1);
+    (thresholds ? fm_ms_thr : fm_ms)(f, rd.pat.p, rd.off.p, 2 * npat, len.p, pos.p);
+    std::vector<uint64_t> moff(2 * npat + 1), qoff(npair + 1), goff;
+    {
+      DBuf<uint64_t> d_moff(c, 2 * npat + 1);
+      fm_mems(f, rd.off.p, 2 * npat, len.p, pos.p, min_seed, d_moff.p, nullptr);
+      d2h(c, moff.data(), d_moff.p, 2 * npat + 1);
+      sync(c);
+    }
+    for (uint64_t q = 0; q <= npair; q++) qoff[q] = moff[4 * q];        // a pair brings the seeds of both strands of both mates
+    for (uint64_t q0 = 0, q1; q0 < npair; q0 = q1) {    // consecutive WHOLE pairs whose seeds stay within the budget
+      q1 = group_end(qoff.data(), q0, npair, budget);
+      const uint64_t p0 = 2 * q0, np = 2 * (q1 - q0);
+      goff.resize(2 * np + 1);
+      for (uint64_t i = 0; i <= 2 * np; i++) goff[i] = moff[2 * p0 + i] - moff[2 * p0];
+      DBuf<uint64_t> g_moff(c, 2 * np + 1), g_aoff(c, 2 * np + 1), g_start, g_end;
+      DBuf<uint8_t> g_dist;
+      h2d(c, g_moff.p, goff.data(), 2 * np + 1);
+      uint64_t A = 0;
+      {
+        AlnKeys keys;
+        fm_align_seeds(f, rd.pat.p, rd.off.p + 2 * p0, 2 * np, min_seed, k, 0, len.p, pos.p, g_moff.p, goff[2 * np], g_aoff.p, keys);
+        A = keys.total;
+        g_start.alloc(c, A); g_end.alloc(c, A); g_dist.alloc(c, A);
+        fm_align_write(f, keys, g_start.p, g_end.p, g_dist.p);
+        sync(c);
+      }
+      // the group's results: nhits, off, start, tlen (np each) and npairs (np / 2); the single-end MAPQ, mapped, rescued, mapq,
+      // strand, dist (np each) and proper (np / 2)
+      DBuf<uint64_t> d_hoff(c, np + 1), d_u64(c, 4 * np + np / 2), d_coff(c, np + 1), d_mdoff(c, np + 1);
+      DBuf<uint8_t> d_u8(c, 6 * np + np / 2), d_md;
+      DBuf<uint32_t> d_seq(c, np), d_cig;
+      uint64_t *d_nh = d_u64.p, *d_off = d_nh + np, *d_start = d_off + np, *d_tlen = d_start + np, *d_npairs = d_tlen + np;
+      uint8_t *d_smapq = d_u8.p, *d_mapped = d_smapq + np, *d_resc = d_mapped + np, *d_mapq = d_resc + np, *d_strand = d_mapq + np,
+              *d_dist = d_strand + np, *d_proper = d_dist + np;
+      MapSel sel;
+      fm_map_select(f, rd.off.p + 2 * p0, np, k, anchors - 1, g_aoff.p, g_start.p, g_end.p, g_dist.p, A, d_hoff.p, d_smapq, d_nh, sel);
+      g_start.release(); g_end.release(); g_dist.release();
+      const PairOut out{d_proper, d_npairs, d_mapped, d_resc, d_mapq, d_strand, d_seq.p, d_off, d_start, d_dist, (int64_t *)d_tlen, d_coff.p, d_mdoff.p};
+      fm_pair(f, rd.pat.p, rd.off.p + 2 * p0, np, k, min_ins, max_ins, anchors, g_aoff.p, d_hoff.p, d_smapq, sel, out, d_cig, d_md);
+      d2h(c, proper + q0, d_proper, np / 2); d2h(c, npairs + q0, d_npairs, np / 2);
+      d2h(c, mapped + p0, d_mapped, np); d2h(c, rescued + p0, d_resc, np); d2h(c, mapq + p0, d_mapq, np); d2h(c, nhits + p0, d_nh, np);
+      d2h(c, strand + p0, d_strand, np); d2h(c, seq + p0, d_seq.p, np); d2h(c, off + p0, d_off, np); d2h(c, start + p0, d_start, np);
+      d2h(c, dist + p0, d_dist, np); d2h(c, (uint64_t *)tlen + p0, d_tlen, np);
+      // the group's script and MD offsets go behind the call's, counted from the call's first run and byte
+      const uint64_t c0 = cig_off[p0], m0 = md_off[p0];
+      d2h(c, cig_off + p0 + 1, d_coff.p + 1, np); d2h(c, md_off + p0 + 1, d_mdoff.p + 1, np);
+      sync(c);
+      for (uint64_t i = 1; i <= np; i++) { cig_off[p0 + i] += c0; md_off[p0 + i] += m0; }
+      h_cig.take(c, d_cig.p, cig_off[p0 + np] - c0);
+      h_md.take(c, d_md.p, md_off[p0 + np] - m0);
+    }
+  }
+  *cig = h_cig.release(); *md = h_md.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

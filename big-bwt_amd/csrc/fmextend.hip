@@ -21,19 +21,19 @@
 //   library's segmented sort of the diagonals inside every pattern, a scan over "differs from its predecessor", a scatter: the
 //   distinct diagonals -> fm_extend -> keys d : s : e - s (6 + 40 + 17 bits, all ones for "no alignment") -> the same sort, scan
 //   and scatter over the keys, with the cap of max_aln per pattern in between.
+//   The pass itself (band_pass) is in fmband.hpp: fmwindow.hip takes its starts from the backward form.
 // Bounds: every loop is bounded by m, k or a directory's size; text is read at positions lo .. hi - 1 only and patterns inside
 // their offsets; outputs are written at the candidate's own index, or below the total the scan gave.
 #include "kernels.hpp"
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
+#include "fmband.hpp"
 
 namespace pfp {
 
 namespace {
 
-constexpr uint8_t kExtNone = 0xFF;
-constexpr uint64_t kExtNoPos = ~0ull;
 constexpr int64_t kDiagMax = 1ll << 62;                 // diagonals are clamped to +-2^62: far outside any text, and sums stay in range
 constexpr uint64_t kDiagBias = 1ull << 17;              // a MEM's diagonal is > -2^16: biased, it is a sort key
 
@@ -51,68 +51,6 @@ __device__ __forceinline__ ExtCand ext_cand(const uint64_t *__restrict__ off, ui
   int64_t d = cand_diag[ci];
   d = d < -kDiagMax ? -kDiagMax : (d > kDiagMax ? kDiagMax : d);
   return ExtCand{o0, (int)(o1 - o0), d, true};
-}
-
-// one pass over the m rows of the band (see the head of the file).  P = the pattern's first byte; the window is L columns wide and
-// column x > k carries text byte org + (x - k) - 1 (forward) or org - (x - k) (BACK: the text read leftwards from org, the pattern
-// from its end).  cur = the last row's cells, cell q of this lane is column m + gl CPL + q.  false: a whole row exceeded k
-template <int CPL, bool BACK>
-__device__ __forceinline__ bool band_pass(const uint8_t *__restrict__ text, const uint8_t *__restrict__ P, int m, uint64_t org, int L, int k,
-                                          int gl, int (&cur)[CPL]) {
-  const int inf = k + 1, base = gl * CPL;
-  auto fetch = [&](int x) -> int {                      // (columns outside the window are not read; no cell that counts uses them)
-    if (x <= k || x > L + k) return 0;
-    return BACK ? text[org - (uint64_t)(x - k)] : text[org + (uint64_t)(x - k) - 1];
-  };
-  // the horizontal moves of one row: v[c] = min over c' <= c of v[c'] + (c - c'), capped
-  auto scan = [&](int (&v)[CPL]) {
-#pragma unroll
-    for (int q = 1; q < CPL; q++) v[q] = min(v[q], v[q - 1] + 1);
-    // the last cells of this lane and those before it, as seen from column 0
-    const int z = gscan16(v[CPL - 1] - base - (CPL - 1), gl, [](int x, int y) { return min(x, y); });
-    int carry = __shfl_up(z, 1, 16);                    // the lanes before this one
-    carry = gl ? carry + base : (1 << 20);
-#pragma unroll
-    for (int q = 0; q < CPL; q++) v[q] = min(min(v[q], carry + q), inf);
-  };
-  int tb[CPL];
-#pragma unroll
-  for (int q = 0; q < CPL; q++) {
-    const int x = base + q;
-    cur[q] = BACK ? (x == k ? 0 : inf) : (x >= k && x <= L + k ? 0 : inf);
-    tb[q] = fetch(1 + x);
-  }
-  scan(cur);
-  for (int i0 = 0; i0 < m; i0 += 16) {
-    // this lane's share of the block's bytes: the pattern byte of row i0 + 1 + gl (0x100 for a byte 0: it equals nothing) and the
-    // text byte that enters the band's right edge after that row
-    const int row = i0 + 1 + gl;
-    int mine = 0x100;
-    if (row <= m) {
-      const int b = BACK ? P[m - row] : P[row - 1];
-      mine = (b ? b : 0x100) | fetch(row + 16 * CPL) << 16;
-    }
-    const int rows = min(16, m - i0);
-    for (int r = 0; r < rows; r++) {
-      const int both = __shfl(mine, r, 16), pb = both & 0xFFFF;
-      const int next = __shfl_down(cur[0] | tb[0] << 8, 1, 16);       // the neighbour's first cell and its text byte
-      const int up = gl == 15 ? inf : (next & 0xFF);
-      int v[CPL];
-#pragma unroll
-      for (int q = 0; q < CPL; q++) v[q] = min(cur[q] + (tb[q] != pb), (q + 1 < CPL ? cur[q + 1] : up) + 1);
-      scan(v);
-#pragma unroll
-      for (int q = 0; q < CPL; q++) cur[q] = v[q];
-#pragma unroll
-      for (int q = 0; q + 1 < CPL; q++) tb[q] = tb[q + 1];
-      tb[CPL - 1] = gl == 15 ? both >> 16 : next >> 8;
-    }
-    int low = cur[0];
-#pragma unroll
-    for (int q = 1; q < CPL; q++) low = min(low, cur[q]);
-    if (gmin16((uint64_t)low) >= (uint64_t)inf) return false;
-  }
-  return true;
 }
 
 // one group of 16 lanes per candidate, 1 <= k <= PFP_FM_EXTEND_MAX_K, 16 CPL >= 5k + 1

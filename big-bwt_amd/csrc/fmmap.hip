@@ -28,25 +28,11 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
+#include "fmhit.hpp"
 
 namespace pfp {
 
 namespace {
-
-constexpr uint64_t kNone = ~0ull;           // the key of an alignment that is not a hit (no key equals it: d <= 32)
-constexpr int kSpanBits = 17, kPosBits = 40;
-
-struct MapAln { uint64_t s, span; uint32_t d, strand; };
-// the place key: the first sort orders a read's alignments by s
-__device__ __forceinline__ uint64_t place_key(const MapAln &a) { return a.s << 24 | a.span << 7 | (uint64_t)a.d << 1 | a.strand; }
-__device__ __forceinline__ MapAln from_place(uint64_t k) {
-  return MapAln{k >> 24, k >> 7 & ((1ull << kSpanBits) - 1), (uint32_t)(k >> 1 & 63), (uint32_t)(k & 1)};
-}
-// the hit key: (d, strand, s, e) in the order of the definition
-__device__ __forceinline__ uint64_t hit_key(const MapAln &a) { return (uint64_t)a.d << 58 | (uint64_t)a.strand << 57 | a.s << kSpanBits | a.span; }
-__device__ __forceinline__ MapAln from_hit(uint64_t k) {
-  return MapAln{k >> kSpanBits & ((1ull << kPosBits) - 1), k & ((1ull << kSpanBits) - 1), (uint32_t)(k >> 58), (uint32_t)(k >> 57 & 1)};
-}
 
 // len2[2p] = len2[2p + 1] = the bytes of read p (decreasing offsets: none); len2[2 npat] = 0
 __global__ void __launch_bounds__(kTB) map_lens_k(const uint64_t *__restrict__ off, uint64_t npat, uint64_t *__restrict__ len2) {
@@ -208,6 +194,10 @@ __global__ void __launch_bounds__(kTB) map_md_k(const uint8_t *__restrict__ text
   if (h > H) return;
   if (h == H) { if (!EMIT) len[h] = 0; return; }
   const uint64_t base = EMIT ? md_off[h] : 0, room = EMIT ? md_off[h + 1] - base : 0;
+  if (cig_off[h] == cig_off[h + 1]) {                   // no script (a read without an alignment: fmpair.hip): no MD either
+    if (!EMIT) len[h] = 0;
+    return;
+  }
   uint64_t at = 0, j = start[h], run = 0;
   auto put = [&](uint8_t b) {
     if (EMIT && at < room) md[base + at] = b;
@@ -317,8 +307,7 @@ void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint
     return;
   }
   DBuf<uint32_t> aln_pat(c, H);
-  DBuf<uint64_t> end(c, H), mdlen(c, H + 1);
-  DBuf<uint8_t> cdist(c, H);
+  DBuf<uint64_t> end(c, H);
   {
     KScope ks(c, "fm_map_hits", 0);
     by_width(f, [&](auto w) {
@@ -328,8 +317,16 @@ void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint
     });
     PFP_HIP(hipGetLastError());
   }
+  fm_map_scripts(f, pat2, pat2_off, 2 * npat, k, aln_pat.p, start, end.p, H, cig_off, cig, md_off, md);
+}
+
+void fm_map_scripts(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat2, int k, const uint32_t *aln_pat, const uint64_t *start,
+                    const uint64_t *end, uint64_t H, uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md) {
+  pfp_ctx *c = f.c;
+  DBuf<uint64_t> mdlen(c, H + 1);
+  DBuf<uint8_t> cdist(c, H);
   CigRuns runs;
-  fm_cigar_runs(f, pat2, pat2_off, 2 * npat, aln_pat.p, start, end.p, H, k, cdist.p, cig_off, runs);
+  fm_cigar_runs(f, pat2, pat2_off, npat2, aln_pat, start, end, H, k, cdist.p, cig_off, runs);
   cig.alloc(c, runs.total);
   fm_cigar_write(f, runs, cig_off, cig.p);
   const uint8_t *text = f.text.p;

@@ -453,6 +453,12 @@ void fm_align_keys(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint
 void fm_align(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
               uint64_t *aln_off, uint64_t *start, uint64_t *end, uint8_t *dist);
 
+// aligning in a window (fmwindow.hip; pfpgpu.h, "Aligning in a window", states the definitions).  Device pointers; the checks are
+// fm_extend's, and a window lo <= hi <= n of more than PFP_FM_WINDOW_MAX_W bytes -> PFP_ELIMIT.
+// candidate i = (cand_pat[i], lo[i], hi[i]) -> (dist[i], start[i], end[i]); 0xFF and UINT64_MAX twice where nothing aligns
+void fm_window(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const uint64_t *lo,
+               const uint64_t *hi, uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end);
+
 // edit scripts (fmcigar.hip; pfpgpu.h, "Edit scripts", states the definitions).  Device pointers; the checks are fm_extend's.
 // what fm_cigar_runs leaves for fm_cigar_write: every alignment's runs, last first, in a slot of S = 2k + 1 words
 struct CigRuns {
@@ -493,11 +499,35 @@ void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, u
 void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat, int k, const uint64_t *aln_off, const uint64_t *hit_off,
                  const MapSel &sel, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist, uint64_t *cig_off,
                  DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
+// the part of fm_map_fill that works from an explicit list: the scripts and the MD strings of the H alignments (aln_pat[h] among
+// the npat2 patterns of pat2, start[h], end[h]); cig_off / md_off (H + 1 each), cig and md are allocated here.  An entry that is
+// no alignment (aln_pat[h] >= npat2) gets no runs and an empty MD
+void fm_map_scripts(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat2, int k, const uint32_t *aln_pat, const uint64_t *start,
+                    const uint64_t *end, uint64_t H, uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
 // all of it over device patterns: fm_map_strands, fm_align_keys on the 2 npat patterns, fm_map_select and, where strand is given,
 // fm_map_fill
 void fm_map(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, bool thresholds,
             uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist,
             uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
+
+// mapping read pairs (fmpair.hip; pfpgpu.h, "Mapping read pairs", states the definitions).  Device pointers.  fm_map_check's
+// errors; an odd number of reads, min_ins > max_ins, max_ins > PFP_FM_WINDOW_MAX_W or anchors outside 1 ..
+// PFP_FM_PAIR_MAX_ANCHORS -> PFP_EINVAL
+void fm_pair_check(const FmIndex &f, uint64_t npat, int k, uint64_t min_seed, bool thresholds, uint64_t min_ins, uint64_t max_ins, uint64_t anchors);
+// where a call's results go: proper and npairs per pair (nread / 2), the rest per read (nread; cig_off and md_off nread + 1)
+struct PairOut {
+  uint8_t *proper; uint64_t *npairs;
+  uint8_t *mapped, *rescued, *mapq, *strand; uint32_t *seq; uint64_t *off, *start; uint8_t *dist; int64_t *tlen;
+  uint64_t *cig_off, *md_off;
+};
+// from the hits of the nread reads as fm_map_select left them with max_sec = C - 1 (aln_off, hit_off, smapq = the single-end MAPQ,
+// sel; pat2 / pat2_off = fm_map_strands' 2 nread patterns): need, rescue, reduce and the scripts; cig and md are allocated here
+void fm_pair(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t nread, int k, uint64_t min_ins, uint64_t max_ins, uint64_t C,
+             const uint64_t *aln_off, const uint64_t *hit_off, const uint8_t *smapq, const MapSel &sel, const PairOut &out, DBuf<uint32_t> &cig,
+             DBuf<uint8_t> &md);
+// all of it over device patterns: fm_pair_check, fm_map_strands, fm_align_keys, fm_map_select and fm_pair; nhits[npat]
+void fm_map_pairs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, bool thresholds, uint64_t min_ins,
+                  uint64_t max_ins, uint64_t anchors, uint64_t *nhits, const PairOut &out, DBuf<uint32_t> &cig, DBuf<uint8_t> &md);
 
 // ---------------------------------------------------------------- PFP_DEBUG=1 (validate.hip)
 void validate_scan(pfp_ctx *c, const DBuf<uint64_t> &ends, uint64_t n_ends, uint64_t n, int w);

@@ -6,6 +6,7 @@
  *   bwtsearch -k K [-l] [-m MAXOCC] [--device D] PATTERNFILE basename
  *   bwtsearch --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename
+ *   bwtsearch --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] ... READS basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -47,6 +48,18 @@
  * reverse complement; POS counts from 1 inside the record; CIGAR with = and X; MAPQ 0..60 is a choice, not a probability) and up
  * to N (--secondary, default 0) further hits with FLAG | 256 and MAPQ 0; a read without hits prints `QNAME 4 * 0 0 * * 0 0 SEQ *`.
  * Not with -l, -k, -m, --ms, --mems, --docs, --align, --cigar or --rc.
+ * --paired (with --sam) maps read pairs, forward/reverse (the definitions: include/pfpgpu.h, "Mapping read pairs"): READS is
+ * interleaved (mate 1, mate 2, ...); with -2 FILE, READS holds the mates 1 and FILE the mates 2 in the same order (-2 implies
+ * --paired; a different number of reads, or an odd number in an interleaved file, is exit 1).  --ins MIN:MAX (default 0:1000, a
+ * choice) bounds a proper pair's insert, from the forward mate's first byte to the reverse mate's last; --anchors C (1..64, default
+ * 8, a choice) is how many hits of each mate are combined.  A mate without a proper partner among the hits is looked for within
+ * MAX bytes of its partner (rescue).  One line per read, mate 1 then mate 2.  QNAME: a trailing /1 and /2 go when mate 1 ends in /1
+ * and mate 2 in /2, otherwise mate 1's name serves both (a line file names a read by its line number in its own file).  FLAG = 1 +
+ * 2 (proper pair) + 4 (unmapped) + 8 (mate unmapped) + 16 (own strand reversed) + 32 (mate's strand reversed) + 64 (mate 1) or 128
+ * (mate 2).  RNEXT is = when the mate lies in the same record, its record's name otherwise, * when it is unmapped; PNEXT its POS or
+ * 0; TLEN as the header defines it.  An unmapped read whose mate is mapped takes the mate's RNAME and POS, with RNEXT =, MAPQ 0
+ * and CIGAR *.  In a proper pair MAPQ is the pair's and NH:i its number of pairs; otherwise they are the read's own.  A rescued
+ * read carries YR:i:1.  None of --paired, -2, --ins, --anchors combines with --secondary, and all need --sam.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -71,7 +84,8 @@ static void usage(const char *argv0) {
          "       %s --ms | --mems L [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
-         "       %s --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename\n\n"
+         "       %s --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename\n"
+         "       %s --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -98,6 +112,14 @@ static void usage(const char *argv0) {
          "                  else one read per line, named by its line number (not with -l, -k, -m, --ms, --mems, --docs, --align,\n"
          "                  --cigar, --rc)\n"
          "      --secondary N with --sam: also print up to N further hits of a read, with FLAG | 256 and MAPQ 0 (def. 0)\n"
+         "      --paired    with --sam: READS is interleaved read pairs (mate 1, mate 2, ...), forward/reverse: one line per read with the\n"
+         "                  pair flags (1, 2 proper, 8 mate unmapped, 32 mate reversed, 64 / 128), RNEXT, PNEXT, TLEN, the pair's MAPQ\n"
+         "                  and NH in a proper pair, YR:i:1 on a mate found by rescue; /1 and /2 are stripped from the names (not\n"
+         "                  with --secondary)\n"
+         "  -2 FILE         with --sam: READS holds the mates 1, FILE the mates 2, in the same order (implies --paired)\n"
+         "      --ins MIN:MAX with --paired: a proper pair's insert, forward mate's first byte to reverse mate's last (def. 0:1000, a\n"
+         "                  choice; MAX <= 16384); a mate without a proper partner is looked for within MAX bytes of its partner\n"
+         "      --anchors C with --paired: the hits of each mate that are combined (1..64, def. 8, a choice)\n"
          "      --text FILE with --ms / --mems / --align / --sam: the text (def. inverted from basename.bwt)\n"
          "      --thresholds with --ms / --mems / --align / --sam: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
@@ -107,7 +129,7 @@ static void usage(const char *argv0) {
          "                  reads basename.ssa and .esa; every occurrence counts)\n"
          "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0, argv0, argv0, argv0, argv0);
+         argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -150,6 +172,7 @@ typedef struct {
   const uint8_t *pat; const uint64_t *off; uint64_t k, *oo, *sp, *ep;
   uint64_t maxocc, min_len, seed;
   int thresholds, locate, kmis, kedit, cigar;
+  uint64_t min_ins, max_ins, anchors;
   uint64_t maxsec, first; char *const *qname;      /* --sam: the batch's first read, and the reads' names (NULL: their numbers) */
 } batch_t;
 
@@ -288,6 +311,95 @@ static int mode_sam(const batch_t *b) {
   return r;
 }
 
+/* --sam --paired: one record per read (the definitions: include/pfpgpu.h, "Mapping read pairs"); b->k is even and b->qname names
+ * every read */
+static int mode_sam_paired(const batch_t *b) {
+  const uint64_t k = b->k, np = k / 2;
+  uint64_t longest = 0;
+  for (uint64_t i = 0; i < k; i++)
+    if (b->off[i + 1] - b->off[i] > longest) longest = b->off[i + 1] - b->off[i];
+  uint64_t *u64 = malloc((6 * k + np + 2) * sizeof(uint64_t));          /* nhits, off, start, tlen (k each), npairs, coff, moff */
+  uint8_t *u8 = malloc(5 * k + np + 1), *rc = malloc(longest + 1), *md = NULL;       /* mapped, rescued, mapq, strand, dist, proper */
+  uint32_t *seq = malloc((k + 1) * sizeof(uint32_t)), *cig = NULL;
+  int r = 1;
+  if (!u64 || !u8 || !rc || !seq) { fprintf(stderr, "out of memory\n"); free(u64); free(u8); free(rc); free(seq); return 1; }
+  uint64_t *nhits = u64, *off = nhits + k, *start = off + k, *npairs = start + k + k, *coff = npairs + np, *moff = coff + k + 1;
+  int64_t *tlen = (int64_t *)(start + k);
+  uint8_t *mapped = u8, *rescued = mapped + k, *mapq = rescued + k, *strand = mapq + k, *dist = strand + k, *proper = dist + k;
+  if ((r = pfp_fm_map_pairs(b->fm, b->pat, b->off, k, b->seed, b->kedit, b->thresholds, b->min_ins, b->max_ins, b->anchors, proper, npairs, mapped,
+                            rescued, mapq, nhits, strand, seq, off, start, dist, tlen, coff, &cig, moff, &md)) != 0)
+    r = fail(b->base, r, b->ctx);
+  for (uint64_t i = 0; !r && i < k; i++) {
+    const uint64_t q = i / 2, o = i ^ 1, m = b->off[i + 1] - b->off[i];
+    const uint8_t *read = b->pat + b->off[i];
+    const char *n1 = b->qname[b->first + 2 * q], *n2 = b->qname[b->first + 2 * q + 1];
+    size_t l1 = strlen(n1);
+    const size_t l2 = strlen(n2);
+    if (l1 >= 2 && l2 >= 2 && !strcmp(n1 + l1 - 2, "/1") && !strcmp(n2 + l2 - 2, "/2")) l1 -= 2;
+    const int flag = 1 | (proper[q] ? 2 : 0) | (mapped[i] ? 0 : 4) | (mapped[o] ? 0 : 8) | (mapped[i] && strand[i] ? 16 : 0) |
+                     (mapped[o] && strand[o] ? 32 : 0) | (i & 1 ? 128 : 64);
+    const uint64_t w = mapped[i] ? i : o;               /* whose place the line shows */
+    fwrite(n1, 1, l1, stdout);
+    if (mapped[w]) printf("\t%d\t%s\t%" PRIu64, flag, b->tab->name[seq[w]], off[w] + 1);
+    else printf("\t%d\t*\t0", flag);
+    printf("\t%u\t", mapped[i] ? (unsigned)mapq[i] : 0u);
+    if (mapped[i]) print_script(cig + coff[i], coff[i + 1] - coff[i]); else putchar('*');
+    if (!mapped[o]) fputs("\t*\t0", stdout);
+    else if (!mapped[i] || seq[o] == seq[i]) printf("\t=\t%" PRIu64, off[o] + 1);
+    else printf("\t%s\t%" PRIu64, b->tab->name[seq[o]], off[o] + 1);
+    printf("\t%" PRId64 "\t", tlen[i]);
+    const int rev = mapped[i] && strand[i];
+    if (rev) revcomp(read, m, rc);
+    if (m) fwrite(rev ? rc : read, 1, m, stdout); else putchar('*');
+    fputs("\t*", stdout);
+    if (mapped[i]) {
+      printf("\tNM:i:%u\tMD:Z:", (unsigned)dist[i]);
+      fwrite(md + moff[i], 1, moff[i + 1] - moff[i], stdout);
+      printf("\tNH:i:%" PRIu64, proper[q] ? npairs[q] : nhits[i]);
+      if (rescued[i]) fputs("\tYR:i:1", stdout);
+    }
+    putchar('\n');
+  }
+  pfp_free(cig); pfp_free(md);
+  free(u64); free(u8); free(rc); free(seq);
+  return r;
+}
+
+/* the lines of a buffer: *lstart gets count + 1 entries, line k = [lstart[k], lstart[k + 1] - 1).  -> their number, or
+ * UINT64_MAX when memory runs out */
+static uint64_t split_lines(const uint8_t *p, uint64_t len, uint64_t **lstart) {
+  uint64_t count = 0;
+  for (uint64_t i = 0; i < len; i++) count += p[i] == '\n';
+  if (len && p[len - 1] != '\n') count++;
+  uint64_t *ls = malloc((count + 1) * sizeof(uint64_t));
+  if (!ls) return UINT64_MAX;
+  uint64_t k = 0, s = 0;
+  for (uint64_t i = 0; i < len; i++)
+    if (p[i] == '\n') { ls[k++] = s; s = i + 1; }
+  if (k < count) ls[k++] = s;
+  /* line k ends one byte before lstart[k + 1]: past the last line sits its '\n', or the end of a file without one */
+  ls[count] = len && p[len - 1] == '\n' ? len : len + 1;
+  *lstart = ls;
+  return count;
+}
+
+static int reads_to_lines(uint8_t **buf, uint64_t *n, pfp_seqs *tab);
+
+/* --sam: the reads of a file, plain or gzip-compressed, as lines (FASTA / FASTQ becomes one read per line and tab gets the names).
+ * 0, or 1 after the error went to stderr */
+static int load_reads(const char *path, uint8_t **buf, uint64_t *len, pfp_seqs *tab, int *named) {
+  size_t n = 0;
+  *buf = pfp_read_maybe_gz(path, &n);
+  if (!*buf) { perror(path); return 1; }
+  *len = n;
+  *named = 0;
+  if (n && ((*buf)[0] == '>' || (*buf)[0] == '@')) {
+    if (reads_to_lines(buf, len, tab)) { fprintf(stderr, "out of memory\n"); return 1; }
+    *named = 1;
+  }
+  return 0;
+}
+
 /* --sam with a FASTA / FASTQ file: *buf (n bytes, malloc'ed) becomes the reads one per line, as a line file holds them; tab gets
  * their names.  0, or -1 when memory runs out */
 static int reads_to_lines(uint8_t **buf, uint64_t *n, pfp_seqs *tab) {
@@ -368,11 +480,13 @@ static int mode_count(const batch_t *b) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0;
-  const char *seqsfile = NULL;
-  pfp_seqs tab, rtab;      /* the collection's table, and with --sam the names of a FASTA / FASTQ file's reads */
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0, paired = 0, have_pair_opt = 0;
+  const char *seqsfile = NULL, *mates2 = NULL;
+  uint64_t min_ins = 0, max_ins = 1000, anchors = 8;
+  pfp_seqs tab, rtab, rtab2;      /* the collection's table, and with --sam the names of a FASTA / FASTQ file's reads (-2: FILE's) */
   pfp_seqs_init(&tab);
   pfp_seqs_init(&rtab);
+  pfp_seqs_init(&rtab2);
   uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
@@ -380,10 +494,11 @@ int main(int argc, char **argv) {
                                {"seqs", optional_argument, 0, 1006}, {"docs", no_argument, 0, 1007}, {"rc", no_argument, 0, 1008},
                                {"align", required_argument, 0, 1009}, {"seed", required_argument, 0, 1010},
                                {"cigar", no_argument, 0, 1011}, {"sam", required_argument, 0, 1012}, {"secondary", required_argument, 0, 1013},
+                               {"paired", no_argument, 0, 1014}, {"ins", required_argument, 0, 1015}, {"anchors", required_argument, 0, 1016},
                                {0, 0, 0, 0}};
   int c;
   char *end;
-  while ((c = getopt_long(argc, argv, "lm:k:h", lo, NULL)) != -1) {
+  while ((c = getopt_long(argc, argv, "lm:k:h2:", lo, NULL)) != -1) {
     switch (c) {
       case 'l': locate = 1; break;
       case 'm':
@@ -431,6 +546,21 @@ int main(int argc, char **argv) {
         if (!*optarg || *end || optarg[0] == '-') { usage(argv[0]); return 2; }
         have_sec = 1;
         break;
+      case 1014: paired = 1; break;
+      case '2': mates2 = optarg; paired = 1; have_pair_opt = 1; break;
+      case 1015: {
+        min_ins = strtoull(optarg, &end, 10);
+        if (!*optarg || optarg[0] == '-' || *end != ':' || !end[1] || end[1] == '-') { usage(argv[0]); return 2; }
+        const char *second = end + 1;
+        max_ins = strtoull(second, &end, 10);
+        if (*end || min_ins > max_ins || max_ins > PFP_FM_WINDOW_MAX_W) { usage(argv[0]); return 2; }
+        have_pair_opt = 1;
+      } break;
+      case 1016:
+        anchors = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-' || anchors < 1 || anchors > PFP_FM_PAIR_MAX_ANCHORS) { usage(argv[0]); return 2; }
+        have_pair_opt = 1;
+        break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -441,6 +571,18 @@ int main(int argc, char **argv) {
   }
   if (sam && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp)) {
     fprintf(stderr, "--sam does not combine with -l, -k, -m, --ms, --mems, --docs, --align, --cigar or --rc (both strands are always searched)\n");
+    return 2;
+  }
+  if ((paired || have_pair_opt) && have_sec) {
+    fprintf(stderr, "--paired, -2, --ins and --anchors do not combine with --secondary\n");
+    return 2;
+  }
+  if ((paired || have_pair_opt) && !sam) {
+    fprintf(stderr, "--paired, -2, --ins and --anchors need --sam\n");
+    return 2;
+  }
+  if (have_pair_opt && !paired) {
+    fprintf(stderr, "--ins and --anchors need --paired or -2 FILE\n");
     return 2;
   }
   if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
@@ -456,31 +598,65 @@ int main(int argc, char **argv) {
   uint8_t *pats = NULL, *buf = NULL, *big = NULL;
   uint64_t plen = 0, npat = 0, *lstart = NULL, *off = NULL, *oo = NULL, *sp = NULL, *ep = NULL;
   char *const *qname = NULL;
+  char **pnames = NULL;      /* --paired: a name per read */
+  uint64_t npnames = 0;
   pfp_ctx *ctx = NULL;
   pfp_fm *fm = NULL;
   int rc = 1;
   if (sam) {      /* plain or gzip-compressed; FASTA / FASTQ becomes one read per line */
-    size_t n = 0;
-    pats = pfp_read_maybe_gz(patfile, &n);
-    if (!pats) { perror(patfile); goto done; }
-    plen = n;
-    if (plen && (pats[0] == '>' || pats[0] == '@')) {
-      if (reads_to_lines(&pats, &plen, &rtab)) { fprintf(stderr, "out of memory\n"); goto done; }
-      qname = rtab.name;
-    }
+    int named = 0;
+    if (load_reads(patfile, &pats, &plen, &rtab, &named)) goto done;
+    if (named) qname = rtab.name;
   } else if (read_file(patfile, &pats, &plen)) { perror(patfile); goto done; }
   /* npat lines; line k = [lstart[k], lstart[k + 1] - 1) */
-  for (uint64_t i = 0; i < plen; i++) npat += pats[i] == '\n';
-  if (plen && pats[plen - 1] != '\n') npat++;
-  lstart = malloc((npat + 1) * sizeof(uint64_t));
-  if (!lstart) { fprintf(stderr, "out of memory\n"); goto done; }
-  {
-    uint64_t k = 0, s = 0;
-    for (uint64_t i = 0; i < plen; i++)
-      if (pats[i] == '\n') { lstart[k++] = s; s = i + 1; }
-    if (k < npat) lstart[k++] = s;
-    /* line k ends one byte before lstart[k + 1]: past the last line sits its '\n', or the end of a file without one */
-    lstart[npat] = plen && pats[plen - 1] == '\n' ? plen : plen + 1;
+  if ((npat = split_lines(pats, plen, &lstart)) == UINT64_MAX) { npat = 0; fprintf(stderr, "out of memory\n"); goto done; }
+  if (paired) {
+    /* every read gets a name of its own (a line file: the read's line number in its file), and -2 FILE is woven in: the lines
+     * become mate 1, mate 2, mate 1, ... */
+    uint8_t *p2 = NULL, *woven = NULL;
+    uint64_t len2 = 0, n2 = 0, *ls2 = NULL;
+    int named2 = 0, bad = 0;
+    if (mates2) {
+      if (load_reads(mates2, &p2, &len2, &rtab2, &named2)) { free(p2); goto done; }
+      if ((n2 = split_lines(p2, len2, &ls2)) == UINT64_MAX) { fprintf(stderr, "out of memory\n"); free(p2); goto done; }
+      if (n2 != npat) {
+        fprintf(stderr, "%s holds %" PRIu64 " reads and %s holds %" PRIu64 ": the mates 1 and the mates 2 of the same pairs, in the same order\n",
+                patfile, npat, mates2, n2);
+        free(p2); free(ls2); goto done;
+      }
+    } else if (npat & 1) {
+      fprintf(stderr, "%s holds %" PRIu64 " reads: an interleaved file holds mate 1, mate 2, mate 1, ..., an even number\n", patfile, npat);
+      goto done;
+    }
+    const uint64_t total = mates2 ? 2 * npat : npat;
+    pnames = calloc(total + 1, sizeof(char *));
+    npnames = total;
+    if (mates2) woven = malloc(plen + len2 + 2 * npat + 2);
+    if (!pnames || (mates2 && !woven)) bad = 1;
+    uint64_t at = 0;
+    for (uint64_t r = 0; !bad && r < total; r++) {
+      const uint64_t i = mates2 ? r / 2 : r;            /* the read's line in its file */
+      const int second = mates2 && (r & 1);
+      char *const *src = second ? (named2 ? rtab2.name : NULL) : qname;
+      char num[24];
+      snprintf(num, sizeof num, "%" PRIu64, i + 1);
+      if (!(pnames[r] = strdup(src ? src[i] : num))) bad = 1;
+      if (mates2) {
+        const uint8_t *from = second ? p2 : pats;
+        const uint64_t *ls = second ? ls2 : lstart, ln = ls[i + 1] - 1 - ls[i];
+        memcpy(woven + at, from + ls[i], ln);
+        at += ln;
+        woven[at++] = '\n';
+      }
+    }
+    free(p2); free(ls2);
+    if (bad) { fprintf(stderr, "out of memory\n"); free(woven); goto done; }
+    if (mates2) {
+      free(pats); free(lstart);
+      pats = woven; plen = at; lstart = NULL;
+      if ((npat = split_lines(pats, plen, &lstart)) == UINT64_MAX) { npat = 0; fprintf(stderr, "out of memory\n"); goto done; }
+    }
+    qname = pnames;
   }
 
   rc = pfp_ctx_create(&ctx, device);
@@ -528,6 +704,7 @@ int main(int argc, char **argv) {
   uint64_t batch = 1 << 20;
   const char *env = getenv("PFP_FM_BATCH");
   if (env && strtoull(env, NULL, 10) > 0) batch = strtoull(env, NULL, 10);
+  if (paired && (batch & 1)) batch++;      /* whole pairs */
   const uint64_t max_bytes = 64ull << 20, mult = rcomp ? 2 : 1;      /* --rc: every line gives two patterns */
   off = malloc((mult * batch + 1) * sizeof(uint64_t)), oo = malloc((mult * batch + 1) * sizeof(uint64_t));
   sp = malloc((mult * batch + 1) * sizeof(uint64_t)), ep = malloc(mult * batch * sizeof(uint64_t));
@@ -536,20 +713,20 @@ int main(int argc, char **argv) {
   static char obuf[1 << 20];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
   if (sam) sam_header(&tab);
-  int (*const mode)(const batch_t *) = sam ? mode_sam : ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
+  int (*const mode)(const batch_t *) = paired ? mode_sam_paired : sam ? mode_sam : ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
                                      : locate && seqs ? mode_locate_seqs : locate ? mode_locate : mode_count;
   for (uint64_t p0 = 0; p0 < npat;) {
     /* a batch: at most `batch` patterns and max_bytes bytes (a single longer line goes alone, from the file buffer) */
     uint64_t k = 0, bytes = 0;
     while (p0 + k < npat && k < batch) {
       const uint64_t len = lstart[p0 + k + 1] - 1 - lstart[p0 + k];
-      if (k && bytes + len > max_bytes) break;
+      if (k && bytes + len > max_bytes && !(paired && (k & 1))) break;       /* (--paired: never between the mates of a pair) */
       bytes += len;
       k++;
     }
     const uint8_t *pat = pats + lstart[p0];
     const uint64_t lines = k;
-    if (bytes <= max_bytes || rcomp) {
+    if (bytes <= max_bytes || rcomp || paired) {
       /* the lines without their '\n' (--rc: each followed by its reverse complement) */
       uint8_t *dst = buf;
       if (bytes > max_bytes) {
@@ -574,7 +751,7 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, maxsec, p0, qname};
+    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, min_ins, max_ins, anchors, maxsec, p0, qname};
     if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }
@@ -585,6 +762,9 @@ done:
   pfp_ctx_destroy(ctx);
   pfp_seqs_free(&tab);
   pfp_seqs_free(&rtab);
+  pfp_seqs_free(&rtab2);
+  for (uint64_t r = 0; pnames && r < npnames; r++) free(pnames[r]);
+  free(pnames);
   free(off); free(oo); free(sp); free(ep); free(buf); free(big); free(pats); free(lstart);
   return rc;
 }

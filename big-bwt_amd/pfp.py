@@ -39,10 +39,16 @@ SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_er
            "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
            "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
            "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats",
-           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar", "pfp_fm_map_dev", "pfp_fm_map"]
+           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_window_dev", "pfp_fm_window", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar", "pfp_fm_map_dev", "pfp_fm_map",
+           "pfp_fm_map_pairs_dev", "pfp_fm_map_pairs"]
 
 FM_APPROX_MAX_K = 3
 FM_EXTEND_MAX_K, FM_EXTEND_MAX_M = 32, 65535
+FM_WINDOW_MAX_W = 16384
+FM_PAIR_MAX_ANCHORS = 64
+# the arrays FmIndex.map_pairs returns, in order: the first two per pair, the next ten per read, then the reads' scripts and MD strings
+PAIR_NAMES = ("proper", "npairs", "mapped", "rescued", "mapq", "nhits", "strand", "seq", "off", "start", "dist", "tlen", "cig_off", "cig",
+              "md_off", "md")
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}    # the BAM codes of the operations an edit script holds
 
 LCP_LCP, LCP_THR = 1, 2
@@ -253,6 +259,30 @@ class FmIndex:
                                                    C.c_void_p(d_cand_diag), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
                                                    C.c_void_p(d_start), C.c_void_p(d_end)))
 
+    def window(self, patterns, cand_pat, lo, hi, k):
+        """the best alignment of a whole pattern anywhere in a window of the text under unit-cost edit distance (pfpgpu.h,
+        "Aligning in a window"; k in 0..FM_EXTEND_MAX_K, an index with text, windows of at most FM_WINDOW_MAX_W bytes).  Candidate i
+        is pattern cand_pat[i] against T[lo[i]:hi[i]) -> (dist, start, end): dist[i] (uint8) edits align the pattern to
+        T[start[i]:end[i]), the shortest span that ends first among the best; 0xFF and 2^64 - 1 twice where nothing within k edits
+        lies in the window, or the window is not one of the text"""
+        _, _, args = self._host_patterns(patterns)
+        cp = np.ascontiguousarray(cand_pat, dtype=np.uint32)
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint64), np.ascontiguousarray(hi, dtype=np.uint64)
+        if not (cp.shape == lo.shape == hi.shape) or cp.ndim != 1:
+            raise ValueError("cand_pat, lo and hi: three 1-D arrays of one length")
+        nc = len(cp)
+        dist, start, end = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
+        self.ctx._check(self.lib.pfp_fm_window(self._h, *args, _ptr(cp, C.c_uint32), _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), C.c_uint64(nc),
+                                               C.c_int(k), _ptr(dist, C.c_uint8), _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
+        return dist, start, end
+
+    def window_dev(self, d_pat, d_pat_off, npat, d_cand_pat, d_lo, d_hi, ncand, k, d_dist, d_start, d_end):
+        """device pointers: pattern bytes, npat+1 uint64 offsets, ncand uint32 pattern indices and uint64 window starts and ends ->
+        ncand uint8 d_dist and uint64 d_start / d_end"""
+        self.ctx._check(self.lib.pfp_fm_window_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_cand_pat),
+                                                   C.c_void_p(d_lo), C.c_void_p(d_hi), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
+                                                   C.c_void_p(d_start), C.c_void_p(d_end)))
+
     def align(self, patterns, k, min_seed, max_aln=0, thresholds=False, cigar=False):
         """seed-and-extend: every maximal exact match of at least min_seed bytes (as mems lists them; thresholds as there) is
         extended along its diagonal with at most k edits -> (aln_off, start, end, dist): pattern p's distinct alignments are
@@ -341,6 +371,46 @@ class FmIndex:
                                                 _vp(d_cig_off), C.byref(d_cig) if fill else None, _vp(d_md_off),
                                                 C.byref(d_md) if fill else None))
         return (d_cig.value, d_md.value) if fill else None
+
+    def map_pairs(self, patterns, k, min_seed, min_ins, max_ins, anchors=8, thresholds=False):
+        """read pairs over a collection (pfpgpu.h, "Mapping read pairs"): patterns 2q and 2q + 1 are mates 1 and 2 of pair q,
+        forward/reverse.  The first `anchors` hits of both mates (as map_reads orders them) are combined into proper pairs - same
+        record, opposite strands, min_ins <= insert <= max_ins - and an anchor without a proper partner has its mate looked for
+        in the window it points at (window()).  -> the arrays PAIR_NAMES names: proper (uint8) and npairs (uint64) per pair;
+        mapped, rescued, mapq (uint8), nhits (uint64), strand (uint8), seq (uint32), off, start (uint64), dist (uint8) and tlen
+        (int64) per read; cig_off, cig, md_off, md: read r's runs are cig[cig_off[r]:cig_off[r+1]], its MD string
+        md[md_off[r]:md_off[r+1]].  In a proper pair a read reports its member of the primary pair and the pair MAPQ, otherwise
+        its own first hit and MAPQ; an unmapped read has seq 2^32 - 1, off = start = 2^64 - 1, dist 0xFF, no runs, no MD"""
+        npat, _, args = self._host_patterns(patterns)
+        z = lambda count, dt: np.zeros(count, dtype=dt)
+        proper, npairs = z(npat // 2, np.uint8), z(npat // 2, np.uint64)
+        mapped, rescued, mapq, nhits, strand = z(npat, np.uint8), z(npat, np.uint8), z(npat, np.uint8), z(npat, np.uint64), z(npat, np.uint8)
+        seq, off, start, dist, tlen = z(npat, np.uint32), z(npat, np.uint64), z(npat, np.uint64), z(npat, np.uint8), z(npat, np.int64)
+        cig_off, md_off = z(npat + 1, np.uint64), z(npat + 1, np.uint64)
+        cig, md = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        u8, u64 = (lambda a: _ptr(a, C.c_uint8)), (lambda a: _ptr(a, C.c_uint64))
+        self.ctx._check(self.lib.pfp_fm_map_pairs(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_int(1 if thresholds else 0),
+                                                  C.c_uint64(min_ins), C.c_uint64(max_ins), C.c_uint64(anchors), u8(proper), u64(npairs),
+                                                  u8(mapped), u8(rescued), u8(mapq), u64(nhits), u8(strand), _ptr(seq, C.c_uint32), u64(off),
+                                                  u64(start), u8(dist), _ptr(tlen, C.c_int64), u64(cig_off), C.byref(cig), u64(md_off),
+                                                  C.byref(md)))
+        return (proper, npairs, mapped, rescued, mapq, nhits, strand, seq, off, start, dist, tlen, cig_off,
+                self._take_free(cig, cig_off[-1], np.uint32), md_off, self._take_free(md, md_off[-1], np.uint8))
+
+    def map_pairs_dev(self, d_pat, d_pat_off, npat, k, min_seed, min_ins, max_ins, d_proper, d_npairs, d_mapped, d_rescued, d_mapq, d_nhits,
+                      d_strand, d_seq, d_off, d_start, d_dist, d_tlen, d_cig_off, d_md_off, anchors=8, thresholds=False):
+        """device pointers: read bytes, npat+1 uint64 offsets -> npat/2 uint8 d_proper and uint64 d_npairs; npat uint8 d_mapped,
+        d_rescued, d_mapq, d_strand, d_dist, uint64 d_nhits, d_off, d_start, uint32 d_seq, int64 d_tlen; npat+1 uint64 d_cig_off and
+        d_md_off.  Returns (d_cig, d_md): the addresses of the runs (uint32) and the MD bytes, device buffers of the library that
+        go back with Context.dev_free (None where there is nothing)"""
+        d_cig, d_md = C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.lib.pfp_fm_map_pairs_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
+                                                      C.c_int(k), C.c_int(1 if thresholds else 0), C.c_uint64(min_ins), C.c_uint64(max_ins),
+                                                      C.c_uint64(anchors), _vp(d_proper), _vp(d_npairs), _vp(d_mapped), _vp(d_rescued),
+                                                      _vp(d_mapq), _vp(d_nhits), _vp(d_strand), _vp(d_seq), _vp(d_off), _vp(d_start),
+                                                      _vp(d_dist), _vp(d_tlen), C.c_void_p(d_cig_off), C.byref(d_cig), C.c_void_p(d_md_off),
+                                                      C.byref(d_md)))
+        return d_cig.value, d_md.value
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

@@ -655,6 +655,41 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
                  int thresholds, uint64_t *aln_off, uint64_t **start, uint64_t **end, uint8_t **dist);
 
 /* ------------------------------------------------------------------------------------
+ * Aligning in a window: the best edit-distance alignment of a whole pattern anywhere in a given window of the text
+ * (csrc/fmwindow.hip).  pfp_fm_extend looks within k columns of one diagonal, so it cannot look through a window as wide as the
+ * insert size of a read pair; this call can, and it also realigns a read inside a known region.  The reference has no
+ * counterpart: the method is Sellers' dynamic programme with a free start (Sellers, 1980, as in "Extending seeds"), unbanded.
+ * Conventions, the byte-0 rule, the unit costs and k in 0..PFP_FM_EXTEND_MAX_K are as in "Extending seeds"; the index is one built
+ * with text.  The text T has n bytes.
+ *   candidate: a triple (p, lo, hi) of a pattern index and an unsigned window T[lo..hi) of the text.
+ *   d(s, e) = Levenshtein(P, T[s..e)) for lo <= s <= e <= hi; d* = the minimum over all such pairs (s, e).
+ *   result (d, s, e): if d* > k there is no alignment: d = 0xFF and s = e = UINT64_MAX.  Otherwise d = d*, e is the smallest e with
+ *     min over s of d(s, e) = d*, and s the largest s with d(s, e) = d*: the shortest span that ends first, the tie rule of
+ *     pfp_fm_extend.  The empty pattern gives (0, lo, lo).  For a candidate (p, delta) of pfp_fm_extend, the window
+ *     lo = clamp(delta - k), hi = clamp(delta + m + k) gives that call's result.
+ *   "No alignment" is also the result where p >= npat, the pattern's offsets decrease, lo > hi, or hi > n.
+ *   The result is a function of (P, T, lo, hi, k) alone - not of the batch, the launch shape, the tiling or the pieces of the launch.
+ * k outside 0..PFP_FM_EXTEND_MAX_K or an index without text: PFP_EINVAL.  A pattern of the call longer than PFP_FM_EXTEND_MAX_M:
+ * PFP_ELIMIT.  A window with lo <= hi <= n of more than PFP_FM_WINDOW_MAX_W bytes: PFP_ELIMIT.  PFP_FM_WINDOW_MAX_W is a choice,
+ * not a measurement: 16 times a usual insert size, and a column index that fits 16 bits.  Nothing is read outside T[lo..hi) or
+ * outside the pattern's offsets.
+ * Bounds: a candidate costs about m (hi - lo) cell updates, 1.07e9 at the limits, and up to m (2k + 1) more for its start.  A call
+ * goes through in consecutive pieces of at most 2^34 cell updates (PFP_FM_WINDOW_CELLS in the source: a choice, not a
+ * measurement; the environment variable PFP_FM_WINDOW_CELLS=N, read per call, lowers it); a candidate with more goes alone.
+ * Device memory on top of the caller's buffers: 32 bytes per candidate and 48 for the plan (cell counts, scratch sizes and their
+ * sums), and during a piece m + 1 bytes for each of its candidates whose window holds 256 bytes or more (the column that a tile
+ * of 256 columns hands to the next): at most 1/128 byte per cell of the piece, 134 MB at 2^34 cells.
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_WINDOW_MAX_W 16384
+/* device pointers, patterns as in pfp_fm_count_dev.  Candidate i is (d_cand_pat[i], d_lo[i], d_hi[i]); d_dist (uint8), d_start and
+ * d_end (ncand entries each) get its result. */
+int pfp_fm_window_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_cand_pat,
+                      const uint64_t *d_lo, const uint64_t *d_hi, uint64_t ncand, int k, uint8_t *d_dist, uint64_t *d_start, uint64_t *d_end);
+/* the same with host buffers (offsets that decrease: PFP_EINVAL) */
+int pfp_fm_window(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const uint64_t *lo,
+                  const uint64_t *hi, uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end);
+
+/* ------------------------------------------------------------------------------------
  * Edit scripts (CIGAR): which edits align a pattern to a span of the text that pfp_fm_extend* or pfp_fm_align* found - or to any
  * other span (csrc/fmcigar.hip).  A separate call: one more banded pass over exactly P against T[s..e), which records the
  * operation of every cell, and a walk back along the records (Ukkonen's band again; the traceback is Needleman and Wunsch's).
@@ -760,6 +795,62 @@ int pfp_fm_map_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uin
 int pfp_fm_map(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, int thresholds,
                uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **start,
                uint8_t **dist, uint64_t **cig_off, uint32_t **cig, uint64_t **md_off, uint8_t **md);
+
+/* ------------------------------------------------------------------------------------
+ * Mapping read pairs: reads 2q and 2q + 1 of a call are mates 1 and 2 of pair q (csrc/fmpair.hip).  The layer over "Mapping
+ * reads" and "Aligning in a window" that paired short reads need: the mates' hits are combined into proper pairs, a mate
+ * whose seeds did not survive its edits is looked for where its partner says it must be, and the mapping quality takes the
+ * mate into account.  The reference has no counterpart.  The orientation is forward/reverse (FR: the mates face each other, as
+ * Illumina paired-end libraries give them) ONLY; other orientations are out of scope.  Arguments: those of pfp_fm_map without
+ * max_sec, plus the insert bounds min_ins <= max_ins <= PFP_FM_WINDOW_MAX_W and anchors = C in 1..PFP_FM_PAIR_MAX_ANCHORS (64: a
+ * choice); a violation of those bounds or an odd npat: PFP_EINVAL.  The other errors are pfp_fm_map's.
+ *   anchors(r): the first min(nhits, C) hits of read r, exactly as "Mapping reads" defines and orders hits.  Each is (d, strand,
+ *     s, e), inside record seq(s) = [b0, b1).
+ *   proper(a, b), a of mate 1 and b of mate 2: same record, different strands, and with f the strand-0 one and r the strand-1
+ *     one: s_f <= s_r, e_f <= e_r and min_ins <= e_r - s_f <= max_ins.
+ *   rescue(a), for an anchor a of read r, only when no anchor of the mate is proper with a: the mate's strand 1 - strand(a)
+ *     pattern is aligned in a window as "Aligning in a window" defines, with the same k.  strand(a) = 0: lo = s_a, hi =
+ *     min(s_a + max_ins, b1).  strand(a) = 1: hi = e_a, lo = max(e_a - min(e_a, max_ins), b0).  A result with s < e is a rescued
+ *     alignment (d, 1 - strand(a), s, e); it is inside by construction.
+ *   pairs of q, as distinct (a, b) values: the proper (a, b) over anchors(2q) x anchors(2q + 1); the proper (a, rescue(a)); the
+ *     proper (rescue(b), b).  A rescued alignment pairs only with the anchor that produced it.
+ *   pair key: (d_a + d_b, key(a), key(b)) with key as in "Mapping reads"; the primary pair is the smallest.
+ *   same locus: a pair (a', b') with the primary's strands where a' intersects a and b' intersects b is at the primary's locus.
+ *     npairs = 1 + the number of pairs not at the primary's locus; D2 = the smallest sum d_a + d_b among those, D1 the primary's.
+ *   pair MAPQ, a choice like the single-end rule: 60 if npairs = 1; 0 if D2 = D1; otherwise min(60, 10 (D2 - D1)).
+ *   per pair: proper (uint8: the pair has pairs) and npairs (uint64; 0 when not proper).
+ *   per read (2 npair entries, no offsets array): mapped, rescued (uint8), mapq (uint8), nhits (uint64, the single-end number),
+ *     strand, seq, off, start, dist as in "Mapping reads", tlen (int64), the edit script as pfp_fm_cigar returns it and the MD
+ *     string.  In a proper pair the read's alignment is its member of the primary pair, rescued says that it is a rescued
+ *     alignment, and mapq is the pair MAPQ.  Otherwise it is the read's single-end primary with its single-end MAPQ.  A read
+ *     without a hit that is in no proper pair: mapped = 0, seq = 0xFFFFFFFF, off = start = UINT64_MAX, dist = 0xFF, no runs, an
+ *     empty MD.
+ *   tlen: when both mates are mapped in one record, max(e) - min(s): positive for the mate with the smaller s, mate 1 on a tie,
+ *     and negated for the other.  Otherwise 0.
+ *   The result is a function of (the pair, index, table, arguments) alone - not of the batch, its order, the groups of the host
+ *   call or the pieces of any launch.
+ * Bounds: per pair at most 2C rescues, each a window of at most max_ins bytes, and two walks over at most C^2 + 2C pairs.
+ * Device memory on top of pfp_fm_map_dev's (with max_sec = C - 1, without its per-hit outputs): 16 C bytes per read for the
+ * flags and their sums, 37 per rescue plus what pfp_fm_window_dev takes, 12 per read for the reported alignments, and the scripts.
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_PAIR_MAX_ANCHORS 64
+/* device pointers, reads as patterns in pfp_fm_count_dev.  d_proper (uint8) and d_npairs (uint64): npat / 2 entries; d_mapped,
+ * d_rescued, d_mapq, d_strand, d_dist (uint8), d_nhits, d_off, d_start (uint64), d_seq (uint32) and d_tlen (int64): npat entries;
+ * d_cig_off and d_md_off: npat + 1.  Read r's runs lie at (*d_cig)[d_cig_off[r] .. d_cig_off[r+1]), its MD string at
+ * (*d_md)[d_md_off[r] .. d_md_off[r+1]).  *d_cig and *d_md are device buffers the LIBRARY allocates, as in pfp_fm_map_dev; the
+ * caller releases each with pfp_dev_free (NULL where there is nothing). */
+int pfp_fm_map_pairs_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, int k, int thresholds,
+                         uint64_t min_ins, uint64_t max_ins, uint64_t anchors, uint8_t *d_proper, uint64_t *d_npairs, uint8_t *d_mapped,
+                         uint8_t *d_rescued, uint8_t *d_mapq, uint64_t *d_nhits, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                         uint64_t *d_start, uint8_t *d_dist, int64_t *d_tlen, uint64_t *d_cig_off, uint32_t **d_cig, uint64_t *d_md_off,
+                         uint8_t **d_md);
+/* host buffers of the same sizes (offsets that decrease: PFP_EINVAL); *cig and *md are malloc'ed (pfp_free; NULL when empty).  The
+ * matching statistics of both strands are computed for the whole call; WHOLE pairs then go through in consecutive groups of at
+ * most PFP_SEQ_BUDGET seeds, both strands of both mates counted (a pair with more goes alone; PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, int thresholds,
+                     uint64_t min_ins, uint64_t max_ins, uint64_t anchors, uint8_t *proper, uint64_t *npairs, uint8_t *mapped, uint8_t *rescued,
+                     uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist, int64_t *tlen,
+                     uint64_t *cig_off, uint32_t **cig, uint64_t *md_off, uint8_t **md);
 
 /* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
