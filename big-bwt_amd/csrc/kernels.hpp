@@ -214,6 +214,10 @@ struct ParseBWT {         // outputs of bwtparse.c in HBM
   DBuf<uint32_t> ilist;    // [P+1]
   DBuf<uint8_t> bwlast;    // [P+1]
   DBuf<uint64_t> bwsai;    // [P+1] (only with SA flags)
+  // [P+1] the sorted symbols of the inverted-list sort: iword[0] = the EOS symbol, iword[e + 1] = 1-based lexicographic rank of
+  // the word inverted-list entry e belongs to.  Live until the merge ends; empty where the lists came from a file (the merge
+  // then derives it from the words' counts)
+  DBuf<uint32_t> iword;
   uint64_t rounds = 0;
 };
 // parse symbols are 1-based lexicographic ranks; occ_lex[r] = occurrences of rank r

@@ -6,8 +6,9 @@
 // the walk is a data-parallel decomposition (the same one pfthreads.hpp:456-493 uses for its
 // thread ranges): every dictionary suffix longer than w contributes occ(word) output chars,
 // an exclusive scan of those counts fixes every output offset, and then
-//   * fill / full-word entries are expanded output-centrically (each thread owns 16
-//     consecutive BWT bytes, finds its SA(D) slot by binary search and walks forward),
+//   * fill entries are expanded output-centrically (each thread owns 16 consecutive BWT
+//     bytes, finds its SA(D) slot by binary search and walks forward), the occurrences of
+//     whole words are written one lane per inverted-list entry,
 //   * groups of equal suffixes whose members disagree (or any multi-word group when SA values
 //     are requested) are merged by rank computation over the members' inverted lists - the
 //     data-parallel form of the reference's heap merge (pfbwt.cpp:537-556).
@@ -26,22 +27,6 @@ constexpr int kOffTileLog = 11;      // slots per offset tile (= one expand work
 // ------------------------------------------------------------------ stage 3: the kernels
 
 template <class I> struct alignas(16) Idx8 { I v[8]; };
-// whole-word slots (preceding char = EndOfWord) of the block's 2048 slots -> tile_full[block]; smallest such slot -> first_full
-__device__ __forceinline__ void tile_full_count(const uint32_t p8[8], int nk, uint64_t t0, uint32_t *__restrict__ tile_full,
-                                                unsigned long long *__restrict__ first_full) {
-  __shared__ uint32_t ws[4];
-  uint32_t cfull = 0;
-  int firstk = -1;
-#pragma unroll
-  for (int k = 7; k >= 0; k--) if (k < nk && p8[k] == kEndOfWord) { cfull++; firstk = k; }
-  const unsigned long long anyf = __ballot(cfull != 0);
-  for (int o = 32; o > 0; o >>= 1) cfull += __shfl_down(cfull, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = cfull;
-  // the first lane of the first wave that holds one reports it (slots ascend with the thread index)
-  if (anyf && (int)(threadIdx.x & 63) == __ffsll((long long)anyf) - 1) atomicMin(first_full, (unsigned long long)(t0 + firstk));
-  __syncthreads();
-  if (threadIdx.x == 0) tile_full[BID] = ws[0] + ws[1] + ws[2] + ws[3];
-}
 // The same per-slot outputs when the records travelled in the top 16 bits of the first-round keys
 // (SuffixOrder::paybits): a streaming read of skeys; only slots that later rounds re-ordered
 // (refined[t]) fetch their record, and a count code of 255 its word's count.
@@ -51,8 +36,7 @@ __global__ __launch_bounds__(256) void slot_payload_kernel(uint64_t N, const I *
                                                            const uint8_t *__restrict__ refined, const uint8_t *__restrict__ b,
                                                            WordView wv,
                                                            const uint32_t *__restrict__ wocc, uint32_t d, int w,
-                                                           uint32_t *__restrict__ cnt, uint8_t *__restrict__ pc,
-                                                           uint32_t *__restrict__ tile_full, unsigned long long *__restrict__ first_full) {
+                                                           uint32_t *__restrict__ cnt, uint8_t *__restrict__ pc) {
   if ((uint64_t)BID * 2048 >= N) return;      // a workgroup of the padded last grid row
   uint64_t t0 = ((uint64_t)BID * 256 + threadIdx.x) * 8;
   uint32_t c8[8], p8[8];
@@ -86,7 +70,6 @@ __global__ __launch_bounds__(256) void slot_payload_kernel(uint64_t N, const I *
   } else {
     for (int k = 0; k < nk; k++) { cnt[t0 + k] = c8[k]; pc[t0 + k] = (uint8_t)p8[k]; }
   }
-  tile_full_count(p8, nk, t0, tile_full, first_full);
 }
 // ------------------------------------------------------------------ one gather per slot (BWT only / sparse SA)
 //
@@ -146,7 +129,7 @@ __device__ __forceinline__ uint4 posrec_at(const WordView &wv, int w, const uint
 }
 
 // Per tile of 2048 slots (256 threads x 8 consecutive slots): gather the records, exclusive scan of the counts inside
-// the tile (loc[], tile total -> tsum[]), preceding chars, whole-word slots per tile, and the hard-group flags: a slot
+// the tile (loc[], tile total -> tsum[]), preceding chars, and the hard-group flags: a slot
 // whose preceding char differs from that of the slot before it IN THE SAME GROUP marks the group's head (members of a
 // group are contiguous, so "not all chars equal" is seen at some adjacent pair; pfbwt.cpp:524-536).  Replaces
 // slot_gather + slot_loc + group_flags: cnt[] (4 B per slot written and read again) is gone, pc[] is not re-read.
@@ -156,7 +139,6 @@ __global__ __launch_bounds__(256) void slot_records_kernel(uint64_t N, const I *
                                                            uint8_t *__restrict__ pc, uint32_t *__restrict__ sfirst,
                                                            uint32_t *__restrict__ slast, uint32_t *__restrict__ ssl,
                                                            uint64_t *__restrict__ tsum, uint32_t *__restrict__ overflow,
-                                                           uint32_t *__restrict__ tile_full, unsigned long long *__restrict__ first_full,
                                                            uint8_t *__restrict__ hard, int any_multi_is_hard, WordView view, int w,
                                                            const uint4 *__restrict__ wrec, int dense_ist) {
   // prec == null: no per-position records - every slot computes its own (posrec_at)
@@ -240,16 +222,6 @@ __global__ __launch_bounds__(256) void slot_records_kernel(uint64_t N, const I *
     if (k < nk && p8[k] != 0 && g8[k] == prev_g && (any_multi_is_hard || p8[k] != prev_pc)) hard[g8[k]] = 1;      // (SA output: any group of several words, pfbwt.cpp:568, 612)
     prev_pc = p8[k]; prev_g = g8[k];
   }
-  tile_full_count(p8, nk, t0, tile_full, first_full);
-}
-
-// whole words are singleton groups and stand in SA(D) in the words' lexicographic order: the q-th whole-word slot
-// belongs to the word of rank q.  Rank of the first whole-word slot held (0 unless the slots are one rank's range).
-template <class I>
-__global__ void full_base0_kernel(const unsigned long long *__restrict__ first_full, const I *__restrict__ sa,
-                                  WordView wv, const uint32_t *__restrict__ lexrank, uint32_t *__restrict__ out) {
-  const unsigned long long f = *first_full;
-  *out = f == ~0ull ? 0u : lexrank[word_of(wv, sa[f])];
 }
 
 // a group is "hard" when its members disagree on the preceding char (pfbwt.cpp:524-536), or, with
@@ -264,9 +236,7 @@ __global__ void group_flags_kernel(uint64_t N, const I *__restrict__ grp, const 
   if (any_multi_is_hard || pc[t] != pc[g]) hard[g] = 1;
 }
 
-// CLS_MULTI (sparse SA mode only): member of a group of several words that all have the same preceding char -
-// its chars are a fill, its SA values (needed at the two ends of the group's range only) come from group_edges_kernel
-enum : uint8_t { CLS_NONE = 0, CLS_FILL = 1, CLS_FULL = 2, CLS_HARD = 3, CLS_MULTI = 4 };
+enum : uint8_t { CLS_NONE = 0, CLS_FILL = 1, CLS_FULL = 2, CLS_HARD = 3 };
 // SA values asked for: none (BWT only), every position (-S), or only where the sampled SA files can look:
 // at run boundaries of the BWT (-s / -e)
 enum : int { SA_NONE = 0, SA_DENSE = 1, SA_SPARSE = 2 };
@@ -304,9 +274,10 @@ struct MergeArgsT {
   const uint8_t *pc, *hard, *gmaj;     // gmaj[g]: majority char of hard group g when the minority path places the rest (else 0)
   const uint64_t *tbase; const uint32_t *loc;    // output offset of slot t = tbase[t >> 11] + loc[t] (slot_off)
   const uint32_t *ilist; const uint8_t *bwlast; const uint64_t *bwsai;
-  // whole-word slots: the q-th one (in slot order) is the word of lexicographic rank q, whose inverted list starts at
-  // istart_lex[q] + 1; fullbase[tile] = whole-word slots before the tile, *fullbase0 = rank of the first one held
-  const uint32_t *istart_lex, *fullbase, *fullbase0;
+  // whole words, one lane per inverted-list entry e (word_chars_kernel, word_sa_kernel): iword[e + 1] - 1 = q, the
+  // lexicographic rank of the entry's word, whose list starts at istart_lex[q] + 1 and whose whole-word slot is wslot_lex[q]
+  // (a global slot: local slot + slot_base)
+  const uint32_t *istart_lex, *iword; const uint64_t *wslot_lex; uint64_t slot_base;
   uint8_t *bwt; uint64_t *out_sa;
   // what a launch writes: BWT chars (bit 0), SA values (bit 1).  Dense SA does both at once; sparse SA needs the finished
   // BWT to know where values are looked at, so its kernels run twice.
@@ -343,7 +314,7 @@ __device__ __forceinline__ uint64_t slot_off(const MergeArgsT<I> &a, uint64_t t)
 
 __device__ __forceinline__ uint8_t fix_char(uint8_t ch) { return ch == kDollar ? 0 : ch; }  // pfbwt.cpp:126
 // start of slot t's word in ilist: stored per slot when SA values are wanted, looked up otherwise
-// (BWT only needs it for whole words and hard groups)
+// (BWT only needs it for hard groups)
 template <class I>
 __device__ __forceinline__ uint32_t slot_ist(const MergeArgsT<I> &a, uint64_t t) {
   return a.ist ? a.ist[t] : a.wistart[word_of(a.wv, a.sa[t])];
@@ -366,8 +337,10 @@ __device__ __forceinline__ uint64_t slot_slen(const MergeArgsT<I> &a, uint64_t t
 // consecutive BWT bytes per iteration (binary search in LDS for the first one, forward walk for
 // the rest) and stores them with one 16-byte store.
 //   fill entry      : the preceding char, occ times                       (pfbwt.cpp:527-533)
-//   full-word entry : bwlast[ilist[..]] per occurrence                    (pfbwt.cpp:153-197)
-//   hard entry      : each occurrence is ranked among all occurrences of all members of its group
+//   full-word entry : bwlast[ilist[..]] per occurrence                    (pfbwt.cpp:153-197): zeros here, the chars
+//                     come from word_chars_kernel, one lane per occurrence - in the 16-byte walk every such byte was
+//                     two dependent random loads on which the other 63 lanes of the wave waited
+//   hard entry     : each occurrence is ranked among all occurrences of all members of its group
 //                     by BWT(P) position - own index + lower_bound in every other member's
 //                     inverted list - and written to that slot of the group's range: the
 //                     data-parallel form of the reference's heap merge (pfbwt.cpp:537-556).
@@ -379,62 +352,45 @@ constexpr int kHardSortMin = 512;   // a group with more occurrences than this (
 constexpr int kSlots = 2048;
 constexpr uint64_t kExpandQuota = 1u << 16;   // output bytes one workgroup expands before the rest is shared
 
+// kDense: SA values everywhere (-S) - expand_sa_1 then asks for a slot's class and, for a whole word, the start of its
+// inverted list; the chars alone need neither (12 KB of LDS per workgroup less)
+template <bool kDense>
 struct ExpandLds {
   uint32_t loff[kSlots + 1];      // offsets inside the tile fit 32 bits (slot_loc_kernel checks)
-  uint32_t lfist[kSlots];         // whole-word slots: start of the word's inverted list
-  uint8_t lpc[kSlots], lcls[kSlots];
-  uint32_t ccnt[kSlots / 64 + 1];
+  uint8_t lch[kSlots];            // the byte the slot's range is filled with (0: written by a later kernel)
+  uint8_t lcls[kDense ? kSlots : 1];
+  uint32_t lfist[kDense ? kSlots : 1];      // whole-word slots: start of the word's inverted list
 };
 
-// tile = index of the 2048-slot tile starting at slot t0
-template <class I>
-__device__ __forceinline__ void expand_stage(const MergeArgsT<I> &a, ExpandLds &L, uint64_t t0, int ns, uint64_t base, uint64_t tile) {
+template <class I, bool kDense>
+__device__ __forceinline__ void expand_stage(const MergeArgsT<I> &a, ExpandLds<kDense> &L, uint64_t t0, int ns, uint64_t base) {
   for (int s = threadIdx.x; s <= ns; s += 256) L.loff[s] = (uint32_t)(slot_off(a, t0 + s) - base);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t fullmask = 0;          // bit it: my slot of iteration it is a whole word; its rank inside the 64-slot chunk
-  uint64_t franks = 0;
-#pragma unroll
-  for (int it = 0; it < kSlots / 256; it++) {
-    const int s = it * 256 + threadIdx.x;
-    uint8_t cls = CLS_NONE;
-    if (s < ns) {
-      const uint64_t t = t0 + s;
-      uint8_t ch = a.pc[t];
-      cls = ch == 0 ? CLS_NONE : (ch == kEndOfWord ? CLS_FULL : CLS_FILL);
-      if (cls == CLS_FILL && a.pass != PASS_SA) {      // (always true: no launch of the expand kernels is SA-only; kept so that their code stays as it is)
-        const I g = a.grp[t];
-        if (a.hard[g]) {
-          cls = CLS_HARD;
-          ch = a.gmaj ? a.gmaj[g] : 0;      // the group's majority char (minority path) or 0 (every position written later)
-        }
-      }
-      L.lpc[s] = ch;
-      L.lcls[s] = cls;
+  for (int s = threadIdx.x; s < ns; s += 256) {
+    const uint64_t t = t0 + s;
+    const uint8_t pc = a.pc[t];
+    uint8_t cls = pc == 0 ? CLS_NONE : (pc == kEndOfWord ? CLS_FULL : CLS_FILL);
+    uint8_t ch = 0;      // whole words: every occurrence has a char of its own (word_chars_kernel)
+    if (cls == CLS_FILL) {
+      ch = fix_char(pc);
+      const I g = a.grp[t];
+      if (a.hard[g]) {
+        cls = CLS_HARD;
+        ch = a.gmaj ? a.gmaj[g] : 0;      // the group's majority char (its other occurrences are placed by hard_minor_kernel), or 0:
+      }                                   // every position of the group is written by the hard-group kernels that run after this one
     }
-    const unsigned long long fb = __ballot(cls == CLS_FULL);
-    if (lane == 0) L.ccnt[it * 4 + wv] = (uint32_t)__popcll(fb);
-    if (cls == CLS_FULL) { fullmask |= 1u << it; franks |= (uint64_t)__popcll(fb & ((1ull << lane) - 1ull)) << (8 * it); }
-  }
-  __syncthreads();
-  if (fullmask) {
-    const uint32_t q0 = a.ist ? 0u : a.fullbase[tile] + *a.fullbase0;
-#pragma unroll
-    for (int it = 0; it < kSlots / 256; it++)
-      if ((fullmask >> it) & 1u) {
-        const int s = it * 256 + threadIdx.x;
-        if (a.ist) { L.lfist[s] = a.ist[t0 + s]; continue; }
-        uint32_t before = 0;
-        for (int c2 = 0; c2 < it * 4 + wv; c2++) before += L.ccnt[c2];
-        L.lfist[s] = a.istart_lex[q0 + before + (uint32_t)((franks >> (8 * it)) & 0xffu)] + 1u;   // +1: ilist[0] is the EOS symbol
-      }
+    L.lch[s] = ch;
+    if constexpr (kDense) {
+      L.lcls[s] = cls;
+      if (cls == CLS_FULL) L.lfist[s] = a.ist[t];
+    }
   }
   __syncthreads();
 }
 
 // 16 output bytes starting at block-relative offset x0 (< Ltot)
-template <class I>
-__device__ __forceinline__ void expand_16(const MergeArgsT<I> &a, const ExpandLds &L, uint64_t t0, int ns, uint64_t base,
-                                          uint64_t x0, uint64_t Ltot) {
+template <class I, bool kDense>
+__device__ __forceinline__ void expand_16(const MergeArgsT<I> &a, const ExpandLds<kDense> &L, int ns, uint64_t base, uint64_t x0,
+                                          uint64_t Ltot) {
   if (base + x0 + 16 <= a.out_lo || base + x0 >= a.out_hi) return;     // outside this rank's slice
   int lo = 0, hi = ns;                    // loff[lo] <= x0 < loff[hi]
   while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (L.loff[mid] <= x0) lo = mid; else hi = mid; }
@@ -447,17 +403,7 @@ __device__ __forceinline__ void expand_16(const MergeArgsT<I> &a, const ExpandLd
     if (k < nb) {
       const uint64_t x = x0 + k;
       while (x >= nxt) { s++; nxt = L.loff[s + 1]; }
-      const uint8_t cl = L.lcls[s];
-      uint32_t ch = 0;
-      if (cl == CLS_FILL || cl == CLS_MULTI) {
-        ch = fix_char(L.lpc[s]);
-      } else if (cl == CLS_FULL) {
-        const uint64_t pos = a.ilist[L.lfist[s] + (uint32_t)(x - L.loff[s])];
-        ch = a.bwlast[pos];
-      } else {      // CLS_HARD: the group's majority char (its other occurrences are placed by hard_minor_kernel), or 0 and
-        ch = L.lpc[s];      // every position of the group is written by the hard-group kernels that run after this one
-      }
-      const uint32_t sh = (uint32_t)ch << (8 * (k & 3));
+      const uint32_t sh = (uint32_t)L.lch[s] << (8 * (k & 3));
       if (k < 4) r0 |= sh; else if (k < 8) r1 |= sh; else if (k < 12) r2 |= sh; else r3 |= sh;
     }
   }
@@ -475,13 +421,13 @@ __device__ __forceinline__ void expand_16(const MergeArgsT<I> &a, const ExpandLd
 // own).  One lane per position, so that the 8-byte stores of a wave are 512 contiguous bytes - the
 // 16-positions-per-thread layout of expand_16 would put every lane's store in a different 128-byte line.
 template <class I>
-__device__ __forceinline__ void expand_sa_1(const MergeArgsT<I> &a, const ExpandLds &L, uint64_t t0, int ns, uint64_t base,
+__device__ __forceinline__ void expand_sa_1(const MergeArgsT<I> &a, const ExpandLds<true> &L, uint64_t t0, int ns, uint64_t base,
                                             uint64_t x) {
   if (base + x < a.out_lo || base + x >= a.out_hi) return;
   int lo = 0, hi = ns;                    // loff[lo] <= x < loff[hi]
   while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (L.loff[mid] <= x) lo = mid; else hi = mid; }
   const uint8_t cl = L.lcls[lo];
-  if (cl != CLS_FULL && (cl != CLS_FILL || a.want_sa == SA_SPARSE)) return;
+  if (cl != CLS_FULL && cl != CLS_FILL) return;
   if (!sa_wanted(a, base + x)) return;
   const uint64_t pos = a.ilist[(cl == CLS_FULL ? L.lfist[lo] : slot_ist(a, t0 + lo)) + (uint32_t)(x - L.loff[lo])];
   sa_put(a, base + x, (cl == CLS_FULL && a.pos_base + base + x == 0) ? a.n_out_global - 1 : a.bwsai[pos] - slot_slen(a, t0 + lo));
@@ -493,66 +439,87 @@ __device__ __forceinline__ void expand_sa_1(const MergeArgsT<I> &a, const Expand
 //   * a slot, or a group of slots, whose chars all agree fills its range with one char: only the first and
 //     the last position of that range can be run boundaries - unit_edges_kernel;
 //   * hard groups: the two ends (unit_edges_kernel) and what the hard-group kernels find inside.
-template <class I>
+template <class I, bool kDense>
 __global__ __launch_bounds__(256) void expand_kernel(MergeArgsT<I> a, uint32_t *__restrict__ heavy, uint32_t *__restrict__ nheavy,
                                                      uint32_t heavy_cap) {
-  __shared__ ExpandLds L;
+  __shared__ ExpandLds<kDense> L;
   const uint64_t t0 = (uint64_t)BID * kSlots;
   if (t0 >= a.N) return;      // a workgroup of the padded last grid row
   const int ns = (a.N - t0) >= (uint64_t)kSlots ? kSlots : (int)(a.N - t0);
   const uint64_t base = slot_off(a, t0);
-  expand_stage(a, L, t0, ns, base, BID);
+  expand_stage(a, L, t0, ns, base);
   const uint64_t Ltot = L.loff[ns];
   if (base + Ltot <= a.out_lo || base >= a.out_hi) return;
   // a block whose slots emit more than the quota (a word with hundreds of thousands of
   // occurrences) finishes only its first quota here; expand_heavy_kernel shares the rest
   const uint64_t mine = Ltot <= kExpandQuota ? Ltot : kExpandQuota;
-  if (Ltot > kExpandQuota && threadIdx.x == 0 && (a.pass & PASS_BWT)) { uint32_t i = atomicAdd(nheavy, 1u); if (i < heavy_cap) heavy[i] = BID; }
-  if (a.pass & PASS_BWT)
-    for (uint64_t x0 = (uint64_t)threadIdx.x * 16; x0 < mine; x0 += 256 * 16) expand_16(a, L, t0, ns, base, x0, Ltot);
-  if (!(a.pass & PASS_SA)) return;
-  if (a.want_sa)
+  if (Ltot > kExpandQuota && threadIdx.x == 0) { uint32_t i = atomicAdd(nheavy, 1u); if (i < heavy_cap) heavy[i] = BID; }
+  for (uint64_t x0 = (uint64_t)threadIdx.x * 16; x0 < mine; x0 += 256 * 16) expand_16(a, L, ns, base, x0, Ltot);
+  if constexpr (kDense)
     for (uint64_t x = threadIdx.x; x < mine; x += 256) expand_sa_1(a, L, t0, ns, base, x);
 }
 
-template <class I>
+template <class I, bool kDense>
 __global__ __launch_bounds__(256) void expand_heavy_kernel(MergeArgsT<I> a, const uint32_t *__restrict__ heavy, uint32_t nheavy) {
-  __shared__ ExpandLds L;
+  __shared__ ExpandLds<kDense> L;
   for (uint32_t q = 0; q < nheavy; q++) {
     const uint64_t t0 = (uint64_t)heavy[q] * kSlots;
     const int ns = (a.N - t0) >= (uint64_t)kSlots ? kSlots : (int)(a.N - t0);
     const uint64_t base = slot_off(a, t0);
     __syncthreads();
-    expand_stage(a, L, t0, ns, base, heavy[q]);
+    expand_stage(a, L, t0, ns, base);
     const uint64_t Ltot = L.loff[ns];
-    if (a.pass & PASS_BWT)
-      for (uint64_t x0 = kExpandQuota + ((uint64_t)BID * 256 + threadIdx.x) * 16; x0 < Ltot; x0 += (uint64_t)GDIM * 256 * 16)
-        expand_16(a, L, t0, ns, base, x0, Ltot);
-    if (a.want_sa && (a.pass & PASS_SA))      // sparse mode: expand_sa_1 writes for full-word slots only (other classes come from unit_edges_kernel)
+    for (uint64_t x0 = kExpandQuota + ((uint64_t)BID * 256 + threadIdx.x) * 16; x0 < Ltot; x0 += (uint64_t)GDIM * 256 * 16)
+      expand_16(a, L, ns, base, x0, Ltot);
+    if constexpr (kDense)
       for (uint64_t x = kExpandQuota + (uint64_t)BID * 256 + threadIdx.x; x < Ltot; x += (uint64_t)GDIM * 256)
         expand_sa_1(a, L, t0, ns, base, x);
   }
 }
 
-// Sparse SA mode, whole words: every occurrence of a whole word carries its own char (bwlast), so any of the P positions
-// they emit can be a run boundary.  One lane per occurrence e of the inverted lists laid end to end (ilist[1 + e], read
-// coalesced): its word is the one of lexicographic rank q with istart_lex[q] <= e (bisection over d entries that stay in
-// L2), the word's slot is wslot_lex[q], the position is that slot's offset plus the occurrence's index in its list.
-// (Staging every tile of expand_kernel again would find a dozen whole words in each.)
+// Whole words, one lane per occurrence e of the inverted lists laid end to end (iword[e + 1], ilist[e + 1]: read coalesced).
+// The entry's word is the one of lexicographic rank q = iword[e + 1] - 1 (the sorted symbols of the inverted-list sort), the
+// word's slot is wslot_lex[q], the output position that slot's offset plus the occurrence's index in its list; lanes of one
+// word read the same q-indexed entries.  false: the word's slot belongs to another rank's range (multi-GPU).
 template <class I>
-__global__ __launch_bounds__(256) void word_sa_kernel(MergeArgsT<I> a, uint64_t P, const uint64_t *__restrict__ wslot_lex,
-                                                      uint64_t slot_base) {
+__device__ __forceinline__ bool word_entry(const MergeArgsT<I> &a, uint64_t e, uint64_t &t, uint64_t &x) {
+  const uint32_t q = a.iword[e + 1] - 1u;
+  const uint64_t gs = a.wslot_lex[q];
+  if (gs < a.slot_base || gs - a.slot_base >= a.N) return false;
+  t = gs - a.slot_base;
+  x = slot_off(a, t) + (e - (uint64_t)a.istart_lex[q]);
+  return true;
+}
+// the chars: every occurrence of a whole word carries its own (bwlast of its BWT(P) position; pfbwt.cpp:153-197) - written
+// over the zeros expand_kernel left there
+template <class I>
+__global__ __launch_bounds__(256) void word_chars_kernel(MergeArgsT<I> a, uint64_t P) {
   const uint64_t e = (uint64_t)BID * 256 + threadIdx.x;
   if (e >= P) return;
-  uint32_t lo = 0, hi = a.d;                 // istart_lex[lo] <= e < istart_lex[hi]  (istart_lex[d] = P)
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)a.istart_lex[mid] <= e) lo = mid; else hi = mid; }
-  const uint64_t gs = wslot_lex[lo];
-  if (gs < slot_base || gs - slot_base >= a.N) return;      // (multi-GPU: the word's slot belongs to another rank's range)
-  const uint64_t t = gs - slot_base;
-  const uint64_t x = slot_off(a, t) + (e - (uint64_t)a.istart_lex[lo]);
-  if (!sa_wanted(a, x)) return;
-  const uint64_t pos = a.ilist[e + 1];       // +1: ilist[0] is the EOS symbol (pfbwt.cpp:389)
+  uint64_t t, x;
+  if (!word_entry(a, e, t, x) || x < a.out_lo || x >= a.out_hi) return;
+  a.bwt[x] = a.bwlast[a.ilist[e + 1]];       // +1: ilist[0] is the EOS symbol (pfbwt.cpp:389)
+}
+// Sparse SA mode: any of the P positions the whole words emit can be a run boundary (unrelated chars).
+// (Staging every tile of expand_kernel again would find a dozen whole words in each.)
+template <class I>
+__global__ __launch_bounds__(256) void word_sa_kernel(MergeArgsT<I> a, uint64_t P) {
+  const uint64_t e = (uint64_t)BID * 256 + threadIdx.x;
+  if (e >= P) return;
+  uint64_t t, x;
+  if (!word_entry(a, e, t, x) || !sa_wanted(a, x)) return;
+  const uint64_t pos = a.ilist[e + 1];
   sa_put(a, x, a.pos_base + x == 0 ? a.n_out_global - 1 : a.bwsai[pos] - slot_slen(a, t));
+}
+// iword[] where the parse stage did not leave it (inverted lists read from a file): entry e belongs to the word of rank q
+// with istart_lex[q] <= e < istart_lex[q + 1]
+__global__ void iword_kernel(uint64_t P, uint32_t d, const uint32_t *__restrict__ istart_lex, uint32_t *__restrict__ iword) {
+  const uint64_t e = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (e > P) return;
+  if (e == P) { iword[0] = 0; return; }
+  uint32_t lo = 0, hi = d;
+  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)istart_lex[mid] <= e) lo = mid; else hi = mid; }
+  iword[e + 1] = lo + 1;
 }
 
 // Sparse SA mode.  A *unit* is a slot that emits, or a group of slots of equal suffixes (several words share the
@@ -561,8 +528,15 @@ __global__ __launch_bounds__(256) void word_sa_kernel(MergeArgsT<I> a, uint64_t 
 // The first position belongs to the smallest BWT(P) position over the members' inverted lists, the last one to the
 // largest (WordRec::first / last per word): O(members) per unit instead of merging the lists (pfbwt.cpp:605-676 walks a
 // heap through all of them).  One lane per slot: whether the two positions can be sampled from the boundary bitmap of
-// the finished BWT, "needed" flags spread over a unit's lanes, segmented min / max by shuffles; a unit that crosses the
-// wave is finished serially by its first (last) lane.
+// the finished BWT, "needed" flags spread over a unit's lanes, segmented min / max by shuffles; the part of a unit that
+// lies outside the wave is fetched by all 64 lanes together.
+// A unit is a contiguous run of lanes, so everything a lane asks about its unit follows from one ballot: cont (the unit
+// goes on in the next slot).  Lanes l and l + o belong to one unit when no cont bit in [l, l + o) is clear; only mn and
+// mx travel through the shuffles (before: the group and the unit flag with them at every step, 70 ds_bpermute per wave).
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+__device__ __forceinline__ uint64_t lane_read(uint64_t v, int l) {
+  return (uint64_t)lane_read((uint32_t)v, l) | ((uint64_t)lane_read((uint32_t)(v >> 32), l) << 32);
+}
 template <class I>
 __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
   const uint64_t t = (uint64_t)BID * 256 + threadIdx.x;
@@ -570,17 +544,18 @@ __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
   const uint64_t wbase = t - lane;
   const bool in = t < a.N;
   const uint32_t ch = in ? a.pc[t] : 0u;
-  const bool unit = ch != 0 && ch != kEndOfWord;        // lanes that belong to a fill / hard unit (whole words: expand_kernel)
-  uint64_t g = t;
+  const bool unit = ch != 0 && ch != kEndOfWord;        // lanes that belong to a fill / hard unit (whole words: word_sa_kernel)
+  I g = 0;                                         // (read of unit lanes only)
   if (unit) g = a.grp[t];
   const unsigned long long um = __ballot(unit);
   // same unit as the next slot?
-  const uint64_t g_next = __shfl_down(g, 1, 64);
+  const I g_next = __shfl_down(g, 1, 64);
   const bool unit_next = (um >> ((lane + 1) & 63)) & 1ull;
   bool cont;                                       // the unit goes on in slot t + 1
   if (lane < 63) cont = unit && unit_next && g_next == g;
-  else cont = unit && t + 1 < a.N && a.pc[t + 1] != 0 && a.pc[t + 1] != kEndOfWord && a.grp[t + 1] == (I)g;
-  const bool head = unit && g == t;
+  else cont = unit && t + 1 < a.N && a.pc[t + 1] != 0 && a.pc[t + 1] != kEndOfWord && a.grp[t + 1] == g;
+  const unsigned long long cm = __ballot(cont);
+  const bool head = unit && (uint64_t)g == t;
   const bool last = unit && !cont;
   // is the unit's first / last position one the sampled files can look at?
   uint64_t o_first = 0, o_last = 0;
@@ -589,64 +564,65 @@ __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
   const bool need_first = head && sa_wanted(a, o_first);
   const bool need_last = last && sa_wanted(a, o_last);
   // spread the two flags over the lanes of the unit that lie in this wave
-  const bool head_here = unit && g >= wbase;
-  const int hl = head_here ? (int)(g - wbase) : lane;
-  const unsigned long long lastmask = __ballot(last);
-  const unsigned long long lm = lastmask >> lane;
+  const bool head_here = unit && (uint64_t)g >= wbase;
+  const int hl = head_here ? (int)((uint64_t)g - wbase) : lane;
+  const unsigned long long lm = __ballot(last) >> lane;      // (the first `last` lane at or after a unit lane is its own unit's)
   const int ll = lm ? lane + (__ffsll((long long)lm) - 1) : lane;
-  const bool nf = __shfl((int)need_first, hl, 64) != 0 && head_here;
-  const bool nlz = __shfl((int)need_last, ll, 64) != 0 && unit && lm != 0;
+  const bool nf = head_here && ((__ballot(need_first) >> hl) & 1ull);
+  const bool nlz = unit && lm != 0 && ((__ballot(need_last) >> ll) & 1ull);
   uint32_t mn = 0xFFFFFFFFu, mx = 0;
   uint64_t mysl = 0;      // length of the (common) suffix: distance to the word's terminator
-  if (unit && (nf || nlz)) {
+  if (nf || nlz) {
     if (nf) mn = slot_first(a, t);
     if (nlz) mx = slot_last(a, t);
     if (need_first || need_last) mysl = slot_slen(a, t);      // (equal suffixes: the same for every member; only the edge lanes store)
   }
-  // segmented reductions: min towards the first lane of the unit, max towards its last lane
+  // segmented reductions: min towards the first lane of the unit, max towards its last lane.  Bit l of r: lanes l .. l + o
+  // are one unit (lane 63's cont bit speaks of the next wave); no bit left = no unit of the wave is longer than o
+  const bool do_min = __ballot(nf) != 0, do_max = __ballot(nlz) != 0;
+  unsigned long long r = cm & ~(1ull << 63);
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t omn = __shfl_down(mn, o, 64);
-    const uint64_t og = __shfl_down(g, o, 64);
-    const int ou = __shfl_down((int)unit, o, 64);
-    if (lane + o < 64 && unit && ou && og == g) mn = omn < mn ? omn : mn;
-    const uint32_t umx = __shfl_up(mx, o, 64);
-    const uint64_t ug = __shfl_up(g, o, 64);
-    const int uu = __shfl_up((int)unit, o, 64);
-    if (lane >= o && unit && uu && ug == g) mx = umx > mx ? umx : mx;
+    if (!r) break;
+    if (do_min) {
+      const uint32_t v = __shfl_down(mn, o, 64);
+      if (((r >> lane) & 1ull) && v < mn) mn = v;
+    }
+    if (do_max) {
+      const uint32_t v = __shfl_up(mx, o, 64);
+      if (lane >= o && ((r >> (lane - o)) & 1ull) && v > mx) mx = v;
+    }
+    r &= r >> o;
   }
   // At most one unit leaves the wave through lane 63 (its head is here and wants the minimum over ALL its members) and at
   // most one enters through lane 0 (its last member is here and wants the maximum): the members outside the wave are
   // fetched by all 64 lanes together, 64 at a time (one lane walking them was a chain of 3 dependent gathers per member,
   // hundreds of members long for the word families of a 1000-copy collection).
-  const uint64_t g63 = __shfl(g, 63, 64);
-  const bool cont63 = __shfl((int)cont, 63, 64) != 0;
+  const I g63 = lane_read(g, 63);
+  const bool cont63 = (cm >> 63) & 1ull;
   const unsigned long long fwd = __ballot(need_first && cont63 && g63 == g);       // the head lane of the unit that goes on
   if (fwd) {
     uint32_t ext = 0xFFFFFFFFu;
     for (uint64_t m0 = wbase + 64;; m0 += 64) {
       const uint64_t m = m0 + lane;
-      const bool mine = m < a.N && a.grp[m] == (I)g63;       // (members are contiguous; a slot of the group emits)
+      const bool mine = m < a.N && a.grp[m] == g63;       // (members are contiguous; a slot of the group emits)
       uint32_t f = 0xFFFFFFFFu;
       if (mine) f = slot_first(a, m);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(f, o, 64); f = v < f ? v : f; }
+      f = wave_min(f);
       ext = f < ext ? f : ext;
       if (__ballot(mine) != ~0ull) break;
     }
     if ((fwd >> lane) & 1ull) mn = ext < mn ? ext : mn;
   }
-  const uint64_t g0 = __shfl(g, 0, 64);
-  const int unit0 = __shfl((int)unit, 0, 64);
-  const unsigned long long bwd = __ballot(need_last && g < wbase);                  // the last lane of the unit that came in
-  if (bwd && unit0) {
+  const uint64_t g0 = lane_read(g, 0);
+  const unsigned long long bwd = __ballot(need_last && (uint64_t)g < wbase);        // the last lane of the unit that came in
+  if (bwd && (um & 1ull)) {
     uint32_t ext = 0;
     for (uint64_t m0 = g0; m0 < wbase; m0 += 64) {
       const uint64_t m = m0 + lane;
       uint32_t l = 0;
       if (m < wbase) l = slot_last(a, m);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(l, o, 64); l = v > l ? v : l; }
+      l = wave_max(l);
       ext = l > ext ? l : ext;
     }
     if ((bwd >> lane) & 1ull) mx = ext > mx ? ext : mx;
@@ -1288,6 +1264,7 @@ struct Merge {
   // ---- per word
   struct {
     DBuf<uint32_t> istart_lex, wistart;      // istart in lexicographic order (pfbwt.cpp:388-396), looked up per word
+    DBuf<uint32_t> iword;                    // the word of every inverted-list entry, where the parse stage left none
     DBuf<WordRec> wrec;                      // list start, occurrences, smallest / largest BWT(P) position, terminator
   } word;
   // ---- per slot
@@ -1295,8 +1272,6 @@ struct Merge {
     DBuf<uint8_t> pc, hard;
     DBuf<uint32_t> loc, ovf;
     DBuf<uint64_t> tsum, tbase;
-    DBuf<uint32_t> tile_full, fullbase, fullbase0;
-    DBuf<unsigned long long> first_full;
     DBuf<uint32_t> sfirst, slast, ssl;
   } slot;
   // ---- hard groups
@@ -1341,6 +1316,10 @@ struct Merge {
     word.wrec.alloc(c, d);
     hipLaunchKernelGGL(wistart_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, ix.lexrank.p, word.istart_lex.p, D.wocc.p, pb.ilist.p,
                        ix.wend.p, word.wistart.p, word.wrec.p);
+    if (!pb.iword.p) {
+      word.iword.alloc(c, pb.P + 1);
+      hipLaunchKernelGGL(iword_kernel, gdim(cdiv(pb.P + 1, TB)), gdim(TB), 0, c->stream, pb.P, d, word.istart_lex.p, word.iword.p);
+    }
   }
 
   // ---- 2. slot tables: chars, hard flags, counts per tile, from wherever the records are (cnt: the from-keys counts)
@@ -1349,16 +1328,12 @@ struct Merge {
     slot.loc.alloc(c, ntile << kOffTileLog); slot.ovf.alloc(c, 1);
     alloc_counts(c, slot.tsum, ntile); slot.tbase.alloc(c, ntile + 1);
     slot.hard.zero();
-    slot.tile_full.alloc(c, ntile + 1); slot.fullbase.alloc(c, ntile + 1); slot.fullbase0.alloc(c, 1);
-    slot.first_full.alloc(c, 1);
-    slot.tile_full.zero();
-    PFP_HIP(hipMemsetAsync(slot.first_full.p, 0xFF, 8, c->stream));
     slot.ovf.zero();
   }
   void slot_tables_from_keys(DBuf<uint32_t> &cnt) {
     { KScope ks(c, "pfp::slot_payload_kernel", N * (8 + 1 + 5));
       hipLaunchKernelGGL(slot_payload_kernel<I>, gdim(cdiv(cdiv64(N, 8), 256)), gdim(256), 0, c->stream, N, so.sa.p, so.skeys.p,
-                         so.refined.p, D.bytes.p, wv, D.wocc.p, d, o.w, cnt.p, slot.pc.p, slot.tile_full.p, slot.first_full.p); }
+                         so.refined.p, D.bytes.p, wv, D.wocc.p, d, o.w, cnt.p, slot.pc.p); }
     { KScope ks(c, "pfp::slot_loc_kernel", N * 8);
       hipLaunchKernelGGL(slot_loc_kernel, gdim((unsigned)ntile), gdim(256), 0, c->stream, cnt.p, N, slot.loc.p, slot.tsum.p, slot.ovf.p); }
     { KScope ks(c, "pfp::group_flags_kernel", N * 5);
@@ -1383,15 +1358,12 @@ struct Merge {
     if (sa_mode != SA_NONE) slot.ssl.alloc(c, ntile << kOffTileLog);
     KScope ks(c, "pfp::slot_records_kernel", N * (2 * sizeof(I) + (prec ? 16 : 64 + 32) + 4 + 1 + 4 + (slot.slast.p ? 4 : 0) + (slot.ssl.p ? 4 : 0)));
     hipLaunchKernelGGL(slot_records_kernel<I>, gdim((unsigned)ntile), gdim(256), 0, c->stream, N, so.sa.p, so.grp.p, prec, slot.loc.p,
-                       slot.pc.p, slot.sfirst.p, slot.slast.p, slot.ssl.p, slot.tsum.p, slot.ovf.p, slot.tile_full.p, slot.first_full.p,
-                       slot.hard.p, dense, wv, o.w, reinterpret_cast<const uint4 *>(word.wrec.p), dense);
+                       slot.pc.p, slot.sfirst.p, slot.slast.p, slot.ssl.p, slot.tsum.p, slot.ovf.p, slot.hard.p, dense, wv, o.w, reinterpret_cast<const uint4 *>(word.wrec.p), dense);
   }
 
   // ---- 3. offsets and totals
   void offsets_and_totals() {
     exclusive_sum_u64(c, slot.tsum.p, slot.tbase.p, ntile + 1);
-    exclusive_sum_u32(c, slot.tile_full.p, slot.fullbase.p, ntile + 1);
-    hipLaunchKernelGGL(full_base0_kernel<I>, dim3(1), dim3(1), 0, c->stream, slot.first_full.p, so.sa.p, wv, ix.lexrank.p, slot.fullbase0.p);
     PFP_REQUIRE(read_scalar(c, slot.ovf.p) == 0, PFP_ELIMIT, "2048 consecutive suffix-array slots emit 2^32 or more BWT positions");
     n_out = read_scalar(c, slot.tbase.p + ntile);
     PFP_REQUIRE(o.expect_n_out == 0 || n_out == o.expect_n_out, PFP_EFORMAT,
@@ -1411,7 +1383,8 @@ struct Merge {
     a.sfirst = dense ? nullptr : slot.sfirst.p; a.slast = slot.slast.p; a.ssl = slot.ssl.p;
     a.pc = slot.pc.p; a.hard = slot.hard.p; a.tbase = slot.tbase.p; a.loc = slot.loc.p;
     a.ilist = pb.ilist.p; a.bwlast = pb.bwlast.p; a.bwsai = pb.bwsai.p;
-    a.istart_lex = word.istart_lex.p; a.fullbase = slot.fullbase.p; a.fullbase0 = slot.fullbase0.p;
+    a.istart_lex = word.istart_lex.p; a.iword = pb.iword.p ? pb.iword.p : word.iword.p;
+    a.wslot_lex = ix.wslot_lex.p; a.slot_base = so.slot_base;
     // the caller's buffers hold positions [out_lo, out_hi): rebase so that kernels index by global position
     a.out_lo = o.out_lo; a.out_hi = o.out_hi < n_out ? o.out_hi : n_out;
     a.bwt = out.d_bwt - o.out_lo; a.out_sa = out.d_sa ? out.d_sa - o.out_lo : nullptr;
@@ -1472,16 +1445,24 @@ struct Merge {
     return HeadList<I>{hg.fb_heads.p, hg.list_len.p + kFallbackHeads, n_fallback};
   }
 
-  // ---- 7. expand: fill and whole-word entries, the majority chars of the hard groups
+  // ---- 7. expand: fill entries and the majority chars of the hard groups, then the whole words' chars occurrence by occurrence
   void expand() {
     const MergeArgsT<I> ap = with_pass(first_pass);
+    const bool dense = sa_mode == SA_DENSE;
     heavy.alloc(c, nblk); nheavy.alloc(c, 1);
     nheavy.zero();
-    { KScope ks(c, "pfp::expand_kernel", N * 14 + n_out * (sa_mode == SA_DENSE ? 17 : 1));
-      hipLaunchKernelGGL(expand_kernel<I>, gdim(nblk), gdim(256), 0, c->stream, ap, heavy.p, nheavy.p, nblk); }
+    // per slot: offset, char, group and its flag; per position the byte (dense: ilist entry, bwsai gather, 8-byte value)
+    { KScope ks(c, "pfp::expand_kernel", N * (4 + 1 + sizeof(I) + 1) + n_out * (dense ? 17 : 1));
+      if (dense) hipLaunchKernelGGL((expand_kernel<I, true>), gdim(nblk), gdim(256), 0, c->stream, ap, heavy.p, nheavy.p, nblk);
+      else hipLaunchKernelGGL((expand_kernel<I, false>), gdim(nblk), gdim(256), 0, c->stream, ap, heavy.p, nheavy.p, nblk); }
     const uint32_t nh = read_scalar(c, nheavy.p);
-    KScope ks2(c, "pfp::expand_heavy_kernel", 0);   // bytes are accounted in expand_kernel's n_out term
-    if (nh) hipLaunchKernelGGL(expand_heavy_kernel<I>, gdim(c->n_cu * 4), gdim(256), 0, c->stream, ap, heavy.p, nh);
+    { KScope ks2(c, "pfp::expand_heavy_kernel", 0);   // bytes are accounted in expand_kernel's n_out term
+      if (nh && dense) hipLaunchKernelGGL((expand_heavy_kernel<I, true>), gdim(c->n_cu * 4), gdim(256), 0, c->stream, ap, heavy.p, nh);
+      else if (nh) hipLaunchKernelGGL((expand_heavy_kernel<I, false>), gdim(c->n_cu * 4), gdim(256), 0, c->stream, ap, heavy.p, nh); }
+    if (pb.P) {      // per entry: its word's rank and BWT(P) position, the word's slot, list start and offset, one char in and out
+      KScope ks(c, "pfp::word_chars_kernel", pb.P * (4 + 4 + 1 + 1) + (uint64_t)d * (8 + 4 + 12));
+      hipLaunchKernelGGL(word_chars_kernel<I>, gdim(cdiv(pb.P, 256)), gdim(256), 0, c->stream, ap, pb.P);
+    }
     PFP_HIP(hipGetLastError());
   }
 
@@ -1616,12 +1597,10 @@ struct Merge {
   // ---- 13. sparse SA, second round: SA values at the boundaries, class by class
   void sa_round(const HeadList<I> &lds) {
     const MergeArgsT<I> ap = with_pass(PASS_SA);
-    // whole words: one lane per occurrence of the inverted lists (every caller ranks the words - compute_lexrank or
-    // compute_lexrank_from_slots - before it merges; a parse without phrases emits nothing)
-    PFP_REQUIRE(ix.wslot_lex.p, PFP_EINVAL, "merge: the dictionary index has no whole-word slots (compute_lexrank has not run)");
-    if (pb.P) {
-      KScope ks(c, "pfp::word_sa_kernel", pb.P * (4 + 8 + 8 + 8));
-      hipLaunchKernelGGL(word_sa_kernel<I>, gdim(cdiv(pb.P, 256)), gdim(256), 0, c->stream, ap, pb.P, ix.wslot_lex.p, so.slot_base);
+    // whole words: one lane per occurrence of the inverted lists (a parse without phrases emits nothing)
+    if (pb.P) {      // per entry: its word's rank; at a boundary its BWT(P) position, the bwsai gather and the value
+      KScope ks(c, "pfp::word_sa_kernel", pb.P * (4 + 1) + (uint64_t)d * (8 + 4 + 12) + out.n_bound * (4 + 8 + 8));
+      hipLaunchKernelGGL(word_sa_kernel<I>, gdim(cdiv(pb.P, 256)), gdim(256), 0, c->stream, ap, pb.P);
     }
     { KScope ks(c, "pfp::unit_edges_kernel", N * (1 + sizeof(I) * 2 + 4));
       hipLaunchKernelGGL(unit_edges_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, ap); }
@@ -1659,6 +1638,9 @@ struct Merge {
 
   void run() {
     PFP_REQUIRE(!o.flags || pb.bwsai.p, PFP_EINVAL, "SA output requested without sa info");
+    // the whole words are written and sampled by inverted-list entry (every caller ranks the words - compute_lexrank or
+    // compute_lexrank_from_slots - before it merges)
+    PFP_REQUIRE(ix.wslot_lex.p, PFP_EINVAL, "merge: the dictionary index has no whole-word slots (compute_lexrank has not run)");
     word_records();
     {
       DBuf<uint32_t> cnt;      // from the sort keys: occurrences per slot, until the offsets are summed

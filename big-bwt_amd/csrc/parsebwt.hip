@@ -59,7 +59,8 @@ void parse_bwt(pfp_ctx *c, const uint32_t *parse_sym, uint64_t P, const uint8_t 
   out.ilist.alloc(c, P + 1);
   out.bwlast.alloc(c, P + 1);
   if (sai) out.bwsai.alloc(c, P + 1);
-  DBuf<uint32_t> bwtp(c, P + 1), bwtp_s(c, P + 1), jidx(c, P + 1);
+  out.iword.alloc(c, P + 1);
+  DBuf<uint32_t> bwtp(c, P + 1), jidx(c, P + 1);
   if (sai) {
     DBuf<uint4> rec(c, P);
     { KScope ks(c, "pfp::parse_pack16_kernel", P * (13 + 16));
@@ -75,8 +76,9 @@ void parse_bwt(pfp_ctx *c, const uint32_t *parse_sym, uint64_t P, const uint8_t 
     hipLaunchKernelGGL(parse_gather_rec_kernel<uint2>, gdim(cdiv(P + 1, TB)), gdim(TB), 0, c->stream, P, (const uint32_t *)so.sa.p, (const uint2 *)rec.p,
                        bwtp.p, out.bwlast.p, (uint64_t *)nullptr, jidx.p);
   }
-  // bwtparse.c:281-303: positions grouped by symbol, ascending inside a group == stable sort
-  { SortTag tag("inverted list"); sort_pairs_u32_u32(c, bwtp.p, bwtp_s.p, jidx.p, out.ilist.p, P + 1, 0, bits_for(d)); }
+  // bwtparse.c:281-303: positions grouped by symbol, ascending inside a group == stable sort.  The sorted symbols are kept:
+  // the word of every inverted-list entry (ParseBWT::iword), which the merge would otherwise bisect for
+  { SortTag tag("inverted list"); sort_pairs_u32_u32(c, bwtp.p, out.iword.p, jidx.p, out.ilist.p, P + 1, 0, bits_for(d)); }
   PFP_HIP(hipGetLastError());
 }
 
