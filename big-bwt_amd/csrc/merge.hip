@@ -241,11 +241,6 @@ enum : uint8_t { CLS_NONE = 0, CLS_FILL = 1, CLS_FULL = 2, CLS_HARD = 3 };
 // at run boundaries of the BWT (-s / -e)
 enum : int { SA_NONE = 0, SA_DENSE = 1, SA_SPARSE = 2 };
 
-template <class I>
-__global__ void gather_idx_kernel(uint64_t n, const I *__restrict__ idx, const I *__restrict__ src, I *__restrict__ dst) {
-  uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
-}
 // per word: start of its inverted list, number of occurrences, smallest / largest BWT(P) position, end - one 32-byte record,
 // one memory sector for everything a hard-group or unit-edge kernel wants to know about a member's word
 struct alignas(32) WordRec { uint32_t ist, occ, first, last; uint64_t wend, pad; };      // wend: position of the word's terminator
@@ -296,6 +291,13 @@ __device__ __forceinline__ void sa_put(const MergeArgsT<I> &a, uint64_t x, uint6
   const uint64_t r = x - a.out_lo, wv = a.bmap[r >> 6];
   if (!((wv >> (r & 63)) & 1ull)) return;
   if (a.sa_c) a.sa_c[a.bpre[r >> 6] + (uint64_t)__popcll(wv & ((1ull << (r & 63)) - 1ull))] = v;
+  else a.out_sa[x] = v;
+}
+// sa_put for a caller that has looked at x itself: x lies in the slice and its bit is set in `word`, the word of the
+// boundary map that holds it, `pre` that word's bpre[] entry (both unused without a map) - the map is not read again
+template <class I>
+__device__ __forceinline__ void sa_put_at(const MergeArgsT<I> &a, uint64_t x, uint64_t word, uint64_t pre, uint64_t v) {
+  if (a.bmap && a.sa_c) a.sa_c[pre + (uint64_t)__popcll(word & ((1ull << ((x - a.out_lo) & 63)) - 1ull))] = v;
   else a.out_sa[x] = v;
 }
 template <class I>
@@ -543,26 +545,44 @@ __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
   const int lane = threadIdx.x & 63;
   const uint64_t wbase = t - lane;
   const bool in = t < a.N;
-  const uint32_t ch = in ? a.pc[t] : 0u;
+  // ---- round trip 1: everything that is addressed by t alone, asked for by every lane with a slot (streams that are read
+  // anyway: most units are one slot, which is head and last member at once).  What keeps each load inside its allocation:
+  //   pc[t + 1], grp[t + 1] : t + 1 <= N, and pc and grp have N + 8 entries (their values at N are never used: `t + 1 < N` below)
+  //   loc[t + 1]            : loc is padded to whole offset tiles, ntile * 2048 > N entries (slot N's is the tile's running total)
+  //   tbase[(t + 1) >> 11]  : (t + 1) >> 11 <= N >> 11 = ntile - 1, and tbase has ntile + 1 entries
+  uint32_t ch = 0, ch_n = 0, loc_t = 0, loc_n = 0;
+  uint64_t tb_t = 0, tb_n = 0;
+  I g = 0, g_n = 0;
+  if (in) {
+    ch = a.pc[t]; g = a.grp[t];
+    loc_t = a.loc[t]; loc_n = a.loc[t + 1];
+    tb_t = a.tbase[t >> kOffTileLog]; tb_n = a.tbase[(t + 1) >> kOffTileLog];
+    if (lane == 63) { ch_n = a.pc[t + 1]; g_n = a.grp[t + 1]; }       // the next wave's first slot
+  }
   const bool unit = ch != 0 && ch != kEndOfWord;        // lanes that belong to a fill / hard unit (whole words: word_sa_kernel)
-  I g = 0;                                         // (read of unit lanes only)
-  if (unit) g = a.grp[t];
+  if (!unit) g = 0;
   const unsigned long long um = __ballot(unit);
   // same unit as the next slot?
   const I g_next = __shfl_down(g, 1, 64);
   const bool unit_next = (um >> ((lane + 1) & 63)) & 1ull;
   bool cont;                                       // the unit goes on in slot t + 1
   if (lane < 63) cont = unit && unit_next && g_next == g;
-  else cont = unit && t + 1 < a.N && a.pc[t + 1] != 0 && a.pc[t + 1] != kEndOfWord && a.grp[t + 1] == g;
+  else cont = unit && t + 1 < a.N && ch_n != 0 && ch_n != kEndOfWord && g_n == g;
   const unsigned long long cm = __ballot(cont);
   const bool head = unit && (uint64_t)g == t;
   const bool last = unit && !cont;
-  // is the unit's first / last position one the sampled files can look at?
-  uint64_t o_first = 0, o_last = 0;
-  if (head) o_first = slot_off(a, t);
-  if (last) o_last = slot_off(a, t + 1) - 1;
-  const bool need_first = head && sa_wanted(a, o_first);
-  const bool need_last = last && sa_wanted(a, o_last);
+  // ---- round trip 2: is the unit's first / last position one the sampled files can look at?  The word of the boundary map
+  // and its prefix count together - the store at the end needs both, and their index is known as soon as the offset is
+  const uint64_t o_first = tb_t + loc_t, o_last = tb_n + loc_n - 1;       // (slot_off(t), slot_off(t + 1) - 1: a unit lane emits)
+  const bool ask_first = head && o_first >= a.out_lo && o_first < a.out_hi;
+  const bool ask_last = last && o_last >= a.out_lo && o_last < a.out_hi;
+  uint64_t w_first = ~0ull, w_last = ~0ull, p_first = 0, p_last = 0;      // (no map: every position of the slice is wanted)
+  if (a.bmap) {
+    if (ask_first) { const uint64_t k = (o_first - a.out_lo) >> 6; w_first = a.bmap[k]; p_first = a.bpre[k]; }
+    if (ask_last) { const uint64_t k = (o_last - a.out_lo) >> 6; w_last = a.bmap[k]; p_last = a.bpre[k]; }
+  }
+  const bool need_first = ask_first && ((w_first >> ((o_first - a.out_lo) & 63)) & 1ull);
+  const bool need_last = ask_last && ((w_last >> ((o_last - a.out_lo) & 63)) & 1ull);
   // spread the two flags over the lanes of the unit that lie in this wave
   const bool head_here = unit && (uint64_t)g >= wbase;
   const int hl = head_here ? (int)((uint64_t)g - wbase) : lane;
@@ -627,8 +647,12 @@ __global__ __launch_bounds__(256) void unit_edges_kernel(MergeArgsT<I> a) {
     }
     if ((bwd >> lane) & 1ull) mx = ext > mx ? ext : mx;
   }
-  if (need_first) sa_put(a, o_first, a.bwsai[mn] - mysl);
-  if (need_last) sa_put(a, o_last, a.bwsai[mx] - mysl);
+  // ---- round trip 4 (3 was sfirst / slast / ssl): the two values, stored through the map word and prefix of round trip 2
+  uint64_t v_first = 0, v_last = 0;
+  if (need_first) v_first = a.bwsai[mn];
+  if (need_last) v_last = a.bwsai[mx];
+  if (need_first) sa_put_at(a, o_first, w_first, p_first, v_first - mysl);
+  if (need_last) sa_put_at(a, o_last, w_last, p_last, v_last - mysl);
 }
 
 // Boundaries of the runs of the BWT slice [out_lo, out_hi): bit r of the map = position out_lo + r starts a run
@@ -889,6 +913,34 @@ __global__ void hard_minor_sa_kernel(MergeArgsT<I> a, const MinorRec *__restrict
 // each other member's segment.  Groups that do not fit the LDS tables are queued for
 // hard_big_kernel.  (One group at a time per wave took 7.7 us per group, 22 ms at 8.8 M groups.)
 struct BigGroup { uint64_t g; uint64_t E; uint32_t k; uint32_t pad; };
+// What phase A of hard_groups_kernel wants of a fallback group - head slot, first output position, occurrences, members -
+// as hard_classify_kernel found it (one 32-byte record next to fb_heads[], same order).  The classifier counts the members
+// by grp alone (gallop and bisection over grp[g + x] == g), phase A's own walk by grp and pc != 0; for the head of a hard group
+// the two agree: pc[t] == 0 says that slot t's suffix is no longer than w (or lies past the last word) and emits nothing
+// (pprec16_kernel, posrec_at), the members of a group are equal strings up to and including the terminator, hence equally
+// long, and a head is flagged only by a member with pc != 0 (slot_records_kernel, group_flags_kernel) - so every member of a
+// flagged group has pc != 0 and the walk ends where grp changes, or at slot N, as the classifier does.  Neither E nor base
+// depends on anything but k and the offsets.  PFP_DEBUG=1 checks it on every record (fb_records_check_kernel).
+struct alignas(16) FallbackRec { uint64_t g, base, E; uint32_t k, pad; };
+template <class I>
+__global__ void fb_records_kernel(MergeArgsT<I> a, uint64_t n, const I *__restrict__ fidx, const HardGroupInfo *__restrict__ info,
+                                  I *__restrict__ fb_heads, FallbackRec *__restrict__ recs) {
+  const uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const HardGroupInfo gi = info[fidx[i]];
+  fb_heads[i] = (I)gi.g;
+  recs[i] = FallbackRec{gi.g, slot_off(a, gi.g), gi.E, gi.k, 0u};
+}
+template <class I>
+__global__ void fb_records_check_kernel(MergeArgsT<I> a, uint64_t n, const FallbackRec *__restrict__ recs,
+                                        unsigned long long *__restrict__ bad) {
+  const uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const FallbackRec r = recs[i];
+  uint64_t kk = 0;
+  while (r.g + kk < a.N && a.grp[r.g + kk] == (I)r.g && a.pc[r.g + kk] != 0) kk++;
+  if (kk != r.k || slot_off(a, r.g) != r.base || slot_off(a, r.g + kk) - r.base != r.E) atomicAdd(bad, 1ull);
+}
 struct HardLds {
   uint32_t lpos[kHardRank];
   uint8_t lq[kHardRank];
@@ -908,6 +960,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 }
 template <class I>
 __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const I *__restrict__ heads,
+                                                          const FallbackRec *__restrict__ recs /* null: phase A walks */,
                                                           const uint64_t *__restrict__ nheads_p,
                                                           unsigned long long *__restrict__ stats,
                                                           BigGroup *__restrict__ big, uint32_t big_cap,
@@ -927,11 +980,17 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
     uint32_t k = 0, E = 0;
     bool live = false;
     if (lane < gpb && hidx < nH) {
-      g = heads[hidx];
       uint32_t kk = 0;
-      while (g + kk < a.N && a.grp[g + kk] == (I)g && a.pc[g + kk] != 0) kk++;
-      base = slot_off(a, g);
-      const uint64_t Eg = slot_off(a, g + kk) - base;
+      uint64_t Eg;
+      if (recs) {      // the classifier's record: one load (FallbackRec has the proof that it is what the walk finds)
+        const FallbackRec r = recs[hidx];
+        g = r.g; kk = r.k; base = r.base; Eg = r.E;
+      } else {         // dense SA, every head unclassified: walk the members
+        g = heads[hidx];
+        while (g + kk < a.N && a.grp[g + kk] == (I)g && a.pc[g + kk] != 0) kk++;
+        base = slot_off(a, g);
+        Eg = slot_off(a, g + kk) - base;
+      }
       if (kk && !(base + Eg <= a.out_lo || base >= a.out_hi)) {      // inside this rank's slice
         my_chars += Eg; my_groups += 1;
         const bool sorted_path = Eg > (uint64_t)kHardSortMin;
@@ -1226,6 +1285,7 @@ static RecordSource choose_record_source(pfp_ctx *c, uint64_t N, uint64_t NP, in
 template <class I>
 struct HeadList {
   const I *heads;
+  const FallbackRec *recs;      // the classifier's record of every head of the list, or null (dense SA: nothing was classified)
   const uint64_t *n_dev;
   uint64_t n;
 };
@@ -1292,6 +1352,7 @@ struct Merge {
     DBuf<MinorMember> mm_list;
     uint64_t n_mm = 0, sum_k = 0, n_minor = 0;
     DBuf<I> fb_heads;
+    DBuf<FallbackRec> fb_recs;    // ... and what the classifier knows of each (phase A of hard_groups_kernel)
     DBuf<MinorRec> recs;          // sparse SA: what a minority occurrence found, for the second round
     int gpb = 64;                 // groups per wave batch of hard_groups_kernel
     uint32_t nmid = 0, nbig = 0;
@@ -1433,16 +1494,23 @@ struct Merge {
     }
     const uint64_t n_fallback = count_flags(c, hg.fallback.p, n_heads);
     hg.n_minor = read_scalar(c, hg.minor_off.p + n_heads);
-    hg.fb_heads.alloc(c, n_fallback + 1);
-    {  // heads of the fallback groups = heads[] where fallback[] is set
+    hg.fb_heads.alloc(c, n_fallback + 1); hg.fb_recs.alloc(c, n_fallback + 1);
+    {  // heads of the fallback groups = heads[] where fallback[] is set, and their records in the same gather
       DBuf<I> fidx(c, n_fallback + 1);
       select_index<I>(c, hg.fallback.p, fidx.p, hg.list_len.p + kFallbackHeads, n_heads);
-      if (n_fallback) hipLaunchKernelGGL(gather_idx_kernel<I>, gdim(cdiv(n_fallback, 256)), gdim(256), 0, c->stream, n_fallback, fidx.p,
-                                         hg.heads.p, hg.fb_heads.p);
+      if (n_fallback) hipLaunchKernelGGL(fb_records_kernel<I>, gdim(cdiv(n_fallback, 256)), gdim(256), 0, c->stream, a, n_fallback, fidx.p,
+                                         hg.ginfo.p, hg.fb_heads.p, hg.fb_recs.p);
       PFP_HIP(hipGetLastError());
       sync(c);
     }
-    return HeadList<I>{hg.fb_heads.p, hg.list_len.p + kFallbackHeads, n_fallback};
+    if (c->debug && n_fallback) {      // the records are what phase A's walk would find (FallbackRec)
+      DBuf<unsigned long long> bad(c, 1);
+      bad.zero();
+      hipLaunchKernelGGL(fb_records_check_kernel<I>, gdim(cdiv(n_fallback, 256)), gdim(256), 0, c->stream, a, n_fallback, hg.fb_recs.p, bad.p);
+      const uint64_t nb = read_scalar(c, (const uint64_t *)bad.p);
+      PFP_REQUIRE(nb == 0, PFP_EHIP, "merge: " + std::to_string(nb) + " fallback records differ from the walk over their group's members");
+    }
+    return HeadList<I>{hg.fb_heads.p, hg.fb_recs.p, hg.list_len.p + kFallbackHeads, n_fallback};
   }
 
   // ---- 7. expand: fill entries and the majority chars of the hard groups, then the whole words' chars occurrence by occurrence
@@ -1492,7 +1560,7 @@ struct Merge {
     for (;;) {
       if (!lds.n) { PFP_HIP(hipMemsetAsync(hg.hstats.p, 0, 40, c->stream)); }
       else { KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-        hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.n_dev, hg.hstats.p, hg.big.p,
+        hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev, hg.hstats.p, hg.big.p,
                            hg.big_cap, hg.mid.p, hg.mid_cap, hg.gpb); }
       PFP_HIP(hipGetLastError());
       PFP_HIP(hipMemcpyAsync(c->h_scalars, hg.hstats.p, 40, hipMemcpyDeviceToHost, c->stream));
@@ -1612,7 +1680,7 @@ struct Merge {
       DBuf<unsigned long long> scratch(c, 5);
       scratch.zero();
       KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-      hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.n_dev, scratch.p, hg.big.p,
+      hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev, scratch.p, hg.big.p,
                          0u, hg.mid.p, 0u, hg.gpb);
       PFP_HIP(hipGetLastError());
       queued_groups(PASS_SA);
@@ -1655,7 +1723,7 @@ struct Merge {
     }
     fill_args();
     find_hard_groups();
-    const HeadList<I> lds = sa_mode != SA_DENSE && hg.n_heads ? classify() : HeadList<I>{hg.heads.p, hg.list_len.p + kAllHeads, hg.n_heads};
+    const HeadList<I> lds = sa_mode != SA_DENSE && hg.n_heads ? classify() : HeadList<I>{hg.heads.p, nullptr, hg.list_len.p + kAllHeads, hg.n_heads};
     expand();
     place_minority(lds);
     rank_in_lds(lds);
