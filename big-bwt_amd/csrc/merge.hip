@@ -254,6 +254,11 @@ __global__ void wistart_kernel(uint32_t d, const uint32_t *__restrict__ lexrank,
   if (wrec) { const uint32_t oc = wocc[j]; wrec[j] = WordRec{st, oc, ilist[st], ilist[st + oc - 1], wend[j], 0}; }
 }
 
+// sparse SA: what the BWT round leaves of a ranked occurrence of a fallback group for the SA round - its BWT(P) position
+// and suffix length; the entry's index says where it landed (staging offset of the group + rank inside the group)
+struct alignas(8) RankedOcc { uint32_t pos, sl; };
+constexpr uint32_t kUnwritten = 0xFFFFFFFFu;      // both fields of an entry nobody wrote (PFP_DEBUG fills the staging with 0xFF)
+
 template <class I>
 struct MergeArgsT {
   uint64_t N, n_out; uint32_t d; int w; int want_sa;
@@ -282,6 +287,9 @@ struct MergeArgsT {
   // (the caller keeps no SA array), or to out_sa[x] - only where the bit is set.
   const uint64_t *bmap, *bpre;
   uint64_t *sa_c;
+  // sparse SA with replay: where the kernels that rank a fallback group's occurrences leave them (null: the SA round
+  // ranks them again) - entry soff[h] + r is the occurrence of rank r of the group whose head is the h-th of the fallback list
+  RankedOcc *ranked; const uint64_t *soff;
 };
 enum : int { PASS_BWT = 1, PASS_SA = 2 };
 template <class I>
@@ -306,6 +314,19 @@ __device__ __forceinline__ bool sa_wanted(const MergeArgsT<I> &a, uint64_t x) { 
   if (!a.bmap) return true;
   const uint64_t r = x - a.out_lo;
   return (a.bmap[r >> 6] >> (r & 63)) & 1ull;
+}
+// SA round of the replay: the occurrence that the BWT round ranked to output position o and staged at ranked[idx].  The
+// boundary bit of o is looked at first; the entry and bwsai[] are read only where a value is stored.  `unwritten`
+// (PFP_DEBUG, else null): every entry of the slice is read and one that nobody wrote is counted
+template <class I>
+__device__ __forceinline__ void sa_replay(const MergeArgsT<I> &a, uint64_t idx, uint64_t o, unsigned long long *unwritten) {
+  if (o < a.out_lo || o >= a.out_hi) return;
+  const uint64_t r = o - a.out_lo, word = a.bmap[r >> 6];
+  const bool at = (word >> (r & 63)) & 1ull;
+  if (!at && !unwritten) return;
+  const RankedOcc e = a.ranked[idx];
+  if (unwritten && e.pos == kUnwritten && e.sl == kUnwritten) { atomicAdd(unwritten, 1ull); return; }
+  if (at) sa_put_at(a, o, word, a.bpre[r >> 6], a.bwsai[e.pos] - (uint64_t)e.sl);
 }
 // Exclusive prefix of the per-slot counts, kept as a 64-bit base per 2048 slots (= one expand workgroup) and a
 // 32-bit offset inside the tile: 4 bytes per slot to write and read instead of 8, and the N-long scan
@@ -912,7 +933,10 @@ __global__ void hard_minor_sa_kernel(MergeArgsT<I> a, const MinorRec *__restrict
 // group's LDS segment, or, when the group is a few long sorted lists, own index + lower_bound in
 // each other member's segment.  Groups that do not fit the LDS tables are queued for
 // hard_big_kernel.  (One group at a time per wave took 7.7 us per group, 22 ms at 8.8 M groups.)
-struct BigGroup { uint64_t g; uint64_t E; uint32_t k; uint32_t pad; };
+// (head: the index of the group's head in the list - soff[head] is where its ranked occurrences are staged for the SA round's
+//  replay: an exclusive sum of E over the list, which does not depend on the order in which the waves' atomics fill the queues.
+//  32 bits: a list of 2^32 heads or more is not replayed)
+struct BigGroup { uint64_t g; uint64_t E; uint32_t k; uint32_t head; };
 // What phase A of hard_groups_kernel wants of a fallback group - head slot, first output position, occurrences, members -
 // as hard_classify_kernel found it (one 32-byte record next to fb_heads[], same order).  The classifier counts the members
 // by grp alone (gallop and bisection over grp[g + x] == g), phase A's own walk by grp and pc != 0; for the head of a hard group
@@ -924,12 +948,13 @@ struct BigGroup { uint64_t g; uint64_t E; uint32_t k; uint32_t pad; };
 struct alignas(16) FallbackRec { uint64_t g, base, E; uint32_t k, pad; };
 template <class I>
 __global__ void fb_records_kernel(MergeArgsT<I> a, uint64_t n, const I *__restrict__ fidx, const HardGroupInfo *__restrict__ info,
-                                  I *__restrict__ fb_heads, FallbackRec *__restrict__ recs) {
+                                  I *__restrict__ fb_heads, FallbackRec *__restrict__ recs, uint64_t *__restrict__ fb_E /* sparse SA, else null */) {
   const uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const HardGroupInfo gi = info[fidx[i]];
   fb_heads[i] = (I)gi.g;
   recs[i] = FallbackRec{gi.g, slot_off(a, gi.g), gi.E, gi.k, 0u};
+  if (fb_E) fb_E[i] = gi.E;      // summed to the groups' staging offsets (MergeArgsT::soff)
 }
 template <class I>
 __global__ void fb_records_check_kernel(MergeArgsT<I> a, uint64_t n, const FallbackRec *__restrict__ recs,
@@ -946,8 +971,8 @@ struct HardLds {
   uint8_t lq[kHardRank];
   uint32_t lmoff[kHardMem + 1], lmist[kHardMem], lmsl[kHardMem];
   uint8_t lmch[kHardMem], lmg[kHardMem];
-  uint64_t gbase[64], ghead[64];
-  uint32_t geoff[65], gk0[65];
+  uint64_t gbase[64], ghead[64], gsoff[64];      // gsoff: the group's staging offset (sparse SA with replay)
+  uint16_t geoff[65], gk0[65];                   // (<= kHardRank, <= kHardMem: 16 bits, so that gsoff[] leaves five workgroups on a CU)
 };
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
@@ -958,13 +983,16 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   for (int o = 32; o > 0; o >>= 1) { const uint32_t x = __shfl_xor(v, o, 64); v = x > v ? x : v; }
   return v;
 }
-template <class I>
+// kReplay (sparse SA, second round): phase A as ever, then no tables and no ranking - entry soff + r of a group that the
+// BWT round ranked here is the occurrence at output position base + r (sa_replay); S[] is not touched
+template <class I, bool kReplay>
 __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const I *__restrict__ heads,
                                                           const FallbackRec *__restrict__ recs /* null: phase A walks */,
                                                           const uint64_t *__restrict__ nheads_p,
-                                                          unsigned long long *__restrict__ stats,
+                                                          unsigned long long *__restrict__ stats /* null: SA round, the queues stand */,
                                                           BigGroup *__restrict__ big, uint32_t big_cap,
-                                                          BigGroup *__restrict__ mid, uint32_t mid_cap, int gpb) {
+                                                          BigGroup *__restrict__ mid, uint32_t mid_cap, int gpb,
+                                                          unsigned long long *__restrict__ unwritten /* replay with PFP_DEBUG, else null */) {
   __shared__ HardLds S[4];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   HardLds &L = S[wv];
@@ -976,12 +1004,13 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
   for (uint64_t b = BID * 4 + wv; b < nbatch; b += GDIM * 4) {
     // ---- A: one group per lane
     const uint64_t hidx = b * gpb + lane;
-    uint64_t g = 0, base = 0;
+    uint64_t g = 0, base = 0, so = 0;
     uint32_t k = 0, E = 0;
     bool live = false;
     if (lane < gpb && hidx < nH) {
       uint32_t kk = 0;
       uint64_t Eg;
+      if (a.ranked) so = a.soff[hidx];
       if (recs) {      // the classifier's record: one load (FallbackRec has the proof that it is what the walk finds)
         const FallbackRec r = recs[hidx];
         g = r.g; kk = r.k; base = r.base; Eg = r.E;
@@ -995,14 +1024,36 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
         my_chars += Eg; my_groups += 1;
         const bool sorted_path = Eg > (uint64_t)kHardSortMin;
         if (Eg <= (uint64_t)kHardRank && kk <= (uint32_t)kHardMem && !sorted_path) { live = true; k = kk; E = (uint32_t)Eg; }
-        else if (Eg <= (uint64_t)kHardLds && sorted_path) {      // one wave sorts it in LDS: hard_sort_kernel
+        else if (stats && Eg <= (uint64_t)kHardLds && sorted_path) {      // one wave sorts it in LDS: hard_sort_kernel
           const unsigned long long idx = atomicAdd(&stats[3], 1ull);
-          if (idx < mid_cap) mid[idx] = BigGroup{g, Eg, kk, 0};
-        } else {     // too large for the LDS tables: hard_big_kernel (whole grid, one thread per occurrence)
+          if (idx < mid_cap) mid[idx] = BigGroup{g, Eg, kk, (uint32_t)hidx};
+        } else if (stats) {     // too large for the LDS tables: hard_big_kernel (whole grid, one thread per occurrence)
           const unsigned long long idx = atomicAdd(&stats[2], 1ull);
-          if (idx < big_cap) big[idx] = BigGroup{g, Eg, kk, 0};
+          if (idx < big_cap) big[idx] = BigGroup{g, Eg, kk, (uint32_t)hidx};
         }
       }
+    }
+    if constexpr (kReplay) {
+      // the batch's ranked occurrences flat over the lanes: which group holds occurrence e, by bisection over the lanes'
+      // running sums of E (six shuffles; every lane takes part in each)
+      uint32_t pE = live ? E : 0u;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const uint32_t vE = __shfl_up(pE, o, 64); if (lane >= o) pE += vE; }
+      const uint32_t Eb = __shfl(pE, 63, 64);
+      for (uint32_t e0 = 0; e0 < Eb; e0 += 64) {
+        const uint32_t e = e0 + lane;
+        int lo = 0, hi = 63;                         // the first lane whose sum exceeds e lies in [lo, hi] (e < Eb)
+#pragma unroll
+        for (int s = 0; s < 6; s++) {
+          const int mdl = (lo + hi) >> 1;
+          if (__shfl(pE, mdl, 64) > e) hi = mdl; else lo = mdl + 1;
+        }
+        lo &= 63;                                    // (e >= Eb: any lane, nothing is done)
+        const uint32_t r = e - (__shfl(pE, lo, 64) - __shfl(E, lo, 64));
+        const uint64_t gb = __shfl(base, lo, 64), gs = __shfl(so, lo, 64);
+        if (e < Eb) sa_replay(a, gs + r, gb + r, unwritten);
+      }
+      continue;
     }
     unsigned long long todo = __ballot(live);
     while (todo) {
@@ -1022,9 +1073,9 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
       const uint32_t M = __shfl(pk, lastl, 64), Eb = __shfl(pE, lastl, 64);
       if (fit) {
         const int gi = __popcll(take & ((1ull << lane) - 1ull));
-        L.ghead[gi] = g; L.gbase[gi] = base; L.geoff[gi] = pE - E; L.gk0[gi] = pk - k;
+        L.ghead[gi] = g; L.gbase[gi] = base; L.gsoff[gi] = so; L.geoff[gi] = (uint16_t)(pE - E); L.gk0[gi] = (uint16_t)(pk - k);
       }
-      if (lane == 0) { L.geoff[nG] = Eb; L.gk0[nG] = M; }
+      if (lane == 0) { L.geoff[nG] = (uint16_t)Eb; L.gk0[nG] = (uint16_t)M; }
       wave_lds_sync();
       // ---- B: one member per lane
       for (uint32_t q = lane; q < M; q += 64) {
@@ -1072,7 +1123,8 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
         const uint64_t o = L.gbase[gi] + r;
         if (o >= a.out_lo && o < a.out_hi) {
           if (a.pass & PASS_BWT) a.bwt[o] = L.lmch[q];
-          if (a.want_sa && (a.pass & PASS_SA)) sa_put(a, o, a.bwsai[pos] - (uint64_t)L.lmsl[q]);
+          if (a.ranked) a.ranked[L.gsoff[gi] + r] = RankedOcc{pos, L.lmsl[q]};
+          if (a.want_sa && (a.pass & PASS_SA) && sa_wanted(a, o)) sa_put(a, o, a.bwsai[pos] - (uint64_t)L.lmsl[q]);
         }
       }
       wave_lds_sync();
@@ -1081,7 +1133,7 @@ __global__ __launch_bounds__(256) void hard_groups_kernel(MergeArgsT<I> a, const
   // statistics (pfbwt.cpp:231-233 "Hard bwt chars")
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { my_chars += __shfl_down(my_chars, o, 64); my_groups += __shfl_down(my_groups, o, 64); }
-  if (lane == 0 && (my_chars | my_groups)) { atomicAdd(&stats[0], my_chars); atomicAdd(&stats[1], my_groups); }
+  if (stats && lane == 0 && (my_chars | my_groups)) { atomicAdd(&stats[0], my_chars); atomicAdd(&stats[1], my_groups); }
 }
 
 // Groups of 513..1024 occurrences (a word family of a collection of hundreds of copies): ranking every
@@ -1130,7 +1182,8 @@ __global__ __launch_bounds__(256) void hard_sort_kernel(MergeArgsT<I> a, const B
       while (hi - lo > 1) { const uint32_t mdl = (lo + hi) >> 1; if (slot_off(a, g + mdl) - base <= e) lo = mdl; else hi = mdl; }
       const uint64_t t = g + lo;
       if (a.pass & PASS_BWT) a.bwt[o] = fix_char(a.pc[t]);
-      if (a.want_sa && (a.pass & PASS_SA)) sa_put(a, o, a.bwsai[pos] - slot_slen(a, t));
+      if (a.ranked) a.ranked[a.soff[mid[qi].head] + r] = RankedOcc{pos, (uint32_t)slot_slen(a, t)};
+      if (a.want_sa && (a.pass & PASS_SA) && sa_wanted(a, o)) sa_put(a, o, a.bwsai[pos] - slot_slen(a, t));
     }
     wave_lds_sync();
   }
@@ -1164,7 +1217,8 @@ __global__ __launch_bounds__(256) void hard_big_kernel(MergeArgsT<I> a, const Bi
     }
     if (base + r >= a.out_lo && base + r < a.out_hi) {
       if (a.pass & PASS_BWT) a.bwt[base + r] = fix_char(a.pc[t]);
-      if (a.want_sa && (a.pass & PASS_SA)) sa_put(a, base + r, a.bwsai[pos] - slot_slen(a, t));
+      if (a.ranked) a.ranked[a.soff[big[lo].head] + r] = RankedOcc{pos, (uint32_t)slot_slen(a, t)};
+      if (a.want_sa && (a.pass & PASS_SA) && sa_wanted(a, base + r)) sa_put(a, base + r, a.bwsai[pos] - slot_slen(a, t));
     }
   }
 }
@@ -1201,10 +1255,34 @@ __global__ __launch_bounds__(256) void big_place_kernel(MergeArgsT<I> a, const B
   if (i >= cnt) return;
   const uint64_t key = keys[i], t = vals[i];
   const uint32_t lo = q0 + (uint32_t)(key >> 32), pos = (uint32_t)key;
-  const uint64_t o = slot_off(a, big[lo].g) + (estart[q0] + i - estart[lo]);
+  const uint64_t r = estart[q0] + i - estart[lo], o = slot_off(a, big[lo].g) + r;
   if (o < a.out_lo || o >= a.out_hi) return;
   if (a.pass & PASS_BWT) a.bwt[o] = fix_char(a.pc[t]);
+  if (a.ranked) a.ranked[a.soff[big[lo].head] + r] = RankedOcc{pos, (uint32_t)slot_slen(a, t)};
   if (a.want_sa && (a.pass & PASS_SA) && sa_wanted(a, o)) sa_put(a, o, a.bwsai[pos] - slot_slen(a, t));
+}
+
+// Sparse SA, second round, the queued groups: nothing is ranked or sorted again - hard_sort_kernel, big_place_kernel and
+// hard_big_kernel staged every occurrence at its rank.  The mid queue has no estart[] and groups of 513 .. 1024 occurrences:
+// one wave per group; the big queue one lane per occurrence over estart[] (absolute from the queue's start), as
+// big_keys_kernel walks it.
+template <class I>
+__global__ __launch_bounds__(256) void hard_replay_kernel(MergeArgsT<I> a, const BigGroup *__restrict__ mid, uint32_t nmid,
+                                                          const BigGroup *__restrict__ big, uint32_t nbig,
+                                                          const uint64_t *__restrict__ estart, uint64_t total,
+                                                          unsigned long long *__restrict__ unwritten /* PFP_DEBUG, else null */) {
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (uint64_t qi = BID * 4 + wv; qi < nmid; qi += GDIM * 4) {
+    const BigGroup q = mid[qi];
+    const uint64_t base = slot_off(a, q.g), so = a.soff[q.head];
+    for (uint32_t r = lane; r < (uint32_t)q.E; r += 64) sa_replay(a, so + r, base + r, unwritten);
+  }
+  for (uint64_t ge = BID * 256 + threadIdx.x; ge < total; ge += GDIM * 256) {
+    uint32_t lo = 0, hi = nbig;               // estart[lo] <= ge < estart[hi]
+    while (hi - lo > 1) { const uint32_t mdl = (lo + hi) >> 1; if (estart[mdl] <= ge) lo = mdl; else hi = mdl; }
+    const uint64_t r = ge - estart[lo];
+    sa_replay(a, a.soff[big[lo].head] + r, slot_off(a, big[lo].g) + r, unwritten);
+  }
 }
 
 // loc[t] = sum of cnt over the slots of t's tile before t; tsum[tile] = the tile's total.  256 threads x 8 slots.
@@ -1253,14 +1331,21 @@ struct MergeSwitches {
   int prec_direct = -1;                  // PFP_PREC_DIRECT: 1 / 0 forces RecordSource::PerSlot / Gathered where the sort keys carry no record
   uint32_t big_cap = 0;                  // PFP_BIG_CAP: capacity of the queue of large hard groups (0: by size)
   uint64_t big_budget = 1ull << 27;      // PFP_BIG_BUDGET: occurrences of queued groups sorted at once
+  int sa_replay = -1;                    // PFP_SA_REPLAY: 1 / 0 forces the SA round of the fallback groups to replay the staged ranks / to rank again
+  uint64_t replay_budget = ~0ull;        // PFP_SA_REPLAY_BUDGET: bytes the staging may take where nothing is forced (unset: an eighth of the device)
   static MergeSwitches read() {
     MergeSwitches s;
+    if (const char *e = getenv("PFP_SA_REPLAY")) s.sa_replay = atoi(e) != 0;
+    if (const char *e = getenv("PFP_SA_REPLAY_BUDGET")) s.replay_budget = strtoull(e, nullptr, 10);
     if (const char *e = getenv("PFP_PREC_DIRECT")) s.prec_direct = atoi(e) != 0;
     if (const char *e = getenv("PFP_BIG_CAP")) { if (atoll(e) > 0) s.big_cap = (uint32_t)atoll(e); }
     if (const char *e = getenv("PFP_BIG_BUDGET")) s.big_budget = strtoull(e, nullptr, 10);
     return s;
   }
 };
+
+// the device's memory, from the pool's soft limit (seven tenths of it)
+static uint64_t device_bytes(const pfp_ctx *c) { return c->pool.soft_limit ? c->pool.soft_limit / 7 * 10 : (64ull << 30); }
 
 template <class I>
 static RecordSource choose_record_source(pfp_ctx *c, uint64_t N, uint64_t NP, int sa_mode, const SuffixOrderT<I> &so, const MergeSwitches &sw) {
@@ -1275,8 +1360,7 @@ static RecordSource choose_record_source(pfp_ctx *c, uint64_t N, uint64_t NP, in
   // (a 30 GB dictionary: 480 GB): then every slot computes its record itself from the dictionary line and its word's
   // entry (posrec_at: two random sectors per slot instead of one).  PFP_PREC_DIRECT=1/0 forces the choice (tests).
   bool direct = N * 4 <= NP;
-  const uint64_t dev_bytes = c->pool.soft_limit ? c->pool.soft_limit / 7 * 10 : (64ull << 30);
-  if (NP * sizeof(PosRec) > dev_bytes / 8) direct = true;
+  if (NP * sizeof(PosRec) > device_bytes(c) / 8) direct = true;
   if (sw.prec_direct >= 0) direct = sw.prec_direct != 0;
   return direct ? RecordSource::PerSlot : RecordSource::Gathered;
 }
@@ -1350,10 +1434,12 @@ struct Merge {
     DBuf<uint32_t> minor_cnt, mm_cnt;
     DBuf<uint64_t> minor_off, mm_off;
     DBuf<MinorMember> mm_list;
-    uint64_t n_mm = 0, sum_k = 0, n_minor = 0;
+    uint64_t n_mm = 0, sum_k = 0, n_minor = 0, n_staged = 0;
     DBuf<I> fb_heads;
     DBuf<FallbackRec> fb_recs;    // ... and what the classifier knows of each (phase A of hard_groups_kernel)
     DBuf<MinorRec> recs;          // sparse SA: what a minority occurrence found, for the second round
+    DBuf<uint64_t> soff;          // sparse SA: occurrences of the fallback groups before each (and, last, of all): staging offsets
+    DBuf<RankedOcc> ranked;       // ... and the staging itself, from the BWT round to the end of the SA round (empty: the SA round ranks again)
     int gpb = 64;                 // groups per wave batch of hard_groups_kernel
     uint32_t nmid = 0, nbig = 0;
     DBuf<uint64_t> estart;        // occurrences of the queued groups, laid end to end
@@ -1497,11 +1583,15 @@ struct Merge {
     hg.fb_heads.alloc(c, n_fallback + 1); hg.fb_recs.alloc(c, n_fallback + 1);
     {  // heads of the fallback groups = heads[] where fallback[] is set, and their records in the same gather
       DBuf<I> fidx(c, n_fallback + 1);
+      DBuf<uint64_t> fb_E;      // sparse SA: occurrences of every fallback group, summed to its staging offset
+      if (sa_mode == SA_SPARSE && n_fallback && sw.sa_replay != 0) { alloc_counts(c, fb_E, n_fallback); hg.soff.alloc(c, n_fallback + 1); }
       select_index<I>(c, hg.fallback.p, fidx.p, hg.list_len.p + kFallbackHeads, n_heads);
       if (n_fallback) hipLaunchKernelGGL(fb_records_kernel<I>, gdim(cdiv(n_fallback, 256)), gdim(256), 0, c->stream, a, n_fallback, fidx.p,
-                                         hg.ginfo.p, hg.fb_heads.p, hg.fb_recs.p);
+                                         hg.ginfo.p, hg.fb_heads.p, hg.fb_recs.p, fb_E.p);
+      if (fb_E.p) exclusive_sum_u64(c, fb_E.p, hg.soff.p, n_fallback + 1);
       PFP_HIP(hipGetLastError());
-      sync(c);
+      if (fb_E.p) hg.n_staged = read_scalar(c, hg.soff.p + n_fallback);      // (syncs, as the other branch)
+      else sync(c);
     }
     if (c->debug && n_fallback) {      // the records are what phase A's walk would find (FallbackRec)
       DBuf<unsigned long long> bad(c, 1);
@@ -1552,7 +1642,21 @@ struct Merge {
     PFP_HIP(hipGetLastError());
   }
 
-  // ---- 9. the groups of the list ranked in LDS; larger ones are queued (hg.mid, hg.big) - redone when the big queue overflows
+  // ---- 9. sparse SA: shall the kernels that rank the fallback groups' occurrences stage them (8 bytes each, hg.soff says
+  //         where), so that the SA round replays the ranks instead of computing them again?  Yes, unless the staging would
+  //         take more than the share of the device that choose_record_source allows the position records
+  //         (PFP_SA_REPLAY_BUDGET: another share, tests); PFP_SA_REPLAY=1/0 forces the choice
+  void stage_ranks() {
+    if (!hg.n_staged) return;
+    const uint64_t budget = sw.replay_budget != ~0ull ? sw.replay_budget : device_bytes(c) / 8;
+    const bool replay = (sw.sa_replay >= 0 ? sw.sa_replay != 0 : hg.n_staged * sizeof(RankedOcc) <= budget) && hg.soff.n <= (1ull << 32);      // (BigGroup::head)
+    if (!replay) { hg.soff.release(); return; }
+    hg.ranked.alloc(c, hg.n_staged);
+    if (c->debug) PFP_HIP(hipMemsetAsync(hg.ranked.p, 0xFF, hg.n_staged * sizeof(RankedOcc), c->stream));      // kUnwritten
+    a.ranked = hg.ranked.p; a.soff = hg.soff.p;
+  }
+
+  // ---- 10. the groups of the list ranked in LDS; larger ones are queued (hg.mid, hg.big) - redone when the big queue overflows
   void rank_in_lds(const HeadList<I> &lds) {
     const MergeArgsT<I> ap = with_pass(first_pass);
     // groups per wave batch: down to 8 while that still leaves every wave of the launch a batch
@@ -1560,8 +1664,8 @@ struct Merge {
     for (;;) {
       if (!lds.n) { PFP_HIP(hipMemsetAsync(hg.hstats.p, 0, 40, c->stream)); }
       else { KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-        hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev, hg.hstats.p, hg.big.p,
-                           hg.big_cap, hg.mid.p, hg.mid_cap, hg.gpb); }
+        hipLaunchKernelGGL((hard_groups_kernel<I, false>), gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev,
+                           hg.hstats.p, hg.big.p, hg.big_cap, hg.mid.p, hg.mid_cap, hg.gpb, (unsigned long long *)nullptr); }
       PFP_HIP(hipGetLastError());
       PFP_HIP(hipMemcpyAsync(c->h_scalars, hg.hstats.p, 40, hipMemcpyDeviceToHost, c->stream));
       sync(c);
@@ -1581,7 +1685,7 @@ struct Merge {
     out.hard_groups += hg.n_heads - lds.n;
   }
 
-  // ---- 10. occurrences of the queued groups, laid end to end
+  // ---- 11. occurrences of the queued groups, laid end to end
   void lay_out_queued() {
     const uint32_t nbig = hg.nbig;
     hg.es.assign(nbig + 1, 0);
@@ -1595,7 +1699,7 @@ struct Merge {
     sync(c);
   }
 
-  // ---- 11. the queued groups: sorted in LDS (mid), merged by device-wide sorts or ranked occurrence by occurrence (big)
+  // ---- 12. the queued groups: sorted in LDS (mid), merged by device-wide sorts or ranked occurrence by occurrence (big)
   void queued_groups(int pass) {
     const MergeArgsT<I> ap = with_pass(pass);
     const std::vector<uint64_t> &es = hg.es;
@@ -1627,7 +1731,7 @@ struct Merge {
     }
   }
 
-  // ---- 12. sparse SA, second round: where can the sampled files look?  The run boundaries of the finished BWT slice
+  // ---- 13. sparse SA, second round: where can the sampled files look?  The run boundaries of the finished BWT slice
   void mark_run_boundaries() {
     const uint64_t cnt_slice = a.out_hi > a.out_lo ? a.out_hi - a.out_lo : 0;
     const uint64_t nw = cdiv64(cnt_slice, 64);
@@ -1662,7 +1766,7 @@ struct Merge {
     }
   }
 
-  // ---- 13. sparse SA, second round: SA values at the boundaries, class by class
+  // ---- 14. sparse SA, second round: SA values at the boundaries, class by class
   void sa_round(const HeadList<I> &lds) {
     const MergeArgsT<I> ap = with_pass(PASS_SA);
     // whole words: one lane per occurrence of the inverted lists (a parse without phrases emits nothing)
@@ -1676,20 +1780,43 @@ struct Merge {
       const uint64_t nr = hg.n_minor;      // one record per minority occurrence, at its precomputed index (MinorMember::roff)
       if (nr) hipLaunchKernelGGL(hard_minor_sa_kernel<I>, gdim(cdiv(nr, 256)), gdim(256), 0, c->stream, ap, hg.recs.p, nr);
     }
-    if (lds.n) {      // the groups the LDS kernels ranked: the same ranks again, SA values this time (queues as they stand)
-      DBuf<unsigned long long> scratch(c, 5);
-      scratch.zero();
-      KScope ks(c, "pfp::hard_groups_kernel", N * 5);
-      hipLaunchKernelGGL(hard_groups_kernel<I>, gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev, scratch.p, hg.big.p,
-                         0u, hg.mid.p, 0u, hg.gpb);
+    if (lds.n && hg.ranked.p) replay_ranks(ap, lds);
+    else if (lds.n) {      // the groups the LDS kernels ranked: the same ranks again, SA values this time (queues as they stand)
+      { KScope ks(c, "pfp::hard_groups_kernel", N * 5);
+        hipLaunchKernelGGL((hard_groups_kernel<I, false>), gdim(c->n_cu * 8), gdim(256), 0, c->stream, ap, lds.heads, lds.recs,
+                           lds.n_dev, (unsigned long long *)nullptr, hg.big.p, 0u, hg.mid.p, 0u, hg.gpb, (unsigned long long *)nullptr); }
       PFP_HIP(hipGetLastError());
       queued_groups(PASS_SA);
       sync(c);
     }
     PFP_HIP(hipGetLastError());
   }
+  // the fallback groups' share of the SA round when the BWT round staged their ranks: the groups ranked in LDS through
+  // hard_groups_kernel's replay (a batch of gpb groups per wave, no LDS: four times the workgroups), the queued ones
+  // through hard_replay_kernel - no inverted-list gather, no ranking, no sort
+  void replay_ranks(const MergeArgsT<I> &ap, const HeadList<I> &lds) {
+    DBuf<unsigned long long> unwritten;      // PFP_DEBUG: staged entries of the slice that nobody wrote
+    if (c->debug) { unwritten.alloc(c, 1); unwritten.zero(); }
+    // (bytes, a lower bound: the groups' records and the map's bits; entries and values are read at boundaries only)
+    { KScope ks(c, "pfp::hard_groups_kernel", lds.n * 40 + hg.n_staged / 8);
+      const uint64_t nwg = std::min<uint64_t>(cdiv64(cdiv64(lds.n, hg.gpb), 4), (uint64_t)c->n_cu * 32);
+      hipLaunchKernelGGL((hard_groups_kernel<I, true>), gdim(nwg), gdim(256), 0, c->stream, ap, lds.heads, lds.recs, lds.n_dev,
+                         (unsigned long long *)nullptr, hg.big.p, 0u, hg.mid.p, 0u, hg.gpb, unwritten.p); }
+    const uint64_t nq = hg.es[hg.nbig];      // occurrences of the big queue
+    if (hg.nmid || nq) {
+      KScope ks(c, "pfp::hard_replay_kernel", ((uint64_t)hg.nmid + hg.nbig) * 32 + (nq + (uint64_t)hg.nmid * (kHardSortMin + 1)) / 8);
+      const uint64_t nwg = std::min<uint64_t>(std::max<uint64_t>(cdiv64(hg.nmid, 4), cdiv64(nq, 256)), (uint64_t)c->n_cu * 32);
+      hipLaunchKernelGGL(hard_replay_kernel<I>, gdim(nwg), gdim(256), 0, c->stream, ap, hg.mid.p, hg.nmid, hg.big.p, hg.nbig, hg.estart.p, nq,
+                         unwritten.p);
+    }
+    PFP_HIP(hipGetLastError());
+    if (c->debug) {
+      const uint64_t u = read_scalar(c, (const uint64_t *)unwritten.p);
+      PFP_REQUIRE(u == 0, PFP_EHIP, "sparse SA: the replay met " + std::to_string(u) + " staged occurrences that the BWT round did not write");
+    }
+  }
 
-  // ---- 14. PFP_DEBUG: every boundary of the BWT must have received its value
+  // ---- 15. PFP_DEBUG: every boundary of the BWT must have received its value
   void check_boundaries_set() {
     if (!c->debug || !a.sa_c) return;
     DBuf<unsigned long long> unset(c, 1);
@@ -1726,6 +1853,7 @@ struct Merge {
     const HeadList<I> lds = sa_mode != SA_DENSE && hg.n_heads ? classify() : HeadList<I>{hg.heads.p, nullptr, hg.list_len.p + kAllHeads, hg.n_heads};
     expand();
     place_minority(lds);
+    stage_ranks();
     rank_in_lds(lds);
     lay_out_queued();
     queued_groups(first_pass);
