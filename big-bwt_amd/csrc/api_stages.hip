@@ -370,13 +370,17 @@ int pfp_merge(pfp_ctx *c, const uint8_t *dict, uint64_t dict_size, const uint32_
   uint64_t expect = 0, tot_occ = 0;
   {
     uint64_t s = 0, j = 0;
-    for (uint64_t i = 0; i < dict_size; i++)
+    for (uint64_t i = 0; i < dict_size; i++) {
+      // (a word's bytes are all above the terminators: the word lookup and the sorter count words by the bytes below 2)
+      PFP_REQUIRE(dict[i] >= kDollar || dict[i] == kEndOfWord || i + 1 == dict_size, PFP_EFORMAT,
+                  "invalid dictionary file: byte 0x00 inside a word at offset " + std::to_string(i));
       if (dict[i] == kEndOfWord) {
         uint64_t len = i - s;
         if (len > (uint64_t)w) expect += (len - (uint64_t)w) * occ[j];
         tot_occ += occ[j];
         j++; s = i + 1;
       }
+    }
   }
   PFP_REQUIRE(tot_occ + 1 == n_plus_1, PFP_EFORMAT, "sum(occ)+1 != parse size (pfbwt.cpp:397)");
   D.wocc.alloc(c, D.d);
@@ -388,7 +392,7 @@ int pfp_merge(pfp_ctx *c, const uint8_t *dict, uint64_t dict_size, const uint32_
   with_width(ord.wide, [&](auto tag) {
     using I = decltype(tag);
     auto &so = ord.get<I>();
-    sort_dict_suffixes<I>(c, D.bytes.p, D.dsize, wv, so, (flags & PFP_FLAG_SA) ? nullptr : &pay);
+    sort_dict_suffixes<I>(c, D.bytes.p, D.dsize, wv, so, (flags & PFP_FLAG_SA) ? nullptr : &pay, w);      // (only the suffixes longer than w: chain.hip)
     if (c->debug) validate_suffix_order<I>(c, D.bytes.p, so, true, "dict SA");
     compute_lexrank<I>(c, D, so, ix);
   });

@@ -80,7 +80,9 @@ void run_parse(pfp_ctx *c, Chain &ch, uint64_t n, int w, uint64_t p, bool want_s
       using I = decltype(tag);
       auto &so = ch.ord.get<I>();
       so.rep_hint = (double)ch.n_used / (double)std::max<uint64_t>(ch.D.dsize, 1);
-      sort_dict_suffixes<I>(c, ch.D.bytes.p, ch.D.dsize, wv, so, dense_sa ? nullptr : &pay);
+      // (w: the suffixes of at most w bytes emit nothing - they are not sorted, so.N < dsize, and every slot number from
+      //  here on - lexrank's, ix.wslot_lex, the merge's - counts the sorted ones alone)
+      sort_dict_suffixes<I>(c, ch.D.bytes.p, ch.D.dsize, wv, so, dense_sa ? nullptr : &pay, w);
       if (c->debug) validate_suffix_order<I>(c, ch.D.bytes.p, so, true, "dict SA");
       compute_lexrank<I>(c, ch.D, so, ch.ix);
       if (!c->debug) { so.rank.release(); so.tab.release(); }      // the merge reads sa / grp / skeys only

@@ -83,7 +83,7 @@ struct pfp_pool {
   size_t soft_limit = 0;                           // bytes held from the driver beyond which any cached block that fits is reused
   size_t test_limit = 0;                           // PFP_TEST_POOL_LIMIT (read at pfp_ctx_create): requests beyond this many live bytes fail like a full device
   uint64_t driver_allocs = 0, trims = 0;           // hipMalloc calls; times a failed one made the pool give its cache back
-  bool trace = false;                              // PFP_TRACE_POOL=1: remember what was live at the peak (printed by pfp_ctx_destroy)
+  bool trace = false;                              // PFP_TRACE_POOL=1: one line per driver allocation; remember what was live at the peak (printed by pfp_ctx_destroy)
   std::vector<Block> peak_blocks;
   void note_peak() {
     if (live_bytes <= peak_bytes) return;
@@ -137,6 +137,7 @@ struct pfp_pool {
       e = hipMalloc(&p, bytes);
     }
     if (e != hipSuccess) { *err = e; (void)hipGetLastError(); return nullptr; }
+    if (trace) fprintf(stderr, "[pfp] pool: driver allocation %llu of %zu bytes for %s:%d\n", (unsigned long long)driver_allocs, bytes, file, line);
     all.push_back({p, bytes, p, file, line, bytes}); total_bytes += bytes;
     live_bytes += bytes; note_peak();
     return p;

@@ -117,7 +117,8 @@ inline bool prefer_wide_index(const pfp_ctx *c, uint64_t dsize) {
 template <class I>
 struct SuffixOrderT {
   double rep_hint = 0;   // set by the caller before sort_dict_suffixes: text bytes per dictionary byte (>= 2: a repetitive collection)
-  uint64_t N = 0;        // slots held here: all NP suffixes, or (key-range sharded sort) one contiguous range of SA(D)
+  uint64_t N = 0;        // slots held here: all NP suffixes, or (key-range sharded sort) one contiguous range of SA(D), or (sort_dict_suffixes
+                         // with a minimum length) the suffixes that emit something, numbered among themselves
   uint64_t NP = 0;       // positions of the sorted string
   uint64_t slot_base = 0;        // range mode: SA(D) slot of local slot 0
   uint64_t range_emits = 0;      // range mode: BWT positions the range emits (when a count source was given)
@@ -164,9 +165,13 @@ template <class I> RankViewT<I> rank_view(const SuffixOrderT<I> &so);
 template <class I> void gather_ranks(pfp_ctx *c, const SuffixOrderT<I> &so, const uint64_t *d_pos, uint64_t count, I *d_out);
 // Suffixes of the dictionary as 0x01-terminated strings (gsacak semantics); wv answers where the
 // word of a position ends (the final 0x00 is its own word).
+// min_len > 0 (and PFP_DROP_SHORT unset or != 0, read per call): only the suffixes LONGER than min_len bytes (terminator not
+// counted) are sorted - the merge's window w: a suffix of at most w bytes emits nothing (pfbwt.cpp:151), nor does the final
+// 0x00.  out.N < out.NP then, sa / grp / skeys and every rank number the kept suffixes alone.  A dictionary with a word of at
+// most min_len bytes, or one whose sort needs a doubling round (ranks of arbitrary positions), is sorted whole as with 0.
 template <class I>
 void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, SuffixOrderT<I> &out,
-                        const SlotPayloadSrc *pay = nullptr);
+                        const SlotPayloadSrc *pay = nullptr, int min_len = 0);
 // multi-GPU: rank `part` of `parts` sorts the suffixes whose first-round key lies in its share of the key
 // space (splitters from a deterministic key sample: every rank derives the same ones, no exchange);
 // groups never straddle shares, and pivot rounds compare strings, not ranks, so a share is finished

@@ -1710,6 +1710,14 @@ struct Merge {
     }
     // queued groups in chunks of at most big_budget occurrences: keys, one sort, placement (a single group beyond the
     // budget is ranked occurrence by occurrence - its sort scratch is not worth the memory)
+    // The sort's four buffers are drawn once, by the first chunk that is sorted (a call whose groups all exceed the budget draws
+    // none), and sized by the budget (or by all queued occurrences, if fewer), not by the chunk.
+    // The queue is filled with atomics, so its order - and with it where the chunks are cut, by a few thousand occurrences -
+    // differs from call to call: a request per chunk came out a few KB larger than the blocks the pool had cached from the
+    // call before every now and then, and the 12.6 GB workload went to the driver for a gigabyte in its steady state
+    // (PFP_TRACE_POOL shows the requests).  The sum of the queue is the same in every order.
+    const uint64_t max_cnt = std::min<uint64_t>(sw.big_budget, es[hg.nbig]);
+    DBuf<uint64_t> bk, bka, bv, bva;
     for (uint32_t q0 = 0; q0 < hg.nbig;) {
       uint32_t q1 = q0 + 1;
       while (q1 < hg.nbig && es[q1 + 1] - es[q0] <= sw.big_budget) q1++;
@@ -1719,7 +1727,7 @@ struct Merge {
         KScope ks(c, "pfp::hard_big_kernel", cnt * (sa_mode ? 21 : 5));
         hipLaunchKernelGGL(hard_big_kernel<I>, gdim(nb), gdim(256), 0, c->stream, ap, hg.big.p + q0, q1 - q0, hg.estart.p + q0, cnt);
       } else {
-        DBuf<uint64_t> bk(c, cnt), bka(c, cnt), bv(c, cnt), bva(c, cnt);
+        if (!bk.p) { bk.alloc(c, max_cnt); bka.alloc(c, max_cnt); bv.alloc(c, max_cnt); bva.alloc(c, max_cnt); }
         { KScope ks(c, "pfp::big_keys_kernel", cnt * 28);
           hipLaunchKernelGGL(big_keys_kernel<I>, gdim(cdiv(cnt, 256)), gdim(256), 0, c->stream, ap, hg.big.p, q0, q1, hg.estart.p, cnt, bk.p, bv.p); }
         { SortTag tag("large hard groups"); sort_pairs_db<uint64_t, uint64_t>(c, bk, bka, bv, bva, cnt, 0, 32 + bits_for(q1 - q0)); }

@@ -210,11 +210,12 @@ struct KeyStreamLds { uint32_t off[257]; uint32_t bs[200]; uint32_t wsum[4]; uns
 // for threadIdx.x < kKeyPos and position < N; every thread of the workgroup must call it
 // Where a position's word ends is read off the block's own characters (the first byte <= 1 at or after it, looked for
 // over the 32 characters a key can cover): no per-position length array is read.
-// word_out (optional, needs wv): the word of position B0 + threadIdx.x - the word of the block's first position (one lookup
-// per block) plus the terminators the ballots count before the lane.
+// word_out (optional, needs wv): the word of position B0 + threadIdx.x - the word of the block's first position (one count
+// per block, see below) plus the terminators the ballots count before the lane.
+// toterm_out (optional; written for the positions that get a key): characters up to and including the terminator, 33 = more than 32.
 __device__ __forceinline__ uint64_t block_stream_key(KeyStreamLds &L, const uint8_t *__restrict__ s, uint64_t N,
                                                      const KeyCode &kp, uint64_t B0, const WordView *view = nullptr,
-                                                     uint32_t *word_out = nullptr) {
+                                                     uint32_t *word_out = nullptr, uint32_t *toterm_out = nullptr) {
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const uint64_t pos = B0 + t;
   if (t < 200) L.bs[t] = 0;
@@ -226,7 +227,16 @@ __device__ __forceinline__ uint64_t block_stream_key(KeyStreamLds &L, const uint
   if (lane == 63) L.wsum[wv] = inc;
   const unsigned long long tmine = __ballot(c <= (uint32_t)kEndOfWord);      // terminators (0x01) and the final 0x00 / the padding behind it
   if (lane == 0) L.tmask[wv] = tmine;
-  if (word_out && t == 0) L.wbase = B0 < N ? word_of(*view, B0) : 0u;
+  // (the word of B0 from the 64-byte line boundary that lies inside the tile: the count there minus the 0x01 bytes the
+  //  first wave sees before it - one load that waits for nothing, where word_of(B0) is a count and then a line of bytes)
+  if (word_out) {
+    const unsigned long long t1 = __ballot(c == (uint32_t)kEndOfWord);
+    if (t == 0) {
+      const uint64_t line = (B0 >> 6) + 1;
+      const uint32_t upto = (uint32_t)(line * 64 - B0);      // 1 .. 64 positions of the tile before that boundary
+      L.wbase = B0 < N ? view->blk_word[line] - (uint32_t)__popcll(upto >= 64 ? t1 : (t1 & ((1ull << upto) - 1ull))) : 0u;
+    }
+  }
   __syncthreads();
   if (word_out) {
     uint32_t before = (uint32_t)__popcll(tmine & ((1ull << lane) - 1ull));
@@ -257,6 +267,7 @@ __device__ __forceinline__ uint64_t block_stream_key(KeyStreamLds &L, const uint
     else if (wv < 3) { const unsigned long long m1 = L.tmask[wv + 1]; if (m1) toterm = (uint32_t)(64 - lane) + (uint32_t)__builtin_ctzll(m1) + 1u; }
     if (toterm > 33u) toterm = 33u;
   }
+  if (toterm_out) *toterm_out = toterm;
   const uint32_t nch = toterm < 32u ? toterm : 32u;
   const uint32_t avail = L.off[t + nch] - p;
   const uint32_t kb = (uint32_t)kp.kbits;
@@ -270,19 +281,48 @@ __device__ __forceinline__ uint64_t block_stream_key(KeyStreamLds &L, const uint
   const uint32_t term = (toterm <= 32u && L.off[t + toterm] - p <= kb) ? 1u : 0u;
   return (k << 1) | term;
 }
+// Suffixes that emit nothing in the merge: at most min_len bytes long (terminator not counted), and the final 0x00.  The
+// first round can leave them out (sort_dict_suffixes with a minimum length).  Where every word is longer than min_len
+// (short_words_kernel looks for others) each word has exactly min_len + 1 such positions, its last ones, so the kept
+// position i of word j is the (i - (min_len + 1) j)-th kept position: init_keys_packed_kernel writes its key there - no
+// count, no scan, no list of positions.  The word comes from the tile's ballots (block_stream_key's word_out), and so
+// does the distance to the terminator while min_len + 1 characters fit into the 32 a tile looks ahead.
+__device__ __forceinline__ bool suffix_kept(const WordView &v, uint32_t wd, uint64_t pos, int min_len) {
+  return wd < v.d && v.wend[wd] - pos > (uint64_t)min_len;
+}
+// *found = 1 if some word has at most min_len bytes (found: a pinned host scalar the host cleared - no device buffer, no copy)
+__global__ void short_words_kernel(WordView view, int min_len, unsigned long long *__restrict__ found) {
+  const uint32_t j = BID * blockDim.x + threadIdx.x;
+  if (j >= view.d) return;
+  const uint64_t start = j ? view.wend[j - 1] + 1 : 0;
+  if (view.wend[j] - start <= (uint64_t)min_len) *found = 1ull;
+}
+// listed == 0: the key of every position, at the position's index.  Else (view, min_len): the keys of the `listed` kept
+// positions, each at its index among the kept ones.
 template <class I>
 __global__ __launch_bounds__(256) void init_keys_packed_kernel(const uint8_t *__restrict__ s, uint64_t N, KeyCode kp,
                                                                SlotPayloadSrc P, int paybits, uint64_t *__restrict__ key,
-                                                               I *__restrict__ val, int idx_bits) {
+                                                               I *__restrict__ val, int idx_bits, WordView view, int min_len,
+                                                               uint64_t listed /* keys of the list, 0 = every position */) {
   __shared__ KeyStreamLds L;
   const uint64_t B0 = (uint64_t)BID * kKeyPos;
-  uint32_t wd = 0;
-  uint64_t k = paybits ? block_stream_key(L, s, N, kp, B0, &P.wv, &wd) : block_stream_key(L, s, N, kp, B0);
+  uint32_t wd = 0, toterm = 0;
+  uint64_t k = (paybits || listed) ? block_stream_key(L, s, N, kp, B0, &view, &wd, &toterm) : block_stream_key(L, s, N, kp, B0);
   const uint64_t pos = B0 + threadIdx.x;
   if (threadIdx.x >= kKeyPos || pos >= N) return;
-  if (idx_bits) { key[pos] = (k << idx_bits) | pos; return; }      // keys-only sort: the position rides in the low bits
+  uint64_t at = pos;
+  if (listed) {
+    // (toterm - 1 = bytes before the terminator, exact up to 31; the final 0x00 ends at once)
+    const bool keep = min_len < 32 ? toterm > (uint32_t)min_len + 1u : suffix_kept(view, wd, pos, min_len);
+    if (!keep) return;
+    at = pos - ((uint64_t)min_len + 1) * wd;
+    // (never true: the host lists only a dictionary whose bytes below 2 are its d terminators and the final 0x00, and whose
+    //  words are all longer than min_len - then the kept positions fill [0, listed) exactly.  Kept as the store's own bound)
+    if (at >= listed) return;
+  }
+  if (idx_bits) { key[at] = (k << idx_bits) | pos; return; }      // keys-only sort: the position rides in the low bits
   if (paybits) k |= (uint64_t)slot_record(s, pos, wd, P) << 48;
-  key[pos] = k; val[pos] = (I)pos;
+  key[at] = k; val[at] = (I)pos;
 }
 // sorted (key << idx_bits | position) words -> the sorted keys and the sorted positions
 template <class I>
@@ -295,11 +335,25 @@ __global__ void split_keys_kernel(const uint64_t *__restrict__ comb, uint64_t n,
   val[a] = (I)(x & ((1ull << idx_bits) - 1ull));
 }
 // PFP_DEBUG: the bit-stream keys against the character-by-character ones
-__global__ void check_keys_kernel(const uint8_t *__restrict__ s, uint64_t N, KeyCode kp, const uint64_t *__restrict__ key,
-                                  uint64_t keymask, unsigned long long *__restrict__ bad, int idx_bits) {
-  uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  if (((key[i] >> idx_bits) & keymask) != packed_key_at(s, i, kp.kbits, kp.lut)) atomicAdd(bad, 1ull);
+// (listed: the keys of the kept positions only, in position order - suffix_kept is asked again about every position named and
+//  about the gap between neighbours, so a position dropped or kept wrongly counts as bad too)
+template <class I>
+__global__ void check_keys_kernel(const uint8_t *__restrict__ s, uint64_t n, KeyCode kp, const uint64_t *__restrict__ key,
+                                  const I *__restrict__ val, uint64_t keymask, unsigned long long *__restrict__ bad, int idx_bits,
+                                  int listed, WordView view, int min_len) {
+  uint64_t a = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  uint64_t i = a;
+  if (listed) {
+    auto pos_at = [&](uint64_t q) { return idx_bits ? (key[q] & ((1ull << idx_bits) - 1ull)) : (uint64_t)val[q]; };
+    i = pos_at(a);
+    const uint64_t from = a ? pos_at(a - 1) + 1 : 0;
+    bool ok = i < view.NP && from <= i && suffix_kept(view, word_of(view, i), i, min_len);
+    for (uint64_t j = from; ok && j < i; j++) ok = !suffix_kept(view, word_of(view, j), j, min_len);
+    if (ok && a + 1 == n) for (uint64_t j = i + 1; ok && j < view.NP; j++) ok = !suffix_kept(view, word_of(view, j), j, min_len);
+    if (!ok) { atomicAdd(bad, 1ull); return; }
+  }
+  if (((key[a] >> idx_bits) & keymask) != packed_key_at(s, i, kp.kbits, kp.lut)) atomicAdd(bad, 1ull);
 }
 template <class I>
 __global__ void init_keys_bytes_kernel(const uint8_t *__restrict__ s, uint64_t N, uint64_t *__restrict__ key,
@@ -1000,7 +1054,9 @@ template RankViewT<uint64_t> rank_view(const SuffixOrderT<uint64_t> &);
 struct DoublingOpts {
   int key_bits = 64;                     // width of the first-round keys
   bool dict = false;                     // dictionary mode: out.lut/bytes/kbits are set by the caller, ranks are lazy
-  std::optional<uint64_t> list_len;      // range mode: key/val hold this many suffixes (the ones of this rank's key range), not all g.N
+  std::optional<uint64_t> list_len;      // list mode: key/val hold this many suffixes (in position order), not all g.N - the ones of this
+                                         // rank's key range (a share), or
+  bool whole_list = false;               // ... every suffix the caller wants sorted (the ones that emit: sort_dict_suffixes), in one piece
   int idx_bits = 0;                      // keys-only first round: the words are (key << idx_bits | position) and val is empty
 };
 
@@ -1029,8 +1085,12 @@ struct Rounds {
   const DoublingOpts o;
   const uint64_t NP, N;         // positions of the string; suffixes sorted here (fewer in range mode)
   const bool lazy;
-  // a share of the suffix array (multi-GPU) never runs a doubling round - it stops where one would be needed - and finds
-  // its whole words by looking at its own slots (gather_slots_range): no rank per dictionary position is kept
+  // A list of suffixes (fewer than NP) never runs a doubling round - that would read ranks of suffixes outside the list: it
+  // stops where one would be needed (out.complete = false).
+  const bool list_mode;
+  // A share of the suffix array (multi-GPU) also finds its whole words by looking at its own slots (gather_slots_range): no
+  // rank per dictionary position is kept.  The list of all suffixes that emit keeps ranks as a whole sort does - slot numbers
+  // among the listed suffixes, rank[] or wordrank[] and the search over skeys (rank_at) - so the words' ranks cost no pass.
   const bool range_mode;
   const int nb;                 // key of a later round = (group head << nb) | (1 + rank of the continuation)
   bool lazy_active = false, late_rank = false;      // (see start_rounds)
@@ -1075,7 +1135,8 @@ struct Rounds {
   DBuf<K> dkey, dkeyo;          // wide build: 128-bit doubling keys (the 32-bit build keeps them in key/keyo)
 
   Rounds(pfp_ctx *c_, const SufGeom &g_, DBuf<uint64_t> &key_, DBuf<I> &val_, uint64_t h0, SuffixOrderT<I> &out_, const DoublingOpts &o_)
-      : c(c_), g(g_), out(out_), o(o_), NP(g_.N), N(o_.list_len.value_or(g_.N)), lazy(o_.dict), range_mode(o_.list_len.has_value()),
+      : c(c_), g(g_), out(out_), o(o_), NP(g_.N), N(o_.list_len.value_or(g_.N)), lazy(o_.dict), list_mode(o_.list_len.has_value()),
+        range_mode(o_.list_len.has_value() && !o_.whole_list),
         nb(bits_for(N)), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_), val(val_) {}
 
   static uint64_t blocks(uint64_t n) { return cdiv(n, TB); }
@@ -1524,13 +1585,13 @@ struct Rounds {
     out.rounds++;
   }
 
-  // choose and run the next round; false: only a doubling round could go on, and this is a share of a suffix array
+  // choose and run the next round; false: only a doubling round could go on, and this is a list of suffixes
   bool next_round() {
     if (dict_pivot_wanted()) { dict_pivot_round(); return true; }
     if constexpr (!kWide) {
       if (parse_pivot_wanted() && parse_pivot_round()) return true;
     }
-    if (range_mode) { out.complete = false; return false; }     // doubling would read ranks of suffixes other ranks hold
+    if (list_mode) { out.complete = false; return false; }     // doubling would read ranks of suffixes outside the list
     prepare_ranks_for_doubling();
     doubling_round();
     return true;
@@ -1582,7 +1643,8 @@ template void gather_ranks<uint64_t>(pfp_ctx *, const SuffixOrderT<uint64_t> &, 
 
 // ---- whole-array entry points: first-round keys for all N positions, then doubling()
 
-static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, double rep_hint = 0) {
+// low_counts (optional): how often the bytes 0x00 and 0x01 occur
+static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, double rep_hint = 0, uint64_t *low_counts = nullptr) {
   DBuf<unsigned long long> hist(c, 256);
   hist.zero();
   hipLaunchKernelGGL(byte_histogram_kernel, gdim(std::min<uint64_t>(cdiv64(N, 4096), (uint64_t)c->n_cu * 8)), gdim(256), 0,
@@ -1590,6 +1652,7 @@ static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, doubl
   std::vector<uint64_t> hh(256);
   PFP_HIP(hipMemcpyAsync(hh.data(), hist.p, 2048, hipMemcpyDeviceToHost, c->stream));
   sync(c);
+  if (low_counts) { low_counts[0] = hh[0]; low_counts[1] = hh[1]; }
   return make_key_code(hh.data(), rep_hint);
 }
 
@@ -1620,48 +1683,85 @@ static uint64_t dict_keymask(const KeyCode &kc) { return kc.kbits + 1 >= 64 ? ~0
 // of the key code, then the rounds
 template <class I>
 static void dict_rounds(pfp_ctx *c, const SufGeom &g, const uint8_t *bytes, const KeyCode &kc, int idx_bits, std::optional<uint64_t> list_len,
-                        DBuf<uint64_t> &key, DBuf<I> &val, SuffixOrderT<I> &out) {
+                        DBuf<uint64_t> &key, DBuf<I> &val, SuffixOrderT<I> &out, bool whole_list = false) {
   out.keymask = dict_keymask(kc);
   out.lut.alloc(c, 256);
   PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
   sync(c);      // kc may be a stack object of the caller
   out.bytes = bytes; out.kbits = kc.kbits;
   DoublingOpts o;
-  o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = list_len, o.idx_bits = idx_bits;
+  o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = list_len, o.whole_list = whole_list, o.idx_bits = idx_bits;
   doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
 }
 
+// PFP_DROP_SHORT=0: a minimum suffix length is ignored, every position is sorted (read per call: the tests compare both ways)
+static bool drop_short_enabled() { const char *e = getenv("PFP_DROP_SHORT"); return !e || atoi(e) != 0; }
+
 template <class I>
 void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, SuffixOrderT<I> &out,
-                        const SlotPayloadSrc *pay) {
+                        const SlotPayloadSrc *pay, int min_len) {
   require_dict_size<I>(N);
   SufGeom g{MODE_DICT, N, wv};
-  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint);
+  // Only the suffixes longer than min_len.  The placement of their keys (init_keys_packed_kernel) needs a dictionary in which
+  // every word is longer than min_len - checked by short_words_kernel while the byte histogram is read back - and in which
+  // the only bytes below 2 are the d terminators and the final 0x00 - read off that histogram: a parse makes no other, but
+  // pfp_merge is handed a file whose bytes nobody looked at.  Then every word has exactly min_len + 1 positions that are not
+  // kept, and the final 0x00 is one more.  Anything else is sorted whole.
+  const uint64_t ntile = cdiv64(N, kKeyPos);
+  const uint64_t dropped = (uint64_t)wv.d * ((uint64_t)min_len + 1) + 1;
+  bool listed = min_len > 0 && wv.d >= 1 && dropped < N && drop_short_enabled();
+  unsigned long long *const short_found = reinterpret_cast<unsigned long long *>(c->h_scalars + 3);
+  if (listed) {
+    *short_found = 0;
+    KScope ks(c, "pfp::short_words_kernel", (uint64_t)wv.d * 8);
+    hipLaunchKernelGGL(short_words_kernel, gdim(cdiv((uint64_t)wv.d, 256)), gdim(256), 0, c->stream, wv, min_len, short_found);
+  }
+  uint64_t low_counts[2] = {0, 0};
+  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint, low_counts);      // (syncs)
+  if (listed && (*short_found != 0 || low_counts[0] != 1 || low_counts[1] != (uint64_t)wv.d)) {
+    listed = false;
+    if (kSwitch.trace_rounds)
+      fprintf(stderr, "[pfp] dictionary with a word of at most %d bytes or a stray byte below 2: every position is sorted\n", min_len);
+  }
+  const uint64_t n = listed ? N - dropped : N;
   // Keys-only first round.  A dictionary of a repetitive collection (text / dictionary >= 2) is mostly families of
   // variants that no first-round key separates, whatever its width: the first round only has to bring the families
   // together.  Then the position fits into the same 64-bit word as a (shorter) key, the sort moves 16 bytes per
   // element and pass instead of 24 and makes 4-5 passes instead of 7, and the merge records in the key's spare bits
   // (which such an input hardly uses: most slots are re-ordered later) are given up.
-  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, kc);
-  DBuf<uint64_t> key(c, N);
+  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, kc);      // (index bits hold a POSITION: by N also where fewer are sorted)
+  DBuf<uint64_t> key(c, n);
   DBuf<I> val;
-  if (!idx_bits) val.alloc(c, N);
+  if (!idx_bits) val.alloc(c, n);
   out.paybits = (pay && !idx_bits && kc.kbits + 1 <= 48) ? 16 : 0;
-  { KScope ks(c, "pfp::init_keys_packed_kernel", N * (9 + (idx_bits ? 0 : sizeof(I)) + (out.paybits ? 9 : 0)));
-    hipLaunchKernelGGL(init_keys_packed_kernel<I>, gdim((unsigned)cdiv64(N, kKeyPos)), gdim(256), 0, c->stream, bytes, N, kc,
-                       pay ? *pay : SlotPayloadSrc{}, out.paybits, key.p, val.p, idx_bits); }
+  { KScope ks(c, "pfp::init_keys_packed_kernel", N + n * (8 + (idx_bits ? 0 : sizeof(I)) + (out.paybits ? 9 : 0)));
+    hipLaunchKernelGGL(init_keys_packed_kernel<I>, gdim((unsigned)ntile), gdim(256), 0, c->stream, bytes, N, kc,
+                       pay ? *pay : SlotPayloadSrc{}, out.paybits, key.p, val.p, idx_bits, wv, min_len, listed ? n : (uint64_t)0); }
   if (c->debug) {
     DBuf<unsigned long long> bad(c, 1);
     bad.zero();
-    hipLaunchKernelGGL(check_keys_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, kc, key.p, dict_keymask(kc), bad.p, idx_bits);
+    hipLaunchKernelGGL(check_keys_kernel<I>, gdim(cdiv(n, 256)), gdim(256), 0, c->stream, bytes, n, kc, key.p, val.p, dict_keymask(kc), bad.p,
+                       idx_bits, listed ? 1 : 0, wv, min_len);
     PFP_HIP(hipMemcpyAsync(c->h_scalars, bad.p, 8, hipMemcpyDeviceToHost, c->stream));
     sync(c);
     PFP_REQUIRE(c->h_scalars[0] == 0, PFP_EHIP, "bit-stream keys differ from packed_key_at at " + std::to_string(c->h_scalars[0]) + " positions");
   }
-  dict_rounds<I>(c, g, bytes, kc, idx_bits, std::nullopt, key, val, out);
+  if (!listed) { dict_rounds<I>(c, g, bytes, kc, idx_bits, std::nullopt, key, val, out); return; }
+  dict_rounds<I>(c, g, bytes, kc, idx_bits, n, key, val, out, true);
+  if (out.complete) return;
+  // A group was left that only a doubling round settles, and that round reads the rank of positions that may not be listed:
+  // the list's result is dropped and every position sorted, once.  (Deterministic and rare: a dictionary of a parse is
+  // settled by the first round and pivot rounds.  The kernel trace shows it: short_words_kernel ran, and the first round twice.)
+  if (kSwitch.trace_rounds) fprintf(stderr, "[pfp] the sort of the %llu suffixes longer than %d bytes needs a doubling round: every position is sorted\n",
+                                    (unsigned long long)n, min_len);
+  key.release(); val.release();
+  const double rep_hint = out.rep_hint;
+  out = SuffixOrderT<I>{};
+  out.rep_hint = rep_hint;
+  sort_dict_suffixes<I>(c, bytes, N, wv, out, pay, 0);
 }
-template void sort_dict_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint32_t> &, const SlotPayloadSrc *);
-template void sort_dict_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint64_t> &, const SlotPayloadSrc *);
+template void sort_dict_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint32_t> &, const SlotPayloadSrc *, int);
+template void sort_dict_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, const WordView &, SuffixOrderT<uint64_t> &, const SlotPayloadSrc *, int);
 
 // (Tried in round 3 and removed: "grouped order without sorting duplicates".  Equal suffixes of a dictionary of variants can be
 //  read off the WORDS: sort the d words by their reversed strings, keep the longest common suffix lcs[r] of neighbours; the
@@ -2024,6 +2124,7 @@ template <class I>
 void gather_slots_range(pfp_ctx *c, const SuffixOrderT<I> &so, const WordView &wv, uint64_t count, uint64_t *d_out) {
   if (!count) return;
   PFP_HIP(hipMemsetAsync(d_out, 0, count * 8, c->stream));
+  KScope ks(c, "pfp::word_slots_range_kernel", so.N * (sizeof(I) + 1) + count * 8);      // (one random byte per slot)
   if (so.N) hipLaunchKernelGGL(word_slots_range_kernel<I>, gdim(cdiv(so.N, 256)), gdim(256), 0, c->stream, so.N, so.sa.p, wv, so.slot_base, d_out);
   PFP_HIP(hipGetLastError());
 }

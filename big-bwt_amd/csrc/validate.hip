@@ -81,15 +81,21 @@ static int cmp_suffix(const std::vector<uint8_t> &b, uint64_t x, uint64_t y) {
   }
 }
 
+// so.N < so.NP: the sorted suffixes are a list of the NP positions (the ones that emit something: sort_dict_suffixes with a
+// minimum length) - sa[] names every listed position once, ranks and group heads are slot numbers among the listed
 template <class I>
 void validate_suffix_order(pfp_ctx *c, const uint8_t *bytes, SuffixOrderT<I> &so, bool dict_mode, const char *what) {
-  const uint64_t N = so.N;
+  const uint64_t N = so.N, NP = so.NP ? so.NP : so.N;
+  if (N > NP) VFAIL(std::string(what) + ": more slots than positions");
   auto sa = fetch(c, so.sa.p, N);
-  // ranks through the sorter's own lookup (rank[] is sparse in dictionary mode), checked against grp[]
+  // ranks through the sorter's own lookup (rank[] is sparse in dictionary mode), checked against grp[]: rk[t] = rank of sa[t]
   std::vector<I> rk(N);
   {
     std::vector<uint64_t> pos(N);
-    for (uint64_t i = 0; i < N; i++) pos[i] = i;
+    for (uint64_t t = 0; t < N; t++) {
+      if (sa[t] >= NP) VFAIL(std::string(what) + ": sa is not a permutation at slot " + std::to_string(t));
+      pos[t] = sa[t];
+    }
     DBuf<uint64_t> dpos(c, N);
     DBuf<I> dr(c, N);
     h2d(c, dpos.p, pos.data(), N);
@@ -97,21 +103,33 @@ void validate_suffix_order(pfp_ctx *c, const uint8_t *bytes, SuffixOrderT<I> &so
     rk = fetch(c, dr.p, N);
   }
   auto gr = fetch(c, so.grp.p, N);
-  std::vector<uint8_t> seen(N, 0);
+  std::vector<uint8_t> seen(NP, 0);
   for (uint64_t t = 0; t < N; t++) {
-    if (sa[t] >= N || seen[sa[t]]) VFAIL(std::string(what) + ": sa is not a permutation at slot " + std::to_string(t));
+    if (seen[sa[t]]) VFAIL(std::string(what) + ": sa is not a permutation at slot " + std::to_string(t));
     seen[sa[t]] = 1;
-    if (rk[sa[t]] > t) VFAIL(std::string(what) + ": rank above slot");
-    if (rk[sa[t]] != gr[t]) VFAIL(std::string(what) + ": rank lookup differs from the slot's group head at slot " + std::to_string(t));
+    if (rk[t] > t) VFAIL(std::string(what) + ": rank above slot");
+    if (rk[t] != gr[t]) VFAIL(std::string(what) + ": rank lookup differs from the slot's group head at slot " + std::to_string(t));
   }
-  if (dict_mode && N < (64u << 20)) {
-    auto b = fetch(c, bytes, N);
+  if (dict_mode && NP < (64u << 20)) {
+    auto b = fetch(c, bytes, NP);
     for (uint64_t t = 1; t < N; t++) {
       int cmp = cmp_suffix(b, sa[t - 1], sa[t]);
-      bool same = rk[sa[t - 1]] == rk[sa[t]];
+      bool same = rk[t - 1] == rk[t];
       if (cmp > 0) VFAIL(std::string(what) + ": suffixes out of order at slot " + std::to_string(t));
       if ((cmp == 0) != same) VFAIL(std::string(what) + ": rank equality != string equality at slot " + std::to_string(t));
       if (cmp == 0 && sa[t - 1] > sa[t]) VFAIL(std::string(what) + ": equal suffixes not in position order");
+    }
+    // a list: no position left out is as long as the shortest listed one (a suffix is kept by its length alone), and every
+    // word start is listed (compute_lexrank asks for its rank)
+    if (N < NP) {
+      auto len_at = [&](uint64_t i) { uint64_t l = 0; while (b[i + l] > kEndOfWord) l++; return l; };
+      uint64_t min_kept = ~0ull;
+      for (uint64_t t = 0; t < N; t++) min_kept = std::min(min_kept, len_at(sa[t]));
+      for (uint64_t i = 0; i < NP; i++) {
+        if (seen[i]) continue;
+        if (len_at(i) >= min_kept) VFAIL(std::string(what) + ": a suffix as long as a sorted one was left out at position " + std::to_string(i));
+        if (i + 1 < NP && (i == 0 || b[i - 1] == kEndOfWord)) VFAIL(std::string(what) + ": a whole word was left out at position " + std::to_string(i));
+      }
     }
   }
 }
