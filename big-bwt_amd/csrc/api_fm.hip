@@ -4,9 +4,11 @@
 // mapping reads (fmmap.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
-// (HostOut::take, fetch_group_offsets).
+// (HostOut::take / take_offsets, fetch_group_offsets).  align, map and map_pairs also share their beginning (seed_call_begin: the
+// patterns the extension reads, their matching statistics and MEM counts) and their groups of candidates (seed_groups).
 #include <algorithm>
 #include <memory>
+#include <utility>
 #include <vector>
 #include "api.hpp"
 
@@ -28,6 +30,10 @@ int dev_call(pfp_fm *fm, F &&body, bool wait = true) {
   return PFP_OK;
   PFP_CATCH(c)
 }
+
+// a buffer leaves a call over device pointers: a block of the pool, as pfp_dev_free takes it
+template <class T>
+T *hand_out(DBuf<T> &b) { return std::exchange(b.p, nullptr); }
 
 // the body of an entry point that makes an index: build(the new index's FmIndex); *out gets the index once it stands
 template <class F>
@@ -84,6 +90,11 @@ uint64_t group_end(const uint64_t *off, uint64_t p0, uint64_t end, uint64_t budg
   return p1;
 }
 
+// `count` offsets on the host, counted from where a group starts, go behind the call's: base is the call's offset of that start
+void rebase_offsets(uint64_t *off, uint64_t count, uint64_t base) {
+  for (uint64_t i = 0; i < count; i++) off[i] += base;
+}
+
 // a malloc'ed result array that grows group by group
 template <class T>
 struct HostOut {
@@ -103,6 +114,14 @@ struct HostOut {
     download(c, grow(count), (const uint8_t *)d_src, count * sizeof(T));
     sync(c);      // (the next download fills the same pinned buffers)
     n += count;
+  }
+  // `count` device offsets, counted from where a group starts, behind the n >= 1 held: they go behind the last one held, which
+  // is the call's offset of the group's start.  Returns what the group brought
+  T take_offsets(pfp_ctx *c, const T *d_src, uint64_t count) {
+    const T base = p[n - 1];
+    take(c, d_src, count);
+    rebase_offsets(p + n - count, count, base);
+    return p[n - 1] - base;
   }
   T *release() { T *q = n ? p : nullptr; if (!n) free(p); p = nullptr; return q; }
 };
@@ -182,23 +201,16 @@ void apx_group_hits(pfp_fm *fm, const ApxCall &s, uint64_t p0, uint64_t p1, int 
 }
 
 // ---------------------------------------------------------------- matching statistics and MEMs (fmsearch.hip: PHONI)
-// host patterns -> device patterns, lengths and positions (entry t of the device arrays belongs to pattern byte t)
+// host patterns -> device patterns (in.upload), lengths and positions (entry t of the device arrays belongs to pattern byte t)
 struct MsOnDevice {
-  const uint8_t *h_pat;
-  const uint64_t *h_off;
-  uint64_t npat, bytes, first, total;
   HostPatterns in;
   DBuf<uint32_t> len;
   DBuf<uint64_t> pos;
-  // (the host arrays are checked here: a caller may look at the lengths before anything is uploaded)
-  MsOnDevice(const uint8_t *pat, const uint64_t *pat_off, uint64_t npat_)
-      : h_pat(pat), h_off(pat_off), npat(npat_), bytes(pattern_bytes(pat, pat_off, npat_)), first(npat_ ? pat_off[0] : 0), total(bytes - first) {}
-  void run(pfp_fm *fm, bool thr) {
-    pfp_ctx *c = fm->f.c;
-    in.upload(c, h_pat, h_off, npat);
-    len.alloc(c, bytes + 1);
-    pos.alloc(c, bytes + 1);
-    (thr ? fm_ms_thr : fm_ms)(fm->f, in.pat.p, in.off.p, npat, len.p, pos.p);
+  // the statistics of n device patterns whose offsets end at `bytes`: the upload, or what a caller has put in its place
+  void stats(pfp_fm *fm, const uint8_t *pat, const uint64_t *off, uint64_t n, uint64_t bytes, bool thr) {
+    len.alloc(fm->f.c, bytes + 1);
+    pos.alloc(fm->f.c, bytes + 1);
+    (thr ? fm_ms_thr : fm_ms)(fm->f, pat, off, n, len.p, pos.p);
   }
 };
 
@@ -209,12 +221,14 @@ int ms_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t np
   require_text(fm, "matching statistics need");
   if (thr) require_thresholds(fm);
   if (!npat) return PFP_OK;
-  MsOnDevice d(pat, pat_off, npat);
-  d.run(fm, thr);
-  if (d.total) {
-    download(c, len, (const uint8_t *)(d.len.p + d.first), d.total * 4);
+  MsOnDevice d;
+  d.in.upload(c, pat, pat_off, npat);
+  d.stats(fm, d.in.pat.p, d.in.off.p, npat, d.in.bytes, thr);
+  const uint64_t first = pat_off[0], total = d.in.bytes - first;
+  if (total) {
+    download(c, len, (const uint8_t *)(d.len.p + first), total * 4);
     sync(c);      // (the next download fills the same pinned buffers)
-    if (pos) download(c, pos, (const uint8_t *)(d.pos.p + d.first), d.total * 8);
+    if (pos) download(c, pos, (const uint8_t *)(d.pos.p + first), total * 8);
   }
   sync(c);
   return PFP_OK;
@@ -230,8 +244,9 @@ int mems_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
   require_text(fm, "maximal exact matches need");
   if (thr) require_thresholds(fm);
   PFP_REQUIRE(min_len >= 1, PFP_EINVAL, "min_len = 0: a maximal exact match is at least 1 byte long");
-  MsOnDevice d(pat, pat_off, npat);
-  d.run(fm, thr);
+  MsOnDevice d;
+  d.in.upload(c, pat, pat_off, npat);
+  d.stats(fm, d.in.pat.p, d.in.off.p, npat, d.in.bytes, thr);
   d.in.pat.release();
   DBuf<uint64_t> d_mem_off(c, npat + 1);
   fm_mems(fm->f, d.in.off.p, npat, d.len.p, d.pos.p, min_len, d_mem_off.p, nullptr);
@@ -250,6 +265,72 @@ int mems_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t 
 int ms_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint32_t *d_len, uint64_t *d_pos, bool thr) {
   if (!fm || (npat && (!d_pat_off || !d_len))) return PFP_EINVAL;
   return dev_call(fm, [&] { (thr ? fm_ms_thr : fm_ms)(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_len, d_pos); });
+}
+
+// ---------------------------------------------------------------- seed-and-extend (fmextend.hip, fmmap.hip, fmpair.hip)
+// fm_extend_check_patterns' rule on the host's copy of the offsets, before any work; noun: what the caller calls a pattern
+void require_extendable(const uint64_t *pat_off, uint64_t npat, const char *noun) {
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
+                std::string(noun) + " " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+}
+
+// MsOnDevice for the patterns the extension reads - pat / off, n of them: the upload itself, or both strands of every read (rd;
+// n = 2 npat; the uploaded bytes go once the strands stand) - and moff, their n + 1 MEM offsets, on the host
+struct SeedCall : MsOnDevice {
+  MapReads rd;
+  const uint8_t *pat = nullptr;
+  const uint64_t *off = nullptr;
+  uint64_t n = 0, min_seed = 0;
+  int k = 0;
+  std::vector<uint64_t> moff;
+};
+// the caller has checked k, min_seed and the thresholds; noun: require_extendable's.  Without patterns nothing but the upload
+void seed_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const char *noun, bool strands, uint64_t min_seed, int k,
+                     bool thresholds, SeedCall &s) {
+  FmIndex &f = fm->f;
+  pfp_ctx *c = f.c;
+  s.min_seed = min_seed; s.k = k;
+  s.in.upload(c, pat, pat_off, npat);                   // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
+  require_extendable(pat_off, npat, noun);
+  if (!npat) return;
+  s.pat = s.in.pat.p; s.off = s.in.off.p; s.n = npat;
+  uint64_t bytes = s.in.bytes;
+  if (strands) {
+    fm_map_strands(f, s.pat, s.off, npat, s.rd);
+    s.in.pat.release();
+    s.pat = s.rd.pat.p; s.off = s.rd.off.p; s.n = 2 * npat;
+    bytes = 2 * (pat_off[npat] - pat_off[0]);
+  }
+  s.stats(fm, s.pat, s.off, s.n, bytes, thresholds);
+  s.moff.resize(s.n + 1);
+  DBuf<uint64_t> d_moff(c, s.n + 1);
+  fm_mems(f, s.off, s.n, s.len.p, s.pos.p, min_seed, d_moff.p, nullptr);
+  d2h(c, s.moff.data(), d_moff.p, s.n + 1);
+  sync(c);
+}
+// The groups of a seeded call: consecutive units of `unit` patterns (1: a pattern, 2: a read's strands, 4: a pair's) whose seeds
+// stay within the budget (group_end); body(first pattern, patterns, their candidates: at most max_aln per pattern, 0: all) runs
+// per group.  hold_keys: the keys live until the body, which fetches results and so waits for the stream, returns
+template <class F>
+void seed_groups(pfp_fm *fm, const SeedCall &s, uint64_t unit, uint64_t max_aln, bool hold_keys, F &&body) {
+  pfp_ctx *c = fm->f.c;
+  if (!s.n) return;
+  const uint64_t budget = seq_budget(), nunit = s.n / unit;
+  std::vector<uint64_t> uoff(nunit + 1), goff;
+  for (uint64_t u = 0; u <= nunit; u++) uoff[u] = s.moff[unit * u];             // a unit brings the seeds of all its patterns
+  for (uint64_t u0 = 0, u1; u0 < nunit; u0 = u1) {
+    u1 = group_end(uoff.data(), u0, nunit, budget);
+    const uint64_t p0 = unit * u0, np = unit * (u1 - u0);
+    goff.resize(np + 1);                                // the group's MEM offsets: the call's, counted from its first pattern
+    for (uint64_t i = 0; i <= np; i++) goff[i] = s.moff[p0 + i] - s.moff[p0];
+    DBuf<uint64_t> g_moff(c, np + 1);
+    h2d(c, g_moff.p, goff.data(), np + 1);
+    AlnKeys keys;
+    MapCands cd;
+    fm_map_cands_ms(fm->f, s.pat, s.off + p0, np, s.min_seed, s.k, max_aln, s.len.p, s.pos.p, g_moff.p, goff[np], cd, hold_keys ? &keys : nullptr);
+    body(p0, np, cd);
+  }
 }
 
 // ---------------------------------------------------------------- sequences of a collection (seqmap.hip)
@@ -603,43 +684,17 @@ int pfp_fm_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64
   *start = nullptr; *end = nullptr; *dist = nullptr;
   pfp_ctx *c = fm->f.c;
   PFP_TRY_DEV(c)
-  fm_extend_check(fm->f, k);
-  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
-  if (thresholds) require_thresholds(fm);
-  const uint64_t budget = seq_budget();
-  MsOnDevice d(pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
-  for (uint64_t p = 0; p < npat; p++)                   // (before any work: fm_extend_check_patterns' rule, on the host's copy)
-    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
-                "pattern " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
-  d.run(fm, thresholds != 0);
-  aln_off[0] = 0;
-  if (!npat) return PFP_OK;
-  std::vector<uint64_t> moff(npat + 1), goff, go;
-  {
-    DBuf<uint64_t> d_moff(c, npat + 1);
-    fm_mems(fm->f, d.in.off.p, npat, d.len.p, d.pos.p, min_seed, d_moff.p, nullptr);
-    d2h(c, moff.data(), d_moff.p, npat + 1);
-    sync(c);
-  }
+  fm_align_check(fm->f, k, min_seed, thresholds != 0);
+  SeedCall s;
+  seed_call_begin(fm, pat, pat_off, npat, "pattern", false, min_seed, k, thresholds != 0, s);
   HostOut<uint64_t> h_start, h_end;
   HostOut<uint8_t> h_dist;
-  for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {       // consecutive patterns whose seeds stay within the budget
-    p1 = group_end(moff.data(), p0, npat, budget);
-    const uint64_t np = p1 - p0;
-    goff.resize(np + 1);                                // the group's MEM offsets: the call's, counted from its first pattern
-    for (uint64_t i = 0; i <= np; i++) goff[i] = moff[p0 + i] - moff[p0];
-    DBuf<uint64_t> g_moff(c, np + 1), g_off(c, np + 1);
-    h2d(c, g_moff.p, goff.data(), np + 1);
-    AlnKeys keys;
-    fm_align_seeds(fm->f, d.in.pat.p, d.in.off.p + p0, np, min_seed, k, max_aln, d.len.p, d.pos.p, g_moff.p, goff[np], g_off.p, keys);
-    DBuf<uint64_t> g_start(c, keys.total), g_end(c, keys.total);
-    DBuf<uint8_t> g_dist(c, keys.total);
-    fm_align_write(fm->f, keys, g_start.p, g_end.p, g_dist.p);
-    fetch_group_offsets(c, g_off.p, np, go, aln_off + p0);
-    h_start.take(c, g_start.p, keys.total);
-    h_end.take(c, g_end.p, keys.total);
-    h_dist.take(c, g_dist.p, keys.total);
-  }
+  std::vector<uint64_t> go;
+  aln_off[0] = 0;
+  seed_groups(fm, s, 1, max_aln, true, [&](uint64_t p0, uint64_t np, MapCands &cd) {
+    fetch_group_offsets(c, cd.aln_off.p, np, go, aln_off + p0);
+    h_start.take(c, cd.start.p, cd.A); h_end.take(c, cd.end.p, cd.A); h_dist.take(c, cd.dist.p, cd.A);
+  });
   *start = h_start.release(); *end = h_end.release(); *dist = h_dist.release();
   return PFP_OK;
   PFP_CATCH(c)
@@ -725,10 +780,7 @@ int pfp_fm_map_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uin
     DBuf<uint8_t> md;
     fm_map(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, max_sec, thresholds != 0, d_hit_off, d_mapq, d_nhits, d_strand, d_seq, d_off,
            d_start, d_dist, d_cig_off, cig, d_md_off, md);
-    if (fill) {                                         // the two buffers leave the call: blocks of the pool, as pfp_dev_free takes them
-      *d_cig = cig.p; cig.p = nullptr;
-      *d_md = md.p; md.p = nullptr;
-    }
+    if (fill) { *d_cig = hand_out(cig); *d_md = hand_out(md); }
   });
 }
 
@@ -744,78 +796,38 @@ int pfp_fm_map(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t
   PFP_TRY_DEV(c)
   FmIndex &f = fm->f;
   fm_map_check(f, k, min_seed, thresholds != 0);
-  const uint64_t budget = seq_budget();
-  HostPatterns in;
-  in.upload(c, pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
-  for (uint64_t p = 0; p < npat; p++)
-    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
-                "read " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+  SeedCall s;
+  seed_call_begin(fm, pat, pat_off, npat, "read", true, min_seed, k, thresholds != 0, s);
   HostOut<uint8_t> h_strand, h_dist, h_md;
   HostOut<uint32_t> h_seq, h_cig;
   HostOut<uint64_t> h_off, h_start, h_cig_off, h_md_off;
+  std::vector<uint64_t> go;
   hit_off[0] = 0;
   *h_cig_off.grow(1) = 0; h_cig_off.n = 1;
   *h_md_off.grow(1) = 0; h_md_off.n = 1;
-  if (npat) {
-    // both strands of every read, their matching statistics for the whole call, and the seeds of every pattern
-    MapReads rd;
-    fm_map_strands(f, in.pat.p, in.off.p, npat, rd);
-    in.pat.release();
-    const uint64_t bytes2 = 2 * (pat_off[npat] - pat_off[0]);
-    DBuf<uint32_t> len(c, bytes2 + 1);
-    DBuf<uint64_t> pos(c, bytes2 + 1);
-    (thresholds ? fm_ms_thr : fm_ms)(f, rd.pat.p, rd.off.p, 2 * npat, len.p, pos.p);
-    std::vector<uint64_t> moff(2 * npat + 1), roff(npat + 1), goff, go;
-    {
-      DBuf<uint64_t> d_moff(c, 2 * npat + 1);
-      fm_mems(f, rd.off.p, 2 * npat, len.p, pos.p, min_seed, d_moff.p, nullptr);
-      d2h(c, moff.data(), d_moff.p, 2 * npat + 1);
-      sync(c);
-    }
-    for (uint64_t p = 0; p <= npat; p++) roff[p] = moff[2 * p];       // a read brings the seeds of both its strands
-    for (uint64_t p0 = 0, p1; p0 < npat; p0 = p1) {     // consecutive reads whose seeds stay within the budget
-      p1 = group_end(roff.data(), p0, npat, budget);
-      const uint64_t np = p1 - p0;
-      goff.resize(2 * np + 1);
-      for (uint64_t i = 0; i <= 2 * np; i++) goff[i] = moff[2 * p0 + i] - moff[2 * p0];
-      DBuf<uint64_t> g_moff(c, 2 * np + 1), g_aoff(c, 2 * np + 1), g_start, g_end;
-      DBuf<uint8_t> g_dist;
-      h2d(c, g_moff.p, goff.data(), 2 * np + 1);
-      uint64_t A = 0;
-      {
-        AlnKeys keys;
-        fm_align_seeds(f, rd.pat.p, rd.off.p + 2 * p0, 2 * np, min_seed, k, 0, len.p, pos.p, g_moff.p, goff[2 * np], g_aoff.p, keys);
-        A = keys.total;
-        g_start.alloc(c, A); g_end.alloc(c, A); g_dist.alloc(c, A);
-        fm_align_write(f, keys, g_start.p, g_end.p, g_dist.p);
-        sync(c);
-      }
-      DBuf<uint64_t> d_hoff(c, np + 1), d_nh(c, np);
-      DBuf<uint8_t> d_mapq(c, np);
-      MapSel sel;
-      fm_map_select(f, rd.off.p + 2 * p0, np, k, max_sec, g_aoff.p, g_start.p, g_end.p, g_dist.p, A, d_hoff.p, d_mapq.p, d_nh.p, sel);
-      g_start.release(); g_end.release(); g_dist.release();
-      fetch_group_offsets(c, d_hoff.p, np, go, hit_off + p0);
-      d2h(c, mapq + p0, d_mapq.p, np);
-      d2h(c, nhits + p0, d_nh.p, np);
-      sync(c);
-      const uint64_t H = sel.H;
-      DBuf<uint8_t> d_strand(c, H), d_dist(c, H), d_md;
-      DBuf<uint32_t> d_seq(c, H), d_cig;
-      DBuf<uint64_t> d_off(c, H), d_start(c, H), d_coff(c, H + 1), d_moff(c, H + 1);
-      fm_map_fill(f, rd.pat.p, rd.off.p + 2 * p0, np, k, g_aoff.p, d_hoff.p, sel, d_strand.p, d_seq.p, d_off.p, d_start.p, d_dist.p, d_coff.p, d_cig,
-                  d_moff.p, d_md);
-      h_strand.take(c, d_strand.p, H); h_seq.take(c, d_seq.p, H); h_off.take(c, d_off.p, H);
-      h_start.take(c, d_start.p, H); h_dist.take(c, d_dist.p, H);
-      // the group's script and MD offsets go behind the call's, counted from the call's first run and byte
-      const uint64_t c0 = h_cig_off.p[h_cig_off.n - 1], m0 = h_md_off.p[h_md_off.n - 1];
-      h_cig_off.take(c, d_coff.p + 1, H);
-      h_md_off.take(c, d_moff.p + 1, H);
-      for (uint64_t i = 1; i <= H; i++) { h_cig_off.p[h_cig_off.n - i] += c0; h_md_off.p[h_md_off.n - i] += m0; }
-      h_cig.take(c, d_cig.p, h_cig_off.p[h_cig_off.n - 1] - c0);
-      h_md.take(c, d_md.p, h_md_off.p[h_md_off.n - 1] - m0);
-    }
-  }
+  seed_groups(fm, s, 2, 0, false, [&](uint64_t p0, uint64_t np2, MapCands &cd) {
+    const uint64_t r0 = p0 / 2, np = np2 / 2;           // the group's reads
+    DBuf<uint64_t> d_hoff(c, np + 1), d_nh(c, np);
+    DBuf<uint8_t> d_mapq(c, np);
+    MapSel sel;
+    fm_map_select(f, s.off + p0, np, k, max_sec, cd, d_hoff.p, d_mapq.p, d_nh.p, sel);
+    cd.drop_triples();
+    fetch_group_offsets(c, d_hoff.p, np, go, hit_off + r0);
+    d2h(c, mapq + r0, d_mapq.p, np);
+    d2h(c, nhits + r0, d_nh.p, np);
+    sync(c);
+    const uint64_t H = sel.H;
+    DBuf<uint8_t> d_strand(c, H), d_dist(c, H), d_md;
+    DBuf<uint32_t> d_seq(c, H), d_cig;
+    DBuf<uint64_t> d_off(c, H), d_start(c, H), d_coff(c, H + 1), d_moff(c, H + 1);
+    fm_map_fill(f, s.pat, s.off + p0, np, k, cd.aln_off.p, d_hoff.p, sel, d_strand.p, d_seq.p, d_off.p, d_start.p, d_dist.p, d_coff.p, d_cig, d_moff.p,
+                d_md);
+    h_strand.take(c, d_strand.p, H); h_seq.take(c, d_seq.p, H); h_off.take(c, d_off.p, H);
+    h_start.take(c, d_start.p, H); h_dist.take(c, d_dist.p, H);
+    const uint64_t runs = h_cig_off.take_offsets(c, d_coff.p + 1, H), md_bytes = h_md_off.take_offsets(c, d_moff.p + 1, H);
+    h_cig.take(c, d_cig.p, runs);
+    h_md.take(c, d_md.p, md_bytes);
+  });
   *strand = h_strand.release(); *seq = h_seq.release(); *off = h_off.release(); *start = h_start.release(); *dist = h_dist.release();
   *cig_off = h_cig_off.release(); *cig = h_cig.release(); *md_off = h_md_off.release(); *md = h_md.release();
   return PFP_OK;
@@ -838,8 +850,7 @@ int pfp_fm_map_pairs_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_of
     DBuf<uint8_t> md;
     const PairOut out{d_proper, d_npairs, d_mapped, d_rescued, d_mapq, d_strand, d_seq, d_off, d_start, d_dist, d_tlen, d_cig_off, d_md_off};
     fm_map_pairs(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, k, thresholds != 0, min_ins, max_ins, anchors, d_nhits, out, cig, md);
-    *d_cig = cig.p; cig.p = nullptr;                    // the two buffers leave the call: blocks of the pool, as pfp_dev_free takes them
-    *d_md = md.p; md.p = nullptr;
+    *d_cig = hand_out(cig); *d_md = hand_out(md);
   });
 }
 
@@ -855,75 +866,38 @@ int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, ui
   PFP_TRY_DEV(c)
   FmIndex &f = fm->f;
   fm_pair_check(f, npat, k, min_seed, thresholds != 0, min_ins, max_ins, anchors);
-  const uint64_t budget = seq_budget();
-  HostPatterns in;
-  in.upload(c, pat, pat_off, npat);                     // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
-  for (uint64_t p = 0; p < npat; p++)
-    PFP_REQUIRE(pat_off[p + 1] - pat_off[p] <= PFP_FM_EXTEND_MAX_M, PFP_ELIMIT,
-                "read " + std::to_string(p) + " holds more than " + std::to_string(PFP_FM_EXTEND_MAX_M) + " bytes (PFP_FM_EXTEND_MAX_M)");
+  SeedCall s;
+  seed_call_begin(fm, pat, pat_off, npat, "read", true, min_seed, k, thresholds != 0, s);
   HostOut<uint32_t> h_cig;
   HostOut<uint8_t> h_md;
   cig_off[0] = 0; md_off[0] = 0;
-  if (npat) {
-    // both strands of every read, their matching statistics for the whole call, and the seeds of every pattern
-    MapReads rd;
-    fm_map_strands(f, in.pat.p, in.off.p, npat, rd);
-    in.pat.release();
-    const uint64_t bytes2 = 2 * (pat_off[npat] - pat_off[0]), npair = npat / 2;
-    DBuf<uint32_t> len(c, bytes2 + 1);
-    DBuf<uint64_t> pos(c, bytes2 + 1);
-    (thresholds ? fm_ms_thr : fm_ms)(f, rd.pat.p, rd.off.p, 2 * npat, len.p, pos.p);
-    std::vector<uint64_t> moff(2 * npat + 1), qoff(npair + 1), goff;
-    {
-      DBuf<uint64_t> d_moff(c, 2 * npat + 1);
-      fm_mems(f, rd.off.p, 2 * npat, len.p, pos.p, min_seed, d_moff.p, nullptr);
-      d2h(c, moff.data(), d_moff.p, 2 * npat + 1);
-      sync(c);
-    }
-    for (uint64_t q = 0; q <= npair; q++) qoff[q] = moff[4 * q];        // a pair brings the seeds of both strands of both mates
-    for (uint64_t q0 = 0, q1; q0 < npair; q0 = q1) {    // consecutive WHOLE pairs whose seeds stay within the budget
-      q1 = group_end(qoff.data(), q0, npair, budget);
-      const uint64_t p0 = 2 * q0, np = 2 * (q1 - q0);
-      goff.resize(2 * np + 1);
-      for (uint64_t i = 0; i <= 2 * np; i++) goff[i] = moff[2 * p0 + i] - moff[2 * p0];
-      DBuf<uint64_t> g_moff(c, 2 * np + 1), g_aoff(c, 2 * np + 1), g_start, g_end;
-      DBuf<uint8_t> g_dist;
-      h2d(c, g_moff.p, goff.data(), 2 * np + 1);
-      uint64_t A = 0;
-      {
-        AlnKeys keys;
-        fm_align_seeds(f, rd.pat.p, rd.off.p + 2 * p0, 2 * np, min_seed, k, 0, len.p, pos.p, g_moff.p, goff[2 * np], g_aoff.p, keys);
-        A = keys.total;
-        g_start.alloc(c, A); g_end.alloc(c, A); g_dist.alloc(c, A);
-        fm_align_write(f, keys, g_start.p, g_end.p, g_dist.p);
-        sync(c);
-      }
-      // the group's results: nhits, off, start, tlen (np each) and npairs (np / 2); the single-end MAPQ, mapped, rescued, mapq,
-      // strand, dist (np each) and proper (np / 2)
-      DBuf<uint64_t> d_hoff(c, np + 1), d_u64(c, 4 * np + np / 2), d_coff(c, np + 1), d_mdoff(c, np + 1);
-      DBuf<uint8_t> d_u8(c, 6 * np + np / 2), d_md;
-      DBuf<uint32_t> d_seq(c, np), d_cig;
-      uint64_t *d_nh = d_u64.p, *d_off = d_nh + np, *d_start = d_off + np, *d_tlen = d_start + np, *d_npairs = d_tlen + np;
-      uint8_t *d_smapq = d_u8.p, *d_mapped = d_smapq + np, *d_resc = d_mapped + np, *d_mapq = d_resc + np, *d_strand = d_mapq + np,
-              *d_dist = d_strand + np, *d_proper = d_dist + np;
-      MapSel sel;
-      fm_map_select(f, rd.off.p + 2 * p0, np, k, anchors - 1, g_aoff.p, g_start.p, g_end.p, g_dist.p, A, d_hoff.p, d_smapq, d_nh, sel);
-      g_start.release(); g_end.release(); g_dist.release();
-      const PairOut out{d_proper, d_npairs, d_mapped, d_resc, d_mapq, d_strand, d_seq.p, d_off, d_start, d_dist, (int64_t *)d_tlen, d_coff.p, d_mdoff.p};
-      fm_pair(f, rd.pat.p, rd.off.p + 2 * p0, np, k, min_ins, max_ins, anchors, g_aoff.p, d_hoff.p, d_smapq, sel, out, d_cig, d_md);
-      d2h(c, proper + q0, d_proper, np / 2); d2h(c, npairs + q0, d_npairs, np / 2);
-      d2h(c, mapped + p0, d_mapped, np); d2h(c, rescued + p0, d_resc, np); d2h(c, mapq + p0, d_mapq, np); d2h(c, nhits + p0, d_nh, np);
-      d2h(c, strand + p0, d_strand, np); d2h(c, seq + p0, d_seq.p, np); d2h(c, off + p0, d_off, np); d2h(c, start + p0, d_start, np);
-      d2h(c, dist + p0, d_dist, np); d2h(c, (uint64_t *)tlen + p0, d_tlen, np);
-      // the group's script and MD offsets go behind the call's, counted from the call's first run and byte
-      const uint64_t c0 = cig_off[p0], m0 = md_off[p0];
-      d2h(c, cig_off + p0 + 1, d_coff.p + 1, np); d2h(c, md_off + p0 + 1, d_mdoff.p + 1, np);
-      sync(c);
-      for (uint64_t i = 1; i <= np; i++) { cig_off[p0 + i] += c0; md_off[p0 + i] += m0; }
-      h_cig.take(c, d_cig.p, cig_off[p0 + np] - c0);
-      h_md.take(c, d_md.p, md_off[p0 + np] - m0);
-    }
-  }
+  seed_groups(fm, s, 4, 0, false, [&](uint64_t pat0, uint64_t np2, MapCands &cd) {      // groups of WHOLE pairs
+    const uint64_t p0 = pat0 / 2, np = np2 / 2, q0 = p0 / 2;                            // the group's reads, its first pair
+    // the group's results: nhits, off, start, tlen (np each) and npairs (np / 2); the single-end MAPQ, mapped, rescued, mapq,
+    // strand, dist (np each) and proper (np / 2)
+    DBuf<uint64_t> d_hoff(c, np + 1), d_u64(c, 4 * np + np / 2), d_coff(c, np + 1), d_mdoff(c, np + 1);
+    DBuf<uint8_t> d_u8(c, 6 * np + np / 2), d_md;
+    DBuf<uint32_t> d_seq(c, np), d_cig;
+    uint64_t *d_nh = d_u64.p, *d_off = d_nh + np, *d_start = d_off + np, *d_tlen = d_start + np, *d_npairs = d_tlen + np;
+    uint8_t *d_smapq = d_u8.p, *d_mapped = d_smapq + np, *d_resc = d_mapped + np, *d_mapq = d_resc + np, *d_strand = d_mapq + np,
+            *d_dist = d_strand + np, *d_proper = d_dist + np;
+    MapSel sel;
+    fm_map_select(f, s.off + pat0, np, k, anchors - 1, cd, d_hoff.p, d_smapq, d_nh, sel);
+    cd.drop_triples();
+    const PairOut out{d_proper, d_npairs, d_mapped, d_resc, d_mapq, d_strand, d_seq.p, d_off, d_start, d_dist, (int64_t *)d_tlen, d_coff.p, d_mdoff.p};
+    fm_pair(f, s.pat, s.off + pat0, np, k, min_ins, max_ins, anchors, cd.aln_off.p, d_hoff.p, d_smapq, sel, out, d_cig, d_md);
+    d2h(c, proper + q0, d_proper, np / 2); d2h(c, npairs + q0, d_npairs, np / 2);
+    d2h(c, mapped + p0, d_mapped, np); d2h(c, rescued + p0, d_resc, np); d2h(c, mapq + p0, d_mapq, np); d2h(c, nhits + p0, d_nh, np);
+    d2h(c, strand + p0, d_strand, np); d2h(c, seq + p0, d_seq.p, np); d2h(c, off + p0, d_off, np); d2h(c, start + p0, d_start, np);
+    d2h(c, dist + p0, d_dist, np); d2h(c, (uint64_t *)tlen + p0, d_tlen, np);
+    // (one wait for all of the group's arrays, the two offset arrays among them, so not fetch_group_offsets, which waits per array)
+    d2h(c, cig_off + p0 + 1, d_coff.p + 1, np); d2h(c, md_off + p0 + 1, d_mdoff.p + 1, np);
+    sync(c);
+    rebase_offsets(cig_off + p0 + 1, np, cig_off[p0]);
+    rebase_offsets(md_off + p0 + 1, np, md_off[p0]);
+    h_cig.take(c, d_cig.p, cig_off[p0 + np] - cig_off[p0]);
+    h_md.take(c, d_md.p, md_off[p0 + np] - md_off[p0]);
+  });
   *cig = h_cig.release(); *md = h_md.release();
   return PFP_OK;
   PFP_CATCH(c)

@@ -229,6 +229,12 @@ void fm_extend_check(const FmIndex &f, int k) {
   PFP_REQUIRE(f.has_text, PFP_EINVAL, "extending seeds needs the text: build the index with pfp_fm_build_ms_dev / pfp_fm_build_ms_files");
 }
 
+void fm_align_check(const FmIndex &f, int k, uint64_t min_seed, bool thresholds) {
+  fm_extend_check(f, k);
+  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
+  PFP_REQUIRE(!thresholds || f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
+}
+
 void fm_extend_check_patterns(FmIndex &f, const uint64_t *pat_off, uint64_t npat) {
   pfp_ctx *c = f.c;
   if (!npat) return;
@@ -269,8 +275,7 @@ void fm_extend(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t
 void fm_align_seeds(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
                     const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, uint64_t *aln_off, AlnKeys &out) {
   pfp_ctx *c = f.c;
-  fm_extend_check(f, k);
-  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
+  fm_align_check(f, k, min_seed, false);
   require_sortable(M, "seeds");
   out.C = out.total = 0;
   if (!M || !npat) {
@@ -332,9 +337,7 @@ void fm_align_write(FmIndex &f, const AlnKeys &keys, uint64_t *start, uint64_t *
 void fm_align_keys(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln, bool thresholds,
                    uint64_t *aln_off, AlnKeys &keys) {
   pfp_ctx *c = f.c;
-  fm_extend_check(f, k);
-  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
-  PFP_REQUIRE(!thresholds || f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
+  fm_align_check(f, k, min_seed, thresholds);
   fm_extend_check_patterns(f, pat_off, npat);
   const uint64_t bytes = npat ? read_scalar(c, pat_off + npat) : 0;
   DBuf<uint32_t> len(c, bytes + 1);

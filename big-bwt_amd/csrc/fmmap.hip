@@ -229,10 +229,9 @@ __global__ void __launch_bounds__(kTB) map_md_k(const uint8_t *__restrict__ text
 }  // namespace
 
 void fm_map_check(const FmIndex &f, int k, uint64_t min_seed, bool thresholds) {
-  fm_extend_check(f, k);
+  fm_extend_check(f, k);                                // (k and the text come before the table, min_seed and the thresholds behind it)
   PFP_REQUIRE(f.nseq, PFP_EINVAL, "this index has no sequence table: give it one with pfp_fm_set_seqs (bigbwt -f --seqs writes it)");
-  PFP_REQUIRE(min_seed >= 1, PFP_EINVAL, "min_seed = 0: a seed is a maximal exact match of at least 1 byte");
-  PFP_REQUIRE(!thresholds || f.has_thr, PFP_EINVAL, "this index has no thresholds: add them with pfp_fm_thresholds_dev / pfp_fm_thresholds_files");
+  fm_align_check(f, k, min_seed, thresholds);
 }
 
 void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out) {
@@ -256,9 +255,33 @@ void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uin
   PFP_HIP(hipGetLastError());
 }
 
-void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, uint64_t max_sec, const uint64_t *aln_off, const uint64_t *start,
-                   const uint64_t *end, const uint8_t *dist, uint64_t A, uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, MapSel &sel) {
+// the end of both ways to the candidates: room for the kept alignments, the triples, and the wait that lets the keys go
+static void cands_write(FmIndex &f, const AlnKeys &keys, bool wait, MapCands &out) {
+  out.A = keys.total;
+  out.start.alloc(f.c, out.A); out.end.alloc(f.c, out.A); out.dist.alloc(f.c, out.A);
+  fm_align_write(f, keys, out.start.p, out.end.p, out.dist.p);
+  if (wait) sync(f.c);
+}
+
+void fm_map_cands(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat2, uint64_t min_seed, int k, bool thresholds, MapCands &out) {
+  out.aln_off.alloc(f.c, npat2 + 1);
+  AlnKeys keys;
+  fm_align_keys(f, pat2, pat2_off, npat2, min_seed, k, 0, thresholds, out.aln_off.p, keys);
+  cands_write(f, keys, true, out);                      // (the keys go back when this returns)
+}
+
+void fm_map_cands_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                     const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, MapCands &out, AlnKeys *held) {
+  out.aln_off.alloc(f.c, npat + 1);
+  AlnKeys own, &keys = held ? *held : own;
+  fm_align_seeds(f, pat, pat_off, npat, min_seed, k, max_aln, len, pos, mem_off, M, out.aln_off.p, keys);
+  cands_write(f, keys, !held, out);
+}
+
+void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, uint64_t max_sec, const MapCands &cd, uint64_t *hit_off, uint8_t *mapq,
+                   uint64_t *nhits, MapSel &sel) {
   pfp_ctx *c = f.c;
+  const uint64_t A = cd.A;
   require_sortable(A, "alignments");
   sel.H = 0;
   if (!npat) {
@@ -271,12 +294,13 @@ void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, u
   sel.key.alloc(c, A);
   {
     KScope ks(c, "fm_map_inside", 0);
-    map_bounds_k<<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(aln_off, npat, sb.p, se.p);
+    map_bounds_k<<<gdim(cdiv(npat, kTB)), kTB, 0, c->stream>>>(cd.aln_off.p, npat, sb.p, se.p);
     PFP_HIP(hipGetLastError());
     if (A) {
       by_width(f, [&](auto w) {
         using I = decltype(w);
-        map_inside_k<I><<<gdim(cdiv(A, kTB)), kTB, 0, c->stream>>>(seq_args<I>(f), aln_off, npat, start, end, dist, A, read.p, key.p);
+        map_inside_k<I><<<gdim(cdiv(A, kTB)), kTB, 0, c->stream>>>(seq_args<I>(f), cd.aln_off.p, npat, cd.start.p, cd.end.p, cd.dist.p, A, read.p,
+                                                                   key.p);
       });
       PFP_HIP(hipGetLastError());
     }
@@ -349,26 +373,16 @@ void fm_map_scripts(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, u
 void fm_map(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, bool thresholds,
             uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist,
             uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md) {
-  pfp_ctx *c = f.c;
   fm_map_check(f, k, min_seed, thresholds);
   MapReads rd;
   fm_map_strands(f, pat, pat_off, npat, rd);
-  DBuf<uint64_t> aln_off(c, 2 * npat + 1), a_start, a_end;
-  DBuf<uint8_t> a_dist;
-  uint64_t A = 0;
-  {
-    AlnKeys keys;
-    fm_align_keys(f, rd.pat.p, rd.off.p, 2 * npat, min_seed, k, 0, thresholds, aln_off.p, keys);
-    A = keys.total;
-    a_start.alloc(c, A); a_end.alloc(c, A); a_dist.alloc(c, A);
-    fm_align_write(f, keys, a_start.p, a_end.p, a_dist.p);
-    sync(c);                                            // (the keys go back when this block ends)
-  }
+  MapCands cd;
+  fm_map_cands(f, rd.pat.p, rd.off.p, 2 * npat, min_seed, k, thresholds, cd);
   MapSel sel;
-  fm_map_select(f, rd.off.p, npat, k, max_sec, aln_off.p, a_start.p, a_end.p, a_dist.p, A, hit_off, mapq, nhits, sel);
-  a_start.release(); a_end.release(); a_dist.release();
-  if (strand) fm_map_fill(f, rd.pat.p, rd.off.p, npat, k, aln_off.p, hit_off, sel, strand, seq, off, start, dist, cig_off, cig, md_off, md);
-  sync(c);
+  fm_map_select(f, rd.off.p, npat, k, max_sec, cd, hit_off, mapq, nhits, sel);
+  cd.drop_triples();
+  if (strand) fm_map_fill(f, rd.pat.p, rd.off.p, npat, k, cd.aln_off.p, hit_off, sel, strand, seq, off, start, dist, cig_off, cig, md_off, md);
+  sync(f.c);
 }
 
 }  // namespace pfp

@@ -246,21 +246,14 @@ void fm_map_pairs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint6
   fm_pair_check(f, npat, k, min_seed, thresholds, min_ins, max_ins, anchors);
   MapReads rd;
   fm_map_strands(f, pat, pat_off, npat, rd);
-  DBuf<uint64_t> aln_off(c, 2 * npat + 1), hit_off(c, npat + 1), a_start, a_end;
-  DBuf<uint8_t> a_dist, smapq(c, npat);
-  uint64_t A = 0;
-  {
-    AlnKeys keys;
-    fm_align_keys(f, rd.pat.p, rd.off.p, 2 * npat, min_seed, k, 0, thresholds, aln_off.p, keys);
-    A = keys.total;
-    a_start.alloc(c, A); a_end.alloc(c, A); a_dist.alloc(c, A);
-    fm_align_write(f, keys, a_start.p, a_end.p, a_dist.p);
-    sync(c);                                            // (the keys go back when this block ends)
-  }
+  DBuf<uint64_t> hit_off(c, npat + 1);
+  DBuf<uint8_t> smapq(c, npat);
+  MapCands cd;
+  fm_map_cands(f, rd.pat.p, rd.off.p, 2 * npat, min_seed, k, thresholds, cd);
   MapSel sel;
-  fm_map_select(f, rd.off.p, npat, k, anchors - 1, aln_off.p, a_start.p, a_end.p, a_dist.p, A, hit_off.p, smapq.p, nhits, sel);
-  a_start.release(); a_end.release(); a_dist.release();
-  fm_pair(f, rd.pat.p, rd.off.p, npat, k, min_ins, max_ins, anchors, aln_off.p, hit_off.p, smapq.p, sel, out, cig, md);
+  fm_map_select(f, rd.off.p, npat, k, anchors - 1, cd, hit_off.p, smapq.p, nhits, sel);
+  cd.drop_triples();
+  fm_pair(f, rd.pat.p, rd.off.p, npat, k, min_ins, max_ins, anchors, cd.aln_off.p, hit_off.p, smapq.p, sel, out, cig, md);
   sync(c);
 }
 

@@ -438,6 +438,8 @@ uint64_t fm_approx_positions(FmIndex &f, uint64_t H, const uint64_t *sp, const u
 // extending seeds (fmextend.hip; pfpgpu.h, "Extending seeds", states the definitions).  Device pointers.  k outside 0 ..
 // PFP_FM_EXTEND_MAX_K or an index without text -> PFP_EINVAL; a pattern longer than PFP_FM_EXTEND_MAX_M -> PFP_ELIMIT
 void fm_extend_check(const FmIndex &f, int k);
+// fm_extend_check, then what seeding asks: min_seed = 0, or thresholds wanted of an index without them -> PFP_EINVAL
+void fm_align_check(const FmIndex &f, int k, uint64_t min_seed, bool thresholds);
 // candidate i = (cand_pat[i], cand_diag[i]) -> (dist[i], start[i], end[i]); 0xFF and UINT64_MAX twice where nothing aligns
 void fm_extend(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *cand_pat, const int64_t *cand_diag,
                uint64_t ncand, int k, uint8_t *dist, uint64_t *start, uint64_t *end);
@@ -493,16 +495,29 @@ struct MapReads {
   DBuf<uint64_t> off;
 };
 void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out);
+// the candidates of some patterns, as fm_align gives them: aln_off (one entry more than the patterns) and the A = aln_off[last]
+// triples start / end / dist.  The triples serve fm_map_select alone: its callers drop them before they fill or pair
+struct MapCands {
+  DBuf<uint64_t> aln_off, start, end;
+  DBuf<uint8_t> dist;
+  uint64_t A = 0;
+  void drop_triples() { start.release(); end.release(); dist.release(); }
+};
+// the candidates of npat2 patterns, every alignment kept: fm_align_keys, then the triples, then a wait (the keys are gone after it)
+void fm_map_cands(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat2, uint64_t min_seed, int k, bool thresholds, MapCands &out);
+// the same from what fm_align_seeds takes (a group of a call whose matching statistics stand, and the group's MEM offsets).
+// held: the caller keeps the keys and waits for the stream itself before they go
+void fm_map_cands_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_aln,
+                     const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, MapCands &out, AlnKeys *held = nullptr);
 // what fm_map_select leaves for fm_map_fill: the candidates' keys (d, strand, s, e - s), sorted inside every read's segment with
 // the hits first, and the number of hits returned
 struct MapSel {
   DBuf<uint64_t> key;
   uint64_t H = 0;
 };
-// from the alignments of the 2 npat patterns (aln_off[0 .. 2 npat] and the A = aln_off[2 npat] triples, as fm_align gave them):
-// inside, shadowing, order and cap -> hit_off[0 .. npat], mapq[npat], nhits[npat]
-void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, uint64_t max_sec, const uint64_t *aln_off, const uint64_t *start,
-                   const uint64_t *end, const uint8_t *dist, uint64_t A, uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, MapSel &sel);
+// from the candidates of the 2 npat patterns: inside, shadowing, order and cap -> hit_off[0 .. npat], mapq[npat], nhits[npat]
+void fm_map_select(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, int k, uint64_t max_sec, const MapCands &cd, uint64_t *hit_off, uint8_t *mapq,
+                   uint64_t *nhits, MapSel &sel);
 // the sel.H returned hits: strand, seq, off, start, dist (room for sel.H each), cig_off / md_off (sel.H + 1 each); cig and md are
 // allocated here once their sizes are known
 void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat, int k, const uint64_t *aln_off, const uint64_t *hit_off,
@@ -513,8 +528,7 @@ void fm_map_fill(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint
 // no alignment (aln_pat[h] >= npat2) gets no runs and an empty MD
 void fm_map_scripts(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat2, int k, const uint32_t *aln_pat, const uint64_t *start,
                     const uint64_t *end, uint64_t H, uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
-// all of it over device patterns: fm_map_strands, fm_align_keys on the 2 npat patterns, fm_map_select and, where strand is given,
-// fm_map_fill
+// all of it over device patterns: fm_map_strands, fm_map_cands, fm_map_select and, where strand is given, fm_map_fill
 void fm_map(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, uint64_t max_sec, bool thresholds,
             uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist,
             uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
@@ -534,7 +548,7 @@ struct PairOut {
 void fm_pair(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t nread, int k, uint64_t min_ins, uint64_t max_ins, uint64_t C,
              const uint64_t *aln_off, const uint64_t *hit_off, const uint8_t *smapq, const MapSel &sel, const PairOut &out, DBuf<uint32_t> &cig,
              DBuf<uint8_t> &md);
-// all of it over device patterns: fm_pair_check, fm_map_strands, fm_align_keys, fm_map_select and fm_pair; nhits[npat]
+// all of it over device patterns: fm_pair_check, fm_map_strands, fm_map_cands, fm_map_select and fm_pair; nhits[npat]
 void fm_map_pairs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, int k, bool thresholds, uint64_t min_ins,
                   uint64_t max_ins, uint64_t anchors, uint64_t *nhits, const PairOut &out, DBuf<uint32_t> &cig, DBuf<uint8_t> &md);
 

@@ -1,8 +1,11 @@
 """The calls of FmIndex that take host patterns (csrc/api_fm.hip: one upload of the patterns, one budget, one rule that cuts a
 call into groups of patterns), on one small input that makes every one of them work in several groups under a small
-PFP_FM_SEQ_BUDGET.  tests/test_fm_host_calls.py asserts the answers; tests/README.md has the note.
+PFP_FM_SEQ_BUDGET.  Mapping reads and pairs run on inputs of their own tests instead, which those tests show to have hits,
+secondary hits, rescues and groups: the reads of map_cases over `copies`, the pairs of pair_cases over `dna`.
+tests/test_fm_host_calls.py asserts the answers; tests/README.md has the note.
 
-As a program it runs every call (or the named ones) under every environment and prints one JSON line per (call, environment):
+As a program it runs every call (or the named ones) without a budget and under its budgets and prints one JSON line per (call,
+environment):
 
     PFP_TRACE_HOST=1 python tests/fm_host_cases.py [CALL ...]
     {"call": "locate", "env": {"PFP_FM_SEQ_BUDGET": "7"}, "launches": {"pfp::fm_count_kernel": [1, 0], ...}, "peak": 123456,
@@ -14,6 +17,7 @@ bytes of each), `waits` the host waits on the stream over the context's life as 
 when the context goes (null without it).  "<call>/empty" is the call without patterns.  Nothing is compared with a reference
 here: two builds that print the same lines launch, wait, allocate and answer alike.
 """
+import collections
 import functools
 import hashlib
 import json
@@ -29,9 +33,14 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-ENVS = ({}, {"PFP_FM_SEQ_BUDGET": "1"}, {"PFP_FM_SEQ_BUDGET": "7"})      # no groups; every pattern alone; some groups
+import map_cases  # noqa: E402
+import pair_cases  # noqa: E402
+
+BUDGETS = ("1", "7")      # every pattern alone; some groups
 K_MISMATCH, K_EDIT, MIN_SEED, MIN_MEM = 1, 2, 6, 4
 SEG_COPIES, NPARTS = 12, 8
+K_CAP, CAP_SEED = 16, 4      # align_cap: edits and seeds at which several patterns have more alignments than max_aln = 2 keeps
+K_MAP, MAP_MIN_SEED, MAP_MAX_SEC = 8, 12, 2     # as test_fm_map.py maps the reads of (`copies`, `records`, 8)
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,39 +95,84 @@ def candidates():
     return np.array(cp, dtype=np.uint32), np.array(cd, dtype=np.int64)
 
 
-# name -> (needs thresholds, call(fm, patterns) -> the tuple of arrays it returns)
+@functools.lru_cache(maxsize=None)
+def windows():
+    """(cand_pat uint32, lo uint64, hi uint64) for window: per candidate of candidates() a window that starts 3 bytes before its
+    diagonal and ends 3 bytes behind the pattern's length from there, or 2 bytes short of it"""
+    n = len(text_and_segment()[0])
+    cp, cd = candidates()
+    lo, hi = [], []
+    for p, dg in zip(cp.tolist(), cd.tolist()):
+        m = len(patterns()[p])
+        a = min(max(dg, 0), n)
+        lo.append(max(a - 3, 0))
+        hi.append(max(min(a + m + (3 if dg % 2 else -2), n), lo[-1]))
+    return cp, np.array(lo, dtype=np.uint64), np.array(hi, dtype=np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def spans():
+    """(aln_pat uint32, start uint64, end uint64) for cigar: every non-empty pattern against a span of its length at the place
+    of its first 8 bytes, one byte further, and elsewhere"""
+    n = len(text_and_segment()[0])
+    cp, cd = candidates()
+    st = np.clip(cd, 0, n)
+    en = np.array([min(s + len(patterns()[p]), n) for p, s in zip(cp.tolist(), st.tolist())], dtype=np.uint64)
+    return cp, st.astype(np.uint64), en
+
+
+def _or_none(arrays, P):
+    """the arrays that go with the patterns, or empty ones of their types for the call without patterns"""
+    return arrays if P else tuple(a[:0] for a in arrays)
+
+
+# What a call needs and gives.  thresholds: the index gets them; run(fm, patterns) -> the tuple of arrays the call returns; index: which
+# text it runs on ("text": this module's, with patterns(); else a text of map_cases with its `records` table and the reads INPUTS
+# names); offsets: which of the returned arrays are offsets ([0] without patterns, where every other array is empty); budgets: the
+# values of PFP_FM_SEQ_BUDGET that cut it into groups
+Call = collections.namedtuple("Call", "thresholds run index offsets budgets", defaults=("text", (0,), BUDGETS))
+_map = lambda fm, P, **kw: fm.map_reads(P, K_MAP, MAP_MIN_SEED, MAP_MAX_SEC, **kw)
 CALLS = {
-    "count": (False, lambda fm, P: fm.count(P)),
-    "count_toehold": (False, lambda fm, P: fm.count(P, toehold=True)),
-    "locate": (False, lambda fm, P: fm.locate(P, ranges=True)),
-    "approx": (False, lambda fm, P: fm.approx(P, K_MISMATCH, toehold=True)),
-    "approx_locate": (False, lambda fm, P: fm.approx_locate(P, K_MISMATCH)),
-    "ms": (False, lambda fm, P: fm.matching_statistics(P)),
-    "ms_thr": (True, lambda fm, P: fm.matching_statistics(P, thresholds=True)),
-    "mems": (False, lambda fm, P: fm.mems(P, MIN_MEM)),
-    "mems_thr": (True, lambda fm, P: fm.mems(P, MIN_MEM, thresholds=True)),
-    "extend": (False, lambda fm, P: fm.extend(P, *(candidates() if P else (np.zeros(0, np.uint32), np.zeros(0, np.int64))), K_EDIT)),
-    "align": (False, lambda fm, P: fm.align(P, K_EDIT, MIN_SEED)),
-    "align_thr": (True, lambda fm, P: fm.align(P, K_EDIT, MIN_SEED, thresholds=True)),
-    "locate_seqs": (False, lambda fm, P: fm.locate_seqs(P, ranges=True)),
-    "doclist": (False, lambda fm, P: fm.doclist(P)),
+    "count": Call(False, lambda fm, P: fm.count(P), offsets=()),
+    "count_toehold": Call(False, lambda fm, P: fm.count(P, toehold=True), offsets=()),
+    "locate": Call(False, lambda fm, P: fm.locate(P, ranges=True)),
+    "approx": Call(False, lambda fm, P: fm.approx(P, K_MISMATCH, toehold=True)),
+    "approx_locate": Call(False, lambda fm, P: fm.approx_locate(P, K_MISMATCH)),
+    "ms": Call(False, lambda fm, P: fm.matching_statistics(P)),
+    "ms_thr": Call(True, lambda fm, P: fm.matching_statistics(P, thresholds=True)),
+    "mems": Call(False, lambda fm, P: fm.mems(P, MIN_MEM)),
+    "mems_thr": Call(True, lambda fm, P: fm.mems(P, MIN_MEM, thresholds=True)),
+    "extend": Call(False, lambda fm, P: fm.extend(P, *_or_none(candidates(), P), K_EDIT), offsets=()),
+    "align": Call(False, lambda fm, P: fm.align(P, K_EDIT, MIN_SEED)),
+    "align_thr": Call(True, lambda fm, P: fm.align(P, K_EDIT, MIN_SEED, thresholds=True)),
+    "locate_seqs": Call(False, lambda fm, P: fm.locate_seqs(P, ranges=True)),
+    "doclist": Call(False, lambda fm, P: fm.doclist(P)),
+    "window": Call(False, lambda fm, P: fm.window(P, *_or_none(windows(), P), K_EDIT), offsets=()),
+    "cigar": Call(False, lambda fm, P: fm.cigar(P, *_or_none(spans(), P), K_EDIT), offsets=(1,)),
+    "align_cap": Call(False, lambda fm, P: fm.align(P, K_CAP, CAP_SEED, max_aln=2)),
+    "map": Call(False, _map, "copies", (0, 8, 10), ("1", "40")),
+    "map_thr": Call(True, lambda fm, P: _map(fm, P, thresholds=True), "copies", (0, 8, 10), ("1", "40")),
+    "map_pairs": Call(False, lambda fm, P: fm.map_pairs(P, K_MAP, pair_cases.MIN_SEED, pair_cases.MIN_INS, pair_cases.MAX_INS), "dna", (12, 14),
+                      ("1", "9")),
 }
+INPUTS = {"text": patterns, "copies": lambda: map_cases.reads_of("copies", "records", K_MAP), "dna": lambda: pair_cases.reads_of("dna")}
 
-_parts = []
+_parts = {}
 
 
-def index_of(O, pkg, ctx, thresholds=False):
-    """an index with text, samples and the sequence table over the text (the BWT and the samples are computed once)"""
-    text = text_and_segment()[0]
-    if not _parts:
+def index_of(O, pkg, ctx, thresholds=False, index="text"):
+    """an index with text, samples and a sequence table (the BWT and the samples are computed once per text): this module's text
+    and seq_starts(), or a text of map_cases with its `records` table"""
+    text = text_and_segment()[0] if index == "text" else map_cases.text_of(index)
+    if index not in _parts:
         bwt = np.asarray(O.simplebwt(text))
         sa = np.concatenate([[len(text)], np.asarray(O.sacak(text), dtype=np.int64)]).astype(np.int64)
         starts = np.flatnonzero(np.concatenate([[True], bwt[1:] != bwt[:-1]]))
         ends = np.flatnonzero(np.concatenate([bwt[1:] != bwt[:-1], [True]]))
         pk = lambda rows: pkg.pack5(np.stack([rows, sa[rows]], axis=1).reshape(-1).astype(np.uint64))
-        _parts.extend((bwt, pk(starts), pk(ends)))
-    fm = ctx.fm_index_ms(*_parts, text)
-    fm.set_sequences(seq_starts())
+        _parts[index] = (bwt, pk(starts), pk(ends))
+    fm = ctx.fm_index_ms(*_parts[index], text)
+    fm.set_sequences(seq_starts() if index == "text" else map_cases.starts_of(index, "records"))
     if thresholds:
         fm.add_thresholds()
     return fm
@@ -168,12 +222,12 @@ def _close_and_count_waits(ctx):
 
 def run_case(pkg, O, name, env, empty=False):
     """one host call in a context of its own; returns the record that main() prints"""
-    thresholds, call = CALLS[name]
+    call = CALLS[name]
     ctx = pkg.Context(0)
     try:
-        with index_of(O, pkg, ctx, thresholds) as fm, Env(env):
+        with index_of(O, pkg, ctx, call.thresholds, call.index) as fm, Env(env):
             ctx.set_kernel_trace(True)
-            out = call(fm, [] if empty else list(patterns()))
+            out = call.run(fm, [] if empty else list(INPUTS[call.index]()))
             rows = {r["name"]: [r["launches"], r["algo_bytes"]] for r in ctx.kernel_trace()}
             ctx.set_kernel_trace(False)
         peak = ctx.mem_stats()["peak"]
@@ -196,7 +250,8 @@ def main(argv):
     pkg = entry.load_package()
     O = entry.load_oracle()
     for name in names:
-        for env, empty in [(e, False) for e in ENVS] + [({}, True)]:
+        envs = [{}] + [{"PFP_FM_SEQ_BUDGET": b} for b in CALLS[name].budgets]
+        for env, empty in [(e, False) for e in envs] + [({}, True)]:
             try:      # an error of the library (a GPU fault among them): nothing more is started
                 rec = run_case(pkg, O, name, env, empty)
             except Exception as ex:

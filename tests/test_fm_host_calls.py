@@ -1,6 +1,7 @@
 """The calls of FmIndex over host patterns (csrc/api_fm.hip) on the inputs of fm_host_cases.py: what a call returns does not
 depend on how PFP_FM_SEQ_BUDGET cuts it into groups of patterns - 1: every pattern alone, 7: some groups, the repeated segment
-alone - and equals what the *_dev methods, which never group, give for the same patterns on device arrays."""
+alone - and equals what the *_dev methods, which never group, give for the same patterns on device arrays.  Mapping reads and
+pairs run on the reads and the index their entry in fm_host_cases.CALLS names, under that entry's budgets."""
 import numpy as np
 import pytest
 
@@ -10,19 +11,33 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def fm(O, pkg, ctx):
-    with H.index_of(O, pkg, ctx, thresholds=True) as f:
-        yield f
+def fm_of(O, pkg, ctx):
+    """index name -> that index with thresholds, built when first asked for"""
+    made = {}
+
+    def get(index):
+        if index not in made:
+            made[index] = H.index_of(O, pkg, ctx, thresholds=True, index=index)
+        return made[index]
+
+    yield get
+    for f in made.values():
+        f.close()
+
+
+@pytest.fixture(scope="module")
+def fm(fm_of):
+    return fm_of("text")
 
 
 _plain = {}
 
 
 def plain(fm, name):
-    """the call without a budget, once"""
+    """the call without a budget, once (fm: the index the call's entry names)"""
     if name not in _plain:
         with H.Env({}):
-            _plain[name] = H.CALLS[name][1](fm, list(H.patterns()))
+            _plain[name] = H.CALLS[name].run(fm, list(H.INPUTS[H.CALLS[name].index]()))
     return _plain[name]
 
 
@@ -43,23 +58,43 @@ def test_the_inputs_make_groups():
     assert sum(text.tobytes().count(p) == 0 for p in P if p) >= 5
 
 
-@pytest.mark.parametrize("budget", ["1", "7"])
-@pytest.mark.parametrize("name", list(H.CALLS))
-def test_groups_do_not_change_the_answer(fm, name, budget):
-    want = plain(fm, name)
-    with H.Env({"PFP_FM_SEQ_BUDGET": budget}):
-        same(H.CALLS[name][1](fm, list(H.patterns())), want, (name, budget))
+def test_the_calls_name_their_offsets():
+    """the fourteen calls of the first consolidation: offsets first (for ms the patterns' own), none from count and extend"""
+    first, none = "locate approx approx_locate ms ms_thr mems mems_thr align align_thr locate_seqs doclist".split(), "count count_toehold extend".split()
+    assert all(H.CALLS[n].offsets == (0,) for n in first) and all(H.CALLS[n].offsets == () for n in none)
+    assert sorted(list(H.CALLS)[:14]) == sorted(first + none)
 
 
-@pytest.mark.parametrize("name", list(H.CALLS))
-def test_no_patterns(fm, name):
-    """offsets [0] from the calls that return offsets (first; for ms the patterns' own), and every other array empty"""
+def test_the_cap_cuts(fm):
+    """align_cap's max_aln = 2 is below what several patterns have: the capped call keeps the first two of each, in order"""
     with H.Env({}):
-        out = [np.asarray(a) for a in H.CALLS[name][1](fm, [])]
-    if name not in ("count", "count_toehold", "extend"):
-        assert out[0].tolist() == [0], name
-        out = out[1:]
-    assert out and all(a.size == 0 for a in out), (name, out)
+        off, start, end, dist = H.CALLS["align_cap"].run(fm, list(H.patterns()))
+        uoff, ustart, uend, udist = fm.align(list(H.patterns()), H.K_CAP, H.CAP_SEED)
+    per, uper = np.diff(off).astype(np.int64), np.diff(uoff).astype(np.int64)
+    assert (uper > 2).sum() >= 2 and np.array_equal(per, np.minimum(uper, 2))
+    keep = np.concatenate([np.arange(int(uoff[p]), int(uoff[p]) + int(per[p])) for p in range(len(per))]).astype(np.int64)
+    same([start, end, dist], [ustart[keep], uend[keep], udist[keep]], "align_cap")
+
+
+@pytest.mark.parametrize("name,budget", [(n, b) for b in H.BUDGETS + ("40", "9") for n in H.CALLS if b in H.CALLS[n].budgets])
+def test_groups_do_not_change_the_answer(fm_of, name, budget):
+    call = H.CALLS[name]
+    f = fm_of(call.index)
+    want = plain(f, name)
+    with H.Env({"PFP_FM_SEQ_BUDGET": budget}):
+        same(call.run(f, list(H.INPUTS[call.index]())), want, (name, budget))
+
+
+@pytest.mark.parametrize("name", list(H.CALLS))
+def test_no_patterns(fm_of, name):
+    """offsets [0] in the arrays the call's entry names as offsets, and every other array empty"""
+    call = H.CALLS[name]
+    with H.Env({}):
+        out = [np.asarray(a) for a in call.run(fm_of(call.index), [])]
+    for i in call.offsets:
+        assert out[i].tolist() == [0], (name, i)
+    rest = [a for i, a in enumerate(out) if i not in call.offsets]
+    assert rest and all(a.size == 0 for a in rest), (name, out)
 
 
 # ---------------------------------------------------------------- the same from the *_dev methods
