@@ -12,11 +12,14 @@ file formats byte for byte:
 
 Everything computes in hand-written HIP kernels on the MI355X; there is no CPU fallback: the
 import succeeds without a GPU (so that symbol checks can run), but creating a Context does not.
+abi.py declares the signature of every function of the library; the calls below pass plain values.
 """
 import ctypes as C
 import os
 
 import numpy as np
+
+from .abi import SIGNATURES, CheckResult, KernelStat, MultiStats, ScanReport, Stats, _BwtResult, _FmInfo, _ParseResult  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpfpgpu.so")
@@ -26,21 +29,7 @@ FLAG_SA, FLAG_SSA, FLAG_ESA = 1, 2, 4
 ERRORS = {0: "PFP_OK", -1: "PFP_EINVAL", -2: "PFP_ENODEV", -3: "PFP_EHIP", -4: "PFP_ECOLLISION",
           -5: "PFP_ELIMIT", -6: "PFP_EFORMAT", -7: "PFP_ENOMEM", -8: "PFP_ESHORT"}
 
-# every symbol include/pfpgpu.h declares
-SYMBOLS = ["pfp_device_count", "pfp_ctx_create", "pfp_ctx_destroy", "pfp_last_error", "pfp_strerror", "pfp_version", "pfp_ctx_stream",
-           "pfp_free", "pfp_debug_check", "pfp_get_mem_stats", "pfp_get_pool_counters", "pfp_pool_trim", "pfp_scan", "pfp_parse", "pfp_parse_result_free", "pfp_sacak_int", "pfp_sacak", "pfp_gsacak", "pfp_sacak_int64", "pfp_sacak64", "pfp_gsacak64", "pfp_gsacak_lcp_da", "pfp_gsacak_lcp_da64",
-           "pfp_bwtparse", "pfp_merge", "pfp_bwt_result_free", "pfp_bigbwt", "pfp_bigbwt_files", "pfp_bigbwt_dev", "pfp_bigbwt_formats_dev", "pfp_dev_free", "pfp_memcpy_d2h", "pfp_pack5_dev", "pfp_sample_runs_dev", "pfp_pwrite_dev", "pfp_get_stats",
-           "pfp_set_profiling", "pfp_set_kernel_trace", "pfp_get_kernel_trace", "pfp_set_max_phrase", "pfp_set_window_hash", "pfp_set_parse_density", "pfp_debug_msd_sort", "pfp_debug_lib_sort", "pfp_debug_scan_chain", "pfp_dist_parse_plan", "pfp_dist_propose_triggers2", "pfp_dist_decide_density", "pfp_dist_local_parse2", "pfp_bigbwt_fd", "pfp_multi_rccl_selftest", "pfp_multi_rccl_selftest2", "pfp_set_index_bits", "pfp_stage_text_dev", "pfp_scan_staged", "pfp_scan_k1_enqueue",
-           "pfp_dist_propose_triggers", "pfp_dist_local_parse", "pfp_dist_export_local", "pfp_dist_global", "pfp_dist_global_sort", "pfp_dist_global_finish", "pfp_dist_partition_words", "pfp_dist_export_partition",
-           "pfp_dist_owner_dedup", "pfp_dist_export_owned", "pfp_dist_global_sort_distinct", "pfp_dist_merge", "pfp_dist_sample_runs", "pfp_dist_release", "pfp_bigbwt_files_multi", "pfp_dist_parse_sort", "pfp_dist_set_parse_sa",
-           "pfp_unbwt_dev", "pfp_unbwt", "pfp_check_bwt_dev", "pfp_check_bwt_files",
-           "pfp_fm_build_dev", "pfp_fm_build_files", "pfp_fm_count_dev", "pfp_fm_locate_dev", "pfp_fm_count", "pfp_fm_locate", "pfp_fm_info",
-           "pfp_fm_free", "pfp_fm_build_ms_dev", "pfp_fm_build_ms_files", "pfp_fm_ms_dev", "pfp_fm_mems_dev", "pfp_fm_ms", "pfp_fm_mems", "pfp_fm_ms_stats",
-           "pfp_lcp_dev", "pfp_lcp_files", "pfp_fm_thresholds_dev", "pfp_fm_thresholds_files", "pfp_fm_ms_thr_dev", "pfp_fm_ms_thr", "pfp_fm_mems_thr",
-           "pfp_fm_set_seqs", "pfp_fm_seqmap_dev", "pfp_fm_locate_seqs_dev", "pfp_fm_doclist_dev", "pfp_fm_locate_seqs", "pfp_fm_doclist",
-           "pfp_fm_approx_dev", "pfp_fm_approx", "pfp_fm_approx_locate", "pfp_fm_approx_stats",
-           "pfp_fm_extend_dev", "pfp_fm_extend", "pfp_fm_window_dev", "pfp_fm_window", "pfp_fm_align_dev", "pfp_fm_align", "pfp_fm_cigar_dev", "pfp_fm_cigar", "pfp_fm_map_dev", "pfp_fm_map",
-           "pfp_fm_map_pairs_dev", "pfp_fm_map_pairs"]
+SYMBOLS = list(SIGNATURES)      # every symbol include/pfpgpu.h declares
 
 FM_APPROX_MAX_K = 3
 FM_EXTEND_MAX_K, FM_EXTEND_MAX_M = 32, 65535
@@ -58,23 +47,6 @@ class PfpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERRORS.get(code, code)}: {msg}")
         self.code = code
-
-
-class CheckResult(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("text_mismatch", C.c_uint64), ("sa_mismatch", C.c_uint64), ("ssa_runs", C.c_uint64),
-                ("esa_runs", C.c_uint64), ("ssa_mismatch", C.c_uint64), ("esa_mismatch", C.c_uint64), ("ms", C.c_double)]
-
-    def as_dict(self):
-        """mismatch fields are None where the output is correct or was not checked (UINT64_MAX in the C struct)"""
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        for k in ("text_mismatch", "sa_mismatch", "ssa_mismatch", "esa_mismatch"):
-            d[k] = None if d[k] == 2**64 - 1 else int(d[k])
-        return d
-
-
-class _FmInfo(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("runs", C.c_uint64), ("sigma", C.c_uint32), ("row_bits", C.c_uint32), ("device_bytes", C.c_uint64),
-                ("has_samples", C.c_int), ("has_thresholds", C.c_int), ("nseq", C.c_uint64)]
 
 
 class _Seqs(C.Structure):
@@ -97,7 +69,7 @@ def read_seqs_file(path, n):
     host.pfp_seqs_free.argtypes = [C.POINTER(_Seqs)]
     host.pfp_seqs_free.restype = None
     t, err = _Seqs(), C.create_string_buffer(1024)
-    rc = host.pfp_seqs_read(os.fsencode(path), C.c_uint64(n), C.byref(t), err, len(err))
+    rc = host.pfp_seqs_read(os.fsencode(path), n, C.byref(t), err, len(err))
     if rc:
         raise PfpError(-1 if rc == -1 else -6, err.value.decode(errors="replace"))
     try:
@@ -129,23 +101,13 @@ def _patterns(patterns):
     return np.frombuffer(b"".join(parts) + b"\0", dtype=np.uint8), off
 
 
-def _vp(x):
-    """a device address as an argument; None (NULL) for an array that is not given"""
-    return C.c_void_p(x) if x else None
+def _addr(p):
+    """the address a pointer holds; None for NULL"""
+    return C.cast(p, C.c_void_p).value
 
 
-class FmIndex:
-    """Count and locate over a BWT and its run samples (pfp_fm, csrc/fmsearch.hip; the r-index of Gagie, Navarro and Prezza).
-    Made by Context.fm_index / fm_index_files; holds device memory of its context until close()."""
-
-    def __init__(self, ctx, handle):
-        self.ctx, self.lib, self._h = ctx, ctx.lib, handle
-
-    def close(self):
-        """hand the device memory back to the context (a context closed before leaves nothing to hand back)"""
-        if self._h and self.ctx._h:
-            self.lib.pfp_fm_free(self._h)
-        self._h = C.c_void_p()
+class _Closing:
+    """a handle of the library: the end of a with block and collection both close() it"""
 
     def __enter__(self):
         return self
@@ -159,12 +121,26 @@ class FmIndex:
         except Exception:
             pass
 
+
+class FmIndex(_Closing):
+    """Count and locate over a BWT and its run samples (pfp_fm, csrc/fmsearch.hip; the r-index of Gagie, Navarro and Prezza).
+    Made by Context.fm_index / fm_index_files; holds device memory of its context until close()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.lib, self._h = ctx, ctx.lib, handle
+
+    def close(self):
+        """hand the device memory back to the context (a context closed before leaves nothing to hand back)"""
+        if self._h and self.ctx._h:
+            self.lib.pfp_fm_free(self._h)
+        self._h = C.c_void_p()
+
     @staticmethod
     def _host_patterns(patterns):
         """-> (npat, the npat+1 offsets, the three leading arguments of a call over host patterns)"""
         pat, off = _patterns(patterns)
         npat = len(off) - 1
-        return npat, off, (_ptr(pat, C.c_uint8), _ptr(off, C.c_uint64), C.c_uint64(npat))
+        return npat, off, (pat, off, npat)
 
     def _take_free(self, ptr, n, dtype):
         """a copy of the n entries of a result array of the library, which goes back to it (pfp_free takes NULL)"""
@@ -182,8 +158,7 @@ class FmIndex:
         npat, _, args = self._host_patterns(patterns)
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         first = np.zeros(npat, dtype=np.uint64) if toehold else None
-        u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_count(self._h, *args, u64(sp), u64(ep), u64(first) if toehold else None))
+        self.ctx._check(self.lib.pfp_fm_count(self._h, *args, sp, ep, first))
         return (sp, ep, first) if toehold else (sp, ep)
 
     def locate(self, patterns, max_occ=0, ranges=False):
@@ -193,8 +168,7 @@ class FmIndex:
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         pos = C.POINTER(C.c_uint64)()
-        u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_locate(self._h, *args, C.c_uint64(max_occ), u64(sp), u64(ep), u64(out_off), C.byref(pos)))
+        self.ctx._check(self.lib.pfp_fm_locate(self._h, *args, max_occ, sp, ep, out_off, C.byref(pos)))
         positions = self._take_free(pos, out_off[-1], np.uint64)
         return (out_off, positions, sp, ep) if ranges else (out_off, positions)
 
@@ -206,7 +180,7 @@ class FmIndex:
         hit_off = np.zeros(npat + 1, dtype=np.uint64)
         sp, ep, first = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
         dist = C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_approx(self._h, *args, C.c_int(k), _ptr(hit_off, C.c_uint64), C.byref(sp), C.byref(ep),
+        self.ctx._check(self.lib.pfp_fm_approx(self._h, *args, k, hit_off, C.byref(sp), C.byref(ep),
                                                C.byref(first) if toehold else None, C.byref(dist)))
         total = hit_off[-1]
         out = hit_off, self._take_free(sp, total, np.uint64), self._take_free(ep, total, np.uint64), self._take_free(dist, total, np.uint8)
@@ -219,15 +193,13 @@ class FmIndex:
         npat, _, args = self._host_patterns(patterns)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         pos, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_approx_locate(self._h, *args, C.c_int(k), C.c_uint64(max_occ), _ptr(out_off, C.c_uint64),
-                                                      C.byref(pos), C.byref(dist)))
+        self.ctx._check(self.lib.pfp_fm_approx_locate(self._h, *args, k, max_occ, out_off, C.byref(pos), C.byref(dist)))
         return out_off, self._take_free(pos, out_off[-1], np.uint64), self._take_free(dist, out_off[-1], np.uint8)
 
     def approx_dev(self, d_pat, d_pat_off, npat, k, d_hit_off, d_sp=None, d_ep=None, d_dist=None, d_first=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_hit_off; d_sp / d_ep (uint64) and d_dist
         (uint8), room for d_hit_off[npat] each, get the hits (all three None: offsets only), d_first their toeholds"""
-        self.ctx._check(self.lib.pfp_fm_approx_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_int(k),
-                                                   C.c_void_p(d_hit_off), _vp(d_sp), _vp(d_ep), _vp(d_first), _vp(d_dist)))
+        self.ctx._check(self.lib.pfp_fm_approx_dev(self._h, d_pat, d_pat_off, npat, k, d_hit_off, d_sp, d_ep, d_first, d_dist))
 
     def approx_stats(self):
         """{launches, pairs, hits} of the approximate searches since the last look; pairs (LF pairs of the walks) are collected
@@ -248,16 +220,13 @@ class FmIndex:
             raise ValueError("cand_pat and cand_diag: two 1-D arrays of one length")
         nc = len(cp)
         dist, start, end = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
-        self.ctx._check(self.lib.pfp_fm_extend(self._h, *args, _ptr(cp, C.c_uint32), _ptr(cd, C.c_int64), C.c_uint64(nc), C.c_int(k),
-                                               _ptr(dist, C.c_uint8), _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
+        self.ctx._check(self.lib.pfp_fm_extend(self._h, *args, cp, cd, nc, k, dist, start, end))
         return dist, start, end
 
     def extend_dev(self, d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end):
         """device pointers: pattern bytes, npat+1 uint64 offsets, ncand uint32 pattern indices and int64 diagonals -> ncand uint8
         d_dist and uint64 d_start / d_end"""
-        self.ctx._check(self.lib.pfp_fm_extend_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_cand_pat),
-                                                   C.c_void_p(d_cand_diag), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
-                                                   C.c_void_p(d_start), C.c_void_p(d_end)))
+        self.ctx._check(self.lib.pfp_fm_extend_dev(self._h, d_pat, d_pat_off, npat, d_cand_pat, d_cand_diag, ncand, k, d_dist, d_start, d_end))
 
     def window(self, patterns, cand_pat, lo, hi, k):
         """the best alignment of a whole pattern anywhere in a window of the text under unit-cost edit distance (pfpgpu.h,
@@ -272,16 +241,13 @@ class FmIndex:
             raise ValueError("cand_pat, lo and hi: three 1-D arrays of one length")
         nc = len(cp)
         dist, start, end = np.zeros(nc, dtype=np.uint8), np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
-        self.ctx._check(self.lib.pfp_fm_window(self._h, *args, _ptr(cp, C.c_uint32), _ptr(lo, C.c_uint64), _ptr(hi, C.c_uint64), C.c_uint64(nc),
-                                               C.c_int(k), _ptr(dist, C.c_uint8), _ptr(start, C.c_uint64), _ptr(end, C.c_uint64)))
+        self.ctx._check(self.lib.pfp_fm_window(self._h, *args, cp, lo, hi, nc, k, dist, start, end))
         return dist, start, end
 
     def window_dev(self, d_pat, d_pat_off, npat, d_cand_pat, d_lo, d_hi, ncand, k, d_dist, d_start, d_end):
         """device pointers: pattern bytes, npat+1 uint64 offsets, ncand uint32 pattern indices and uint64 window starts and ends ->
         ncand uint8 d_dist and uint64 d_start / d_end"""
-        self.ctx._check(self.lib.pfp_fm_window_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_cand_pat),
-                                                   C.c_void_p(d_lo), C.c_void_p(d_hi), C.c_uint64(ncand), C.c_int(k), C.c_void_p(d_dist),
-                                                   C.c_void_p(d_start), C.c_void_p(d_end)))
+        self.ctx._check(self.lib.pfp_fm_window_dev(self._h, d_pat, d_pat_off, npat, d_cand_pat, d_lo, d_hi, ncand, k, d_dist, d_start, d_end))
 
     def align(self, patterns, k, min_seed, max_aln=0, thresholds=False, cigar=False):
         """seed-and-extend: every maximal exact match of at least min_seed bytes (as mems lists them; thresholds as there) is
@@ -292,8 +258,7 @@ class FmIndex:
         npat, _, args = self._host_patterns(patterns)
         aln_off = np.zeros(npat + 1, dtype=np.uint64)
         start, end, dist = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)()
-        self.ctx._check(self.lib.pfp_fm_align(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_uint64(max_aln),
-                                              C.c_int(1 if thresholds else 0), _ptr(aln_off, C.c_uint64), C.byref(start), C.byref(end),
+        self.ctx._check(self.lib.pfp_fm_align(self._h, *args, min_seed, k, max_aln, bool(thresholds), aln_off, C.byref(start), C.byref(end),
                                               C.byref(dist)))
         total = aln_off[-1]
         out = aln_off, self._take_free(start, total, np.uint64), self._take_free(end, total, np.uint64), self._take_free(dist, total, np.uint8)
@@ -315,23 +280,19 @@ class FmIndex:
         na = len(ap)
         dist, cig_off = np.zeros(na, dtype=np.uint8), np.zeros(na + 1, dtype=np.uint64)
         cig = C.POINTER(C.c_uint32)()
-        self.ctx._check(self.lib.pfp_fm_cigar(self._h, *args, _ptr(ap, C.c_uint32), _ptr(st, C.c_uint64), _ptr(en, C.c_uint64), C.c_uint64(na),
-                                              C.c_int(k), _ptr(dist, C.c_uint8), _ptr(cig_off, C.c_uint64), C.byref(cig)))
+        self.ctx._check(self.lib.pfp_fm_cigar(self._h, *args, ap, st, en, na, k, dist, cig_off, C.byref(cig)))
         return dist, cig_off, self._take_free(cig, cig_off[-1], np.uint32)
 
     def cigar_dev(self, d_pat, d_pat_off, npat, d_aln_pat, d_start, d_end, naln, k, d_dist, d_cig_off, d_cig=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets, naln uint32 pattern indices and uint64 starts and ends -> naln
         uint8 d_dist and naln+1 uint64 d_cig_off; d_cig (uint32, room for d_cig_off[naln]) gets the runs (None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_cigar_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_aln_pat),
-                                                  C.c_void_p(d_start), C.c_void_p(d_end), C.c_uint64(naln), C.c_int(k), C.c_void_p(d_dist),
-                                                  C.c_void_p(d_cig_off), _vp(d_cig)))
+        self.ctx._check(self.lib.pfp_fm_cigar_dev(self._h, d_pat, d_pat_off, npat, d_aln_pat, d_start, d_end, naln, k, d_dist, d_cig_off, d_cig))
 
     def align_dev(self, d_pat, d_pat_off, npat, k, min_seed, d_aln_off, d_start=None, d_end=None, d_dist=None, max_aln=0, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_aln_off; d_start / d_end (uint64) and d_dist
         (uint8), room for d_aln_off[npat] each, get the alignments (all three None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_align_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
-                                                  C.c_int(k), C.c_uint64(max_aln), C.c_int(1 if thresholds else 0), C.c_void_p(d_aln_off),
-                                                  _vp(d_start), _vp(d_end), _vp(d_dist)))
+        self.ctx._check(self.lib.pfp_fm_align_dev(self._h, d_pat, d_pat_off, npat, min_seed, k, max_aln, bool(thresholds), d_aln_off,
+                                                  d_start, d_end, d_dist))
 
     def map_reads(self, patterns, k, min_seed, max_sec=0, thresholds=False):
         """one answer per read over a collection (pfpgpu.h, "Mapping reads"; an index with text and a sequence table): both
@@ -343,11 +304,10 @@ class FmIndex:
         md[md_off[i]:md_off[i+1]] (uint8; md_string reads it)"""
         npat, _, args = self._host_patterns(patterns)
         hit_off, mapq, nhits = np.zeros(npat + 1, dtype=np.uint64), np.zeros(npat, dtype=np.uint8), np.zeros(npat, dtype=np.uint64)
-        p8, p32, p64 = (lambda: C.POINTER(C.c_uint8)()), (lambda: C.POINTER(C.c_uint32)()), (lambda: C.POINTER(C.c_uint64)())
-        strand, seq, off, start, dist, cig_off, cig, md_off, md = p8(), p32(), p64(), p64(), p8(), p64(), p32(), p64(), p8()
-        self.ctx._check(self.lib.pfp_fm_map(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_uint64(max_sec),
-                                            C.c_int(1 if thresholds else 0), _ptr(hit_off, C.c_uint64), _ptr(mapq, C.c_uint8),
-                                            _ptr(nhits, C.c_uint64), C.byref(strand), C.byref(seq), C.byref(off), C.byref(start),
+        u8, u32, u64 = C.c_uint8, C.c_uint32, C.c_uint64
+        strand, seq, off, start, dist, cig_off, cig, md_off, md = (C.POINTER(t)() for t in (u8, u32, u64, u64, u8, u64, u32, u64, u8))
+        self.ctx._check(self.lib.pfp_fm_map(self._h, *args, min_seed, k, max_sec, bool(thresholds), hit_off, mapq, nhits,
+                                            C.byref(strand), C.byref(seq), C.byref(off), C.byref(start),
                                             C.byref(dist), C.byref(cig_off), C.byref(cig), C.byref(md_off), C.byref(md)))
         H = int(hit_off[-1])
         t = self._take_free
@@ -364,13 +324,12 @@ class FmIndex:
         with Context.dev_free (None where there is no hit)"""
         per_hit = (d_strand, d_seq, d_off, d_start, d_dist, d_cig_off, d_md_off)
         fill = any(x for x in per_hit)
-        d_cig, d_md = C.c_void_p(), C.c_void_p()
-        self.ctx._check(self.lib.pfp_fm_map_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
-                                                C.c_int(k), C.c_uint64(max_sec), C.c_int(1 if thresholds else 0), C.c_void_p(d_hit_off),
-                                                _vp(d_mapq), _vp(d_nhits), _vp(d_strand), _vp(d_seq), _vp(d_off), _vp(d_start), _vp(d_dist),
-                                                _vp(d_cig_off), C.byref(d_cig) if fill else None, _vp(d_md_off),
+        d_cig, d_md = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        self.ctx._check(self.lib.pfp_fm_map_dev(self._h, d_pat, d_pat_off, npat, min_seed, k, max_sec, bool(thresholds), d_hit_off,
+                                                d_mapq, d_nhits, d_strand, d_seq, d_off, d_start, d_dist,
+                                                d_cig_off, C.byref(d_cig) if fill else None, d_md_off,
                                                 C.byref(d_md) if fill else None))
-        return (d_cig.value, d_md.value) if fill else None
+        return (_addr(d_cig), _addr(d_md)) if fill else None
 
     def map_pairs(self, patterns, k, min_seed, min_ins, max_ins, anchors=8, thresholds=False):
         """read pairs over a collection (pfpgpu.h, "Mapping read pairs"): patterns 2q and 2q + 1 are mates 1 and 2 of pair q,
@@ -388,12 +347,9 @@ class FmIndex:
         seq, off, start, dist, tlen = z(npat, np.uint32), z(npat, np.uint64), z(npat, np.uint64), z(npat, np.uint8), z(npat, np.int64)
         cig_off, md_off = z(npat + 1, np.uint64), z(npat + 1, np.uint64)
         cig, md = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
-        u8, u64 = (lambda a: _ptr(a, C.c_uint8)), (lambda a: _ptr(a, C.c_uint64))
-        self.ctx._check(self.lib.pfp_fm_map_pairs(self._h, *args, C.c_uint64(min_seed), C.c_int(k), C.c_int(1 if thresholds else 0),
-                                                  C.c_uint64(min_ins), C.c_uint64(max_ins), C.c_uint64(anchors), u8(proper), u64(npairs),
-                                                  u8(mapped), u8(rescued), u8(mapq), u64(nhits), u8(strand), _ptr(seq, C.c_uint32), u64(off),
-                                                  u64(start), u8(dist), _ptr(tlen, C.c_int64), u64(cig_off), C.byref(cig), u64(md_off),
-                                                  C.byref(md)))
+        self.ctx._check(self.lib.pfp_fm_map_pairs(self._h, *args, min_seed, k, bool(thresholds), min_ins, max_ins, anchors, proper, npairs,
+                                                  mapped, rescued, mapq, nhits, strand, seq, off, start, dist, tlen, cig_off, C.byref(cig),
+                                                  md_off, C.byref(md)))
         return (proper, npairs, mapped, rescued, mapq, nhits, strand, seq, off, start, dist, tlen, cig_off,
                 self._take_free(cig, cig_off[-1], np.uint32), md_off, self._take_free(md, md_off[-1], np.uint8))
 
@@ -403,20 +359,17 @@ class FmIndex:
         d_rescued, d_mapq, d_strand, d_dist, uint64 d_nhits, d_off, d_start, uint32 d_seq, int64 d_tlen; npat+1 uint64 d_cig_off and
         d_md_off.  Returns (d_cig, d_md): the addresses of the runs (uint32) and the MD bytes, device buffers of the library that
         go back with Context.dev_free (None where there is nothing)"""
-        d_cig, d_md = C.c_void_p(), C.c_void_p()
-        self.ctx._check(self.lib.pfp_fm_map_pairs_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_uint64(min_seed),
-                                                      C.c_int(k), C.c_int(1 if thresholds else 0), C.c_uint64(min_ins), C.c_uint64(max_ins),
-                                                      C.c_uint64(anchors), _vp(d_proper), _vp(d_npairs), _vp(d_mapped), _vp(d_rescued),
-                                                      _vp(d_mapq), _vp(d_nhits), _vp(d_strand), _vp(d_seq), _vp(d_off), _vp(d_start),
-                                                      _vp(d_dist), _vp(d_tlen), C.c_void_p(d_cig_off), C.byref(d_cig), C.c_void_p(d_md_off),
-                                                      C.byref(d_md)))
-        return d_cig.value, d_md.value
+        d_cig, d_md = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        self.ctx._check(self.lib.pfp_fm_map_pairs_dev(self._h, d_pat, d_pat_off, npat, min_seed, k, bool(thresholds), min_ins, max_ins,
+                                                      anchors, d_proper, d_npairs, d_mapped, d_rescued, d_mapq, d_nhits, d_strand, d_seq,
+                                                      d_off, d_start, d_dist, d_tlen, d_cig_off, C.byref(d_cig), d_md_off, C.byref(d_md)))
+        return _addr(d_cig), _addr(d_md)
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the
         first 0, non-decreasing, the last n; a second call replaces the table"""
         st = _arr(np.asarray(starts), np.uint64)
-        self.ctx._check(self.lib.pfp_fm_set_seqs(self._h, _ptr(st, C.c_uint64), C.c_uint64(max(len(st), 1) - 1)))
+        self.ctx._check(self.lib.pfp_fm_set_seqs(self._h, st, max(len(st), 1) - 1))
         return self
 
     def set_sequences_file(self, path):
@@ -444,9 +397,7 @@ class FmIndex:
         sp, ep = np.zeros(npat, dtype=np.uint64), np.zeros(npat, dtype=np.uint64)
         out_off = np.zeros(npat + 1, dtype=np.uint64)
         seq, off = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
-        u64 = lambda a: _ptr(a, C.c_uint64)
-        self.ctx._check(self.lib.pfp_fm_locate_seqs(self._h, *args, C.c_uint64(max_occ), u64(sp), u64(ep), u64(out_off), C.byref(seq),
-                                                    C.byref(off)))
+        self.ctx._check(self.lib.pfp_fm_locate_seqs(self._h, *args, max_occ, sp, ep, out_off, C.byref(seq), C.byref(off)))
         seqs, offs = self._take_free(seq, out_off[-1], np.uint32), self._take_free(off, out_off[-1], np.uint64)
         return (out_off, seqs, offs, sp, ep) if ranges else (out_off, seqs, offs)
 
@@ -456,46 +407,40 @@ class FmIndex:
         npat, _, args = self._host_patterns(patterns)
         doc_off = np.zeros(npat + 1, dtype=np.uint64)
         doc, cnt = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
-        self.ctx._check(self.lib.pfp_fm_doclist(self._h, *args, _ptr(doc_off, C.c_uint64), C.byref(doc), C.byref(cnt)))
+        self.ctx._check(self.lib.pfp_fm_doclist(self._h, *args, doc_off, C.byref(doc), C.byref(cnt)))
         return doc_off, self._take_free(doc, doc_off[-1], np.uint32), self._take_free(cnt, doc_off[-1], np.uint64)
 
     def seqmap_dev(self, d_pos, count, d_seq=None, d_off=None):
         """device pointers: count uint64 positions -> uint32 d_seq / uint64 d_off (either may be None)"""
-        self.ctx._check(self.lib.pfp_fm_seqmap_dev(self._h, C.c_void_p(d_pos), C.c_uint64(count), _vp(d_seq), _vp(d_off)))
+        self.ctx._check(self.lib.pfp_fm_seqmap_dev(self._h, d_pos, count, d_seq, d_off))
 
     def locate_seqs_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq=None, d_off=None):
         """device pointers from count_dev -> npat+1 offsets of the kept hits; d_seq (uint32) / d_off (uint64), each with room for
         what locate_dev's offsets-only call reports, get them (both None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_locate_seqs_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp),
-                                                        C.c_void_p(d_ep), _vp(d_first), C.c_uint64(max_occ), C.c_void_p(d_out_off),
-                                                        _vp(d_seq), _vp(d_off)))
+        self.ctx._check(self.lib.pfp_fm_locate_seqs_dev(self._h, d_pat_off, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_seq, d_off))
 
     def doclist_dev(self, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, d_doc=None, d_cnt=None):
         """device pointers from count_dev -> npat+1 offsets of the documents; d_doc (uint32) / d_cnt (uint64), room for
         offsets[npat] each, get them (both None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_doclist_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep),
-                                                    _vp(d_first), C.c_void_p(d_doc_off), _vp(d_doc), _vp(d_cnt)))
+        self.ctx._check(self.lib.pfp_fm_doclist_dev(self._h, d_pat_off, npat, d_sp, d_ep, d_first, d_doc_off, d_doc, d_cnt))
 
     def add_thresholds(self, thr=None):
         """give the index its thresholds (pfpgpu.h, "The LCP array and thresholds"): thr=None computes them on the GPU, else the
         bytes of a .thr_pos file (5 per run), or a path base whose base.thr_pos is read"""
         if thr is None:
-            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, None, C.c_uint64(0)))
+            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, None, 0))
         elif isinstance(thr, (str, os.PathLike)):
-            self.ctx._check(self.lib.pfp_fm_thresholds_files(self._h, C.c_char_p(os.fsencode(thr))))
+            self.ctx._check(self.lib.pfp_fm_thresholds_files(self._h, os.fsencode(thr)))
         else:
             import torch
-            b = _arr(thr, np.uint8)
-            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
-            if len(b):
-                t[:len(b)] = torch.from_numpy(b.copy())
+            d_thr5, nbytes, keep = self.ctx._upload_padded(thr)
             torch.cuda.synchronize()
-            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, C.c_void_p(t.data_ptr()), C.c_uint64(len(b))))
+            self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, d_thr5, nbytes))
         return self
 
     def add_thresholds_dev(self, d_thr5, nbytes):
         """the same from a device image of a .thr_pos file (5 bytes per run)"""
-        self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, C.c_void_p(d_thr5), C.c_uint64(nbytes)))
+        self.ctx._check(self.lib.pfp_fm_thresholds_dev(self._h, d_thr5, nbytes))
         return self
 
     def matching_statistics(self, patterns, thresholds=False):
@@ -507,7 +452,7 @@ class FmIndex:
         total = int(off[-1])
         ln, pos = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint64)
         call = self.lib.pfp_fm_ms_thr if thresholds else self.lib.pfp_fm_ms
-        self.ctx._check(call(self._h, *args, _ptr(ln, C.c_uint32), _ptr(pos, C.c_uint64)))
+        self.ctx._check(call(self._h, *args, ln, pos))
         return off, ln, pos
 
     def mems(self, patterns, min_len=1, thresholds=False):
@@ -518,7 +463,7 @@ class FmIndex:
         mem_off = np.zeros(npat + 1, dtype=np.uint64)
         out = C.POINTER(C.c_uint64)()
         call = self.lib.pfp_fm_mems_thr if thresholds else self.lib.pfp_fm_mems
-        self.ctx._check(call(self._h, *args, C.c_uint64(min_len), _ptr(mem_off, C.c_uint64), C.byref(out)))
+        self.ctx._check(call(self._h, *args, min_len, mem_off, C.byref(out)))
         return mem_off, self._take_free(out, 3 * int(mem_off[-1]), np.uint64).reshape(-1, 3)
 
     def ms_stats(self):
@@ -531,73 +476,27 @@ class FmIndex:
     def matching_statistics_dev(self, d_pat, d_pat_off, npat, d_len, d_pos=None, thresholds=False):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> uint32 d_len / uint64 d_pos, entry t for pattern byte d_pat[t]"""
         call = self.lib.pfp_fm_ms_thr_dev if thresholds else self.lib.pfp_fm_ms_dev
-        self.ctx._check(call(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len), _vp(d_pos)))
+        self.ctx._check(call(self._h, d_pat, d_pat_off, npat, d_len, d_pos))
 
     def mems_dev(self, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem=None):
         """device pointers from matching_statistics_dev -> npat+1 offsets; d_mem (room for 3 * offsets[npat] uint64) gets the
         triples (None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_mems_dev(self._h, C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_len), _vp(d_pos),
-                                                 C.c_uint64(min_len), C.c_void_p(d_mem_off), _vp(d_mem)))
+        self.ctx._check(self.lib.pfp_fm_mems_dev(self._h, d_pat_off, npat, d_len, d_pos, min_len, d_mem_off, d_mem))
 
     def count_dev(self, d_pat, d_pat_off, npat, d_sp, d_ep, d_first=None):
         """device pointers: pattern bytes, npat+1 uint64 offsets -> npat uint64 sp / ep (and SA[sp] where d_first is given)"""
-        self.ctx._check(self.lib.pfp_fm_count_dev(self._h, C.c_void_p(d_pat), C.c_void_p(d_pat_off), C.c_uint64(npat), C.c_void_p(d_sp),
-                                                  C.c_void_p(d_ep), _vp(d_first)))
+        self.ctx._check(self.lib.pfp_fm_count_dev(self._h, d_pat, d_pat_off, npat, d_sp, d_ep, d_first))
 
     def locate_dev(self, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos=None):
         """device pointers from count_dev -> npat+1 offsets; d_pos (room for offsets[npat]) gets the positions (None: offsets only)"""
-        self.ctx._check(self.lib.pfp_fm_locate_dev(self._h, C.c_uint64(npat), C.c_void_p(d_sp), C.c_void_p(d_ep), _vp(d_first),
-                                                   C.c_uint64(max_occ), C.c_void_p(d_out_off), _vp(d_pos)))
-
-
-class _ParseResult(C.Structure):
-    _fields_ = [("n_used", C.c_uint64), ("dict", C.POINTER(C.c_uint8)), ("dict_size", C.c_uint64),
-                ("occ", C.POINTER(C.c_uint32)), ("n_words", C.c_uint64),
-                ("parse", C.POINTER(C.c_uint32)), ("n_phrases", C.c_uint64),
-                ("last", C.POINTER(C.c_uint8)), ("sai", C.POINTER(C.c_uint8))]
-
-
-class _BwtResult(C.Structure):
-    _fields_ = [("bwt", C.POINTER(C.c_uint8)), ("bwt_size", C.c_uint64),
-                ("sa", C.POINTER(C.c_uint8)), ("sa_bytes", C.c_uint64),
-                ("ssa", C.POINTER(C.c_uint8)), ("ssa_bytes", C.c_uint64),
-                ("esa", C.POINTER(C.c_uint8)), ("esa_bytes", C.c_uint64)]
-
-
-class KernelStat(C.Structure):
-    _fields_ = [("name", C.c_char * 64), ("launches", C.c_uint64), ("total_ms", C.c_double), ("algo_bytes", C.c_uint64)]
-
-
-class Stats(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("n_phrases", C.c_uint64), ("n_words", C.c_uint64), ("dict_size", C.c_uint64),
-                ("sa_rounds_dict", C.c_uint64), ("sa_rounds_parse", C.c_uint64),
-                ("hard_groups", C.c_uint64), ("hard_chars", C.c_uint64),
-                ("hard_big_groups", C.c_uint64), ("hard_max_chars", C.c_uint64), ("hard_max_members", C.c_uint64),
-                ("hash_reseeds", C.c_uint64),
-                ("extra_triggers", C.c_uint64), ("index_bits", C.c_uint64),
-                ("hard_minor_groups", C.c_uint64), ("hard_minor_chars", C.c_uint64),
-                ("ms_scan", C.c_double), ("ms_phrases", C.c_double), ("ms_sa_dict", C.c_double),
-                ("ms_sa_parse", C.c_double), ("ms_merge", C.c_double), ("ms_total", C.c_double), ("parse_density", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class ScanReport(C.Structure):
-    _fields_ = [("n_used", C.c_uint64), ("n_ends", C.c_uint64),
-                ("fast", C.c_uint32), ("fthr", C.c_uint32), ("fseed", C.c_uint32), ("fthr_nom", C.c_uint32),
-                ("fauto", C.c_uint32), ("fthr_first", C.c_uint32), ("n_extra", C.c_uint32), ("reserved", C.c_uint32),
-                ("extra", C.c_uint32 * 32), ("density", C.c_double), ("parse_density", C.c_double),
-                ("chose", C.c_uint64), ("dense", C.c_uint64), ("kr_fallback", C.c_uint64),
-                ("dense_cuts", C.c_uint64), ("n_nominal", C.c_uint64), ("sampled", C.c_uint64), ("kept", C.c_uint64),
-                ("distinct", C.c_uint64), ("singles", C.c_uint64)]
+        self.ctx._check(self.lib.pfp_fm_locate_dev(self._h, npat, d_sp, d_ep, d_first, max_occ, d_out_off, d_pos))
 
 
 _lib = None
 
 
 def load_library():
-    """dlopen libpfpgpu.so (built in-tree by __graft_entry__.build / csrc/Makefile)."""
+    """dlopen libpfpgpu.so (built in-tree by __graft_entry__.build / csrc/Makefile) and give its functions the signatures of abi.py."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -612,22 +511,11 @@ def load_library():
         except Exception:
             pass
         lib = C.CDLL(LIB_PATH)
-        lib.pfp_last_error.restype = C.c_char_p
-        lib.pfp_strerror.restype = C.c_char_p
-        lib.pfp_version.restype = C.c_char_p
-        lib.pfp_ctx_stream.restype = C.c_void_p
-        lib.pfp_ctx_destroy.restype = None
-        lib.pfp_free.restype = None
-        lib.pfp_set_profiling.restype = None
-        lib.pfp_set_max_phrase.restype = None
-        lib.pfp_set_window_hash.restype = None
-        lib.pfp_set_kernel_trace.restype = None
-        lib.pfp_dist_release.restype = None
-        lib.pfp_dev_free.restype = None
-        lib.pfp_pool_trim.restype = None
-        lib.pfp_parse_result_free.restype = None
-        lib.pfp_bwt_result_free.restype = None
-        lib.pfp_fm_free.restype = None
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if not hasattr(lib, name):
+                raise ImportError(f"{LIB_PATH} does not export {name}, which include/pfpgpu.h declares")
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
 
@@ -639,10 +527,6 @@ def _arr(a, dtype):
     if a.dtype != dtype:
         a = a.astype(dtype) if dtype != np.uint8 or a.dtype.itemsize == 1 else a.view(np.uint8)
     return a
-
-
-def _ptr(a, ctype):
-    return a.ctypes.data_as(C.POINTER(ctype))
 
 
 def _take(ptr, n, dtype):
@@ -657,10 +541,26 @@ def _adopt(lib, ptr, n):
     if n == 0 or not ptr:
         return np.zeros(0, dtype=np.uint8)
     import weakref
-    addr = C.cast(ptr, C.c_void_p).value
     arr = np.ctypeslib.as_array(ptr, shape=(int(n),))
-    weakref.finalize(arr, lib.pfp_free, C.c_void_p(addr))
+    weakref.finalize(arr, lib.pfp_free, _addr(ptr))
     return arr
+
+
+def _text_nul(text):
+    """-> (the text's bytes and one NUL: never a NULL pointer, for an empty text neither; the text's length)"""
+    t = _arr(text, np.uint8)
+    return np.concatenate([t, np.zeros(1, dtype=np.uint8)]), len(t)
+
+
+def _sort_info(info):
+    """out_info of pfp_dist_global_sort / pfp_dist_global_sort_distinct"""
+    return dict(words=int(info[0]), dict_bytes=int(info[1]), rounds=int(info[2]), complete=bool(info[3]), slots=int(info[4]),
+                slot_base=int(info[5]), emits=int(info[6]), index_bits=int(info[7]))
+
+
+def _local_sizes(sizes):
+    """out_sizes of pfp_dist_local_parse / pfp_dist_local_parse2"""
+    return dict(dict_bytes=int(sizes[0]), words=int(sizes[1]), phrases=int(sizes[2]), last_trigger=int(sizes[3]))
 
 
 def unpack5(b):
@@ -676,13 +576,13 @@ def pack5(v):
     return v.view(np.uint8).reshape(-1, 8)[:, :5].copy().reshape(-1)
 
 
-class Context:
+class Context(_Closing):
     """One HIP stream + memory pool on one GPU (pfp_ctx)."""
 
     def __init__(self, device=0):
         self.lib = load_library()
         self._h = C.c_void_p()
-        rc = self.lib.pfp_ctx_create(C.byref(self._h), C.c_int(device))
+        rc = self.lib.pfp_ctx_create(C.byref(self._h), device)
         if rc:
             raise PfpError(rc, "pfp_ctx_create failed: " + self.lib.pfp_strerror(rc).decode() +
                            " (the HIP path is mandatory; no CPU fallback exists)")
@@ -693,21 +593,21 @@ class Context:
             self.lib.pfp_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _check(self, rc):
         if rc:
             raise PfpError(rc, self.lib.pfp_last_error(self._h).decode(errors="replace"))
+
+    def _upload_padded(self, a):
+        """host bytes -> (address, length, t): t, a zeroed uint8 torch tensor of length + 16 bytes on the context's device, begins
+        with them; (None, 0, None) for None.  torch fills t on its own stream: torch.cuda.synchronize before the library reads it."""
+        if a is None:
+            return None, 0, None
+        import torch
+        b = _arr(a, np.uint8)
+        t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if len(b):
+            t[:len(b)] = torch.from_numpy(b.copy())
+        return t.data_ptr(), len(b), t
 
     @property
     def stream(self):
@@ -731,36 +631,34 @@ class Context:
         return dict(driver_allocs=int(out[0]), trims=int(out[1]))
 
     def set_profiling(self, on=True):
-        self.lib.pfp_set_profiling(self._h, C.c_int(1 if on else 0))
+        self.lib.pfp_set_profiling(self._h, bool(on))
 
     def set_kernel_trace(self, on=True):
         """start (and clear) / stop per-kernel HIP-event timing on the ctx stream"""
-        self.lib.pfp_set_kernel_trace(self._h, C.c_int(1 if on else 0))
+        self.lib.pfp_set_kernel_trace(self._h, bool(on))
 
     def kernel_trace(self):
         """rows {name, launches, total_ms, algo_bytes} accumulated since set_kernel_trace(True)"""
-        n = self.lib.pfp_get_kernel_trace(self._h, None, C.c_int(0))
+        n = self.lib.pfp_get_kernel_trace(self._h, None, 0)
         if n <= 0:
             return []
         arr = (KernelStat * n)()
-        self.lib.pfp_get_kernel_trace(self._h, arr, C.c_int(n))
+        self.lib.pfp_get_kernel_trace(self._h, arr, n)
         return [dict(name=r.name.decode(), launches=int(r.launches), total_ms=float(r.total_ms), algo_bytes=int(r.algo_bytes))
                 for r in arr]
 
     def set_max_phrase(self, max_phrase):
         """fused chain: split phrases longer than this with extra trigger windows (0 = reference parse)"""
-        self.lib.pfp_set_max_phrase(self._h, C.c_uint64(max_phrase))
+        self.lib.pfp_set_max_phrase(self._h, max_phrase)
 
     def set_window_hash(self, fast):
         """fused chain: cut the text by the cheap window hash (True, default) or by the reference's Karp-Rabin hash (False)"""
-        self.lib.pfp_set_window_hash(self._h, C.c_int(1 if fast else 0))
+        self.lib.pfp_set_window_hash(self._h, bool(fast))
 
     def debug_msd_sort(self, keys, vals, lo, hi):
         """radix.hip's sort on numpy arrays (uint64 keys, optional uint32 values), in place; stable on key bits [lo, hi)"""
         assert keys.dtype == np.uint64 and keys.flags.c_contiguous and (vals is None or (vals.dtype == np.uint32 and vals.flags.c_contiguous))
-        self._check(self.lib.pfp_debug_msd_sort(self._h, keys.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                vals.ctypes.data_as(C.POINTER(C.c_uint32)) if vals is not None else None,
-                                                C.c_uint64(len(keys)), C.c_int(lo), C.c_int(hi)))
+        self._check(self.lib.pfp_debug_msd_sort(self._h, keys, vals, len(keys), lo, hi))
 
     LIB_SORT_KINDS = {"pairs_u64_u32": (0, np.uint64, np.uint32), "pairs_u64_u64": (1, np.uint64, np.uint64), "keys_db": (2, np.uint64, None),
                       "keys_raw": (3, np.uint64, None), "seg_u32_u32": (4, np.uint32, np.uint32), "seg_u32_u64": (5, np.uint32, np.uint64),
@@ -779,11 +677,8 @@ class Context:
             assert seg_begin.dtype == np.uint32 and seg_end.dtype == np.uint32 and len(seg_begin) == len(seg_end)
             assert seg_begin.flags.c_contiguous and seg_end.flags.c_contiguous
             nseg = len(seg_begin)
-        self._check(self.lib.pfp_debug_lib_sort(self._h, C.c_int(code), keys.ctypes.data_as(C.c_void_p),
-                                                vals.ctypes.data_as(C.c_void_p) if vals is not None else None, C.c_uint64(n),
-                                                C.c_int(begin_bit), C.c_int(end_bit),
-                                                _ptr(seg_begin, C.c_uint32) if nseg else None, _ptr(seg_end, C.c_uint32) if nseg else None,
-                                                C.c_uint64(nseg)))
+        self._check(self.lib.pfp_debug_lib_sort(self._h, code, keys.ctypes.data, vals.ctypes.data if vals is not None else None, n,
+                                                begin_bit, end_bit, seg_begin if nseg else None, seg_end if nseg else None, nseg))
 
     def debug_scan_chain(self, text, w=10, p=100, plan=None, extra=()):
         """stage 1a as the fused chain runs it under the context's settings - or, with a settled plan, as a rank of the multi-GPU
@@ -794,8 +689,7 @@ class Context:
         rep = ScanReport()
         pl = (C.c_uint64 * 4)(*plan) if plan is not None else None
         ex = np.ascontiguousarray(np.array(list(extra), dtype=np.uint32))
-        rc = self.lib.pfp_debug_scan_chain(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p), pl,
-                                           _ptr(ex, C.c_uint32) if len(ex) else None, C.c_uint32(len(ex)),
+        rc = self.lib.pfp_debug_scan_chain(self._h, t, len(t), w, p, pl, ex if len(ex) else None, len(ex),
                                            C.byref(ends), C.byref(dends), C.byref(nom), C.byref(rep))
         try:
             self._check(rc)
@@ -812,11 +706,11 @@ class Context:
 
     def set_parse_density(self, density):
         """fused chain, opt-in: the window hash cuts with probability density / p (outputs unchanged, see pfpgpu.h)"""
-        self._check(self.lib.pfp_set_parse_density(self._h, C.c_double(density)))
+        self._check(self.lib.pfp_set_parse_density(self._h, density))
 
     def set_index_bits(self, bits):
         """0: index width by size (32 bits below 4 GiB), 64: always the wide build (bigbwt:109-151)"""
-        self._check(self.lib.pfp_set_index_bits(self._h, C.c_int(bits)))
+        self._check(self.lib.pfp_set_index_bits(self._h, bits))
 
     def stats(self):
         st = Stats()
@@ -828,8 +722,7 @@ class Context:
         t = _arr(text, np.uint8)
         ends = C.POINTER(C.c_uint64)()
         ne, used = C.c_uint64(), C.c_uint64()
-        self._check(self.lib.pfp_scan(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p),
-                                      C.byref(ends), C.byref(ne), C.byref(used)))
+        self._check(self.lib.pfp_scan(self._h, t, len(t), w, p, C.byref(ends), C.byref(ne), C.byref(used)))
         out = _take(ends, ne.value, np.uint64)
         self.lib.pfp_free(ends)
         return out, used.value
@@ -838,59 +731,44 @@ class Context:
     def parse(self, text, w=10, p=100, want_sai=False):
         t = _arr(text, np.uint8)
         r = _ParseResult()
-        self._check(self.lib.pfp_parse(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p),
-                                       C.c_int(1 if want_sai else 0), C.byref(r)))
+        self._check(self.lib.pfp_parse(self._h, t, len(t), w, p, bool(want_sai), C.byref(r)))
         out = dict(n_used=int(r.n_used), dict=_take(r.dict, r.dict_size, np.uint8), occ=_take(r.occ, r.n_words, np.uint32),
                    parse=_take(r.parse, r.n_phrases, np.uint32), last=_take(r.last, r.n_phrases, np.uint8),
                    sai=_take(r.sai, 5 * r.n_phrases, np.uint8) if want_sai else None)
         self.lib.pfp_parse_result_free(C.byref(r))
         return out
 
-    # -- gsa/gsacak.h
-    def sacak_int(self, s, k=0):
-        s = _arr(s, np.uint32)
-        sa = np.zeros(len(s), dtype=np.uint32)
-        self._check(self.lib.pfp_sacak_int(self._h, _ptr(s, C.c_uint32), _ptr(sa, C.c_uint32), C.c_uint64(len(s)), C.c_uint64(k)))
+    # -- gsa/gsacak.h, and its -DM64 build (the names that end in 64): 64-bit SA entries
+    def _suffix_array(self, name, s, s_dtype, sa_dtype, *k):
+        s = _arr(s, s_dtype)
+        sa = np.zeros(len(s), dtype=sa_dtype)
+        self._check(getattr(self.lib, name)(self._h, s, sa, len(s), *k))
         return sa
+
+    def sacak_int(self, s, k=0):
+        return self._suffix_array("pfp_sacak_int", s, np.uint32, np.uint32, k)
 
     def sacak(self, s):
-        s = _arr(s, np.uint8)
-        sa = np.zeros(len(s), dtype=np.uint32)
-        self._check(self.lib.pfp_sacak(self._h, _ptr(s, C.c_uint8), _ptr(sa, C.c_uint32), C.c_uint64(len(s))))
-        return sa
+        return self._suffix_array("pfp_sacak", s, np.uint8, np.uint32)
 
     def gsacak(self, s):
-        s = _arr(s, np.uint8)
-        sa = np.zeros(len(s), dtype=np.uint32)
-        self._check(self.lib.pfp_gsacak(self._h, _ptr(s, C.c_uint8), _ptr(sa, C.c_uint32), C.c_uint64(len(s))))
-        return sa
+        return self._suffix_array("pfp_gsacak", s, np.uint8, np.uint32)
 
-    # -- the -DM64 build of gsa/gsacak.h: 64-bit SA entries
     def sacak_int64(self, s, k=0):
-        s = _arr(s, np.uint32)
-        sa = np.zeros(len(s), dtype=np.uint64)
-        self._check(self.lib.pfp_sacak_int64(self._h, _ptr(s, C.c_uint32), _ptr(sa, C.c_uint64), C.c_uint64(len(s)), C.c_uint64(k)))
-        return sa
+        return self._suffix_array("pfp_sacak_int64", s, np.uint32, np.uint64, k)
 
     def sacak64(self, s):
-        s = _arr(s, np.uint8)
-        sa = np.zeros(len(s), dtype=np.uint64)
-        self._check(self.lib.pfp_sacak64(self._h, _ptr(s, C.c_uint8), _ptr(sa, C.c_uint64), C.c_uint64(len(s))))
-        return sa
+        return self._suffix_array("pfp_sacak64", s, np.uint8, np.uint64)
 
     def gsacak64(self, s):
-        s = _arr(s, np.uint8)
-        sa = np.zeros(len(s), dtype=np.uint64)
-        self._check(self.lib.pfp_gsacak64(self._h, _ptr(s, C.c_uint8), _ptr(sa, C.c_uint64), C.c_uint64(len(s))))
-        return sa
+        return self._suffix_array("pfp_gsacak64", s, np.uint8, np.uint64)
 
     def gsacak_lcp_da(self, s, wide=False):
         """gsacak(s, SA, LCP, DA, n) with all three outputs (gsa/gsacak.h:96-105)"""
         s = _arr(s, np.uint8)
         it, ut, fn = (np.int64, np.uint64, self.lib.pfp_gsacak_lcp_da64) if wide else (np.int32, np.uint32, self.lib.pfp_gsacak_lcp_da)
         sa = np.zeros(len(s), dtype=ut); lcp = np.zeros(len(s), dtype=it); da = np.zeros(len(s), dtype=it)
-        self._check(fn(self._h, _ptr(s, C.c_uint8), sa.ctypes.data_as(C.c_void_p), lcp.ctypes.data_as(C.c_void_p),
-                       da.ctypes.data_as(C.c_void_p), C.c_uint64(len(s))))
+        self._check(fn(self._h, s, sa, lcp, da, len(s)))
         return sa, lcp, da
 
     # -- stage 2: bwtparse.c main
@@ -901,150 +779,116 @@ class Context:
         bwlast = np.zeros(P + 1, dtype=np.uint8)
         bwsai = np.zeros(5 * (P + 1), dtype=np.uint8) if sai is not None else None
         sai_a = _arr(sai, np.uint8) if sai is not None else None
-        self._check(self.lib.pfp_bwtparse(self._h, _ptr(parse, C.c_uint32), C.c_uint64(P), _ptr(last, C.c_uint8),
-                                          _ptr(sai_a, C.c_uint8) if sai is not None else None,
-                                          _ptr(occ, C.c_uint32), C.c_uint64(len(occ)), _ptr(ilist, C.c_uint32),
-                                          _ptr(bwlast, C.c_uint8),
-                                          _ptr(bwsai, C.c_uint8) if sai is not None else None))
+        self._check(self.lib.pfp_bwtparse(self._h, parse, P, last, sai_a, occ, len(occ), ilist, bwlast, bwsai))
         return ilist, bwlast, bwsai
 
     def _bwt_result(self, r):
-        out = dict(bwt=_adopt(self.lib, r.bwt, r.bwt_size), sa=_adopt(self.lib, r.sa, r.sa_bytes),
-                   ssa=_adopt(self.lib, r.ssa, r.ssa_bytes), esa=_adopt(self.lib, r.esa, r.esa_bytes))
-        return out
+        return dict(bwt=_adopt(self.lib, r.bwt, r.bwt_size), sa=_adopt(self.lib, r.sa, r.sa_bytes),
+                    ssa=_adopt(self.lib, r.ssa, r.ssa_bytes), esa=_adopt(self.lib, r.esa, r.esa_bytes))
 
     # -- stage 3: pfbwt.cpp main
     def merge(self, dict_, occ, ilist, bwlast, bwsai=None, w=10, flags=0):
         d = _arr(dict_, np.uint8); occ = _arr(occ, np.uint32); ilist = _arr(ilist, np.uint32); bwlast = _arr(bwlast, np.uint8)
         bs = _arr(bwsai, np.uint8) if bwsai is not None else None
         r = _BwtResult()
-        self._check(self.lib.pfp_merge(self._h, _ptr(d, C.c_uint8), C.c_uint64(len(d)), _ptr(occ, C.c_uint32),
-                                       C.c_uint64(len(occ)), _ptr(ilist, C.c_uint32), _ptr(bwlast, C.c_uint8),
-                                       _ptr(bs, C.c_uint8) if bs is not None else None, C.c_uint64(len(ilist)),
-                                       C.c_int(w), C.c_int(flags), C.byref(r)))
+        self._check(self.lib.pfp_merge(self._h, d, len(d), occ, len(occ), ilist, bwlast, bs, len(ilist), w, flags, C.byref(r)))
         return self._bwt_result(r)
 
     # -- bigbwt chain, host buffers
     def bigbwt(self, text, w=10, p=100, flags=0):
         t = _arr(text, np.uint8)
         r = _BwtResult()
-        self._check(self.lib.pfp_bigbwt(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p),
-                                        C.c_int(flags), C.byref(r)))
+        self._check(self.lib.pfp_bigbwt(self._h, t, len(t), w, p, flags, C.byref(r)))
         return self._bwt_result(r)
 
     def bigbwt_files(self, text, base, w=10, p=100, flags=0):
         """host text in, <base>.bwt/.sa/.ssa/.esa out (streamed from HBM); returns the sizes written"""
         t = _arr(text, np.uint8)
         sizes = (C.c_uint64 * 4)()
-        self._check(self.lib.pfp_bigbwt_files(self._h, _ptr(t, C.c_uint8), C.c_uint64(len(t)), C.c_int(w), C.c_uint64(p),
-                                              C.c_int(flags), C.c_char_p(os.fsencode(base)), sizes))
+        self._check(self.lib.pfp_bigbwt_files(self._h, t, len(t), w, p, flags, os.fsencode(base), sizes))
         return dict(bwt=int(sizes[0]), sa=int(sizes[1]), ssa=int(sizes[2]), esa=int(sizes[3]))
 
     # -- bigbwt chain, device-resident (raw device pointers, e.g. torch tensor.data_ptr())
     def bigbwt_dev(self, d_text_ptr, n, d_bwt_ptr, d_sa_ptr=None, w=10, p=100, flags=0):
         used = C.c_uint64()
-        self._check(self.lib.pfp_bigbwt_dev(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_int(w), C.c_uint64(p),
-                                            C.c_int(flags), C.c_void_p(d_bwt_ptr),
-                                            C.c_void_p(d_sa_ptr) if d_sa_ptr else None, C.byref(used)))
+        self._check(self.lib.pfp_bigbwt_dev(self._h, d_text_ptr, n, w, p, flags, d_bwt_ptr, d_sa_ptr, C.byref(used)))
         return used.value
 
     def bigbwt_formats_dev(self, d_text_ptr, n, d_bwt_ptr, w=10, p=100, flags=0):
         """device text in, .bwt into d_bwt, .sa/.ssa/.esa as library-owned device buffers: -> (n_used, {name: (ptr, bytes)});
         release every ptr with dev_free"""
-        used = C.c_uint64()
-        outs = (C.c_void_p * 3)()
-        sizes = (C.c_uint64 * 3)()
-        self._check(self.lib.pfp_bigbwt_formats_dev(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_int(w), C.c_uint64(p), C.c_int(flags),
-                                                    C.c_void_p(d_bwt_ptr), outs, sizes, C.byref(used)))
+        used, outs, sizes = C.c_uint64(), (C.c_void_p * 3)(), (C.c_uint64 * 3)()
+        self._check(self.lib.pfp_bigbwt_formats_dev(self._h, d_text_ptr, n, w, p, flags, d_bwt_ptr, outs, sizes, C.byref(used)))
         return used.value, {k: (outs[i], int(sizes[i])) for i, k in enumerate(("sa", "ssa", "esa")) if outs[i]}
 
     def fetch_dev(self, d_ptr, nbytes):
         """device bytes (a buffer the library handed out) -> numpy uint8 array"""
         out = np.empty(int(nbytes), dtype=np.uint8)
-        self._check(self.lib.pfp_memcpy_d2h(self._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(d_ptr), C.c_uint64(nbytes)))
+        self._check(self.lib.pfp_memcpy_d2h(self._h, out.ctypes.data, d_ptr, nbytes))
         return out
 
     def dev_free(self, d_ptr):
-        self.lib.pfp_dev_free(self._h, C.c_void_p(d_ptr))
+        self.lib.pfp_dev_free(self._h, d_ptr)
 
     def pack5_dev(self, d_vals_ptr, count, d_out5_ptr):
         """count u64 device values -> 5-byte LE ints in device memory (utils.c:112-129)"""
-        self._check(self.lib.pfp_pack5_dev(self._h, C.c_void_p(d_vals_ptr), C.c_uint64(count), C.c_void_p(d_out5_ptr)))
+        self._check(self.lib.pfp_pack5_dev(self._h, d_vals_ptr, count, d_out5_ptr))
 
     def sample_runs_dev(self, d_bwt_ptr, d_sa_ptr, count, pos_base=0, left=-1, right=-1, run_end=False, d_out10_ptr=None, cap_pairs=0):
         """.ssa / .esa pairs of a BWT slice in device memory (pfbwt.cpp:605-676); returns the number of pairs"""
         k = C.c_uint64()
-        rc = self.lib.pfp_sample_runs_dev(self._h, C.c_void_p(d_bwt_ptr), C.c_void_p(d_sa_ptr) if d_sa_ptr else None, C.c_uint64(count),
-                                          C.c_uint64(pos_base), C.c_int(left), C.c_int(right), C.c_int(1 if run_end else 0),
-                                          C.c_void_p(d_out10_ptr) if d_out10_ptr else None, C.c_uint64(cap_pairs), C.byref(k))
-        self._check(rc)
+        self._check(self.lib.pfp_sample_runs_dev(self._h, d_bwt_ptr, d_sa_ptr, count, pos_base, left, right, bool(run_end),
+                                                 d_out10_ptr, cap_pairs, C.byref(k)))
         return k.value
 
     def pwrite_dev(self, path, file_offset, d_src_ptr, nbytes):
         """device bytes -> file at an offset (pfthreads.hpp:369-376 pattern), through pinned staging buffers"""
-        self._check(self.lib.pfp_pwrite_dev(self._h, C.c_char_p(os.fsencode(path)), C.c_uint64(file_offset), C.c_void_p(d_src_ptr),
-                                            C.c_uint64(nbytes)))
+        self._check(self.lib.pfp_pwrite_dev(self._h, os.fsencode(path), file_offset, d_src_ptr, nbytes))
 
     # -- inverting / checking a BWT (the reference's readme: "check the correctness of the BWT by ... inverting it")
     def unbwt(self, bwt):
         """host .bwt bytes (n+1, one 0) -> the text (numpy uint8, n bytes); PfpError(PFP_EFORMAT) if they are not a BWT"""
         b = _arr(bwt, np.uint8)
         out = np.empty(max(len(b) - 1, 0), dtype=np.uint8)
-        self._check(self.lib.pfp_unbwt(self._h, _ptr(b, C.c_uint8) if len(b) else None, C.c_uint64(len(b)),
-                                       _ptr(out, C.c_uint8) if len(out) else None))
+        self._check(self.lib.pfp_unbwt(self._h, b if len(b) else None, len(b), out if len(out) else None))
         return out
 
     def unbwt_dev(self, d_bwt_ptr, n_plus_1, d_text_ptr):
         """device .bwt (n_plus_1 bytes) -> device text (n_plus_1 - 1 bytes)"""
-        self._check(self.lib.pfp_unbwt_dev(self._h, C.c_void_p(d_bwt_ptr), C.c_uint64(n_plus_1), C.c_void_p(d_text_ptr) if d_text_ptr else None))
+        self._check(self.lib.pfp_unbwt_dev(self._h, d_bwt_ptr, n_plus_1, d_text_ptr))
 
     def check_bwt_dev(self, d_bwt_ptr, n_plus_1, d_text_ptr=None, d_sa5_ptr=None, d_ssa10_ptr=None, ssa_bytes=0, d_esa10_ptr=None, esa_bytes=0):
         """invert a device .bwt and compare with whatever is given (device pointers): -> dict of pfp_check_result"""
-        vp = lambda x: C.c_void_p(x) if x else None
         r = CheckResult()
-        self._check(self.lib.pfp_check_bwt_dev(self._h, C.c_void_p(d_bwt_ptr), C.c_uint64(n_plus_1), vp(d_text_ptr), vp(d_sa5_ptr),
-                                               vp(d_ssa10_ptr), C.c_uint64(ssa_bytes), vp(d_esa10_ptr), C.c_uint64(esa_bytes), C.byref(r)))
+        self._check(self.lib.pfp_check_bwt_dev(self._h, d_bwt_ptr, n_plus_1, d_text_ptr, d_sa5_ptr, d_ssa10_ptr, ssa_bytes, d_esa10_ptr,
+                                               esa_bytes, C.byref(r)))
         return r.as_dict()
 
     def check_bwt_files(self, base, text, flags=0):
         """<base>.bwt (and .sa / .ssa / .esa as flags ask) against a host text: -> dict of pfp_check_result"""
         t = _arr(text, np.uint8)
         r = CheckResult()
-        self._check(self.lib.pfp_check_bwt_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(t, C.c_uint8) if len(t) else None, C.c_int(-1),
-                                                 C.c_uint64(0), C.c_uint64(len(t)), C.c_int(flags), C.byref(r)))
+        self._check(self.lib.pfp_check_bwt_files(self._h, os.fsencode(base), t if len(t) else None, -1, 0, len(t), flags, C.byref(r)))
         return r.as_dict()
 
     # -- searching a BWT (csrc/fmsearch.hip): count and locate, pfpgpu.h states the definitions
     def fm_index(self, bwt, ssa=None, esa=None):
         """an FmIndex over host .bwt bytes and, for locate, the .ssa / .esa bytes (bigbwt -s -e); the index keeps its own copy"""
         import torch
-        dev = torch.device("cuda", self.device)
-        keep = []
-        for a in (bwt, ssa, esa):
-            if a is None:
-                keep.append(None)
-                continue
-            b = _arr(a, np.uint8)
-            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
-            if len(b):
-                t[:len(b)] = torch.from_numpy(b.copy())
-            keep.append((t, len(b)))
-        torch.cuda.synchronize(dev)
-        return self.fm_index_dev(keep[0][0].data_ptr(), keep[0][1], keep[1][0].data_ptr() if keep[1] else None, keep[1][1] if keep[1] else 0,
-                                 keep[2][0].data_ptr() if keep[2] else None, keep[2][1] if keep[2] else 0)
+        up = [self._upload_padded(a) for a in (bwt, ssa, esa)]
+        torch.cuda.synchronize(torch.device("cuda", self.device))
+        return self.fm_index_dev(*up[0][:2], *up[1][:2], *up[2][:2])
 
     def fm_index_dev(self, d_bwt, n_plus_1, d_ssa10=None, ssa_bytes=0, d_esa10=None, esa_bytes=0):
         """an FmIndex over device buffers (copied: the caller may free them afterwards)"""
         h = C.c_void_p()
-        vp = lambda x: C.c_void_p(x) if x else None
-        self._check(self.lib.pfp_fm_build_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes), vp(d_esa10),
-                                              C.c_uint64(esa_bytes), C.byref(h)))
+        self._check(self.lib.pfp_fm_build_dev(self._h, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, C.byref(h)))
         return FmIndex(self, h)
 
     def fm_index_files(self, base, flags=0):
         """an FmIndex over <base>.bwt and, when flags holds FLAG_SSA | FLAG_ESA, <base>.ssa / .esa"""
         h = C.c_void_p()
-        self._check(self.lib.pfp_fm_build_files(self._h, C.c_char_p(os.fsencode(base)), C.c_int(flags), C.byref(h)))
+        self._check(self.lib.pfp_fm_build_files(self._h, os.fsencode(base), flags, C.byref(h)))
         return FmIndex(self, h)
 
     # -- matching statistics and MEMs: an index that also keeps the text and the run-end values
@@ -1052,46 +896,30 @@ class Context:
         """an FmIndex for matching_statistics / mems over host .bwt, .ssa and .esa bytes; text=None: the text is inverted from
         the BWT on the GPU, else a numpy array / bytes of len(bwt) - 1 bytes"""
         import torch
-        dev = torch.device("cuda", self.device)
         if ssa is None or esa is None:
             raise PfpError(-1, "matching statistics need the run samples: .ssa and .esa (bigbwt -s -e writes them)")
-        keep = []
-        for a in (bwt, ssa, esa, text):
-            if a is None:
-                keep.append(None)
-                continue
-            b = _arr(a, np.uint8)
-            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
-            if len(b):
-                t[:len(b)] = torch.from_numpy(b.copy())
-            keep.append((t, len(b)))
-        if keep[3] is not None and keep[3][1] + 1 != keep[0][1]:
-            raise PfpError(-1, f"the text holds {keep[3][1]} bytes; the BWT holds {keep[0][1]} rows, so its text holds {max(keep[0][1], 1) - 1}")
-        torch.cuda.synchronize(dev)
-        return self.fm_index_ms_dev(keep[0][0].data_ptr(), keep[0][1], keep[1][0].data_ptr(), keep[1][1], keep[2][0].data_ptr(), keep[2][1],
-                                    keep[3][0].data_ptr() if keep[3] else None)
+        up = [self._upload_padded(a) for a in (bwt, ssa, esa, text)]
+        self._text_fits(text, up)
+        torch.cuda.synchronize(torch.device("cuda", self.device))
+        return self.fm_index_ms_dev(*up[0][:2], *up[1][:2], *up[2][:2], up[3][0])
+
+    @staticmethod
+    def _text_fits(text, up):
+        """up: the uploads of (bwt, ssa, esa, text)"""
+        if text is not None and up[3][1] + 1 != up[0][1]:
+            raise PfpError(-1, f"the text holds {up[3][1]} bytes; the BWT holds {up[0][1]} rows, so its text holds {max(up[0][1], 1) - 1}")
 
     def fm_index_ms_dev(self, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text=None):
         """the same over device buffers (copied); d_text: n_plus_1 - 1 device bytes, None: inverted"""
         h = C.c_void_p()
-        vp = lambda x: C.c_void_p(x) if x else None
-        self._check(self.lib.pfp_fm_build_ms_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes),
-                                                 vp(d_esa10), C.c_uint64(esa_bytes), vp(d_text), C.byref(h)))
+        self._check(self.lib.pfp_fm_build_ms_dev(self._h, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text, C.byref(h)))
         return FmIndex(self, h)
 
     def fm_index_ms_files(self, base, text=None):
         """the same over <base>.bwt / .ssa / .esa; text=None: inverted"""
         h = C.c_void_p()
-        if text is None:
-            self._check(self.lib.pfp_fm_build_ms_files(self._h, C.c_char_p(os.fsencode(base)), None, C.c_int(-1), C.c_uint64(0), C.c_uint64(0),
-                                                       C.byref(h)))
-        else:
-            t = _arr(text, np.uint8)
-            if not len(t):
-                t = np.zeros(1, dtype=np.uint8)[:0]
-            buf = np.concatenate([t, np.zeros(1, dtype=np.uint8)])       # (never a NULL pointer for an empty text)
-            self._check(self.lib.pfp_fm_build_ms_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(buf, C.c_uint8), C.c_int(-1), C.c_uint64(0),
-                                                       C.c_uint64(len(t)), C.byref(h)))
+        buf, n = _text_nul(text) if text is not None else (None, 0)
+        self._check(self.lib.pfp_fm_build_ms_files(self._h, os.fsencode(base), buf, -1, 0, n, C.byref(h)))
         return FmIndex(self, h)
 
     # -- the LCP array and thresholds (csrc/lcp.hip; pfpgpu.h states the definitions)
@@ -1099,24 +927,13 @@ class Context:
         """host .bwt / .ssa / .esa bytes (text=None: inverted) -> dict with "lcp" (n + 1 uint64) and / or "thr" (one uint64 per run)"""
         import torch
         dev = torch.device("cuda", self.device)
-        keep = []
-        for a in (bwt, ssa, esa, text):
-            if a is None:
-                keep.append(None)
-                continue
-            b = _arr(a, np.uint8)
-            t = torch.zeros(len(b) + 16, dtype=torch.uint8, device=dev)
-            if len(b):
-                t[:len(b)] = torch.from_numpy(b.copy())
-            keep.append((t, len(b)))
-        if keep[1] is None or keep[2] is None:
+        up = [self._upload_padded(a) for a in (bwt, ssa, esa, text)]
+        if ssa is None or esa is None:
             raise PfpError(-1, "the LCP array needs the run samples: .ssa and .esa (bigbwt -s -e writes them)")
-        if keep[3] is not None and keep[3][1] + 1 != keep[0][1]:
-            raise PfpError(-1, f"the text holds {keep[3][1]} bytes; the BWT holds {keep[0][1]} rows, so its text holds {max(keep[0][1], 1) - 1}")
-        n1 = keep[0][1]
-        args = (keep[0][0].data_ptr(), n1, keep[1][0].data_ptr(), keep[1][1], keep[2][0].data_ptr(), keep[2][1],
-                keep[3][0].data_ptr() if keep[3] else None)
-        runs = keep[1][1] // 10          # (a .ssa of another size is refused before anything is written)
+        self._text_fits(text, up)
+        n1 = up[0][1]
+        args = (*up[0][:2], *up[1][:2], *up[2][:2], up[3][0])
+        runs = up[1][1] // 10          # (a .ssa of another size is refused before anything is written)
         d_lcp = torch.zeros(n1 + 1, dtype=torch.int64, device=dev) if "lcp" in want else None
         d_thr = torch.zeros(runs + 1, dtype=torch.int64, device=dev) if "thr" in want else None
         torch.cuda.synchronize(dev)
@@ -1130,175 +947,132 @@ class Context:
 
     def lcp_dev(self, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text=None, d_lcp=None, d_thr=None):
         """device pointers; d_lcp: room for n_plus_1 uint64, d_thr: one uint64 per run; -> the number of runs (both None: only that)"""
-        vp = lambda x: C.c_void_p(x) if x else None
         runs = C.c_uint64()
-        self._check(self.lib.pfp_lcp_dev(self._h, C.c_void_p(d_bwt), C.c_uint64(n_plus_1), vp(d_ssa10), C.c_uint64(ssa_bytes), vp(d_esa10),
-                                         C.c_uint64(esa_bytes), vp(d_text), vp(d_lcp), vp(d_thr), C.byref(runs)))
+        self._check(self.lib.pfp_lcp_dev(self._h, d_bwt, n_plus_1, d_ssa10, ssa_bytes, d_esa10, esa_bytes, d_text, d_lcp, d_thr, C.byref(runs)))
         return int(runs.value)
 
     def lcp_files(self, base, text=None, want=("lcp", "thr")):
         """<base>.bwt / .ssa / .esa (text=None: inverted) -> <base>.lcp and / or <base>.thr_pos, 5-byte ints"""
         what = (LCP_LCP if "lcp" in want else 0) | (LCP_THR if "thr" in want else 0)
-        if text is None:
-            self._check(self.lib.pfp_lcp_files(self._h, C.c_char_p(os.fsencode(base)), None, C.c_int(-1), C.c_uint64(0), C.c_uint64(0), C.c_int(what)))
-        else:
-            t = _arr(text, np.uint8)
-            buf = np.concatenate([t, np.zeros(1, dtype=np.uint8)])       # (never a NULL pointer for an empty text)
-            self._check(self.lib.pfp_lcp_files(self._h, C.c_char_p(os.fsencode(base)), _ptr(buf, C.c_uint8), C.c_int(-1), C.c_uint64(0),
-                                               C.c_uint64(len(t)), C.c_int(what)))
+        buf, n = _text_nul(text) if text is not None else (None, 0)
+        self._check(self.lib.pfp_lcp_files(self._h, os.fsencode(base), buf, -1, 0, n, what))
 
     # -- multi-GPU chain, one rank's share (device pointers; collectives are the caller's: dist.py)
     def dist_propose_triggers(self, d_text_ptr, n, w, p):
-        hashes = (C.c_uint32 * 8)()
-        cnt = C.c_uint32()
-        self._check(self.lib.pfp_dist_propose_triggers(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_int(w),
-                                                       C.c_uint64(p), hashes, C.byref(cnt)))
+        hashes, cnt = (C.c_uint32 * 8)(), C.c_uint32()
+        self._check(self.lib.pfp_dist_propose_triggers(self._h, d_text_ptr, n, w, p, hashes, C.byref(cnt)))
         return [int(hashes[i]) for i in range(cnt.value)]
 
     def dist_local_parse(self, d_text_ptr, n, halo_len, w, p, is_first, is_last, global_offset, want_sai, extra=()):
-        sizes = (C.c_uint64 * 4)()
-        ex = (C.c_uint32 * max(1, len(extra)))(*extra)
-        self._check(self.lib.pfp_dist_local_parse(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_uint64(halo_len),
-                                                  C.c_int(w), C.c_uint64(p), C.c_int(int(is_first)), C.c_int(int(is_last)),
-                                                  C.c_uint64(global_offset), C.c_int(int(want_sai)), ex,
-                                                  C.c_uint32(len(extra)), sizes))
-        return dict(dict_bytes=int(sizes[0]), words=int(sizes[1]), phrases=int(sizes[2]), last_trigger=int(sizes[3]))
+        sizes, ex = (C.c_uint64 * 4)(), (C.c_uint32 * max(1, len(extra)))(*extra)
+        self._check(self.lib.pfp_dist_local_parse(self._h, d_text_ptr, n, halo_len, w, p, int(is_first), int(is_last), global_offset,
+                                                  int(want_sai), ex, len(extra), sizes))
+        return _local_sizes(sizes)
 
     def dist_parse_plan(self, first_bytes, w, p, ranks=1):
         """rank 0: (plan, first_hash) from the text's first bytes (pfp_dist_parse_plan); plan = four 64-bit integers"""
         fb = np.ascontiguousarray(np.frombuffer(bytes(first_bytes), dtype=np.uint8))
-        plan = (C.c_uint64 * 4)()
-        fh = C.c_uint64()
-        self._check(self.lib.pfp_dist_parse_plan(self._h, fb.ctypes.data_as(C.POINTER(C.c_uint8)) if len(fb) else None, C.c_uint64(len(fb)),
-                                                 C.c_int(w), C.c_uint64(p), C.c_uint32(ranks), plan, C.byref(fh)))
+        plan, fh = (C.c_uint64 * 4)(), C.c_uint64()
+        self._check(self.lib.pfp_dist_parse_plan(self._h, fb if len(fb) else None, len(fb), w, p, ranks, plan, C.byref(fh)))
         return [int(x) for x in plan], int(fh.value)
 
     def dist_propose_triggers2(self, d_text_ptr, n, halo_len, w, p, plan, d_sample_ptr, sample_cap):
-        hashes = (C.c_uint32 * 8)()
-        cnt = C.c_uint32()
-        ns = C.c_uint64()
+        hashes, cnt, ns = (C.c_uint32 * 8)(), C.c_uint32(), C.c_uint64()
         pl = (C.c_uint64 * 4)(*plan)
-        self._check(self.lib.pfp_dist_propose_triggers2(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_uint64(halo_len), C.c_int(w),
-                                                        C.c_uint64(p), pl, hashes, C.byref(cnt), C.c_void_p(d_sample_ptr) if sample_cap else None,
-                                                        C.c_uint64(sample_cap), C.byref(ns)))
+        self._check(self.lib.pfp_dist_propose_triggers2(self._h, d_text_ptr, n, halo_len, w, p, pl, hashes, C.byref(cnt),
+                                                        d_sample_ptr if sample_cap else None, sample_cap, C.byref(ns)))
         return [int(hashes[i]) for i in range(cnt.value)], int(ns.value)
 
     def dist_decide_density(self, d_samples_ptr, count, p, plan):
         pl = (C.c_uint64 * 4)(*plan)
-        self._check(self.lib.pfp_dist_decide_density(self._h, C.c_void_p(d_samples_ptr) if count else None, C.c_uint64(count), C.c_uint64(p), pl))
+        self._check(self.lib.pfp_dist_decide_density(self._h, d_samples_ptr if count else None, count, p, pl))
         return [int(x) for x in pl]
 
     def dist_local_parse2(self, d_text_ptr, n, halo_len, w, p, is_first, is_last, global_offset, want_sai, plan, extra=()):
-        sizes = (C.c_uint64 * 4)()
-        ex = (C.c_uint32 * max(1, len(extra)))(*extra)
-        pl = (C.c_uint64 * 4)(*plan)
-        self._check(self.lib.pfp_dist_local_parse2(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_uint64(halo_len),
-                                                   C.c_int(w), C.c_uint64(p), C.c_int(int(is_first)), C.c_int(int(is_last)),
-                                                   C.c_uint64(global_offset), C.c_int(int(want_sai)), pl, ex,
-                                                   C.c_uint32(len(extra)), sizes))
-        return dict(dict_bytes=int(sizes[0]), words=int(sizes[1]), phrases=int(sizes[2]), last_trigger=int(sizes[3]))
+        sizes, ex, pl = (C.c_uint64 * 4)(), (C.c_uint32 * max(1, len(extra)))(*extra), (C.c_uint64 * 4)(*plan)
+        self._check(self.lib.pfp_dist_local_parse2(self._h, d_text_ptr, n, halo_len, w, p, int(is_first), int(is_last), global_offset,
+                                                   int(want_sai), pl, ex, len(extra), sizes))
+        return _local_sizes(sizes)
 
     def dist_export_local(self, d_dict=None, d_occ=None, d_last=None, d_sai=None):
-        vp = lambda x: C.c_void_p(x) if x else None
-        self._check(self.lib.pfp_dist_export_local(self._h, vp(d_dict), vp(d_occ), vp(d_last), vp(d_sai)))
+        self._check(self.lib.pfp_dist_export_local(self._h, d_dict, d_occ, d_last, d_sai))
 
     def dist_global(self, d_union, union_bytes, d_union_occ, n_union, my_word_base, d_sym_out):
         info = (C.c_uint64 * 3)()
-        self._check(self.lib.pfp_dist_global(self._h, C.c_void_p(d_union), C.c_uint64(union_bytes), C.c_void_p(d_union_occ),
-                                             C.c_uint64(n_union), C.c_uint64(my_word_base), C.c_void_p(d_sym_out), info))
+        self._check(self.lib.pfp_dist_global(self._h, d_union, union_bytes, d_union_occ, n_union, my_word_base, d_sym_out, info))
         return dict(words=int(info[0]), dict_bytes=int(info[1]), rounds=int(info[2]))
 
     def dist_global_sort(self, d_union, union_bytes, d_union_occ, n_union, part, parts, d_wslot_out):
         info = (C.c_uint64 * 8)()
-        self._check(self.lib.pfp_dist_global_sort(self._h, C.c_void_p(d_union), C.c_uint64(union_bytes), C.c_void_p(d_union_occ),
-                                                  C.c_uint64(n_union), C.c_uint32(part), C.c_uint32(parts), C.c_void_p(d_wslot_out),
-                                                  info))
-        return dict(words=int(info[0]), dict_bytes=int(info[1]), rounds=int(info[2]), complete=bool(info[3]), slots=int(info[4]),
-                    slot_base=int(info[5]), emits=int(info[6]), index_bits=int(info[7]))
+        self._check(self.lib.pfp_dist_global_sort(self._h, d_union, union_bytes, d_union_occ, n_union, part, parts, d_wslot_out, info))
+        return _sort_info(info)
 
     def dist_partition_words(self, parts):
         """-> [(words, bytes)] this rank sends to every owner (hash-partitioned dedup)"""
         cnt = (C.c_uint64 * (2 * parts))()
-        self._check(self.lib.pfp_dist_partition_words(self._h, C.c_uint32(parts), cnt))
+        self._check(self.lib.pfp_dist_partition_words(self._h, parts, cnt))
         return [(int(cnt[2 * o]), int(cnt[2 * o + 1])) for o in range(parts)]
 
     def dist_export_partition(self, d_bytes, d_occ):
-        self._check(self.lib.pfp_dist_export_partition(self._h, C.c_void_p(d_bytes), C.c_void_p(d_occ)))
+        self._check(self.lib.pfp_dist_export_partition(self._h, d_bytes, d_occ))
 
     def dist_owner_dedup(self, d_bytes, nbytes, d_occ, n_words, d_pid_out):
         out = (C.c_uint64 * 2)()
-        vp = lambda x: C.c_void_p(x) if x else None
-        self._check(self.lib.pfp_dist_owner_dedup(self._h, vp(d_bytes), C.c_uint64(nbytes), vp(d_occ), C.c_uint64(n_words), vp(d_pid_out), out))
+        self._check(self.lib.pfp_dist_owner_dedup(self._h, d_bytes, nbytes, d_occ, n_words, d_pid_out, out))
         return int(out[0]), int(out[1])
 
     def dist_export_owned(self, d_bytes, d_occ):
-        vp = lambda x: C.c_void_p(x) if x else None
-        self._check(self.lib.pfp_dist_export_owned(self._h, vp(d_bytes), vp(d_occ)))
+        self._check(self.lib.pfp_dist_export_owned(self._h, d_bytes, d_occ))
 
     def dist_global_sort_distinct(self, d_dict, dict_bytes, d_occ, n_words, d_gid_sent, part, parts, d_wslot_out):
         info = (C.c_uint64 * 8)()
-        self._check(self.lib.pfp_dist_global_sort_distinct(self._h, C.c_void_p(d_dict), C.c_uint64(dict_bytes), C.c_void_p(d_occ),
-                                                           C.c_uint64(n_words), C.c_void_p(d_gid_sent), C.c_uint32(part), C.c_uint32(parts),
-                                                           C.c_void_p(d_wslot_out), info))
-        return dict(words=int(info[0]), dict_bytes=int(info[1]), rounds=int(info[2]), complete=bool(info[3]), slots=int(info[4]),
-                    slot_base=int(info[5]), emits=int(info[6]), index_bits=int(info[7]))
+        self._check(self.lib.pfp_dist_global_sort_distinct(self._h, d_dict, dict_bytes, d_occ, n_words, d_gid_sent, part, parts,
+                                                           d_wslot_out, info))
+        return _sort_info(info)
 
     def dist_global_finish(self, d_wslot_all, parts, my_word_base, d_sym_out):
-        self._check(self.lib.pfp_dist_global_finish(self._h, C.c_void_p(d_wslot_all), C.c_uint32(parts), C.c_uint64(my_word_base),
-                                                    C.c_void_p(d_sym_out)))
+        self._check(self.lib.pfp_dist_global_finish(self._h, d_wslot_all, parts, my_word_base, d_sym_out))
 
     def dist_parse_sort(self, d_sym, P, part, parts, d_sa_out):
         info = (C.c_uint64 * 4)()
-        self._check(self.lib.pfp_dist_parse_sort(self._h, C.c_void_p(d_sym), C.c_uint64(P), C.c_uint32(part), C.c_uint32(parts),
-                                                 C.c_void_p(d_sa_out), info))
+        self._check(self.lib.pfp_dist_parse_sort(self._h, d_sym, P, part, parts, d_sa_out, info))
         return dict(entries=int(info[0]), slot_base=int(info[1]), complete=bool(info[2]), rounds=int(info[3]))
 
     def dist_set_parse_sa(self, d_sa, count):
-        self._check(self.lib.pfp_dist_set_parse_sa(self._h, C.c_void_p(d_sa) if count else None, C.c_uint64(count)))
+        self._check(self.lib.pfp_dist_set_parse_sa(self._h, d_sa if count else None, count))
 
     def dist_merge(self, d_sym, P, d_last, d_sai, flags, n_total, out_lo, out_hi, d_bwt_slice, d_sa_slice=None):
-        self._check(self.lib.pfp_dist_merge(self._h, C.c_void_p(d_sym), C.c_uint64(P), C.c_void_p(d_last),
-                                            C.c_void_p(d_sai) if d_sai else None, C.c_int(flags), C.c_uint64(n_total),
-                                            C.c_uint64(out_lo), C.c_uint64(out_hi), C.c_void_p(d_bwt_slice),
-                                            C.c_void_p(d_sa_slice) if d_sa_slice else None))
+        self._check(self.lib.pfp_dist_merge(self._h, d_sym, P, d_last, d_sai, flags, n_total, out_lo, out_hi, d_bwt_slice, d_sa_slice))
 
     def dist_sample_runs(self, run_end, drop_edge, d_out10_ptr=None, cap_pairs=0):
         """.ssa / .esa pairs of the slice the last dist_merge emitted (-s / -e without an SA slice), from its run maps;
         returns the number of pairs (count only without an output pointer)"""
         k = C.c_uint64()
-        self._check(self.lib.pfp_dist_sample_runs(self._h, C.c_int(1 if run_end else 0), C.c_int(1 if drop_edge else 0),
-                                                  C.c_void_p(d_out10_ptr) if d_out10_ptr else None, C.c_uint64(cap_pairs), C.byref(k)))
+        self._check(self.lib.pfp_dist_sample_runs(self._h, bool(run_end), bool(drop_edge), d_out10_ptr, cap_pairs, C.byref(k)))
         return k.value
 
     def dist_release(self):
         self.lib.pfp_dist_release(self._h)
 
     def stage_text_dev(self, d_text_ptr, n, w=10):
-        self._check(self.lib.pfp_stage_text_dev(self._h, C.c_void_p(d_text_ptr), C.c_uint64(n), C.c_int(w)))
+        self._check(self.lib.pfp_stage_text_dev(self._h, d_text_ptr, n, w))
 
     def scan_staged(self, p=100):
         ne = C.c_uint64()
-        self._check(self.lib.pfp_scan_staged(self._h, C.c_uint64(p), C.byref(ne)))
+        self._check(self.lib.pfp_scan_staged(self._h, p, C.byref(ne)))
         return ne.value
 
     def scan_k1_enqueue(self, p=100):
-        self._check(self.lib.pfp_scan_k1_enqueue(self._h, C.c_uint64(p)))
+        self._check(self.lib.pfp_scan_k1_enqueue(self._h, p))
 
 
 def bigbwt_files_multi(text, base, devices, w=10, p=100, flags=0, halo=0):
     """pfp_bigbwt_files_multi: one BWT on len(devices) GPUs from this process (csrc/multi.hip); returns its statistics"""
     lib = load_library()
-
-    class MultiStats(C.Structure):
-        _fields_ = [(k, C.c_uint64) for k in ("n", "n_words", "n_phrases", "dict_size", "index_bits", "ranks", "sa_shares", "parse_shares")] + \
-                   [("ms_chain", C.c_double), ("ms_total", C.c_double), ("parse_density", C.c_double)]
     text = _arr(text, np.uint8)
-    st = MultiStats()
-    err = C.create_string_buffer(1024)
+    st, err = MultiStats(), C.create_string_buffer(1024)
     devs = (C.c_int * len(devices))(*devices)
-    lib.pfp_bigbwt_files_multi.restype = C.c_int
-    rc = lib.pfp_bigbwt_files_multi(C.c_int(len(devices)), devs, _ptr(text, C.c_uint8), C.c_uint64(len(text)), C.c_int(w), C.c_uint64(p),
-                                    C.c_int(flags), C.c_uint64(halo), str(base).encode(), C.byref(st), err, C.c_uint64(len(err)))
+    rc = lib.pfp_bigbwt_files_multi(len(devices), devs, text, len(text), w, p, flags, halo, str(base).encode(), C.byref(st), err, len(err))
     if rc != 0:
         raise PfpError(rc, err.value.decode(errors="replace"))
     return {k: getattr(st, k) for k, _ in MultiStats._fields_}
@@ -1309,6 +1083,6 @@ def multi_rccl_selftest(device=0, inject_failure=False):
     inject_failure: also the error path - a failure inside an open group, the communicators aborted"""
     lib = load_library()
     err = C.create_string_buffer(1024)
-    rc = lib.pfp_multi_rccl_selftest2(C.c_int(device), C.c_int(1 if inject_failure else 0), err, C.c_uint64(len(err)))
+    rc = lib.pfp_multi_rccl_selftest2(device, bool(inject_failure), err, len(err))
     if rc:
         raise PfpError(rc, err.value.decode(errors="replace"))
