@@ -31,10 +31,6 @@ int dev_call(pfp_fm *fm, F &&body, bool wait = true) {
   PFP_CATCH(c)
 }
 
-// a buffer leaves a call over device pointers: a block of the pool, as pfp_dev_free takes it
-template <class T>
-T *hand_out(DBuf<T> &b) { return std::exchange(b.p, nullptr); }
-
 // the body of an entry point that makes an index: build(the new index's FmIndex); *out gets the index once it stands
 template <class F>
 int build_call(pfp_ctx *c, pfp_fm **out, F &&build) {

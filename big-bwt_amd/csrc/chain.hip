@@ -134,34 +134,35 @@ static void run_chain_dev(pfp_ctx *c, Chain &ch, uint64_t n, int w, uint64_t p, 
 }
 
 // the reference's output files from the device results of a finished chain, produced one after the other into
-// `sink(name, device pointer, bytes)` (host buffers of a pfp_bwt_result, or files)
+// `sink(name, device pointer, bytes, buffer)` (host buffers of a pfp_bwt_result, files, or device blocks for the caller);
+// buffer: the pool block that was filled for this output alone - a sink may take it over (hand_out) - or nullptr for the BWT
 template <class Sink>
 static void emit_outputs(pfp_ctx *c, const uint8_t *d_bwt, const SaView &d_sa, uint64_t n_out, int flags, Sink &&sink) {
-  sink("bwt", d_bwt, n_out);
+  sink("bwt", d_bwt, n_out, nullptr);
   if (flags & PFP_FLAG_SA) {                       // .sa: n entries, SA[0]=n omitted (pfbwt.cpp:158-162)
     uint64_t cnt = n_out - 1;
     DBuf<uint8_t> packed(c, cnt * 5 + 16);
     PFP_REQUIRE(d_sa.dense, PFP_EINVAL, "full SA output without the SA values");
     pack5_dev(c, d_sa.dense + 1, cnt, packed.p);
-    sink("sa", packed.p, cnt * 5);
+    sink("sa", packed.p, cnt * 5, &packed);
     sync(c);
   }
   if (flags & PFP_FLAG_SSA) {
     DBuf<uint8_t> pairs;
     uint64_t k = sample_runs_dev(c, d_bwt, d_sa, n_out, false, pairs);
-    sink("ssa", pairs.p, k * 10);
+    sink("ssa", pairs.p, k * 10, &pairs);
     sync(c);
   }
   if (flags & PFP_FLAG_ESA) {
     DBuf<uint8_t> pairs;
     uint64_t k = sample_runs_dev(c, d_bwt, d_sa, n_out, true, pairs);
-    sink("esa", pairs.p, k * 10);
+    sink("esa", pairs.p, k * 10, &pairs);
     sync(c);
   }
   sync(c);
 }
 void fetch_outputs(pfp_ctx *c, const uint8_t *d_bwt, const SaView &d_sa, uint64_t n_out, int flags, pfp_bwt_result *out) {
-  emit_outputs(c, d_bwt, d_sa, n_out, flags, [&](const char *name, const uint8_t *d, uint64_t bytes) {
+  emit_outputs(c, d_bwt, d_sa, n_out, flags, [&](const char *name, const uint8_t *d, uint64_t bytes, DBuf<uint8_t> *) {
     uint8_t *h = fetch_bytes(c, d, bytes);
     if (name[0] == 'b') { out->bwt = h; out->bwt_size = bytes; }
     else if (name[0] == 's' && name[1] == 'a') { out->sa = h; out->sa_bytes = bytes; }
@@ -201,7 +202,7 @@ static int bigbwt_to_files(pfp_ctx *c, uint64_t n, int w, uint64_t p, int flags,
   const auto t2 = now();
   uint64_t sizes[4] = {0, 0, 0, 0};
   int n_mapped = 0;
-  emit_outputs(c, d_bwt.p, sa_view(ch.out), used + 1, flags, [&](const char *name, const uint8_t *d, uint64_t bytes) {
+  emit_outputs(c, d_bwt.p, sa_view(ch.out), used + 1, flags, [&](const char *name, const uint8_t *d, uint64_t bytes, DBuf<uint8_t> *) {
     sizes[name[0] == 'b' ? 0 : (name[1] == 'a' ? 1 : (name[0] == 's' ? 2 : 3))] = bytes;
     if (trace_host()) fprintf(stderr, "[pfp]   %.1f ms after the chain: .%s (%.2f GB) is on the device\n", ms(t2, now()), name, bytes / 1e9);
     MappedOut *mo = name[0] == 'b' ? (map_bwt ? &m_bwt : nullptr) : (name[0] == 's' && name[1] == 'a' && name[2] == 0 ? (map_sa ? &m_sa : nullptr) : nullptr);
@@ -323,15 +324,12 @@ int pfp_bigbwt_formats_dev(pfp_ctx *c, const void *d_text, uint64_t n, int w, ui
   uint64_t used = 0;
   run_chain_dev(c, ch, n, w, p, flags, (uint8_t *)d_bwt, nullptr, &used);
   if (n_used) *n_used = used;
-  emit_outputs(c, (const uint8_t *)d_bwt, sa_view(ch.out), used + 1, flags, [&](const char *name, const uint8_t *d, uint64_t bytes) {
+  emit_outputs(c, (const uint8_t *)d_bwt, sa_view(ch.out), used + 1, flags, [&](const char *name, const uint8_t *, uint64_t bytes, DBuf<uint8_t> *buf) {
     if (name[0] == 'b') return;
     const int k = name[1] == 'a' ? 0 : (name[0] == 's' ? 1 : 2);
-    // a block of the context's pool (handed back by pfp_dev_free): steady-state calls do not reach the driver
-    hipError_t e = hipSuccess;
-    void *q = c->pool.get(bytes ? bytes : 1, &e, __FILE__, __LINE__);
-    if (!q) throw Error(PFP_ENOMEM, std::string("device allocation of an output buffer failed: ") + hipGetErrorString(e));
-    PFP_HIP(hipMemcpyAsync(q, d, bytes, hipMemcpyDeviceToDevice, c->stream));
-    d_out[k] = q; out_bytes[k] = bytes;
+    // the block the output was written into goes to the caller as it is (a block of the context's pool, handed back by
+    // pfp_dev_free: steady-state calls do not reach the driver); never null, an empty output included
+    d_out[k] = hand_out(*buf); out_bytes[k] = bytes;
   });
   sync(c);
   return PFP_OK;

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <map>
 #include <thread>
+#include <utility>
 #include "../../include/pfpgpu.h"
 
 struct K1Scratch; struct DistState;      // api_debug.hip, api_dist.hip
@@ -296,6 +297,9 @@ struct DBuf {
   void zero() { PFP_HIP(hipMemsetAsync(p, 0, n * sizeof(T), ctx->stream)); }
   size_t bytes() const { return n * sizeof(T); }
 };
+// a buffer leaves a call over device pointers: a block of the pool, as pfp_dev_free takes it
+template <class T>
+inline T *hand_out(DBuf<T> &b) { return std::exchange(b.p, nullptr); }
 
 // counts for an exclusive sum over n + 1 entries, whose last entry is then the total: n elements for the caller to fill and a
 // zeroed one behind them (pad: elements allocated past the n, for kernels that store whole vectors)

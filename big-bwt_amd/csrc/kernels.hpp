@@ -45,8 +45,9 @@ uint64_t keep_nominal_cuts(pfp_ctx *c, DBuf<uint64_t> &d_ends, uint64_t ne, cons
 uint32_t window_hash_host(const uint8_t *win, int w, uint32_t seed);      // the seeded window hash of scan.hip, on the host
 void scan_flags(pfp_ctx *c, const uint8_t *tbase, uint64_t n, int w, uint64_t p, uint16_t *flags16,
                 uint32_t *block_counts, unsigned long long *first_bad, const KRParams *kp_override = nullptr);
+// classify (the window hash's first pass with automatic density): the settled pass also fills it, as classify_cuts(min_end = 0) would
 uint64_t scan_text(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t p, DBuf<uint64_t> &d_ends,
-                   uint64_t *n_used, const KRParams *kp_override = nullptr);
+                   uint64_t *n_used, const KRParams *kp_override = nullptr, CutSample *classify = nullptr);
 uint32_t propose_extra_triggers(pfp_ctx *c, const StagedText &tx, uint64_t n_used, int w, uint64_t max_phrase,
                                 const DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp);
 // what scan_text_adaptive did, for the diagnostic entry point pfp_debug_scan_chain (host memory only; the chain passes none)

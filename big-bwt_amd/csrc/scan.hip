@@ -211,11 +211,35 @@ __global__ __launch_bounds__(256) void kr_flag_kernel(const uint8_t *__restrict_
 // counted, not written (the caller repeats with the true size - a text whose windows trigger four times as often as 1 / p).
 constexpr unsigned long long kTagAgg = 1ull << 62, kTagPre = 2ull << 62, kTagMask = 3ull << 62;      // tag in the two top bits
 constexpr int kScanChunks = 16;                      // 4096-position chunks per tile: one look-back per 64 KB of text
-template <int W, bool FAST>
+// x = (h(window that ends at e) + seed) * K, the value kr_mask16<W, true> compares with kp.fthr: the same dot products over the
+// 16 bytes that end at e (the staging buffer's front padding covers a window at the text's start)
+template <int W>
+__device__ __forceinline__ uint32_t fast_x_at(const uint8_t *__restrict__ tbase, uint64_t e, uint32_t seed) {
+  const uint4 v = ld16u(tbase + e - 15);
+  const uint32_t d[4] = {v.w, v.z, v.y, v.x};      // d[q]: the four bytes that end 4 q bytes before e
+  constexpr int nq = (W + 3) / 4;
+  uint32_t h = seed;
+#pragma unroll
+  for (int q = 0; q < nq && q < 4; q++) h = __builtin_amdgcn_udot4(d[q], fast_mvec(W, q), h, false);
+  if constexpr (nq > 4) h = __builtin_amdgcn_udot4((uint32_t)tbase[e - 16] << 24, fast_mvec(W, 4), h, false);
+  return h * kFastK;
+}
+// what the first pass of the automatic density (CLS) leaves beside the cuts: nominal[o] = cut o lies inside the nominal threshold;
+// the positions of the sampled cuts (x < thr_sample) in nslots lists of slot_cap places, a tile's in list tile % nslots; slot_n
+// counts every sampled cut of a list, also those that found no room
+struct ScanClassify {
+  uint8_t *nominal;
+  uint64_t *sample_pos;
+  unsigned long long *slot_n;
+  uint64_t slot_cap;
+  uint32_t nslots, thr_sample;
+};
+template <int W, bool FAST, bool CLS = false>
 __global__ __launch_bounds__(256) void kr_scan_kernel(const uint8_t *__restrict__ tbase, uint64_t n, KRParams kp, uint64_t ntiles,
                                                       unsigned int *__restrict__ ticket, unsigned long long *__restrict__ state,
                                                       uint64_t *__restrict__ ends, uint64_t cap,
-                                                      unsigned long long *__restrict__ first_bad) {
+                                                      unsigned long long *__restrict__ first_bad, ScanClassify cls) {
+  static_assert(FAST || !CLS, "the cuts are classified by the window hash");
   __shared__ uint32_t wsum[kScanChunks][4];
   __shared__ unsigned int s_tile;
   __shared__ unsigned long long s_excl;
@@ -285,6 +309,62 @@ __global__ __launch_bounds__(256) void kr_scan_kernel(const uint8_t *__restrict_
     }
     chunk_base += (uint64_t)wsum[j][0] + wsum[j][1] + wsum[j][2] + wsum[j][3];
   }
+  if constexpr (CLS) {
+    // the tile's cuts once more while their windows are still in the cache: one cut per lane and round, so that the loads of a
+    // round do not wait for each other (inside the store loop above every cut of a lane would wait for the one before).
+    // The workgroup's own stores are read back past the vector cache: a neighbouring tile's line may sit there from before.
+    __syncthreads();
+    const uint64_t first = s_excl, last = chunk_base < cap ? chunk_base : cap;
+    unsigned long long *slot_n = cls.slot_n + tile % cls.nslots;
+    uint64_t *list = cls.sample_pos + (tile % cls.nslots) * cls.slot_cap;
+    for (uint64_t k0 = first + (uint64_t)wv * 64; k0 < last; k0 += 256) {      // (uniform in a wave)
+      const uint64_t k = k0 + (uint64_t)lane;
+      bool smp = false;
+      uint64_t e = 0;
+      if (k < last) {
+        e = __hip_atomic_load(&ends[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t x = fast_x_at<W>(tbase, e, kp.fseed);
+        cls.nominal[k] = x < kp.fthr_nom ? 1 : 0;
+        smp = x < cls.thr_sample;
+      }
+      const unsigned long long m = __ballot(smp);
+      if (!m) continue;
+      // (wave-aggregated append, a counter per list: one counter for all waves was 2.3 ms of contended atomics on 16 M cuts)
+      const int leader = __ffsll((long long)m) - 1;
+      unsigned long long base = 0;
+      if (lane == leader) base = atomicAdd(slot_n, (unsigned long long)__popcll(m));
+      base = __shfl(base, leader, 64);
+      const uint64_t at = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (smp && at < cls.slot_cap) list[at] = e;
+    }
+  }
+}
+
+constexpr uint64_t kSampleSlots = 1024;
+// hash of the 64 bytes that end with the window of the cut at e (the staging buffer has 64 bytes of front padding)
+__device__ __forceinline__ uint64_t context_hash(const uint8_t *__restrict__ tbase, uint64_t e) {
+  const uint8_t *q = tbase + e - 63;
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+  for (int j = 0; j < 8; j++) h = fmix64(h ^ ld8u(q + 8 * j)) + 0x632BE59BD9B4E019ull * (uint64_t)(j + 1);
+  return h;
+}
+// the context hashes of the sampled cuts a classifying scan (kr_scan_kernel<W, true, true>) has listed, list after list without
+// gaps: bps workgroups per list; out[] has room for the sum of the lists' lengths (each at most slot_cap)
+__global__ __launch_bounds__(256) void sample_context_kernel(const uint8_t *__restrict__ tbase, const uint64_t *__restrict__ sample_pos,
+                                                             const unsigned long long *__restrict__ slot_n, uint32_t nslots, uint64_t slot_cap,
+                                                             uint32_t bps, uint64_t *__restrict__ out) {
+  __shared__ unsigned long long ws[4];
+  const uint64_t slot = BID / bps;
+  if (slot >= nslots) return;      // (a workgroup of the padded last grid row)
+  unsigned long long before = 0;      // places the lists before this one take
+  for (uint64_t s = threadIdx.x; s < slot; s += 256) before += slot_n[s] < slot_cap ? slot_n[s] : slot_cap;
+  for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = before;
+  __syncthreads();
+  before = ws[0] + ws[1] + ws[2] + ws[3];
+  const uint64_t i = (BID % bps) * 256 + threadIdx.x, cnt = slot_n[slot] < slot_cap ? slot_n[slot] : slot_cap;
+  if (i < cnt) out[before + i] = context_hash(tbase, sample_pos[slot * slot_cap + i]);
 }
 
 // generic window size (w > 17): same arithmetic, bytes fetched from memory
@@ -489,17 +569,22 @@ void scan_flags(pfp_ctx *c, const uint8_t *tbase, uint64_t n, int w, uint64_t p,
 
 template <int W>
 static void launch_scan(pfp_ctx *c, uint64_t ntiles, const uint8_t *tbase, uint64_t n, const KRParams &kp, unsigned int *ticket,
-                        unsigned long long *state, uint64_t *ends, uint64_t cap, unsigned long long *fb) {
-  if (kp.fast) hipLaunchKernelGGL((kr_scan_kernel<W, true>), gdim(ntiles), gdim(256), 0, c->stream, tbase, n, kp, ntiles, ticket, state, ends, cap, fb);
-  else hipLaunchKernelGGL((kr_scan_kernel<W, false>), gdim(ntiles), gdim(256), 0, c->stream, tbase, n, kp, ntiles, ticket, state, ends, cap, fb);
+                        unsigned long long *state, uint64_t *ends, uint64_t cap, unsigned long long *fb, const ScanClassify *cls) {
+  if (cls) hipLaunchKernelGGL((kr_scan_kernel<W, true, true>), gdim(ntiles), gdim(256), 0, c->stream, tbase, n, kp, ntiles, ticket, state, ends, cap, fb, *cls);
+  else if (kp.fast) hipLaunchKernelGGL((kr_scan_kernel<W, true>), gdim(ntiles), gdim(256), 0, c->stream, tbase, n, kp, ntiles, ticket, state, ends, cap, fb, ScanClassify{});
+  else hipLaunchKernelGGL((kr_scan_kernel<W, false>), gdim(ntiles), gdim(256), 0, c->stream, tbase, n, kp, ntiles, ticket, state, ends, cap, fb, ScanClassify{});
 }
 
 // Full stage 1a on a staged text.  Returns the number of trigger ends; d_ends receives them.
 // If a byte <= 2 is found before n, *n_used is set to its position and the scan is redone on
 // the prefix (the reference stops reading there: newscan.cpp:364).
+// classify != nullptr (window hash without extra triggers, 4 <= w <= 17 only): the pass that settles also leaves the cuts' nominal
+// flags and the sorted context hashes of the sampled cuts there, as classify_cuts would with min_end = 0
 uint64_t scan_text(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t p, DBuf<uint64_t> &d_ends,
-                   uint64_t *n_used, const KRParams *kp_override) {
+                   uint64_t *n_used, const KRParams *kp_override, CutSample *classify) {
   PFP_REQUIRE(w >= 1 && w <= 4096, PFP_EINVAL, "window size out of range");
+  PFP_REQUIRE(!classify || (w >= 4 && w <= 17 && kp_override && kp_override->fast && !kp_override->nextra), PFP_EINVAL,
+              "scan: only the window hash's own cuts are classified");
   uint64_t cur_n = n;
   uint64_t cap_hint = 0;      // a pass that found more ends than it had room for tells the next one how many
   for (int attempt = 0; attempt < 4; attempt++) {
@@ -507,32 +592,49 @@ uint64_t scan_text(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t
     int nblocks = (int)cdiv64(nchunks, 256);
     *n_used = cur_n;
     if (nblocks == 0) { d_ends.alloc(c, 1); return 0; }
-    DBuf<unsigned long long> fbad(c, 1);
+    // the first special byte and, behind it, the counters of the sample lists (one read-back for both).  Every attempt starts
+    // from flags, lists and counters of its own: nothing of an abandoned one is looked at again.
+    // (a list per 16 tiles, at most kSampleSlots: a short text's sample has the whole room in one list)
+    const uint64_t ntiles = cdiv64((uint64_t)nblocks, kScanChunks);
+    const uint32_t nslots = classify ? (uint32_t)std::min<uint64_t>(kSampleSlots, std::max<uint64_t>(1, ntiles / 16)) : 0u;
+    DBuf<unsigned long long> fbad(c, 1 + nslots);
     PFP_HIP(hipMemsetAsync(fbad.p, 0xff, 8, c->stream));
+    if (nslots) PFP_HIP(hipMemsetAsync(fbad.p + 1, 0, (size_t)nslots * 8, c->stream));
     if (w >= 4 && w <= 17) {
       // one pass: masks, counts, look-back and placement in one kernel (kr_scan_kernel)
       const KRParams kp = kp_override ? *kp_override : make_kr_params(w, p);
-      const uint64_t ntiles = cdiv64((uint64_t)nblocks, kScanChunks);
       const uint64_t expect = (uint64_t)((double)(cur_n / (p ? p : 1)) * (kp.fast && kp.fdens > 1.0f ? (double)kp.fdens : 1.0));
       const uint64_t cap = cap_hint ? cap_hint : std::min<uint64_t>(cur_n, expect * 4 + 65536);
       d_ends.alloc(c, cap + 1);
       DBuf<unsigned long long> state(c, ntiles);
       DBuf<unsigned int> ticket(c, 1);
       state.zero(); ticket.zero();
+      ScanClassify cls{};
+      DBuf<uint64_t> sample_pos;
+      if (classify) {
+        // room for the sample: what classify_cuts gives `cap` cuts (an eighth of them and 64 per slot), shared out among the lists
+        const uint64_t scap = ((cap / 8 + kSampleSlots - 1) / kSampleSlots + 64) * kSampleSlots;
+        cls.slot_cap = cdiv64(scap, nslots);
+        classify->nominal.alloc(c, cap + 16);
+        sample_pos.alloc(c, cls.slot_cap * nslots);
+        cls.nominal = classify->nominal.p; cls.sample_pos = sample_pos.p; cls.slot_n = fbad.p + 1;
+        cls.nslots = nslots; cls.thr_sample = kp.fthr_nom / 16u;
+      }
       {
         KScope ks(c, "pfp::kr_scan_kernel", cur_n + 8 * std::min<uint64_t>(cap, expect));
         switch (w) {
-#define CASE(W) case W: launch_scan<W>(c, ntiles, tx.tbase(), cur_n, kp, ticket.p, state.p, d_ends.p, cap, fbad.p); break;
+#define CASE(W) case W: launch_scan<W>(c, ntiles, tx.tbase(), cur_n, kp, ticket.p, state.p, d_ends.p, cap, fbad.p, classify ? &cls : nullptr); break;
           CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17)
 #undef CASE
         }
         PFP_HIP(hipGetLastError());
       }
+      std::vector<unsigned long long> hb(1 + nslots);
       PFP_HIP(hipMemcpyAsync(c->h_scalars, state.p + (ntiles - 1), 8, hipMemcpyDeviceToHost, c->stream));
-      PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, fbad.p, 8, hipMemcpyDeviceToHost, c->stream));
+      PFP_HIP(hipMemcpyAsync(hb.data(), fbad.p, hb.size() * 8, hipMemcpyDeviceToHost, c->stream));
       sync(c);
       const uint64_t total = c->h_scalars[0] & ~kTagMask;
-      const uint64_t fb = c->h_scalars[1];
+      const uint64_t fb = hb[0];
       if (fb < cur_n) {
         PFP_REQUIRE(cur_n == n, PFP_EHIP, "scan: special byte after truncation");
         cur_n = fb;
@@ -541,6 +643,24 @@ uint64_t scan_text(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, uint64_t
         continue;
       }
       if (total > cap) { cap_hint = total; continue; }      // more triggers than room: once more with the true size
+      if (classify) {
+        PFP_HIP(hipMemsetAsync(classify->nominal.p + total, 0, 16, c->stream));
+        uint64_t ns = 0, counted = 0, longest = 0;
+        for (uint32_t s = 0; s < nslots; s++) {
+          const uint64_t kept = std::min<uint64_t>(hb[1 + s], cls.slot_cap);
+          ns += kept; counted += hb[1 + s]; longest = std::max(longest, kept);
+        }
+        classify->ns = ns; classify->counted = counted;
+        classify->hashes.alloc(c, ns);
+        if (ns) {
+          DBuf<uint64_t> h(c, ns);
+          const uint32_t bps = (uint32_t)cdiv64(longest, 256);
+          hipLaunchKernelGGL(sample_context_kernel, gdim((uint64_t)nslots * bps), gdim(256), 0, c->stream, tx.tbase(), sample_pos.p, fbad.p + 1,
+                             nslots, cls.slot_cap, bps, h.p);
+          PFP_HIP(hipGetLastError());
+          sort_keys_raw(c, h.p, classify->hashes.p, ns, 0, 64);
+        }
+      }
       return total;
     }
     DBuf<uint16_t> flags16(c, nchunks);
@@ -670,7 +790,8 @@ uint32_t propose_extra_triggers(pfp_ctx *c, const StagedText &tx, uint64_t n_use
 // twice are loci, contexts seen once the variants around them; where the variants outweigh the loci all cuts are kept, else the
 // cuts outside the nominal threshold are dropped again and the parse is the one -p asks for.
 // pfp_set_parse_density(ctx, 1) / PFP_PARSE_DENSITY=1 pins the nominal density; pfp_stats.parse_density reports what was used.
-constexpr uint64_t kSampleSlots = 1024;
+// (the single-GPU chain's first pass does this inside the scan kernel: kr_scan_kernel<W, true, true>, sample_context_kernel; the
+//  pass below is the multi-GPU shard's, whose sample starts behind its halo)
 // one pass over the cuts: is a cut inside the nominal threshold (nominal[k])?  is it one of the sample (x < thr_sample)? - then the
 // hash of the 64 bytes that end with its window goes on the sample list (wave-aggregated append: the list is sorted afterwards,
 // its order does not matter); sample_n counts every sampled cut, also those beyond the list's capacity
@@ -699,19 +820,29 @@ __global__ __launch_bounds__(256) void classify_ends_kernel(const uint8_t *__res
   uint64_t at = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
   if (at >= slot_cap) return;
   at += slot * slot_cap;
-  const uint8_t *q = tbase + e - 63;      // (the staging buffer has 64 bytes of front padding)
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-#pragma unroll
-  for (int j = 0; j < 8; j++) h = fmix64(h ^ ld8u(q + 8 * j)) + 0x632BE59BD9B4E019ull * (uint64_t)(j + 1);
-  sample_hash[at] = h;
+  sample_hash[at] = context_hash(tbase, e);
 }
-// out[0] = distinct values, out[1] = values that occur exactly once
-__global__ void count_distinct_kernel(const uint64_t *__restrict__ sorted, uint64_t ns, unsigned long long *__restrict__ out) {
-  const uint64_t k = (uint64_t)BID * blockDim.x + threadIdx.x;
-  const bool head = k < ns && (k == 0 || sorted[k] != sorted[k - 1]);
-  const bool single = head && (k + 1 == ns || sorted[k + 1] != sorted[k]);
-  const unsigned long long m = __ballot(head), m1 = __ballot(single);
-  if ((threadIdx.x & 63) == 0 && m) { atomicAdd(out, (unsigned long long)__popcll(m)); if (m1) atomicAdd(out + 1, (unsigned long long)__popcll(m1)); }
+// out[0] = distinct values, out[1] = values that occur exactly once.  A workgroup counts kDistinctTile consecutive values and adds
+// its two sums once (one pair of same-address atomics per wave was 0.16 ms for 0.5 M values)
+constexpr int kDistinctTile = 2048;
+__global__ __launch_bounds__(256) void count_distinct_kernel(const uint64_t *__restrict__ sorted, uint64_t ns, unsigned long long *__restrict__ out) {
+  __shared__ uint32_t ws[2][4];
+  uint32_t heads = 0, singles = 0;      // (the wave's, the same in every lane)
+#pragma unroll
+  for (int r = 0; r < kDistinctTile / 256; r++) {
+    const uint64_t k = (uint64_t)BID * kDistinctTile + (uint64_t)r * 256 + threadIdx.x;
+    const bool head = k < ns && (k == 0 || sorted[k] != sorted[k - 1]);
+    const bool single = head && (k + 1 == ns || sorted[k + 1] != sorted[k]);
+    heads += (uint32_t)__popcll(__ballot(head));
+    singles += (uint32_t)__popcll(__ballot(single));
+  }
+  if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = heads; ws[1][threadIdx.x >> 6] = singles; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t a = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3], b = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
+    if (a) atomicAdd(out, (unsigned long long)a);
+    if (b) atomicAdd(out + 1, (unsigned long long)b);
+  }
 }
 __global__ void gather_ends_kernel(const uint64_t *__restrict__ ends, const uint32_t *__restrict__ idx, uint64_t cnt, uint64_t *__restrict__ out) {
   const uint64_t k = (uint64_t)BID * blockDim.x + threadIdx.x;
@@ -753,7 +884,7 @@ bool sample_says_dense(pfp_ctx *c, const uint64_t *d_sorted, uint64_t ns, uint64
   if (ns < 1024 && !(counts && ns)) return false;
   DBuf<unsigned long long> nd(c, 2);
   nd.zero();
-  hipLaunchKernelGGL(count_distinct_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, d_sorted, ns, nd.p);
+  hipLaunchKernelGGL(count_distinct_kernel, gdim(cdiv64(ns, kDistinctTile)), gdim(256), 0, c->stream, d_sorted, ns, nd.p);
   PFP_HIP(hipMemcpyAsync(c->h_scalars, nd.p, 16, hipMemcpyDeviceToHost, c->stream));
   sync(c);
   const uint64_t distinct = c->h_scalars[0], singles = c->h_scalars[1], loci = distinct - singles;
@@ -779,10 +910,9 @@ uint64_t keep_nominal_cuts(pfp_ctx *c, DBuf<uint64_t> &d_ends, uint64_t ne, cons
 }
 // the scan cut at kp.fthr = the dense candidate: keep that (returns ne, *dense = true) or fall back to the nominal cuts
 // (d_ends compacted, kp.fthr lowered to the nominal threshold for every later rescan)
-static uint64_t choose_parse_density(pfp_ctx *c, const StagedText &tx, int w, uint64_t p, DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp, bool *dense,
+// cs: the cuts' flags and the sorted sample, as the first pass left them (scan_text with `classify`)
+static uint64_t choose_parse_density(pfp_ctx *c, uint64_t p, DBuf<uint64_t> &d_ends, uint64_t ne, KRParams &kp, const CutSample &cs, bool *dense,
                                      ScanReport *rep) {
-  CutSample cs;
-  classify_cuts(c, tx, w, d_ends, ne, kp, 0, cs);
   uint64_t counts[2] = {0, 0};
   *dense = sample_says_dense(c, cs.hashes.p, cs.ns, p, rep ? counts : nullptr);
   if (rep) {      // (diagnostic: the first pass's cuts and their flags, before the cuts are thinned out)
@@ -803,13 +933,17 @@ uint64_t scan_text_adaptive(pfp_ctx *c, const StagedText &tx, uint64_t n, int w,
   KRParams kp = c->fast_triggers ? make_fast_params(c, tx, n, w, p) : make_kr_params(w, p);
   *n_extra = 0;
   if (rep) { *rep = ScanReport(); rep->first = kp; }
-  uint64_t ne = scan_text(c, tx, n, w, p, d_ends, n_used, &kp);
+  // (automatic density: the first pass classifies its cuts as it finds them)
+  CutSample cs;
+  const bool choose = kp.fast && kp.fauto;
+  uint64_t ne = scan_text(c, tx, n, w, p, d_ends, n_used, &kp, choose ? &cs : nullptr);
   c->stats.parse_density = kp.fast ? (c->parse_density > 0 ? c->parse_density : 1.0) : 1.0;
-  if (kp.fast && kp.fauto && ne > 0) {
+  if (choose && ne > 0) {
     bool dense = false;
-    ne = choose_parse_density(c, tx, w, p, d_ends, ne, kp, &dense, rep);
+    ne = choose_parse_density(c, p, d_ends, ne, kp, cs, &dense, rep);
     c->stats.parse_density = dense ? (double)kp.fdens : 1.0;
   }
+  cs = CutSample();
   if (kp.fast && ne == 0) {      // no cut at all: the reference's own hash decides whether this text has a parse (bwtparse.c:244)
     kp = make_kr_params(w, p);
     ne = scan_text(c, tx, n, w, p, d_ends, n_used, &kp);
