@@ -1,7 +1,7 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
-// of a collection (seqmap.hip); extending seeds (fmextend.hip), aligning in a window (fmwindow.hip), edit scripts (fmcigar.hip) and
-// mapping reads (fmmap.hip).
+// of a collection (seqmap.hip); extending seeds (fmextend.hip), aligning in a window (fmwindow.hip), edit scripts (fmcigar.hip),
+// mapping reads (fmmap.hip) and chaining anchors (fmchain.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
 // (HostOut::take / take_offsets, fetch_group_offsets).  align, map and map_pairs also share their beginning (seed_call_begin: the
@@ -281,19 +281,20 @@ struct SeedCall : MsOnDevice {
   int k = 0;
   std::vector<uint64_t> moff;
 };
-// the caller has checked k, min_seed and the thresholds; noun: require_extendable's.  Without patterns nothing but the upload
+// the caller has checked k, min_seed and the thresholds; noun: require_extendable's (extendable = false: patterns of any length,
+// for the callers that put them through no band).  Without patterns nothing but the upload
 void seed_call_begin(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const char *noun, bool strands, uint64_t min_seed, int k,
-                     bool thresholds, SeedCall &s) {
+                     bool thresholds, SeedCall &s, bool extendable = true) {
   FmIndex &f = fm->f;
   pfp_ctx *c = f.c;
   s.min_seed = min_seed; s.k = k;
   s.in.upload(c, pat, pat_off, npat);                   // (decreasing offsets: PFP_EINVAL before the lengths are looked at)
-  require_extendable(pat_off, npat, noun);
+  if (extendable) require_extendable(pat_off, npat, noun);
   if (!npat) return;
   s.pat = s.in.pat.p; s.off = s.in.off.p; s.n = npat;
   uint64_t bytes = s.in.bytes;
   if (strands) {
-    fm_map_strands(f, s.pat, s.off, npat, s.rd);
+    fm_map_strands(f, s.pat, s.off, npat, s.rd, !extendable);
     s.in.pat.release();
     s.pat = s.rd.pat.p; s.off = s.rd.off.p; s.n = 2 * npat;
     bytes = 2 * (pat_off[npat] - pat_off[0]);
@@ -326,6 +327,29 @@ void seed_groups(pfp_fm *fm, const SeedCall &s, uint64_t unit, uint64_t max_aln,
     MapCands cd;
     fm_map_cands_ms(fm->f, s.pat, s.off + p0, np, s.min_seed, s.k, max_aln, s.len.p, s.pos.p, g_moff.p, goff[np], cd, hold_keys ? &keys : nullptr);
     body(p0, np, cd);
+  }
+}
+
+// The groups of a call that lists anchors (fmchain.hip), cut as seed_groups cuts them: body(first pattern, patterns, their
+// anchor offsets counted from the group's first, the triples, their number, the skipped MEMs per pattern) runs per group
+template <class F>
+void anchor_groups(pfp_fm *fm, const SeedCall &s, uint64_t unit, uint64_t max_occ, F &&body) {
+  pfp_ctx *c = fm->f.c;
+  if (!s.n) return;
+  const uint64_t budget = seq_budget(), nunit = s.n / unit;
+  std::vector<uint64_t> uoff(nunit + 1), goff;
+  for (uint64_t u = 0; u <= nunit; u++) uoff[u] = s.moff[unit * u];
+  for (uint64_t u0 = 0, u1; u0 < nunit; u0 = u1) {
+    u1 = group_end(uoff.data(), u0, nunit, budget);
+    const uint64_t p0 = unit * u0, np = unit * (u1 - u0);
+    goff.resize(np + 1);
+    for (uint64_t i = 0; i <= np; i++) goff[i] = s.moff[p0 + i] - s.moff[p0];
+    DBuf<uint64_t> g_moff(c, np + 1), d_aoff(c, np + 1), d_anc;
+    DBuf<uint32_t> d_skip(c, np);
+    h2d(c, g_moff.p, goff.data(), np + 1);
+    const uint64_t total = fm_anchors_ms(fm->f, s.pat, s.off + p0, np, s.min_seed, max_occ, s.len.p, s.pos.p, g_moff.p, goff[np], d_aoff.p, d_anc,
+                                         d_skip.p);
+    body(p0, np, d_aoff, d_anc, total, d_skip);
   }
 }
 
@@ -895,6 +919,152 @@ int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, ui
     h_md.take(c, d_md.p, md_off[p0 + np] - md_off[p0]);
   });
   *cig = h_cig.release(); *md = h_md.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+// ---------------------------------------------------------------- chaining anchors (fmchain.hip)
+int pfp_fm_anchors_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                       int thresholds, uint64_t *d_anc_off, uint64_t *d_anc, uint32_t *d_skipped) {
+  if (!fm || !d_anc_off || (npat && !d_pat_off)) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    pfp_ctx *c = fm->f.c;
+    DBuf<uint64_t> anc;
+    const uint64_t total = fm_anchors(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, max_occ, thresholds != 0, d_anc_off, anc, d_skipped);
+    if (d_anc && total) PFP_HIP(hipMemcpyAsync(d_anc, anc.p, 24 * total, hipMemcpyDeviceToDevice, c->stream));
+    sync(c);                                            // (the triples go back when this returns)
+  });
+}
+
+int pfp_fm_anchors(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, int thresholds,
+                   uint64_t *anc_off, uint64_t **anc, uint32_t *skipped) {
+  if (!fm || !anc_off || !anc || (npat && !pat_off)) return PFP_EINVAL;
+  *anc = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_anchors_check(fm->f, min_seed, max_occ, thresholds != 0);
+  SeedCall s;
+  seed_call_begin(fm, pat, pat_off, npat, "pattern", false, min_seed, 0, thresholds != 0, s, false);
+  HostOut<uint64_t> h_anc;
+  std::vector<uint64_t> go;
+  anc_off[0] = 0;
+  anchor_groups(fm, s, 1, max_occ, [&](uint64_t p0, uint64_t np, DBuf<uint64_t> &d_aoff, DBuf<uint64_t> &d_anc, uint64_t total, DBuf<uint32_t> &d_skip) {
+    fetch_group_offsets(c, d_aoff.p, np, go, anc_off + p0);
+    if (skipped) { d2h(c, skipped + p0, d_skip.p, np); sync(c); }
+    h_anc.take(c, d_anc.p, 3 * total);
+  });
+  *anc = h_anc.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_chain_dev(pfp_fm *fm, const uint64_t *d_anc_off, const uint64_t *d_anc, uint64_t npat, uint64_t max_gap, uint64_t band,
+                     uint64_t min_score, uint64_t max_chains, uint64_t *d_chain_off, uint32_t *d_score, uint32_t *d_n, uint32_t *d_qs,
+                     uint32_t *d_qe, uint64_t *d_ts, uint64_t *d_te, uint32_t *d_match) {
+  if (!fm || !d_chain_off || (npat && !d_anc_off)) return PFP_EINVAL;
+  const bool fill = d_score || d_n || d_qs || d_qe || d_ts || d_te || d_match;
+  if (fill && !(d_score && d_n && d_qs && d_qe && d_ts && d_te && d_match)) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    ChainSel sel;
+    fm_chains_run(fm->f, d_anc_off, d_anc, npat, max_gap, band, min_score, max_chains, d_chain_off, sel);
+    if (fill) fm_chains_write(fm->f, d_anc, npat, d_chain_off, sel, ChainOut{d_score, d_n, d_qs, d_qe, d_ts, d_te, d_match});
+    sync(fm->f.c);                                      // (what the write reads goes back when this returns)
+  });
+}
+
+int pfp_fm_chain(pfp_fm *fm, const uint64_t *anc_off, const uint64_t *anc, uint64_t npat, uint64_t max_gap, uint64_t band, uint64_t min_score,
+                 uint64_t max_chains, uint64_t *chain_off, uint32_t **score, uint32_t **n, uint32_t **qs, uint32_t **qe, uint64_t **ts,
+                 uint64_t **te, uint32_t **match) {
+  if (!fm || !chain_off || !score || !n || !qs || !qe || !ts || !te || !match || (npat && !anc_off)) return PFP_EINVAL;
+  *score = nullptr; *n = nullptr; *qs = nullptr; *qe = nullptr; *ts = nullptr; *te = nullptr; *match = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_chain_check(fm->f, max_gap, band, min_score);
+  chain_off[0] = 0;
+  if (!npat) return PFP_OK;
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(anc_off[p] <= anc_off[p + 1], PFP_EINVAL, "anchor offsets decrease at pattern " + std::to_string(p));
+  const uint64_t A = anc_off[npat];
+  PFP_REQUIRE(anc || !A, PFP_EINVAL, "no anchors");
+  DBuf<uint64_t> d_aoff(c, npat + 1), d_anc(c, 3 * A), d_coff(c, npat + 1);
+  h2d(c, d_aoff.p, anc_off, npat + 1);
+  if (A) h2d(c, d_anc.p, anc, 3 * A);
+  ChainSel sel;
+  fm_chains_run(fm->f, d_aoff.p, d_anc.p, npat, max_gap, band, min_score, max_chains, d_coff.p, sel);
+  const uint64_t C = sel.total;
+  DBuf<uint32_t> d32(c, 5 * C);
+  DBuf<uint64_t> d64(c, 2 * C);
+  fm_chains_write(fm->f, d_anc.p, npat, d_coff.p, sel, ChainOut{d32.p, d32.p + C, d32.p + 2 * C, d32.p + 3 * C, d64.p, d64.p + C, d32.p + 4 * C});
+  d2h(c, chain_off, d_coff.p, npat + 1);
+  sync(c);
+  HostOut<uint32_t> h_score, h_n, h_qs, h_qe, h_match;
+  HostOut<uint64_t> h_ts, h_te;
+  h_score.take(c, d32.p, C); h_n.take(c, d32.p + C, C); h_qs.take(c, d32.p + 2 * C, C); h_qe.take(c, d32.p + 3 * C, C);
+  h_match.take(c, d32.p + 4 * C, C); h_ts.take(c, d64.p, C); h_te.take(c, d64.p + C, C);
+  *score = h_score.release(); *n = h_n.release(); *qs = h_qs.release(); *qe = h_qe.release(); *ts = h_ts.release(); *te = h_te.release();
+  *match = h_match.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_map_long_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                        uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *d_hit_off,
+                        uint8_t *d_mapq, uint64_t *d_nchains, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off, uint64_t *d_ts,
+                        uint64_t *d_te, uint32_t *d_qs, uint32_t *d_qe, uint32_t *d_score, uint32_t *d_n, uint32_t *d_match) {
+  if (!fm || !d_hit_off || (npat && (!d_pat_off || !d_mapq || !d_nchains))) return PFP_EINVAL;
+  const bool fill = d_strand || d_seq || d_off || d_ts || d_te || d_qs || d_qe || d_score || d_n || d_match;
+  if (fill && !(d_strand && d_seq && d_off && d_ts && d_te && d_qs && d_qe && d_score && d_n && d_match)) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    const LongOut out{d_strand, d_seq, d_off, d_ts, d_te, d_qs, d_qe, d_score, d_n, d_match};
+    fm_map_long(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec, thresholds != 0, d_hit_off,
+                d_mapq, d_nchains, fill ? &out : nullptr);
+  });
+}
+
+int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                    uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
+                    uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
+                    uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match) {
+  if (!fm || !hit_off || !strand || !seq || !off || !ts || !te || !qs || !qe || !score || !n || !match ||
+      (npat && (!pat_off || !mapq || !nchains)))
+    return PFP_EINVAL;
+  *strand = nullptr; *seq = nullptr; *off = nullptr; *ts = nullptr; *te = nullptr; *qs = nullptr; *qe = nullptr; *score = nullptr; *n = nullptr;
+  *match = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  FmIndex &f = fm->f;
+  fm_anchors_check(f, min_seed, max_occ, thresholds != 0);
+  fm_chain_check(f, max_gap, band, min_score);
+  SeedCall s;
+  seed_call_begin(fm, pat, pat_off, npat, "read", true, min_seed, 0, thresholds != 0, s, false);
+  HostOut<uint8_t> h_strand;
+  HostOut<uint32_t> h_seq, h_qs, h_qe, h_score, h_n, h_match;
+  HostOut<uint64_t> h_off, h_ts, h_te;
+  std::vector<uint64_t> go;
+  hit_off[0] = 0;
+  anchor_groups(fm, s, 2, max_occ, [&](uint64_t p0, uint64_t np2, DBuf<uint64_t> &d_aoff, DBuf<uint64_t> &d_anc, uint64_t, DBuf<uint32_t> &) {
+    const uint64_t r0 = p0 / 2, np = np2 / 2;           // the group's reads
+    DBuf<uint64_t> d_hoff(c, np + 1), d_nc(c, np);
+    DBuf<uint8_t> d_mapq(c, np);
+    LongSel sel;
+    fm_map_long_select(f, d_aoff.p, d_anc.p, np, max_gap, band, min_score, max_sec, d_hoff.p, d_mapq.p, d_nc.p, sel);
+    fetch_group_offsets(c, d_hoff.p, np, go, hit_off + r0);
+    d2h(c, mapq + r0, d_mapq.p, np);
+    d2h(c, nchains + r0, d_nc.p, np);
+    sync(c);
+    const uint64_t H = sel.H;
+    DBuf<uint8_t> d_strand(c, H);
+    DBuf<uint32_t> d32(c, 6 * H);
+    DBuf<uint64_t> d64(c, 3 * H);
+    fm_map_long_fill(f, s.off + p0, np, d_hoff.p, sel,
+                     LongOut{d_strand.p, d32.p, d64.p, d64.p + H, d64.p + 2 * H, d32.p + H, d32.p + 2 * H, d32.p + 3 * H, d32.p + 4 * H, d32.p + 5 * H});
+    sync(c);
+    h_strand.take(c, d_strand.p, H); h_seq.take(c, d32.p, H); h_off.take(c, d64.p, H); h_ts.take(c, d64.p + H, H); h_te.take(c, d64.p + 2 * H, H);
+    h_qs.take(c, d32.p + H, H); h_qe.take(c, d32.p + 2 * H, H); h_score.take(c, d32.p + 3 * H, H); h_n.take(c, d32.p + 4 * H, H);
+    h_match.take(c, d32.p + 5 * H, H);
+  });
+  *strand = h_strand.release(); *seq = h_seq.release(); *off = h_off.release(); *ts = h_ts.release(); *te = h_te.release();
+  *qs = h_qs.release(); *qe = h_qe.release(); *score = h_score.release(); *n = h_n.release(); *match = h_match.release();
   return PFP_OK;
   PFP_CATCH(c)
 }

@@ -186,16 +186,17 @@ __device__ __forceinline__ uint64_t lce16(const uint8_t *__restrict__ text, uint
 
 // ---------------------------------------------------------------- kernels with one group of 16 lanes per pattern
 // their start: the code table into LDS (code[256], every thread of the block), this lane's place in its group, the group's pattern
-// and its offsets.  false: no such pattern (whole groups leave together: the shuffles stay inside groups)
+// and its offsets: off[p] .. off[p + 1], or off[p] .. end[p] where the ends are given apart (strings that lie anywhere in the
+// buffer: fm_count_spans).  false: no such pattern (whole groups leave together: the shuffles stay inside groups)
 struct PatGroup { int gl; uint64_t p, o0, o1; };
 __device__ __forceinline__ bool pat_group(uint8_t *code, const uint8_t *__restrict__ codes, const uint64_t *__restrict__ off, uint64_t npat,
-                                          PatGroup &g) {
+                                          PatGroup &g, const uint64_t *__restrict__ end = nullptr) {
   code[threadIdx.x] = codes[threadIdx.x];
   __syncthreads();
   g.gl = threadIdx.x & 15;
   g.p = BID * (kTB / 16) + (threadIdx.x >> 4);
   if (g.p >= npat) return false;
-  g.o0 = off[g.p]; g.o1 = off[g.p + 1];
+  g.o0 = off[g.p]; g.o1 = end ? end[g.p] : off[g.p + 1];
   return true;
 }
 

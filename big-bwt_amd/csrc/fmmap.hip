@@ -234,9 +234,9 @@ void fm_map_check(const FmIndex &f, int k, uint64_t min_seed, bool thresholds) {
   fm_align_check(f, k, min_seed, thresholds);
 }
 
-void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out) {
+void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out, bool any_length) {
   pfp_ctx *c = f.c;
-  fm_extend_check_patterns(f, pat_off, npat);           // (PFP_ELIMIT before anything is sized by a length)
+  if (!any_length) fm_extend_check_patterns(f, pat_off, npat);      // (PFP_ELIMIT before anything is sized by a length)
   out.off.alloc(c, 2 * npat + 1);
   uint64_t bytes = 0;
   {

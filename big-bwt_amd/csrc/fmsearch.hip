@@ -137,13 +137,14 @@ __global__ void __launch_bounds__(kTB) fm_pairs(const uint8_t *__restrict__ ssa,
 }
 
 // ---------------------------------------------------------------- searches
-// one group of 16 lanes per pattern
+// one group of 16 lanes per pattern: pat[off[p] .. off[p + 1]), or pat[off[p] .. end[p]) where end is given
 template <class I>
-__global__ void __launch_bounds__(kTB) fm_count_k(FmArgs<I> a, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
-                                                  uint64_t *__restrict__ sp_out, uint64_t *__restrict__ ep_out, uint64_t *__restrict__ first_out) {
+__global__ void __launch_bounds__(kTB) fm_count_k(FmArgs<I> a, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off,
+                                                  const uint64_t *__restrict__ end, uint64_t npat, uint64_t *__restrict__ sp_out,
+                                                  uint64_t *__restrict__ ep_out, uint64_t *__restrict__ first_out) {
   __shared__ uint8_t code[256];
   PatGroup g;
-  if (!pat_group(code, a.codes, off, npat, g)) return;
+  if (!pat_group(code, a.codes, off, npat, g, end)) return;
   const int gl = g.gl;
   const uint64_t p = g.p, o0 = g.o0, o1 = g.o1;
   uint64_t sp = 0, ep = o1 < o0 ? 0 : a.n1, first = a.n1 - 1;      // (decreasing offsets: no pattern, no occurrence)
@@ -535,15 +536,20 @@ void fm_mem_triples(FmIndex &f, const uint64_t *pat_off, uint64_t npat, const ui
   PFP_HIP(hipGetLastError());
 }
 
-void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
+void fm_count_spans(FmIndex &f, const uint8_t *pat, const uint64_t *begin, const uint64_t *end, uint64_t npat, uint64_t *sp, uint64_t *ep,
+                    uint64_t *first) {
   pfp_ctx *c = f.c;
   require_toehold(f, first != nullptr);
   if (!npat) return;
   KScope ks(c, "fm_count", 0);
   by_width(f, [&](auto w) {
-    fm_count_k<decltype(w)><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<decltype(w)>(f), pat, pat_off, npat, sp, ep, first);
+    fm_count_k<decltype(w)><<<gdim(cdiv(npat, kTB / 16)), kTB, 0, c->stream>>>(args_of<decltype(w)>(f), pat, begin, end, npat, sp, ep, first);
   });
   PFP_HIP(hipGetLastError());
+}
+
+void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first) {
+  fm_count_spans(f, pat, pat_off, nullptr, npat, sp, ep, first);
 }
 
 template <class I>

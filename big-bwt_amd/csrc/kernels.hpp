@@ -394,6 +394,9 @@ void fm_ms_thr(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t
 template <class I> void lcp_by_rows(pfp_ctx *c, const uint8_t *bwt, uint64_t n1, const I *plcp, I *lcp);
 // device pointers; first may be NULL (needs samples otherwise)
 void fm_count(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t *sp, uint64_t *ep, uint64_t *first);
+// the same kernel over strings that lie anywhere in pat: string j is pat[begin[j] .. end[j]) (end == NULL: begin[j + 1])
+void fm_count_spans(FmIndex &f, const uint8_t *pat, const uint64_t *begin, const uint64_t *end, uint64_t npat, uint64_t *sp, uint64_t *ep,
+                    uint64_t *first);
 // out_off[0..npat] (device): exclusive sums of min(ep - sp, max_occ); pos == NULL: only those
 void fm_locate(FmIndex &f, uint64_t npat, const uint64_t *sp, const uint64_t *ep, const uint64_t *first, uint64_t max_occ,
                uint64_t *out_off, uint64_t *pos);
@@ -495,7 +498,8 @@ struct MapReads {
   DBuf<uint8_t> pat;
   DBuf<uint64_t> off;
 };
-void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out);
+// (any_length: reads that go through no band - fmchain.hip - skip fm_extend_check_patterns)
+void fm_map_strands(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, MapReads &out, bool any_length = false);
 // the candidates of some patterns, as fm_align gives them: aln_off (one entry more than the patterns) and the A = aln_off[last]
 // triples start / end / dist.  The triples serve fm_map_select alone: its callers drop them before they fill or pair
 struct MapCands {
@@ -534,6 +538,59 @@ void fm_map(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t np
             uint64_t *hit_off, uint8_t *mapq, uint64_t *nhits, uint8_t *strand, uint32_t *seq, uint64_t *off, uint64_t *start, uint8_t *dist,
             uint64_t *cig_off, DBuf<uint32_t> &cig, uint64_t *md_off, DBuf<uint8_t> &md);
 
+// chaining anchors (fmchain.hip; pfpgpu.h, "Chaining anchors", states the definitions).  Device pointers.  An index without text
+// or samples, min_seed = 0, max_occ outside 1 .. 65536, thresholds wanted of an index without them -> PFP_EINVAL
+void fm_anchors_check(const FmIndex &f, uint64_t min_seed, uint64_t max_occ, bool thresholds);
+// the anchors of npat patterns whose matching statistics stand (len / pos as fm_ms or fm_ms_thr gave them; mem_off[0..npat] as
+// fm_mems gave them for the same patterns, counted from the first, M = mem_off[npat]): anc_off[0..npat] and, sized here, the
+// triples; skipped (npat, may be NULL).  2^32 - 1 or more occurrences -> PFP_ELIMIT.  Returns the number of anchors
+uint64_t fm_anchors_ms(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                       const uint32_t *len, const uint64_t *pos, const uint64_t *mem_off, uint64_t M, uint64_t *anc_off, DBuf<uint64_t> &anc,
+                       uint32_t *skipped);
+// matching statistics (thresholds: by fm_ms_thr), MEMs and fm_anchors_ms
+uint64_t fm_anchors(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, bool thresholds,
+                    uint64_t *anc_off, DBuf<uint64_t> &anc, uint32_t *skipped);
+// G or B outside 1 .. 2^31 - 1, S = 0 -> PFP_EINVAL
+void fm_chain_check(const FmIndex &f, uint64_t max_gap, uint64_t band, uint64_t min_score);
+// what fm_chains_run leaves for fm_chains_write: per anchor that ends a kept chain its fields, and the kept chains' end anchors
+// in the order of output inside every pattern's segment
+struct ChainSel {
+  DBuf<uint32_t> score, n, qs, match, order, sb;
+  DBuf<uint64_t> ts;
+  uint64_t total = 0;
+};
+// the programme and the peel over npat patterns' anchors (anc_off as the caller gave it: offsets that decrease, anchors out of
+// order, len = 0 or i + len >= 2^32 -> PFP_EINVAL): chain_off[0..npat], at most max_chains per pattern (0: all)
+void fm_chains_run(FmIndex &f, const uint64_t *anc_off, const uint64_t *anc, uint64_t npat, uint64_t max_gap, uint64_t band, uint64_t min_score,
+                   uint64_t max_chains, uint64_t *chain_off, ChainSel &sel);
+struct ChainOut {
+  uint32_t *score, *n, *qs, *qe;
+  uint64_t *ts, *te;
+  uint32_t *match;
+};
+void fm_chains_write(FmIndex &f, const uint64_t *anc, uint64_t npat, const uint64_t *chain_off, const ChainSel &sel, const ChainOut &out);
+// what fm_map_long_select leaves for fm_map_long_fill: both strands' patterns, their chains and the reads' order of them
+struct LongSel {
+  MapReads rd;
+  DBuf<uint64_t> chain_off, ts, te;
+  DBuf<uint32_t> score, n, qs, qe, match, order;
+  uint64_t H = 0;
+};
+struct LongOut {
+  uint8_t *strand;
+  uint32_t *seq;
+  uint64_t *off, *ts, *te;
+  uint32_t *qs, *qe, *score, *n, *match;
+};
+// the chains of npat reads from their 2 npat strands' anchors (anc_off2, anc; pat2_off = fm_map_strands' offsets, moved into
+// sel.rd by the caller or given): hit_off[0..npat], mapq and nchains
+void fm_map_long_select(FmIndex &f, const uint64_t *anc_off2, const uint64_t *anc, uint64_t npat, uint64_t max_gap, uint64_t band,
+                        uint64_t min_score, uint64_t max_sec, uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains, LongSel &sel);
+void fm_map_long_fill(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, const uint64_t *hit_off, const LongSel &sel, const LongOut &out);
+// all of it over device patterns; out == NULL: hit_off, mapq and nchains only
+void fm_map_long(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, uint64_t max_gap,
+                 uint64_t band, uint64_t min_score, uint64_t max_sec, bool thresholds, uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains,
+                 const LongOut *out);
 // mapping read pairs (fmpair.hip; pfpgpu.h, "Mapping read pairs", states the definitions).  Device pointers.  fm_map_check's
 // errors; an odd number of reads, min_ins > max_ins, max_ins > PFP_FM_WINDOW_MAX_W or anchors outside 1 ..
 // PFP_FM_PAIR_MAX_ANCHORS -> PFP_EINVAL

@@ -7,6 +7,8 @@
  *   bwtsearch --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename
  *   bwtsearch --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] ... READS basename
+ *   bwtsearch --paf [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE]
+ *             [--seqs=FILE] [--device D] READS basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
  * not start an empty one).  One output line per pattern: its count, or with -l `count<TAB>pos pos ...`, the positions in row
@@ -60,6 +62,16 @@
  * 0; TLEN as the header defines it.  An unmapped read whose mate is mapped takes the mate's RNAME and POS, with RNEXT =, MAPQ 0
  * and CIGAR *.  In a proper pair MAPQ is the pair's and NH:i its number of pairs; otherwise they are the read's own.  A rescued
  * read carries YR:i:1.  None of --paired, -2, --ins, --anchors combines with --secondary, and all need --sam.
+ * --paf maps long reads by chaining and prints PAF (the definitions: include/pfpgpu.h, "Chaining anchors"): both strands of every
+ * read, every occurrence of every maximal exact match of at least L bytes (--seed, default 20) that occurs at most N times
+ * (--max-occ, 1..65536, default 500), chained with gaps of at most G bytes (--gap, default 5000) and at most B bytes off the
+ * diagonal (--band, default 500); chains that score below S (--min-score, default 40) are dropped.  All five defaults are
+ * choices.  READS is read as --sam reads it; --text and --thresholds as --mems takes them.  One line per returned chain, none for
+ * a read without one: `qname qlen qs qe strand tname tlen ts te match span mapq` (tab-separated; strand + or -; qs, qe in the read
+ * as given; ts, te inside the record; match = the bytes in seeds; span = max(qe - qs, te - ts); MAPQ 0..60 is a choice) and the
+ * tags tp:A:P (the best chain) or tp:A:S (up to N further ones, --secondary, default 0, with MAPQ 0), cm:i: the chain's anchors,
+ * s1:i: its score and, on a primary line with a runner-up, s2:i: the runner-up's.  With --seqs[=FILE] tname and tlen are the
+ * record's; without a table tname is basename's file name and tlen the text's length.  --paf combines with no other mode.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -85,7 +97,8 @@ static void usage(const char *argv0) {
          "       %s -k K [-l] [-m MAXOCC] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename\n"
-         "       %s --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n\n"
+         "       %s --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n"
+         "       %s --paf [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -120,8 +133,17 @@ static void usage(const char *argv0) {
          "      --ins MIN:MAX with --paired: a proper pair's insert, forward mate's first byte to reverse mate's last (def. 0:1000, a\n"
          "                  choice; MAX <= 16384); a mate without a proper partner is looked for within MAX bytes of its partner\n"
          "      --anchors C with --paired: the hits of each mate that are combined (1..64, def. 8, a choice)\n"
-         "      --text FILE with --ms / --mems / --align / --sam: the text (def. inverted from basename.bwt)\n"
-         "      --thresholds with --ms / --mems / --align / --sam: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
+         "      --paf       map the long reads of READS (read as --sam reads it) by chaining and print PAF: both strands, every\n"
+         "                  occurrence of every maximal exact match of at least L bytes (--seed, def. 20) chained; one line per chain,\n"
+         "                  qname qlen qs qe strand tname tlen ts te match span mapq tp:A:P|S cm:i:anchors s1:i:score [s2:i:runner-up],\n"
+         "                  none for a read without one; --secondary N prints up to N further chains (tp:A:S, MAPQ 0); with\n"
+         "                  --seqs[=FILE] the target is the record, else the whole text under basename's name (no other mode)\n"
+         "      --max-occ N with --paf: a match that occurs more than N times is left out (1..65536, def. 500, a choice)\n"
+         "      --gap G     with --paf: two anchors chain when they end at most G bytes apart in the read and the text (def. 5000, a choice)\n"
+         "      --band B    with --paf: ... and at most B bytes off each other's diagonal (def. 500, a choice)\n"
+         "      --min-score S with --paf: a chain that scores below S is dropped (def. 40, a choice)\n"
+         "      --text FILE with --ms / --mems / --align / --sam / --paf: the text (def. inverted from basename.bwt)\n"
+         "      --thresholds with --ms / --mems / --align / --sam / --paf: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
          "                  count<TAB>name:offset ... : the hits inside one sequence among the at most MAXOCC rows examined;\n"
          "                  count stays the number of rows, matches that span two sequences included\n"
@@ -129,7 +151,7 @@ static void usage(const char *argv0) {
          "                  reads basename.ssa and .esa; every occurrence counts)\n"
          "      --rc        search every line as given, then its reverse complement (A<->T, C<->G): two output lines per line\n"
          "      --device D  GPU to use (def. 0)\n",
-         argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+         argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
 static int read_file(const char *path, uint8_t **out, uint64_t *len) {
@@ -174,6 +196,7 @@ typedef struct {
   int thresholds, locate, kmis, kedit, cigar;
   uint64_t min_ins, max_ins, anchors;
   uint64_t maxsec, first; char *const *qname;      /* --sam: the batch's first read, and the reads' names (NULL: their numbers) */
+  uint64_t max_occ, gap, band, min_score, n; const char *tname;      /* --paf; n, tname: the text's length and name (no table) */
 } batch_t;
 
 static int fail(const char *what, int rc, pfp_ctx *ctx) {
@@ -308,6 +331,39 @@ static int mode_sam(const batch_t *b) {
   }
   pfp_free(strand); pfp_free(seq); pfp_free(off); pfp_free(start); pfp_free(dist); pfp_free(coff); pfp_free(cig); pfp_free(moff); pfp_free(md);
   free(mapq); free(rc);
+  return r;
+}
+
+/* --paf: one line per returned chain (the definitions: include/pfpgpu.h, "Chaining anchors").  The runner-up is always asked for:
+ * its score goes into the primary line */
+static int mode_paf(const batch_t *b) {
+  uint64_t *oo = b->oo, *nchains = b->sp, *off = NULL, *ts = NULL, *te = NULL;
+  uint8_t *strand = NULL, *mapq = malloc(b->k + 1);
+  uint32_t *seq = NULL, *qs = NULL, *qe = NULL, *score = NULL, *cn = NULL, *match = NULL;
+  int r = 1;
+  if (!mapq) fprintf(stderr, "out of memory\n");
+  else if ((r = pfp_fm_map_long(b->fm, b->pat, b->off, b->k, b->seed, b->max_occ, b->gap, b->band, b->min_score, b->maxsec ? b->maxsec : 1,
+                                b->thresholds, oo, mapq, nchains, &strand, &seq, &off, &ts, &te, &qs, &qe, &score, &cn, &match)) != 0)
+    r = fail(b->base, r, b->ctx);
+  for (uint64_t i = 0; !r && i < b->k; i++) {
+    char num[24];
+    snprintf(num, sizeof num, "%" PRIu64, b->first + i + 1);
+    const char *qn = b->qname ? b->qname[b->first + i] : num;
+    for (uint64_t j = oo[i]; j < oo[i + 1] && j - oo[i] <= b->maxsec; j++) {
+      const int second = j > oo[i];
+      const uint64_t qspan = qe[j] - qs[j], tspan = te[j] - ts[j];
+      const uint64_t tlen = b->tab->nseq ? b->tab->start[seq[j] + 1] - b->tab->start[seq[j]] : b->n;
+      printf("%s\t%" PRIu64 "\t%" PRIu32 "\t%" PRIu32 "\t%c\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu32 "\t%" PRIu64 "\t%u",
+             qn, b->off[i + 1] - b->off[i], qs[j], qe[j], strand[j] ? '-' : '+', b->tab->nseq ? b->tab->name[seq[j]] : b->tname, tlen, off[j],
+             off[j] + tspan, match[j], qspan > tspan ? qspan : tspan, second ? 0u : (unsigned)mapq[i]);
+      printf("\ttp:A:%c\tcm:i:%" PRIu32 "\ts1:i:%" PRIu32, second ? 'S' : 'P', cn[j], score[j]);
+      if (!second && oo[i + 1] - oo[i] > 1) printf("\ts2:i:%" PRIu32, score[j + 1]);
+      putchar('\n');
+    }
+  }
+  pfp_free(strand); pfp_free(seq); pfp_free(off); pfp_free(ts); pfp_free(te); pfp_free(qs); pfp_free(qe); pfp_free(score); pfp_free(cn);
+  pfp_free(match);
+  free(mapq);
   return r;
 }
 
@@ -480,14 +536,14 @@ static int mode_count(const batch_t *b) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0, paired = 0, have_pair_opt = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0, paired = 0, have_pair_opt = 0, paf = 0, have_paf_opt = 0;
   const char *seqsfile = NULL, *mates2 = NULL;
   uint64_t min_ins = 0, max_ins = 1000, anchors = 8;
   pfp_seqs tab, rtab, rtab2;      /* the collection's table, and with --sam the names of a FASTA / FASTQ file's reads (-2: FILE's) */
   pfp_seqs_init(&tab);
   pfp_seqs_init(&rtab);
   pfp_seqs_init(&rtab2);
-  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0;
+  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0, paf_occ = 500, gap = 5000, band = 500, min_score = 40;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
@@ -495,6 +551,8 @@ int main(int argc, char **argv) {
                                {"align", required_argument, 0, 1009}, {"seed", required_argument, 0, 1010},
                                {"cigar", no_argument, 0, 1011}, {"sam", required_argument, 0, 1012}, {"secondary", required_argument, 0, 1013},
                                {"paired", no_argument, 0, 1014}, {"ins", required_argument, 0, 1015}, {"anchors", required_argument, 0, 1016},
+                               {"paf", no_argument, 0, 1017}, {"max-occ", required_argument, 0, 1018}, {"gap", required_argument, 0, 1019},
+                               {"band", required_argument, 0, 1020}, {"min-score", required_argument, 0, 1021},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -561,6 +619,14 @@ int main(int argc, char **argv) {
         if (!*optarg || *end || optarg[0] == '-' || anchors < 1 || anchors > PFP_FM_PAIR_MAX_ANCHORS) { usage(argv[0]); return 2; }
         have_pair_opt = 1;
         break;
+      case 1017: paf = 1; break;
+      case 1018: case 1019: case 1020: case 1021: {
+        const uint64_t v = strtoull(optarg, &end, 10);
+        const uint64_t most = c == 1018 ? 65536 : c == 1021 ? UINT32_MAX : INT32_MAX;
+        if (!*optarg || *end || optarg[0] == '-' || v < 1 || v > most) { usage(argv[0]); return 2; }
+        *(c == 1018 ? &paf_occ : c == 1019 ? &gap : c == 1020 ? &band : &min_score) = v;
+        have_paf_opt = 1;
+      } break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -568,6 +634,18 @@ int main(int argc, char **argv) {
       case 'h': usage(argv[0]); return 0;
       default: usage(argv[0]); return 2;
     }
+  }
+  if (paf && sam) {      /* (two mappers' outputs on one stream) */
+    usage(argv[0]);
+    return 1;
+  }
+  if (paf && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp || paired || have_pair_opt)) {
+    fprintf(stderr, "--paf does not combine with the other modes or with --rc (both strands are always searched)\n");
+    return 2;
+  }
+  if (have_paf_opt && !paf) {
+    fprintf(stderr, "--max-occ, --gap, --band and --min-score need --paf\n");
+    return 2;
   }
   if (sam && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp)) {
     fprintf(stderr, "--sam does not combine with -l, -k, -m, --ms, --mems, --docs, --align, --cigar or --rc (both strands are always searched)\n");
@@ -586,9 +664,9 @@ int main(int argc, char **argv) {
     return 2;
   }
   if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
-      ((textfile || thresholds) && !ms && !mems && !align && !sam) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
-      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align && !sam) || (cigar && !align) ||
-      (have_sec && !sam)) {
+      ((textfile || thresholds) && !ms && !mems && !align && !sam && !paf) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
+      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align && !sam && !paf) || (cigar && !align) ||
+      (have_sec && !sam && !paf)) {
     usage(argv[0]);
     return 2;
   }
@@ -603,7 +681,7 @@ int main(int argc, char **argv) {
   pfp_ctx *ctx = NULL;
   pfp_fm *fm = NULL;
   int rc = 1;
-  if (sam) {      /* plain or gzip-compressed; FASTA / FASTQ becomes one read per line */
+  if (sam || paf) {      /* plain or gzip-compressed; FASTA / FASTQ becomes one read per line */
     int named = 0;
     if (load_reads(patfile, &pats, &plen, &rtab, &named)) goto done;
     if (named) qname = rtab.name;
@@ -661,7 +739,7 @@ int main(int argc, char **argv) {
 
   rc = pfp_ctx_create(&ctx, device);
   if (rc) { fprintf(stderr, "Cannot initialise the GPU (%s): this tool has no CPU path\n", pfp_strerror(rc)); rc = 1; goto done; }
-  if (ms || mems || align || sam) {
+  if (ms || mems || align || sam || paf) {
     int fd = -1;
     uint64_t n = 0;
     if (textfile) {
@@ -713,7 +791,10 @@ int main(int argc, char **argv) {
   static char obuf[1 << 20];
   setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
   if (sam) sam_header(&tab);
-  int (*const mode)(const batch_t *) = paired ? mode_sam_paired : sam ? mode_sam : ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
+  pfp_fm_info_t info;
+  pfp_fm_info(fm, &info);
+  const char *tname = strrchr(base, '/') ? strrchr(base, '/') + 1 : base;
+  int (*const mode)(const batch_t *) = paf ? mode_paf : paired ? mode_sam_paired : sam ? mode_sam : ms ? mode_ms : mems ? mode_mems : align ? mode_align : docs ? mode_docs : approx ? mode_approx
                                      : locate && seqs ? mode_locate_seqs : locate ? mode_locate : mode_count;
   for (uint64_t p0 = 0; p0 < npat;) {
     /* a batch: at most `batch` patterns and max_bytes bytes (a single longer line goes alone, from the file buffer) */
@@ -751,7 +832,8 @@ int main(int argc, char **argv) {
     } else {
       off[0] = 0; off[1] = bytes;
     }
-    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, min_ins, max_ins, anchors, maxsec, p0, qname};
+    const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, min_ins, max_ins, anchors, maxsec, p0, qname,
+                       paf_occ, gap, band, min_score, info.n, tname};
     if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }

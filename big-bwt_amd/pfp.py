@@ -38,6 +38,9 @@ FM_PAIR_MAX_ANCHORS = 64
 # the arrays FmIndex.map_pairs returns, in order: the first two per pair, the next ten per read, then the reads' scripts and MD strings
 PAIR_NAMES = ("proper", "npairs", "mapped", "rescued", "mapq", "nhits", "strand", "seq", "off", "start", "dist", "tlen", "cig_off", "cig",
               "md_off", "md")
+FM_CHAIN_PRED = 64
+# the arrays FmIndex.map_long returns, in order: the first three per read, the others per returned chain
+LONG_NAMES = ("hit_off", "mapq", "nchains", "strand", "seq", "off", "ts", "te", "qs", "qe", "score", "n", "match")
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}    # the BAM codes of the operations an edit script holds
 
 LCP_LCP, LCP_THR = 1, 2
@@ -364,6 +367,78 @@ class FmIndex(_Closing):
                                                       anchors, d_proper, d_npairs, d_mapped, d_rescued, d_mapq, d_nhits, d_strand, d_seq,
                                                       d_off, d_start, d_dist, d_tlen, d_cig_off, C.byref(d_cig), d_md_off, C.byref(d_md)))
         return _addr(d_cig), _addr(d_md)
+
+    def anchors(self, patterns, min_seed, max_occ=500, thresholds=False):
+        """every occurrence of every maximal exact match of at least min_seed bytes (pfpgpu.h, "Chaining anchors", 1; an index with
+        text) -> (anc_off, anc, skipped): pattern p's anchors are the rows anc[anc_off[p]:anc_off[p+1]] of a (k, 3) uint64 array,
+        each (i, len, t): P[i:i+len] = T[t:t+len], by increasing (t + len, i + len).  A MEM with more than max_occ occurrences is
+        left out and counted in skipped[p] (uint32); with a sequence table set, so is an occurrence that crosses a record border
+        (uncounted).  max_occ = 500 is a choice."""
+        npat, _, args = self._host_patterns(patterns)
+        anc_off, skipped = np.zeros(npat + 1, dtype=np.uint64), np.zeros(npat, dtype=np.uint32)
+        out = C.POINTER(C.c_uint64)()
+        self.ctx._check(self.lib.pfp_fm_anchors(self._h, *args, min_seed, max_occ, bool(thresholds), anc_off, C.byref(out), skipped))
+        return anc_off, self._take_free(out, 3 * int(anc_off[-1]), np.uint64).reshape(-1, 3), skipped
+
+    def anchors_dev(self, d_pat, d_pat_off, npat, min_seed, d_anc_off, d_anc=None, d_skipped=None, max_occ=500, thresholds=False):
+        """device pointers: pattern bytes, npat+1 uint64 offsets -> npat+1 uint64 d_anc_off; d_anc (room for 3 * d_anc_off[npat]
+        uint64) gets the triples (None: offsets only), d_skipped (npat uint32, may be None) the skipped MEMs"""
+        self.ctx._check(self.lib.pfp_fm_anchors_dev(self._h, d_pat, d_pat_off, npat, min_seed, max_occ, bool(thresholds), d_anc_off, d_anc,
+                                                    d_skipped))
+
+    def chain(self, anc_off, anc, max_gap=5000, band=500, min_score=40, max_chains=0):
+        """the chains of every pattern's anchors (pfpgpu.h, "Chaining anchors", 2): anc_off / anc as anchors() gives them, or any
+        anchors in strictly increasing (t + len, i + len) order per pattern -> (chain_off, score, n, qs, qe, ts, te, match): pattern
+        p's chains, by (score descending, te, qe), at most max_chains (0: all), are i in chain_off[p]:chain_off[p+1]: n[i]
+        anchors spanning P[qs[i]:qe[i]] and T[ts[i]:te[i]], match[i] bytes in seeds (uint32 but ts, te: uint64).  Two anchors
+        chain when they lie at most max_gap apart on either side and at most band off each other's diagonal; a chain scoring
+        below min_score is dropped.  The defaults are choices."""
+        off = _arr(np.asarray(anc_off), np.uint64)
+        a = _arr(np.asarray(anc).reshape(-1), np.uint64)
+        npat = len(off) - 1
+        if npat < 0 or len(a) % 3:
+            raise ValueError("anc_off: npat + 1 offsets; anc: three values per anchor")
+        chain_off = np.zeros(npat + 1, dtype=np.uint64)
+        u32, u64 = C.c_uint32, C.c_uint64
+        score, n, qs, qe, ts, te, match = (C.POINTER(t)() for t in (u32, u32, u32, u32, u64, u64, u32))
+        self.ctx._check(self.lib.pfp_fm_chain(self._h, off, a, npat, max_gap, band, min_score, max_chains, chain_off, C.byref(score),
+                                              C.byref(n), C.byref(qs), C.byref(qe), C.byref(ts), C.byref(te), C.byref(match)))
+        t, total = self._take_free, int(chain_off[-1])
+        return (chain_off, t(score, total, np.uint32), t(n, total, np.uint32), t(qs, total, np.uint32), t(qe, total, np.uint32),
+                t(ts, total, np.uint64), t(te, total, np.uint64), t(match, total, np.uint32))
+
+    def chain_dev(self, d_anc_off, d_anc, npat, d_chain_off, d_score=None, d_n=None, d_qs=None, d_qe=None, d_ts=None, d_te=None, d_match=None,
+                  max_gap=5000, band=500, min_score=40, max_chains=0):
+        """device pointers: npat+1 uint64 anchor offsets and the triples -> npat+1 uint64 d_chain_off; the seven arrays behind it
+        (uint32 but d_ts, d_te: uint64; room for d_chain_off[npat] each) get the chains (all None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_chain_dev(self._h, d_anc_off, d_anc, npat, max_gap, band, min_score, max_chains, d_chain_off, d_score,
+                                                  d_n, d_qs, d_qe, d_ts, d_te, d_match))
+
+    def map_long(self, patterns, min_seed, max_occ=500, max_gap=5000, band=500, min_score=40, max_sec=0, thresholds=False):
+        """where long reads lie (pfpgpu.h, "Chaining anchors", 3): both strands of every read through anchors() and chain(), their
+        chains merged by (score descending, strand, te, qe) -> the arrays LONG_NAMES names: read p has nchains[p] chains (uint64)
+        and mapping quality mapq[p] (uint8; 0 without a chain, 60 with one, else min(60, 60 (s1 - s2) / s1): a choice); the first
+        1 + max_sec are i in hit_off[p]:hit_off[p+1], the first the primary: strand[i] (uint8), record seq[i] (uint32; 0 without
+        a table) at offset off[i], T[ts[i]:te[i]], the read's bytes qs[i]:qe[i] as given, score[i], n[i] anchors, match[i] bytes
+        in seeds.  The defaults are choices."""
+        npat, _, args = self._host_patterns(patterns)
+        hit_off, mapq, nchains = np.zeros(npat + 1, dtype=np.uint64), np.zeros(npat, dtype=np.uint8), np.zeros(npat, dtype=np.uint64)
+        u8, u32, u64 = C.c_uint8, C.c_uint32, C.c_uint64
+        kinds = (u8, u32, u64, u64, u64, u32, u32, u32, u32, u32)
+        ptrs = [C.POINTER(t)() for t in kinds]
+        self.ctx._check(self.lib.pfp_fm_map_long(self._h, *args, min_seed, max_occ, max_gap, band, min_score, max_sec, bool(thresholds), hit_off,
+                                                 mapq, nchains, *(C.byref(q) for q in ptrs)))
+        H = int(hit_off[-1])
+        return (hit_off, mapq, nchains) + tuple(self._take_free(q, H, np.dtype(t)) for q, t in zip(ptrs, kinds))
+
+    def map_long_dev(self, d_pat, d_pat_off, npat, min_seed, d_hit_off, d_mapq, d_nchains, d_strand=None, d_seq=None, d_off=None, d_ts=None,
+                     d_te=None, d_qs=None, d_qe=None, d_score=None, d_n=None, d_match=None, max_occ=500, max_gap=5000, band=500, min_score=40,
+                     max_sec=0, thresholds=False):
+        """device pointers: read bytes, npat+1 uint64 offsets -> npat+1 uint64 d_hit_off, npat uint8 d_mapq and uint64 d_nchains; the
+        ten per-chain outputs (LONG_NAMES[3:]; room for d_hit_off[npat] each) all None: those three only"""
+        self.ctx._check(self.lib.pfp_fm_map_long_dev(self._h, d_pat, d_pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec,
+                                                     bool(thresholds), d_hit_off, d_mapq, d_nchains, d_strand, d_seq, d_off, d_ts, d_te, d_qs,
+                                                     d_qe, d_score, d_n, d_match))
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

@@ -853,6 +853,119 @@ int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, ui
                      uint64_t *cig_off, uint32_t **cig, uint64_t *md_off, uint8_t **md);
 
 /* ------------------------------------------------------------------------------------
+ * Chaining anchors: where a long read lies (csrc/fmchain.hip).  "Extending seeds" aligns a whole read within k <= 32 edits of one
+ * seed's diagonal; a read of 10 kb carries hundreds of edits, and every one of its seeds finds the right place all the same.
+ * The first step of every long-read mapper is to chain the seeds and report the chain; base-level alignment of a chain (a band in
+ * the hundreds) is not done here, and a chain's span and anchors are what such an aligner takes.  The reference has no
+ * counterpart; the method is seed chaining as in Li, "Minimap2: pairwise alignment for nucleotide sequences" (Bioinformatics
+ * 2018), section 2.1, over MEM anchors instead of minimizers, in integer arithmetic.  Conventions as in "Searching a BWT" and
+ * "Matching statistics".  The index is one built with text and samples (pfp_fm_build_ms_*); otherwise PFP_EINVAL, as for
+ * pfp_fm_mems*.  Three layers, each usable on its own, each a function of its inputs alone - not of the batch, the launch shape,
+ * the budget or the schedule.
+ *
+ * 1. Anchors: every occurrence of every MEM.  Arguments: min_seed >= 1, 1 <= max_occ <= 65536, thresholds.  For a pattern P:
+ *   MEMs: its MEMs (i, len) of at least min_seed bytes are exactly those pfp_fm_mems lists (thresholds != 0: pfp_fm_mems_thr; the
+ *     lengths are the same either way, so the anchors do not depend on thresholds).  A MEM carries ONE position of its string;
+ *     in a collection of near-identical copies the positions of neighbouring MEMs lie in different copies, so a chain needs all.
+ *   row range: [sp, ep) of P[i .. i+len) as pfp_fm_count defines it.  ep - sp > max_occ: the MEM is skipped (a repeat filter); the
+ *     number of skipped MEMs per pattern is an output.
+ *   anchors: otherwise every t = SA[r], sp <= r < ep, gives an anchor (i, len, t).
+ *   record borders: with a sequence table set (pfp_fm_set_seqs), an anchor whose bytes [t, t+len) do not lie inside one record is
+ *     dropped (it does count towards ep - sp).
+ *   order: a pattern's anchors are listed by increasing (t + len, i + len).  The order is strict: two MEMs of a pattern never end
+ *     at the same pattern byte, and the occurrences of one MEM differ in t.
+ *   2^32 - 1 or more occurrences to look at in one device call: PFP_ELIMIT.
+ *
+ * 2. Chains.  Inputs: anc_off and anc as layer 1 gives them, or any anchors of the caller's.  A pattern's anchors that are not in
+ * strictly increasing (t + len, i + len) order, an anchor with len = 0 or with i + len >= 2^32, offsets that decrease: PFP_EINVAL.
+ * Arguments: max_gap G and band B, both in 1 .. 2^31 - 1; min_score S >= 1; max_chains (0: all).  H = PFP_FM_CHAIN_PRED = 64
+ * predecessors are looked at: a choice (one wavefront), not a measurement.  For the anchors a_0 .. a_{A-1} of a pattern, in the
+ * given order, write qe_x = i_x + len_x, te_x = t_x + len_x, rec_x = the record that holds t_x (no table: the whole text is
+ * record 0).
+ *   predecessors: j is a predecessor of x iff x - H <= j < x, rec_j = rec_x, dq = qe_x - qe_j >= 1, dt = te_x - te_j >= 1,
+ *     dq <= G, dt <= G and g = |dt - dq| <= B.
+ *   gain(j, x) = min(dq, dt, len_x) - cost(g), cost(g) = (g + 3) >> 2: signed, it can be negative.  The first term is the number
+ *     of new bytes the anchor adds; a quarter per byte of gap is a choice.
+ *   score: f_x = max(len_x, max over predecessors j of f_j + gain(j, x)).
+ *   parent_x: the predecessor that attains that maximum, provided f_j + gain(j, x) > len_x strictly; among equal values the
+ *     largest j.  Otherwise x has no parent.  (1 <= f_x <= qe_x < 2^32.)
+ *   peel: visit the pattern's anchors by (f descending, index ascending).  For each unvisited x walk y = x, parent_x, ... while y
+ *     exists and is unvisited, marking each visited.  The anchors walked are a chain with score = f_x - f_y, y the visited anchor
+ *     the walk stopped at, or f_x if the walk ran out of parents.  The chain is kept iff score >= S; its anchors stay visited
+ *     either way.
+ *   fields of a chain: score; n, its number of anchors; qs = the least i of its anchors and qe = qe_x; ts = the least t of its
+ *     anchors and te = te_x; match: along the chain in increasing order, len of the first anchor plus min(dq, dt, len) of each
+ *     later one against the one before it - the gain without its cost.
+ *   order of output: a pattern's chains by (score descending, te, qe): strict, because end anchors differ.  Only the first
+ *     max_chains are kept.
+ *   Example: anchors (0,30,1000) (31,25,1031) (60,40,1062) (101,30,1103) (10,22,5000) (40,35,5030), G = 5000, B = 500, S = 20: f =
+ *     30, 55, 94, 124, 22, 57; parents -, 0, 1, 2, -, 4 (anchor 2: dq = 44, dt = 46, g = 2, 55 + 40 - 1 = 94); chains (score 124,
+ *     n 4, q 0..131, t 1000..1133, match 125) and (57, 2, 10..75, 5000..5065, 57).
+ *
+ * 3. Mapping long reads.  Strand 0 of a read is the read, strand 1 its reverse complement: exactly the bytes pfp_fm_map searches.
+ * Both go through layer 1 (min_seed, max_occ, thresholds) and layer 2 (G, B, S, max_chains = 0).  The read's chains are those of
+ * both strands by (score descending, strand, te, qe); nchains is their number, the first is the primary, and up to max_sec
+ * further ones are returned behind it.
+ *   MAPQ: a choice, as the other MAPQs here are: 0 for a read without a chain, 60 for a read with one, otherwise
+ *     min(60, 60 (s1 - s2) / s1) in integer division over the scores of the first two.
+ *   per returned chain: strand (uint8); seq (uint32, the record of ts; 0 without a table) and off (ts minus the record's start);
+ *     ts, te; qs, qe in coordinates of the read AS GIVEN (strand 1: m - qe and m - qs of the strand's pattern); score, n, match.
+ *
+ * Bounds: the programme is sequential along a pattern's anchors and parallel over the H predecessors: one wave per pattern, 64
+ * evaluations and one wave-wide maximum per anchor.  Both the programme and the peel are bounded, resumable launches: a launch
+ * advances a pattern by at most PFP_FM_CHAIN_STEPS anchors (the peel: visits and steps of its walks); the default 65536 is a
+ * choice, the environment variable of the same name lowers it, is read per call and is never below 1.  The programme resumes by
+ * reloading f and the fields of the previous H anchors, the peel from its place in the sorted order and its current walk.  A
+ * pattern has up to m * max_occ anchors; no launch is bounded by that.  The peel is O(A) per pattern, one lane each.
+ * Device memory on top of the caller's buffers.  Anchors: what pfp_fm_ms_dev's outputs take (12 bytes per pattern byte) and 32 per
+ * pattern; 80 bytes per MEM (its triple, its span, its row range, toehold, clipped end and offset); per occurrence 8 for its
+ * position and 32 for its end, keys and order, plus what pfp_fm_locate_dev and the library's segmented sort take; 24 per anchor
+ * for the triples, which the call sizes itself.  Chains: 58 bytes per anchor (f, parent, visited flag, the sort's keys and values,
+ * the fields of the chain it may end, the order of output) plus the sort's scratch, 56 per pattern (segments, counts, the
+ * programme's and the peel's records); 36 bytes per chain.  Long reads: 2 bytes per read byte and 32 per read for the strands,
+ * the anchors and chains of 2 npat patterns as above, and 60 per chain of either strand for its fields, key and order.
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_CHAIN_PRED 64
+/* device pointers, patterns as in pfp_fm_count_dev.  d_anc_off (npat + 1) gets the exclusive sums of the numbers of anchors;
+ * d_anc, room for 3 * d_anc_off[npat] uint64 - which a call with d_anc == NULL reports - gets {i, len, t} per anchor (NULL: offsets
+ * only); d_skipped (uint32 per pattern, may be NULL) the MEMs the repeat filter skipped. */
+int pfp_fm_anchors_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                       int thresholds, uint64_t *d_anc_off, uint64_t *d_anc, uint32_t *d_skipped);
+/* host buffers (offsets that decrease: PFP_EINVAL): anc_off (npat + 1) and skipped (npat, may be NULL) are filled; *anc is a
+ * malloc'ed array of 3 * anc_off[npat] entries (pfp_free; NULL when none).  The matching statistics are computed for the whole
+ * call; the patterns then go through in consecutive groups of at most PFP_SEQ_BUDGET MEMs, as in pfp_fm_align (a pattern with
+ * more goes alone; PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_anchors(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, int thresholds,
+                   uint64_t *anc_off, uint64_t **anc, uint32_t *skipped);
+/* device pointers: pattern p's anchors are the triples d_anc[3 * d_anc_off[p] .. 3 * d_anc_off[p+1]).  d_chain_off (npat + 1) gets
+ * the exclusive sums of the numbers of chains.  The seven arrays behind it all NULL: offsets only; otherwise all are required
+ * (PFP_EINVAL), with room for d_chain_off[npat] entries each: score, n, qs, qe and match as uint32, ts and te as uint64. */
+int pfp_fm_chain_dev(pfp_fm *fm, const uint64_t *d_anc_off, const uint64_t *d_anc, uint64_t npat, uint64_t max_gap, uint64_t band,
+                     uint64_t min_score, uint64_t max_chains, uint64_t *d_chain_off, uint32_t *d_score, uint32_t *d_n, uint32_t *d_qs,
+                     uint32_t *d_qe, uint64_t *d_ts, uint64_t *d_te, uint32_t *d_match);
+/* host buffers: chain_off (npat + 1) is filled; *score, *n, *qs, *qe, *ts, *te and *match are malloc'ed arrays of chain_off[npat]
+ * entries (pfp_free each; NULL when there is no chain). */
+int pfp_fm_chain(pfp_fm *fm, const uint64_t *anc_off, const uint64_t *anc, uint64_t npat, uint64_t max_gap, uint64_t band, uint64_t min_score,
+                 uint64_t max_chains, uint64_t *chain_off, uint32_t **score, uint32_t **n, uint32_t **qs, uint32_t **qe, uint64_t **ts,
+                 uint64_t **te, uint32_t **match);
+/* device pointers, reads as patterns in pfp_fm_count_dev.  d_hit_off (npat + 1) gets the exclusive sums of the numbers of chains
+ * returned, d_mapq (uint8) and d_nchains (uint64) npat entries each.  The ten outputs behind them all NULL: those three only;
+ * otherwise all ten are required (PFP_EINVAL), with room for d_hit_off[npat] entries - which the first kind of call reports, and
+ * npat (1 + max_sec) bounds. */
+int pfp_fm_map_long_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                        uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *d_hit_off,
+                        uint8_t *d_mapq, uint64_t *d_nchains, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off, uint64_t *d_ts,
+                        uint64_t *d_te, uint32_t *d_qs, uint32_t *d_qe, uint32_t *d_score, uint32_t *d_n, uint32_t *d_match);
+/* host buffers (offsets that decrease: PFP_EINVAL): hit_off (npat + 1), mapq and nchains (npat each) are filled; the ten arrays
+ * behind them are malloc'ed, hit_off[npat] entries each (pfp_free each; NULL when there is none).  The matching statistics of
+ * both strands are computed for the whole call; the reads then go through in consecutive groups of at most PFP_SEQ_BUDGET MEMs,
+ * both strands counted (a read with more goes alone; PFP_FM_SEQ_BUDGET=K lowers it). */
+int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                    uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
+                    uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
+                    uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match);
+
+/* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
  * the method is PHONI (Boucher, Gagie, I, Koppl, Langmead, Manzini, Navarro, Pacheco, Rossi, "PHONI: Streamed Matching
  * Statistics with Multi-Genome References", DCC 2021), which refines Bannai, Gagie, I, "Refining the r-index" (2020): backward
