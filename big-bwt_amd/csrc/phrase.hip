@@ -8,9 +8,12 @@
 //     chunks, so an 8-lane group hashes a typical phrase with one 16-byte unaligned load per
 //     lane and a giant phrase (an 18 Mb run of N) is split over the whole chip and combined
 //     with 64-bit atomic adds - no sequential Horner chain as in kr_hash (newscan.cpp:229-239).
-//   * dedup = radix sort of (hash, phrase#) + adjacent compare.  Every occurrence is verified
-//     byte-for-byte against its predecessor (the reference compares strings on every hit,
-//     newscan.cpp:282); a mismatch reseeds the hash and retries, so the result is exact.
+//   * dedup = radix sort of (hash, phrase#); a run of equal hashes is one word, its first phrase the word's representative.
+//     Once the dictionary is written every phrase is verified, in text order, byte-for-byte against the dictionary copy of
+//     the word it was given (the reference compares strings on every hit, newscan.cpp:282): the phrase is a streaming read
+//     its neighbours share, the word comes from the dictionary (most frequent words first - cache-resident), and .last /
+//     .sai are written from the phrase ends the same kernel holds.  A mismatch drops the dictionary, reseeds the hash and
+//     retries, so the result is exact.
 //   * words are numbered by descending occurrence count (ties: first occurrence); the lexicographic ranks the reference
 //     assigns with std::sort (newscan.cpp:622-636) fall out of the dictionary suffix sort.
 #include "kernels.hpp"
@@ -61,26 +64,61 @@ __device__ __forceinline__ uint64_t finish_hash(uint64_t sum, uint64_t len) {
   return fmix64(sum ^ (len * 0xA24BAED4963EE407ULL));
 }
 
+// A workgroup of the two kernels that walk the text takes a contiguous block of phrases, one phrase per thread for the
+// bookkeeping and 2^LG lanes per phrase for the bytes: the block size is the workgroup size the kernel is launched with.
+constexpr uint32_t kHashBlockPhrases = 256;    // phrases per workgroup (= threads) of phrase_hash_kernel
+constexpr uint32_t kVerifyBlockPhrases = 256;  // phrases per workgroup (= threads) of phrase_verify_kernel
+
+// Start and length of the G phrases from `base` on into LDS, thread t taking phrase base + t (blockDim.x == G): every entry of
+// ends[] is read once, coalesced, and a phrase's start comes from its left neighbour's end.  Phrases past P get length 0 at
+// start 0.  Returns the length of the thread's own phrase; ends with a barrier.
+template <uint32_t G>
+__device__ __forceinline__ uint64_t load_phrase_block(const PhraseGeom &g, uint64_t P, uint64_t base, uint64_t *s_start,
+                                                      uint64_t *s_len) {
+  const uint32_t t = threadIdx.x;
+  const uint64_t k = base + t;
+  uint64_t e = 0, s = 0, len = 0;
+  if (k < P) { e = ph_end(g, k); s_len[t] = e; }
+  __syncthreads();
+  if (k < P) {
+    s = (g.xstart || t == 0) ? ph_start(g, k) : s_len[t - 1] + 1 - (uint64_t)g.w;
+    len = e - s + 1;
+  }
+  __syncthreads();
+  s_start[t] = s; s_len[t] = len;
+  __syncthreads();
+  return len;
+}
+
 // 2^LG lanes per phrase, 16 bytes a lane and step: 8 lanes for phrases of ~100 bytes (the nominal -p 100), 4 where the chain chose
 // phrases of ~48 bytes (with 8 lanes five of them had nothing to hash).  The sum of the terms does not depend on who adds them.
+// Lane group q takes phrases q, q + NG, q + 2 NG .. of the block, one after the other (neighbouring groups read neighbouring
+// text); only a phrase longer than one stride goes round the inner loop again.  (Several phrases' loads in the air at once - two
+// or four per lane group - were built and measured: no faster here, slower in the verification)
 template <int LG>
-__global__ __launch_bounds__(256) void phrase_hash_kernel(const uint8_t *__restrict__ tp, PhraseGeom g, uint64_t P,
+__global__ __launch_bounds__(kHashBlockPhrases) void phrase_hash_kernel(const uint8_t *__restrict__ tp, PhraseGeom g, uint64_t P,
                                                           uint64_t seed, uint64_t *__restrict__ hash,
                                                           uint32_t *__restrict__ long_list,
                                                           uint32_t *__restrict__ long_count) {
-  uint64_t t = (uint64_t)BID * 256 + threadIdx.x;
-  uint64_t k = t >> LG;
-  int l8 = (int)(t & ((1u << LG) - 1u));
-  if (k >= P) return;
-  uint64_t s = ph_start(g, k), len = ph_end(g, k) - s + 1;
-  if (len > kLongPhrase) {
-    if (l8 == 0) { uint32_t i = atomicAdd(long_count, 1u); long_list[i] = (uint32_t)k; }
-    return;
+  constexpr uint32_t G = kHashBlockPhrases, NG = G >> LG, PER = G / NG;      // lane groups; phrases a lane group takes
+  static_assert(G % 64 == 0 && G <= 1024, "whole waves, one phrase per thread");
+  __shared__ uint64_t s_start[G], s_len[G], s_hash[G];
+  const uint32_t t = threadIdx.x, q = t >> LG, l8 = t & ((1u << LG) - 1u);
+  const uint64_t base = (uint64_t)BID * G;
+  const uint64_t mylen = load_phrase_block<G>(g, P, base, s_start, s_len);
+  if (mylen > kLongPhrase) { uint32_t i = atomicAdd(long_count, 1u); long_list[i] = (uint32_t)(base + t); }
+  for (uint32_t b = 0; b < PER; b++) {
+    const uint32_t idx = q + b * NG;
+    const uint8_t *src = tp + s_start[idx];
+    const uint64_t full = s_len[idx];
+    const uint32_t len = full > kLongPhrase ? 0u : (uint32_t)full;      // the whole device hashes a long one (phrase_hash_long_kernel)
+    uint64_t sum = 0;
+    for (uint32_t off = l8 * 16; off < len; off += (16u << LG)) sum += piece_terms(src, off, len, seed);
+    sum = group_sum<LG>(sum);
+    if (l8 == 0) s_hash[idx] = finish_hash(sum, len);
   }
-  uint64_t sum = 0;
-  for (uint64_t off = (uint64_t)l8 * 16; off < len; off += (16u << LG)) sum += piece_terms(tp + s, off, len, seed);
-  sum = group_sum<LG>(sum);
-  if (l8 == 0) hash[k] = finish_hash(sum, len);
+  __syncthreads();
+  if (base + t < P && mylen <= kLongPhrase) hash[base + t] = s_hash[t];      // (an empty word of a list has its hash too)
 }
 // lanes per phrase from the average phrase length
 static inline int lanes_log2_for(uint64_t bytes, uint64_t phrases) { return phrases && bytes / phrases <= 72 ? 2 : 3; }
@@ -122,32 +160,10 @@ __global__ void iota_u32_kernel(uint32_t *p, uint64_t n) {
   if (i < n) p[i] = (uint32_t)i;
 }
 
-// sorted by hash: head flags + byte verification against the predecessor
-template <int LG>
-__global__ __launch_bounds__(256) void dedup_verify_kernel(const uint8_t *__restrict__ tp, PhraseGeom g, uint64_t P,
-                                                           const uint64_t *__restrict__ ks,
-                                                           const uint32_t *__restrict__ vs,
-                                                           uint32_t *__restrict__ head, uint32_t *__restrict__ collision) {
-  uint64_t t = (uint64_t)BID * 256 + threadIdx.x;
-  uint64_t i = t >> LG;
-  int l8 = (int)(t & ((1u << LG) - 1u));
-  if (i >= P) return;
-  bool hd = (i == 0) || ks[i] != ks[i - 1];
-  if (l8 == 0) head[i] = hd ? 1u : 0u;
-  if (hd) return;
-  uint64_t a = vs[i], b = vs[i - 1];
-  uint64_t sa = ph_start(g, a), la = ph_end(g, a) - sa + 1;
-  uint64_t sb = ph_start(g, b), lb = ph_end(g, b) - sb + 1;
-  uint32_t diff = (la != lb) ? 1u : 0u;
-  if (!diff && sa != sb) {
-    for (uint64_t off = (uint64_t)l8 * 16; off < la; off += (16u << LG)) {
-      int keep = (la - off) >= 16 ? 16 : (int)(la - off);
-      uint4 va = keep_bytes16(ld16u(tp + sa + off), keep), vb = keep_bytes16(ld16u(tp + sb + off), keep);
-      diff |= (va.x ^ vb.x) | (va.y ^ vb.y) | (va.z ^ vb.z) | (va.w ^ vb.w);
-    }
-  }
-  diff = group_or<LG>(diff);
-  if (diff && l8 == 0) atomicOr(collision, 1u);
+// sorted by hash: a run of equal hashes is one word
+__global__ void phrase_head_flags_kernel(uint64_t P, const uint64_t *__restrict__ ks, uint32_t *__restrict__ head) {
+  uint64_t i = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (i < P) head[i] = (i == 0 || ks[i] != ks[i - 1]) ? 1u : 0u;
 }
 
 __global__ void collect_words_kernel(uint64_t P, const uint32_t *__restrict__ head, const uint32_t *__restrict__ hscan,
@@ -237,7 +253,9 @@ __global__ __launch_bounds__(256) void dict_copy_long_kernel(const uint8_t *__re
                                                              const uint64_t *__restrict__ wsrc,
                                                              const uint32_t *__restrict__ wlen,
                                                              const uint64_t *__restrict__ woff, uint8_t *__restrict__ D,
-                                                             const uint32_t *__restrict__ long_list, uint32_t nlong) {
+                                                             const uint32_t *__restrict__ long_list, uint32_t nlong,
+                                                             const uint32_t *__restrict__ nlong_dev) {
+  if (nlong_dev) nlong = *nlong_dev;      // the count dict_copy_kernel left on the device: no host wait between the two
   for (uint32_t li = 0; li < nlong; li++) {
     uint32_t j = long_list[li];
     uint64_t len = wlen[j];
@@ -249,14 +267,78 @@ __global__ __launch_bounds__(256) void dict_copy_long_kernel(const uint8_t *__re
   }
 }
 
-// .last (newscan.cpp:296) and .sai (newscan.cpp:298-301)
-__global__ void last_sai_kernel(const uint8_t *__restrict__ tp, PhraseGeom g, uint64_t P, uint64_t sai_base,
-                                uint8_t *__restrict__ last, uint64_t *__restrict__ sai) {
-  uint64_t k = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (k >= P) return;
-  uint64_t e = ph_end(g, k);
-  last[k] = tp[e - (uint64_t)g.w];
-  if (sai) sai[k] = e + sai_base;
+// Every phrase, in text order, against the dictionary copy of the word it was given: a phrase is a collision if its length is
+// not the word's (compared first: the bytes behind a shorter word's terminator are the next word's) or any of its bytes differs.
+// 16-byte pieces masked by keep_bytes16 and strided over the lane group, phrase after phrase as in phrase_hash_kernel.
+// The thread that holds a phrase's end also writes its .last (newscan.cpp:296) and .sai (newscan.cpp:298-301) where
+// last != null.  Phrases longer than kLongPhrase are left to phrase_verify_long_kernel.  A wave that saw a difference sets
+// the flag once.
+template <int LG>
+__global__ __launch_bounds__(kVerifyBlockPhrases) void phrase_verify_kernel(const uint8_t *__restrict__ tp, PhraseGeom g, uint64_t P,
+                                                            const uint32_t *__restrict__ pid,
+                                                            const uint64_t *__restrict__ woff,
+                                                            const uint32_t *__restrict__ wlen,
+                                                            const uint8_t *__restrict__ dict, uint64_t sai_base,
+                                                            uint8_t *__restrict__ last, uint64_t *__restrict__ sai,
+                                                            uint32_t *__restrict__ collision) {
+  constexpr uint32_t G = kVerifyBlockPhrases, NG = G >> LG, PER = G / NG;
+  static_assert(G % 64 == 0 && G <= 1024, "whole waves, one phrase per thread");
+  __shared__ uint64_t s_start[G], s_len[G], s_woff[G];
+  const uint32_t t = threadIdx.x, q = t >> LG, l8 = t & ((1u << LG) - 1u);
+  const uint64_t k = (uint64_t)BID * G + t;
+  const uint64_t mylen = load_phrase_block<G>(g, P, (uint64_t)BID * G, s_start, s_len);
+  uint64_t cmp_len = 0, wo = 0;
+  uint32_t diff = 0;
+  if (k < P) {
+    if (last) {
+      const uint64_t e = s_start[t] + mylen - 1;
+      last[k] = tp[e - (uint64_t)g.w];
+      if (sai) sai[k] = e + sai_base;
+    }
+    const uint32_t j = pid[k];
+    wo = woff[j];
+    if ((uint64_t)wlen[j] != mylen) diff = 1;
+    else if (mylen <= kLongPhrase) cmp_len = mylen;
+  }
+  s_len[t] = cmp_len; s_woff[t] = wo;      // (s_len[t] was this thread's alone to read so far)
+  __syncthreads();
+  for (uint32_t b = 0; b < PER; b++) {
+    const uint32_t idx = q + b * NG;
+    const uint8_t *pa = tp + s_start[idx], *pb = dict + s_woff[idx];
+    const uint32_t len = (uint32_t)s_len[idx];      // (at most kLongPhrase)
+    for (uint32_t off = l8 * 16; off < len; off += (16u << LG)) {
+      const int keep = (len - off) >= 16 ? 16 : (int)(len - off);
+      const uint4 x = keep_bytes16(ld16u(pa + off), keep), y = keep_bytes16(ld16u(pb + off), keep);
+      diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+    }
+  }
+  if (__any(diff != 0) && (threadIdx.x & 63) == 0) atomicOr(collision, 1u);
+}
+
+// the long phrases (the list phrase_hash_kernel made), each compared by the whole grid
+__global__ __launch_bounds__(256) void phrase_verify_long_kernel(const uint8_t *__restrict__ tp, PhraseGeom g,
+                                                                 const uint32_t *__restrict__ long_list, uint32_t nlong,
+                                                                 const uint32_t *__restrict__ pid,
+                                                                 const uint64_t *__restrict__ woff,
+                                                                 const uint32_t *__restrict__ wlen,
+                                                                 const uint8_t *__restrict__ dict,
+                                                                 uint32_t *__restrict__ collision) {
+  uint32_t diff = 0;
+  for (uint32_t li = 0; li < nlong; li++) {
+    const uint64_t k = long_list[li];
+    const uint64_t s = ph_start(g, k), len = ph_end(g, k) - s + 1;
+    const uint32_t j = pid[k];
+    if ((uint64_t)wlen[j] != len) continue;      // phrase_verify_kernel has flagged it
+    const uint8_t *a = tp + s, *b = dict + woff[j];
+    const uint64_t npieces = (len + 15) >> 4;
+    for (uint64_t c = (uint64_t)BID * 256 + threadIdx.x; c < npieces; c += (uint64_t)GDIM * 256) {
+      const uint64_t off = c * 16;
+      const int keep = (len - off) >= 16 ? 16 : (int)(len - off);
+      const uint4 x = keep_bytes16(ld16u(a + off), keep), y = keep_bytes16(ld16u(b + off), keep);
+      diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+    }
+  }
+  if (__any(diff != 0) && (threadIdx.x & 63) == 0) atomicOr(collision, 1u);
 }
 
 // identity hashes of a word list over a byte buffer (the multi-GPU chain routes every word to the rank that owns
@@ -268,7 +350,7 @@ void hash_word_list(pfp_ctx *c, const uint8_t *bytes, const uint64_t *wstart, co
   PhraseGeom g{nullptr, 0, 0, 0, 0, wstart, wlen};
   DBuf<uint32_t> long_list(c, U), counters(c, 1);
   counters.zero();
-  hipLaunchKernelGGL(phrase_hash_kernel<3>, gdim(cdiv(U * 8, TB)), gdim(TB), 0, c->stream, bytes, g, U, seed, d_hash, long_list.p, counters.p);
+  hipLaunchKernelGGL(phrase_hash_kernel<3>, gdim(cdiv(U, kHashBlockPhrases)), gdim(kHashBlockPhrases), 0, c->stream, bytes, g, U, seed, d_hash, long_list.p, counters.p);
   const uint32_t nlong = read_scalar(c, counters.p);
   if (nlong) {
     DBuf<unsigned long long> hsum(c, nlong);
@@ -294,101 +376,111 @@ static void build_dictionary_core(pfp_ctx *c, const uint8_t *tp, PhraseGeom g, u
   const uint64_t n = hbytes;
   D.P = P;
   const int TB = 256;
-  DBuf<uint64_t> hash(c, P), ks(c, P);
-  DBuf<uint32_t> iota(c, P), vs(c, P), head(c, P), hscan(c, P);
-  DBuf<uint32_t> long_list(c, P), counters(c, 4);  // [0] long count, [1] collision, [2] too long, [3] long count (copy)
+  DBuf<uint32_t> iota(c, P);
+  DBuf<uint32_t> long_list(c, P), counters(c, 4);  // [0] long phrases, [1] collision, [2] too long, [3] long words
   hipLaunchKernelGGL(iota_u32_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, iota.p, P);
   uint64_t seed = 0x243F6A8885A308D3ULL;
-  uint32_t d = 0;
   const int lg = lanes_log2_for(n, P);
+  // One attempt = hash, sort, words, dictionary, verification of every phrase against its word's dictionary copy.  A phrase that
+  // differs from its word (two different phrases shared a hash) drops the attempt's dictionary; the next one has another seed.
   for (int attempt = 0;; attempt++) {
     counters.zero();
-    { KScope kscope(c, "pfp::phrase_hash_kernel", n + 16 * P);
-    if (lg == 2) hipLaunchKernelGGL(phrase_hash_kernel<2>, gdim(cdiv(P * 4, TB)), gdim(TB), 0, c->stream, tp, g, P, seed, hash.p, long_list.p, counters.p);
-    else hipLaunchKernelGGL(phrase_hash_kernel<3>, gdim(cdiv(P * 8, TB)), gdim(TB), 0, c->stream, tp, g, P, seed, hash.p, long_list.p, counters.p); }
-    uint32_t nlong = read_scalar(c, counters.p);
-    if (nlong) {
-      DBuf<unsigned long long> hsum(c, nlong);
-      hsum.zero();
-      hipLaunchKernelGGL(phrase_hash_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, tp, g, seed, long_list.p,
-                         nlong, hsum.p);
-      hipLaunchKernelGGL(phrase_hash_long_finish_kernel, gdim(cdiv(nlong, 64)), gdim(64), 0, c->stream, g, long_list.p,
-                         nlong, hsum.p, hash.p);
+    uint32_t nlong = 0, d = 0;
+    DBuf<uint64_t> wsrc;
+    {
+      // (hash, ks, vs, head, hscan live up to assign_pid only: never beside D.bytes)
+      DBuf<uint64_t> hash(c, P), ks(c, P);
+      DBuf<uint32_t> vs(c, P), head(c, P), hscan(c, P);
+      { KScope kscope(c, "pfp::phrase_hash_kernel", n + 8 * P + 8 * P);
+      if (lg == 2) hipLaunchKernelGGL(phrase_hash_kernel<2>, gdim(cdiv(P, kHashBlockPhrases)), gdim(kHashBlockPhrases), 0, c->stream, tp, g, P, seed, hash.p, long_list.p, counters.p);
+      else hipLaunchKernelGGL(phrase_hash_kernel<3>, gdim(cdiv(P, kHashBlockPhrases)), gdim(kHashBlockPhrases), 0, c->stream, tp, g, P, seed, hash.p, long_list.p, counters.p); }
+      nlong = read_scalar(c, counters.p);
+      if (nlong) {
+        DBuf<unsigned long long> hsum(c, nlong);
+        hsum.zero();
+        hipLaunchKernelGGL(phrase_hash_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, tp, g, seed, long_list.p,
+                           nlong, hsum.p);
+        hipLaunchKernelGGL(phrase_hash_long_finish_kernel, gdim(cdiv(nlong, 64)), gdim(64), 0, c->stream, g, long_list.p,
+                           nlong, hsum.p, hash.p);
+      }
+      // test hook (PFP_TEST_HASH_BITS=n: the first attempt keeps only n bits of every hash; -n: every attempt): different phrases then
+      // share a hash, the byte verification below finds it and the pass is repeated with another seed / gives up after four
+      const char *tb_env = getenv("PFP_TEST_HASH_BITS");      // (per call: tests switch it)
+      const int test_bits = tb_env ? atoi(tb_env) : 0;
+      if (test_bits && (attempt == 0 || test_bits < 0)) {
+        const int b = test_bits < 0 ? -test_bits : test_bits;
+        hipLaunchKernelGGL(mask_u64_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, hash.p, P, b >= 64 ? ~0ull : ((1ull << b) - 1ull));
+      }
+      { SortTag tag("phrase hashes"); sort_pairs_u64_u32(c, hash.p, ks.p, iota.p, vs.p, P, 0, 64); }
+      { KScope kscope(c, "pfp::phrase_head_flags_kernel", 12 * P);
+      hipLaunchKernelGGL(phrase_head_flags_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, ks.p, head.p); }
+      inclusive_sum_u32(c, head.p, hscan.p, P);
+      PFP_HIP(hipGetLastError());
+      d = read_scalar(c, hscan.p + (P - 1));
+      D.d = d;
+      // words by descending occurrence count, ties in first-occurrence order.  (The order inside the device dictionary is free -
+      // the outputs depend on the words' lexicographic ranks only - and this one makes the lowest position of a family of
+      // near-identical words its most frequent member: the pivot of the suffix sorter's pivot rounds is then the word the variants
+      // deviate from, and every variant is placed by its own difference in one round.)
+      DBuf<uint32_t> hrep(c, d), hpos(c, (size_t)d + 1), hwi(c, d), hw_sorted(c, d), fo_of_hw(c, d);
+      DBuf<uint64_t> okey(c, d), rep_sorted(c, d);
+      DBuf<uint32_t> hocc;
+      if (weight) {
+        hocc.alloc(c, d);
+        hocc.zero();
+        hipLaunchKernelGGL(weighted_occ_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, hscan.p, vs.p, weight, hocc.p);
+      }
+      hipLaunchKernelGGL(collect_words_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, head.p, hscan.p, vs.p, hrep.p,
+                         hpos.p, d);
+      hipLaunchKernelGGL(iota_u32_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, hwi.p, (uint64_t)d);
+      hipLaunchKernelGGL(word_order_keys_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, hrep.p, hpos.p,
+                         weight ? hocc.p : (const uint32_t *)nullptr, okey.p);
+      sort_pairs_u64_u32(c, okey.p, rep_sorted.p, hwi.p, hw_sorted.p, d, 0, 64);
+      D.wlen.alloc(c, d); D.wocc.alloc(c, d); D.woff.alloc(c, (size_t)d + 1); D.pid.alloc(c, P);
+      DBuf<uint32_t> wlen1(c, (size_t)d + 1);
+      wsrc.alloc(c, d);
+      hipLaunchKernelGGL(finish_words_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, g, d, rep_sorted.p, hw_sorted.p,
+                         hpos.p, weight ? hocc.p : (const uint32_t *)nullptr, fo_of_hw.p, D.wlen.p, wlen1.p, wsrc.p, D.wocc.p,
+                         counters.p + 2);
+      hipLaunchKernelGGL(assign_pid_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, hscan.p, vs.p, fo_of_hw.p, D.pid.p);
+      exclusive_sum_u32_u64(c, wlen1.p, D.woff.p, (size_t)d + 1);
+      PFP_HIP(hipMemcpyAsync(c->h_scalars, D.woff.p + d, 8, hipMemcpyDeviceToHost, c->stream));
+      PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, counters.p + 2, 4, hipMemcpyDeviceToHost, c->stream));
+      sync(c);
     }
-    // test hook (PFP_TEST_HASH_BITS=n: the first attempt keeps only n bits of every hash; -n: every attempt): different phrases then
-    // share a hash, the byte verification below finds it and the pass is repeated with another seed / gives up after four
-    const char *tb_env = getenv("PFP_TEST_HASH_BITS");      // (per call: tests switch it)
-    const int test_bits = tb_env ? atoi(tb_env) : 0;
-    if (test_bits && (attempt == 0 || test_bits < 0)) {
-      const int b = test_bits < 0 ? -test_bits : test_bits;
-      hipLaunchKernelGGL(mask_u64_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, hash.p, P, b >= 64 ? ~0ull : ((1ull << b) - 1ull));
+    uint32_t toolong; memcpy(&toolong, c->h_scalars + 1, 4);
+    D.dsize = c->h_scalars[0] + 1;
+    PFP_REQUIRE(!toolong, PFP_ELIMIT, "a phrase of 4 GiB or more");
+    PFP_REQUIRE(D.dsize < (1ull << 40), PFP_ELIMIT, "dictionary of 2^40 bytes or more");
+    D.bytes.alloc(c, D.dsize + 64);
+    PFP_HIP(hipMemsetAsync(D.bytes.p + (D.dsize - 1), 0, 65, c->stream));
+    // a long word is a long phrase's: none without one, and with one the copy takes its count from the device
+    DBuf<uint32_t> long_words(c, nlong);
+    hipLaunchKernelGGL(dict_copy_kernel, gdim(cdiv((uint64_t)d * 8, TB)), gdim(TB), 0, c->stream, tp, d, wsrc.p, D.wlen.p,
+                       D.woff.p, D.bytes.p, long_words.p, counters.p + 3);
+    if (nlong)
+      hipLaunchKernelGGL(dict_copy_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, tp, wsrc.p, D.wlen.p, D.woff.p,
+                         D.bytes.p, long_words.p, 0u, counters.p + 3);
+    if (want_last) {
+      D.last.alloc(c, P);
+      if (want_sai) D.sai.alloc(c, P);
     }
-    { SortTag tag("phrase hashes"); sort_pairs_u64_u32(c, hash.p, ks.p, iota.p, vs.p, P, 0, 64); }
-    { KScope kscope(c, "pfp::dedup_verify_kernel", 2 * n + 16 * P);
-    if (lg == 2) hipLaunchKernelGGL(dedup_verify_kernel<2>, gdim(cdiv(P * 4, TB)), gdim(TB), 0, c->stream, tp, g, P, ks.p, vs.p, head.p, counters.p + 1);
-    else hipLaunchKernelGGL(dedup_verify_kernel<3>, gdim(cdiv(P * 8, TB)), gdim(TB), 0, c->stream, tp, g, P, ks.p, vs.p, head.p, counters.p + 1); }
-    inclusive_sum_u32(c, head.p, hscan.p, P);
+    uint8_t *const last = want_last ? D.last.p : (uint8_t *)nullptr;
+    uint64_t *const sai = want_last && want_sai ? D.sai.p : (uint64_t *)nullptr;
+    { KScope kscope(c, "pfp::phrase_verify_kernel", n + 4 * P + 16ull * d + (want_last ? P : 0) + (sai ? 8 * P : 0));
+    if (lg == 2) hipLaunchKernelGGL(phrase_verify_kernel<2>, gdim(cdiv(P, kVerifyBlockPhrases)), gdim(kVerifyBlockPhrases), 0, c->stream, tp, g, P, D.pid.p, D.woff.p, D.wlen.p, D.bytes.p, sai_base, last, sai, counters.p + 1);
+    else hipLaunchKernelGGL(phrase_verify_kernel<3>, gdim(cdiv(P, kVerifyBlockPhrases)), gdim(kVerifyBlockPhrases), 0, c->stream, tp, g, P, D.pid.p, D.woff.p, D.wlen.p, D.bytes.p, sai_base, last, sai, counters.p + 1); }
+    if (nlong)
+      hipLaunchKernelGGL(phrase_verify_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, tp, g, long_list.p, nlong, D.pid.p,
+                         D.woff.p, D.wlen.p, D.bytes.p, counters.p + 1);
     PFP_HIP(hipGetLastError());
-    PFP_HIP(hipMemcpyAsync(c->h_scalars, counters.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
-    PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, hscan.p + (P - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    uint32_t coll; memcpy(&coll, c->h_scalars, 4);
-    memcpy(&d, c->h_scalars + 1, 4);
+    const uint32_t coll = read_scalar(c, counters.p + 1);
     if (!coll) break;
+    D.bytes.release(); D.woff.release(); D.wlen.release(); D.wocc.release(); D.pid.release(); D.last.release(); D.sai.release();
     PFP_REQUIRE(attempt < 3, PFP_ECOLLISION, "phrase hash collision survived 4 seeds (newscan.cpp:282-286)");
     seed = seed * 0x9E3779B97F4A7C15ULL + 0x7F4A7C15ULL;
     D.reseeds++;
   }
-  D.d = d;
-  // words by descending occurrence count, ties in first-occurrence order.  (The order inside the device dictionary is free -
-  // the outputs depend on the words' lexicographic ranks only - and this one makes the lowest position of a family of
-  // near-identical words its most frequent member: the pivot of the suffix sorter's pivot rounds is then the word the variants
-  // deviate from, and every variant is placed by its own difference in one round.)
-  DBuf<uint32_t> hrep(c, d), hpos(c, (size_t)d + 1), hwi(c, d), hw_sorted(c, d), fo_of_hw(c, d);
-  DBuf<uint64_t> okey(c, d), rep_sorted(c, d);
-  DBuf<uint32_t> hocc;
-  if (weight) {
-    hocc.alloc(c, d);
-    hocc.zero();
-    hipLaunchKernelGGL(weighted_occ_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, hscan.p, vs.p, weight, hocc.p);
-  }
-  hipLaunchKernelGGL(collect_words_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, head.p, hscan.p, vs.p, hrep.p,
-                     hpos.p, d);
-  hipLaunchKernelGGL(iota_u32_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, hwi.p, (uint64_t)d);
-  hipLaunchKernelGGL(word_order_keys_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, d, hrep.p, hpos.p,
-                     weight ? hocc.p : (const uint32_t *)nullptr, okey.p);
-  sort_pairs_u64_u32(c, okey.p, rep_sorted.p, hwi.p, hw_sorted.p, d, 0, 64);
-  D.wlen.alloc(c, d); D.wocc.alloc(c, d); D.woff.alloc(c, (size_t)d + 1); D.pid.alloc(c, P);
-  DBuf<uint32_t> wlen1(c, (size_t)d + 1);
-  DBuf<uint64_t> wsrc(c, d);
-  hipLaunchKernelGGL(finish_words_kernel, gdim(cdiv(d, TB)), gdim(TB), 0, c->stream, g, d, rep_sorted.p, hw_sorted.p,
-                     hpos.p, weight ? hocc.p : (const uint32_t *)nullptr, fo_of_hw.p, D.wlen.p, wlen1.p, wsrc.p, D.wocc.p,
-                     counters.p + 2);
-  hipLaunchKernelGGL(assign_pid_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, P, hscan.p, vs.p, fo_of_hw.p, D.pid.p);
-  exclusive_sum_u32_u64(c, wlen1.p, D.woff.p, (size_t)d + 1);
-  PFP_HIP(hipMemcpyAsync(c->h_scalars, D.woff.p + d, 8, hipMemcpyDeviceToHost, c->stream));
-  PFP_HIP(hipMemcpyAsync(c->h_scalars + 1, counters.p + 2, 4, hipMemcpyDeviceToHost, c->stream));
-  sync(c);
-  uint32_t toolong; memcpy(&toolong, c->h_scalars + 1, 4);
-  D.dsize = c->h_scalars[0] + 1;
-  PFP_REQUIRE(!toolong, PFP_ELIMIT, "a phrase of 4 GiB or more");
-  PFP_REQUIRE(D.dsize < (1ull << 40), PFP_ELIMIT, "dictionary of 2^40 bytes or more");
-  D.bytes.alloc(c, D.dsize + 64);
-  PFP_HIP(hipMemsetAsync(D.bytes.p + (D.dsize - 1), 0, 65, c->stream));
-  PFP_HIP(hipMemsetAsync(counters.p + 3, 0, 4, c->stream));
-  hipLaunchKernelGGL(dict_copy_kernel, gdim(cdiv((uint64_t)d * 8, TB)), gdim(TB), 0, c->stream, tp, d, wsrc.p, D.wlen.p,
-                     D.woff.p, D.bytes.p, long_list.p, counters.p + 3);
-  uint32_t nlongw = read_scalar(c, counters.p + 3);
-  if (nlongw)
-    hipLaunchKernelGGL(dict_copy_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, tp, wsrc.p, D.wlen.p, D.woff.p,
-                       D.bytes.p, long_list.p, nlongw);
-  if (want_last) {
-    D.last.alloc(c, P);
-    if (want_sai) D.sai.alloc(c, P);
-    hipLaunchKernelGGL(last_sai_kernel, gdim(cdiv(P, TB)), gdim(TB), 0, c->stream, tp, g, P, sai_base, D.last.p,
-                       want_sai ? D.sai.p : (uint64_t *)nullptr);
-  }
-  PFP_HIP(hipGetLastError());
 }
 
 void build_dictionary(pfp_ctx *c, const StagedText &tx, uint64_t n, int w, const DBuf<uint64_t> &ends, uint64_t n_ends,
@@ -453,7 +545,7 @@ void reorder_dictionary_by_occ(pfp_ctx *c, Dictionary &D, DBuf<uint32_t> &perm) 
   const uint32_t nlong = read_scalar(c, cnt.p);
   if (nlong)
     hipLaunchKernelGGL(dict_copy_long_kernel, gdim(c->n_cu * 4), gdim(TB), 0, c->stream, D.bytes.p, wsrc.p, nlen.p, nwoff.p, nb.p, long_list.p,
-                       nlong);
+                       nlong, (const uint32_t *)nullptr);
   PFP_HIP(hipGetLastError());
   D.bytes = std::move(nb); D.woff = std::move(nwoff); D.wlen = std::move(nlen); D.wocc = std::move(nocc);
 }
