@@ -374,11 +374,18 @@ __global__ void init_keys_int_kernel(const uint32_t *__restrict__ s, uint64_t N,
 // run of that symbol ends.  Suffixes inside a run x^r y order by (y < x: shorter run first | y > x:
 // longer run first), which plain doubling needs log2(r) rounds to find out - a parse of a text with
 // a long N run holds a run of 300 k equal phrases (18 rounds; with the run key 8).
+// out[0] = the largest symbol; out[1] != 0 where two neighbours are equal (s[i] == s[i+1], i + 1 < N): one pass answers both
 __global__ __launch_bounds__(256) void max_u32_kernel(const uint32_t *__restrict__ s, uint64_t N, uint32_t *__restrict__ out) {
   uint32_t m = 0;
-  for (uint64_t i = (uint64_t)BID * 256 + threadIdx.x; i < N; i += (uint64_t)GDIM * 256) m = s[i] > m ? s[i] : m;
+  bool pair = false;
+  for (uint64_t i = (uint64_t)BID * 256 + threadIdx.x; i < N; i += (uint64_t)GDIM * 256) {
+    const uint32_t x = s[i];
+    m = x > m ? x : m;
+    if (i + 1 < N && s[i + 1] == x) pair = true;
+  }
   for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_down(m, o, 64); m = v > m ? v : m; }
   if ((threadIdx.x & 63) == 0) atomicMax(out, m);
+  if (__any(pair) && (threadIdx.x & 63) == 0) atomicOr(out + 1, 1u);
 }
 __global__ void run_marks_kernel(const uint32_t *__restrict__ s, uint32_t N, uint32_t *__restrict__ v) {
   uint32_t j = BID * blockDim.x + threadIdx.x;      // reversed index
@@ -391,6 +398,11 @@ __global__ void init_keys_int_run_kernel(const uint32_t *__restrict__ s, uint32_
   uint32_t i = BID * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const uint64_t a = s[i], b = (i + 1 < N) ? s[i + 1] : 0;
+  val[i] = i;
+  // pm null: the string has no two equal neighbours, e would be 0 everywhere: the two symbols alone, right-aligned.  That is
+  // the run key shifted right by 64 - 2 sb: order and equality of the keys are the same, the stable sort leaves ties in position
+  // order either way, so the sorted permutation is the same - from a sort of 2 sb bits instead of 64
+  if (!pm) { key[i] = (a << sb) | b; return; }
   const int eb = 64 - 2 * sb;
   uint64_t e = 0;
   if (b == a && i + 1 < N) {
@@ -402,7 +414,6 @@ __global__ void init_keys_int_run_kernel(const uint32_t *__restrict__ s, uint32_
     e = up ? ((1ull << (eb - 1)) | (cap - r)) : r;
   }
   key[i] = (a << (64 - sb)) | (b << (64 - 2 * sb)) | e;
-  val[i] = i;
 }
 template <class I>
 __global__ void iota_kernel(I *p, uint64_t n) {
@@ -562,9 +573,18 @@ static uint64_t parse_pivot_min() {
   const uint64_t v = strtoull(e, nullptr, 10);
   return v ? v : ~0ull;
 }
+// 16-byte load steps a member issues together in the pivot round's key kernel.  (Measured on configs[2], 15.2 M members: 4 steps
+// 0.69 ms at 54 VGPRs, 8 steps 0.80 ms at 86 VGPRs and five waves per SIMD, the one-step loop 0.85 ms)
+// PFP_IPIVOT_BATCH=0, read per call, takes the one-step loop.
+constexpr int kIntPivBatch = 4;
+static bool ipivot_batched() {
+  const char *e = getenv("PFP_IPIVOT_BATCH");
+  return !(e && atoi(e) == 0);
+}
 template <class I>
 __global__ void ipivot_select_kernel(uint64_t m, uint64_t N, uint64_t h, const I *__restrict__ act_i, const I *__restrict__ act_grp,
-                                     const uint32_t *__restrict__ dist, unsigned long long *__restrict__ best) {
+                                     const uint32_t *__restrict__ dist, unsigned long long *__restrict__ best,
+                                     uint32_t *__restrict__ dvs) {
   const uint64_t a = (uint64_t)BID * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   unsigned long long v = 0;
@@ -573,6 +593,7 @@ __global__ void ipivot_select_kernel(uint64_t m, uint64_t N, uint64_t h, const I
     const uint64_t i = act_i[a];
     g = act_grp[a];
     const uint32_t dv = i + h < N ? dist[i + h] : 0u;
+    if (dvs) dvs[a] = dv;      // (coalesced; ipivot_keys_batch_kernel sizes its loads by it instead of gathering dist[] again)
     v = ((unsigned long long)dv << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)a);      // ties: the first member
   }
   // the members of a group are neighbours: maximum over the run of equal groups that ends at this lane, one atomic per run and wave
@@ -615,6 +636,68 @@ __global__ void ipivot_keys_kernel(uint64_t m, uint64_t N, uint64_t h, uint32_t 
           k = ((uint64_t)(x[j] < y[j] ? qq : 2 * cap + 2 - qq) << 32) | x[j];
           done = true;
         }
+    }
+  }
+  key[a] = k;
+  val[a] = (I)i;
+}
+// The same key from loads that are issued together.  The loop above is a chain: every step's two loads wait for the compare of the
+// step before, and a wave waits for its longest lane.  But a member leaves the pivot at its own variant, dvs[a] symbols on
+// (ipivot_select_kernel has just read that distance), so the likely length of its walk is known before the first symbol is loaded:
+// the lane issues the load pairs of the ceil(need / 4) steps that reach its variant, at most B of them, before the first compare,
+// then compares in order.  The loads are predicated per lane: none reads past its own need, its batch or the end of the string.
+// A lane still equal after its batch (a distance of more than 4 B symbols; beyond its own variant: the rest of cap) takes the next
+// one.  Steps that would cross the end of the string go one by one, as above; the key is bit for bit the one of the loop above.
+template <class I, int B>
+__global__ __launch_bounds__(256) void ipivot_keys_batch_kernel(uint64_t m, uint64_t N, uint64_t h, uint32_t cap,
+                                                                const uint32_t *__restrict__ sym, const I *__restrict__ act_i,
+                                                                const I *__restrict__ act_grp, const unsigned long long *__restrict__ best,
+                                                                const uint32_t *__restrict__ dvs, uint64_t *__restrict__ key,
+                                                                I *__restrict__ val) {
+  const uint64_t a = (uint64_t)BID * blockDim.x + threadIdx.x;
+  if (a >= m) return;
+  const uint64_t i = act_i[a];
+  const uint64_t piv = act_i[0xFFFFFFFFu - (uint32_t)(best[act_grp[a]] & 0xFFFFFFFFull)];
+  uint64_t k = (uint64_t)(cap + 1) << 32;      // the pivot itself, and whoever equals it for cap symbols
+  if (i != piv) {
+    const uint32_t dv = dvs[a];
+    const uint32_t need = dv < cap ? dv + 1 : cap;      // symbols up to and including the member's own variant
+    bool done = false;
+    uint32_t q = 0;
+    auto differ = [&](uint32_t qq, uint32_t x, uint32_t y) {
+      if (!done && qq < cap && x != y) {
+        k = ((uint64_t)(x < y ? qq : 2 * cap + 2 - qq) << 32) | x;
+        done = true;
+      }
+    };
+    while (q < cap && !done) {
+      const uint64_t pi = i + h + q, pp = piv + h + q;
+      const uint64_t far = pi > pp ? pi : pp;
+      const uint64_t room = far + 4 <= N ? (N - far) / 4 : 0;      // whole 16-byte steps that both strings still hold
+      if (room == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) differ(q + (uint32_t)j, pi + j < N ? sym[pi + j] : 0u, pp + j < N ? sym[pp + j] : 0u);
+        q += 4;
+        continue;
+      }
+      const uint32_t want = need > q ? need - q : cap - q;
+      uint32_t steps = (want + 3) / 4;
+      if (steps > (uint32_t)B) steps = B;
+      if (steps > room) steps = (uint32_t)room;
+      uint4 X[B], Y[B];
+#pragma unroll
+      for (int s = 0; s < B; s++)
+        if ((uint32_t)s < steps) {
+          X[s] = ld16u(reinterpret_cast<const uint8_t *>(sym + pi + 4 * s));
+          Y[s] = ld16u(reinterpret_cast<const uint8_t *>(sym + pp + 4 * s));
+        }
+#pragma unroll
+      for (int s = 0; s < B; s++)
+        if ((uint32_t)s < steps && !done) {
+          const uint32_t qs = q + 4 * (uint32_t)s;
+          differ(qs, X[s].x, Y[s].x); differ(qs + 1, X[s].y, Y[s].y); differ(qs + 2, X[s].z, Y[s].z); differ(qs + 3, X[s].w, Y[s].w);
+        }
+      q += 4 * steps;
     }
   }
   key[a] = k;
@@ -1499,9 +1582,17 @@ struct Rounds {
       DBuf<unsigned long long> best(c, N);
       best.zero();
       KScope ks(c, "pfp::ipivot_keys_kernel", m * (4 + 4 + 4 + 8 + 16 + 12 + 64));
-      hipLaunchKernelGGL(ipivot_select_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, act_i.p, act_grp.p, g.dist, best.p);
-      hipLaunchKernelGGL(ipivot_keys_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, kIntPivCap, g.sym, act_i.p,
-                         act_grp.p, best.p, key.p, val.p);
+      // the members' distances travel from one kernel to the other in hv[] (list_cap >= m entries of at least 4 bytes; nothing
+      // of the list's scratch is live between next_list() and the heads of the coming sort)
+      const bool batched = ipivot_batched();
+      uint32_t *dvs = batched ? reinterpret_cast<uint32_t *>(hv.p) : nullptr;
+      hipLaunchKernelGGL(ipivot_select_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, act_i.p, act_grp.p, g.dist, best.p, dvs);
+      if (batched)
+        hipLaunchKernelGGL((ipivot_keys_batch_kernel<I, kIntPivBatch>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, kIntPivCap, g.sym,
+                           act_i.p, act_grp.p, best.p, dvs, key.p, val.p);
+      else
+        hipLaunchKernelGGL(ipivot_keys_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, kIntPivCap, g.sym, act_i.p,
+                           act_grp.p, best.p, key.p, val.p);
     }
     // small groups (pairs of copies with a common SNP): placed by counting in LDS, whatever PFP_NO_SMALLSEG says
     bool sorted = m / ngrp <= kSmallSeg / 2 && place_small_groups(key.p, keyo.p);
@@ -1793,17 +1884,24 @@ template void sort_byte_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t,
 // allocated itself is not allocated here: each entry point keeps the order of its requests to the pool, which hands out its cached
 // blocks by that order - the buffers of a sort lie where they lay when each sorter had its own setup.
 struct IntKeys {
-  DBuf<uint32_t> mx, dist, val;      // (mx: the largest symbol; held with the rest, as it always has been: the pool's peak counts it)
+  DBuf<uint32_t> mx, dist, val;      // (mx: the largest symbol and the equal-neighbours flag; held with the rest, as it always has been: the pool's peak counts it)
   DBuf<uint64_t> key;
+  int key_bits = 64;                 // the keys' width, for DoublingOpts::key_bits
 };
+// narrow_ok: the caller sorts the keys as doubling() does and reads them for order and equality only, so a string without equal
+// neighbours may get the two-symbol key of 2 sb bits (init_keys_int_run_kernel) instead of the 64-bit run key.  PFP_PARSE_KEYBITS=0
+// (read per call: tests and measurements switch it) keeps the run key.
 static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t N, uint32_t max_sym, const uint32_t *occ, uint32_t n_sym,
-                           bool want_dist, const char *dist_scope, const char *plain_scope, uint64_t plain_bytes, IntKeys &k) {
+                           bool want_dist, const char *dist_scope, const char *plain_scope, uint64_t plain_bytes, bool narrow_ok,
+                           IntKeys &k) {
   // the symbol width is measured, not taken on trust (max_sym is only an upper bound for the check)
   auto need = [&](auto &b) { if (!b.p) b.alloc(c, N); };
-  k.mx.alloc(c, 1);
+  k.mx.alloc(c, 2);
   k.mx.zero();
   hipLaunchKernelGGL(max_u32_kernel, gdim((int)std::min<uint64_t>(cdiv64(N, 256), 1024)), gdim(256), 0, c->stream, sym, N, k.mx.p);
-  const uint32_t real_max = read_scalar(c, k.mx.p);
+  const uint64_t mx2 = read_scalar(c, reinterpret_cast<const uint64_t *>(k.mx.p));      // (one read-back for both words)
+  const uint32_t real_max = (uint32_t)mx2;
+  const bool has_pair = (mx2 >> 32) != 0;
   PFP_REQUIRE(real_max <= max_sym, PFP_EFORMAT, "integer string holds a symbol above its alphabet size");
   const int sb = bits_for(real_max);
   g.sym = sym;
@@ -1822,17 +1920,33 @@ static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t
   }
   need(k.key);
   need(k.val);
+  const char *layout = "plain";
   if (64 - 2 * sb >= 6) {
-    ks.emplace(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
-    DBuf<uint32_t> v(c, N), pm(c, N);
-    hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
-    inclusive_max_u32(c, v.p, pm.p, N);
-    hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, k.key.p,
-                       k.val.p);
+    const char *e = getenv("PFP_PARSE_KEYBITS");
+    const bool narrow = narrow_ok && !has_pair && !(e && atoi(e) == 0);
+    if (narrow) {
+      // no run ends to find: no marks, no running maximum, no N-long temporaries; the same kernel under the same label
+      ks.emplace(c, "pfp::init_keys_int_run_kernel", N * 16);
+      hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, (const uint32_t *)nullptr, sb,
+                         k.key.p, k.val.p);
+      k.key_bits = 2 * sb;
+      layout = "two symbols";
+    } else {
+      ks.emplace(c, "pfp::init_keys_int_run_kernel", N * 28);      // (+ run_marks_kernel and its running maximum)
+      DBuf<uint32_t> v(c, N), pm(c, N);
+      hipLaunchKernelGGL(run_marks_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, v.p);
+      inclusive_max_u32(c, v.p, pm.p, N);
+      hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, pm.p, sb, k.key.p,
+                         k.val.p);
+      layout = "run";
+    }
   } else {
     ks.emplace(c, plain_scope, plain_bytes);
     hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, k.key.p, k.val.p);
   }
+  // (per call, unlike the round lines: the tests tell the layouts apart by this line inside one process)
+  if (getenv("PFP_TRACE_ROUNDS"))
+    fprintf(stderr, "[pfp] integer first-round keys N=%llu sb=%d: %s layout, sorted bits [0, %d)\n", (unsigned long long)N, sb, layout, k.key_bits);
 }
 
 void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder &out, uint32_t max_sym, const uint32_t *occ,
@@ -1842,8 +1956,10 @@ void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder 
   IntKeys k;
   k.key.alloc(c, N);
   k.val.alloc(c, N);
-  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, occ && n_sym && N >= parse_pivot_min(), nullptr, "pfp::init_keys_int_kernel", N * (8 + 8 + 4), k);
-  doubling<uint32_t>(c, g, k.key, k.val, 2, out, DoublingOpts{});
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, occ && n_sym && N >= parse_pivot_min(), nullptr, "pfp::init_keys_int_kernel", N * (8 + 8 + 4), true, k);
+  DoublingOpts o;
+  o.key_bits = k.key_bits;
+  doubling<uint32_t>(c, g, k.key, k.val, 2, out, o);
 }
 
 // ---- one rank's share of a suffix array (multi-GPU chain): the suffixes of one key range out of `parts`.  First what the two share
@@ -2168,7 +2284,9 @@ void sort_int_suffixes_range(pfp_ctx *c, const uint32_t *sym, uint64_t N, uint32
   SufGeom g{MODE_PLAIN, N, WordView{}};
   IntKeys k;
   k.dist.alloc(c, N);
-  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, true, "pfp::rare_dist_kernel", "pfp::init_keys_int_run_kernel", N * 28, k);
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, true, "pfp::rare_dist_kernel", "pfp::init_keys_int_run_kernel", N * 28, false, k);
+  // (narrow_ok false: the share keeps the 64-bit run key - its splitters and out.klo / out.khi are first-round keys that leave this
+  //  function, and every rank and the caller must read them in one layout)
   k.val.release();      // unread: the list's values are gathered from the positions
   const Splitters sp = share_splitters(c, N, part, parts, false, [&](uint64_t stride, uint32_t ns, uint64_t *sk, uint32_t *sv) {
     hipLaunchKernelGGL(sample_u64_kernel, gdim(cdiv(ns, 256)), gdim(256), 0, c->stream, k.key.p, stride, ns, sk, sv);
