@@ -128,7 +128,7 @@ struct SuffixOrderT {
   DBuf<I> sa;            // [N] suffix start positions in sorted order (ties: position order)
   DBuf<I> grp;           // [N] grp[t] = first sa slot of slot t's group (equal strings share it)
   DBuf<I> rank;          // [NP] rank[i] = grp[slot of i]; kNone where the sorter never needed it (see RankView); not allocated
-                         // where no round ever read it (then: wordrank)
+                         // where no round ever read it (then: wordrank; plain mode: nothing - sa and grp are the result)
   DBuf<I> wordrank;      // [d+1] rank of word j's whole-word suffix where a round after the first settled it, else kNone
   uint64_t rounds = 0;
   // Dictionary mode keeps the sorted first-round keys: the rank of a suffix that the first round

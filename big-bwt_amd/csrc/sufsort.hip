@@ -785,7 +785,9 @@ __global__ void heads_kernel(uint64_t m, const K *__restrict__ key, const I *__r
 // Per workgroup of 256 slots also the index of its last head (0 = none, slot 0 is always a head): a
 // max-scan over those 4 bytes per 256 slots gives every workgroup of write_back0 its carry-in, and
 // the head of each slot is found from the head flags with ballots - no N-long scan of head indices.
-template <class I>
+// Plain mode (DICT false: the first round of a parse or a byte text) takes the same kernel without the key mask, the bucket
+// table.
+template <class I, bool DICT>
 __global__ __launch_bounds__(256) void heads0_kernel(uint64_t m, const uint64_t *__restrict__ key, uint64_t keymask, int shift,
                                                      uint32_t T, uint8_t *__restrict__ hd, I *__restrict__ tile_last,
                                                      I *__restrict__ tab) {
@@ -794,10 +796,14 @@ __global__ __launch_bounds__(256) void heads0_kernel(uint64_t m, const uint64_t 
   const uint64_t a = (uint64_t)BID * 256 + threadIdx.x;
   bool h = false;
   if (a < m) {
-    const uint64_t k = key[a] & keymask, kprev = a ? (key[a - 1] & keymask) : ~k;
-    h = k != kprev;
+    if constexpr (DICT) {
+      const uint64_t k = key[a] & keymask, kprev = a ? (key[a - 1] & keymask) : ~k;
+      h = k != kprev;
+      if (a == 0 || (k >> shift) != (kprev >> shift)) tab[T - 1 - (uint32_t)(k >> shift)] = IdxTraits<I>::kNone - (I)a;
+    } else {
+      h = a == 0 || key[a] != key[a - 1];
+    }
     hd[a] = h ? 1 : 0;
-    if (a == 0 || (k >> shift) != (kprev >> shift)) tab[T - 1 - (uint32_t)(k >> shift)] = IdxTraits<I>::kNone - (I)a;
   }
   const unsigned long long mask = __ballot(h);
   if ((threadIdx.x & 63) == 0)
@@ -816,13 +822,18 @@ __global__ void fill_kernel(I *p, uint64_t n, I v) {
 }
 // First round of dictionary mode: sa and grp are the sorted values / scanned heads themselves
 // (streaming copies); rank[] is written only for the suffixes that stay unresolved.
-template <class I>
+// Plain mode (DICT false): no terminator flag in the key, nothing settles but a singleton, and rank[] - where there is one - gets
+// every suffix, as no search over the sorted keys stands in for it there.
+// tile_keep / tile_heads (not null): kept slots and kept group heads of these 256 slots, as active_count_kernel counts them.
+template <class I, bool DICT>
 __global__ __launch_bounds__(256) void write_back0_kernel(uint64_t m, const I *__restrict__ val,
                                                           const I *__restrict__ tile_scan,
                                                           const uint8_t *__restrict__ hd, const uint64_t *__restrict__ key0,
                                                           I *__restrict__ rank,
-                                                          I *__restrict__ grp, uint8_t *__restrict__ keep, int write_ranks) {
+                                                          I *__restrict__ grp, uint8_t *__restrict__ keep, int write_ranks,
+                                                          uint32_t *__restrict__ tile_keep, uint32_t *__restrict__ tile_heads) {
   __shared__ I wl[4];
+  __shared__ uint32_t wk[4], wh[4];
   if ((uint64_t)BID * 256 >= m) return;      // a workgroup of the padded last grid row
   const uint64_t a = (uint64_t)BID * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -831,12 +842,24 @@ __global__ __launch_bounds__(256) void write_back0_kernel(uint64_t m, const I *_
   const bool h = in && hd[a];
   const bool hnext = in && (a + 1 == m || hd[a + 1]);
   const I i = in ? val[a] : (I)0;
-  const uint32_t flagbit = in ? (uint32_t)(key0[a] & 1ull) : 0u;
+  uint32_t flagbit = 0u;
+  if constexpr (DICT) flagbit = in ? (uint32_t)(key0[a] & 1ull) : 0u;
   const I carry = BID ? tile_scan[BID - 1] : (I)0;
   const unsigned long long mask = __ballot(h);
   const I wbase = (I)(BID * 256ull + (threadIdx.x & ~63));
+  const bool single = h && hnext;
+  const bool fin = !single && flagbit;       // the terminator is inside the key: the tied strings are identical
+  const bool k = in && !single && !fin;
   if (lane == 0) wl[wv] = mask ? wbase + (63 - __clzll((long long)mask)) : (I)0;
+  if (tile_keep) {
+    const unsigned long long km = __ballot(k), khm = __ballot(k && h);
+    if (lane == 0) { wk[wv] = (uint32_t)__popcll(km); wh[wv] = (uint32_t)__popcll(khm); }
+  }
   __syncthreads();
+  if (tile_keep && threadIdx.x == 0) {
+    tile_keep[BID] = wk[0] + wk[1] + wk[2] + wk[3];
+    tile_heads[BID] = wh[0] + wh[1] + wh[2] + wh[3];
+  }
   if (!in) return;
   // head of slot a: the last head flag at or before it - in its wave, else in an earlier wave of the
   // workgroup, else the carry-in (last head of all earlier workgroups)
@@ -848,10 +871,11 @@ __global__ __launch_bounds__(256) void write_back0_kernel(uint64_t m, const I *_
     for (int q = 0; q < wv; q++) head = wl[q] > head ? wl[q] : head;
   }
   grp[a] = head;       // sa[] is the sorted value array itself (moved into place by the host)
-  const bool single = h && hnext;
-  const bool fin = !single && flagbit;       // the terminator is inside the key: the tied strings are identical
-  const bool k = !single && !fin;
-  if (k && write_ranks) rank[i] = head;       // lazy mode: rank[] of an unresolved suffix is filled in when a doubling round asks
+  if constexpr (DICT) {
+    if (k && write_ranks) rank[i] = head;     // lazy mode: rank[] of an unresolved suffix is filled in when a doubling round asks
+  } else {
+    if (rank) rank[i] = head;
+  }
   keep[a] = k ? 1 : 0;
 }
 
@@ -861,7 +885,7 @@ template <class I>
 __global__ void scatter_settled_kernel(uint64_t N, const I *__restrict__ sa, const I *__restrict__ grp,
                                        const uint8_t *__restrict__ keep, I finbit, I *__restrict__ rank) {
   uint64_t t = (uint64_t)BID * blockDim.x + threadIdx.x;
-  if (t < N && !keep[t]) rank[sa[t]] = grp[t] | finbit;
+  if (t < N && !(keep && keep[t])) rank[sa[t]] = grp[t] | finbit;      // (keep null, plain mode's late rank[]: every slot)
 }
 
 // Pivot rounds.  The unresolved groups of a dictionary of near-identical phrases (a collection of
@@ -1125,6 +1149,11 @@ struct SorterSwitches {
   uint32_t pivot_cap = []() { const char *e = getenv("PFP_PIVOT_CAP"); uint32_t v = e ? (uint32_t)atoll(e) : 512u; return v > kPivCapMax ? kPivCapMax : v; }();
 };
 static const SorterSwitches kSwitch;
+// ... and the ones read per call (0 = the path before it; the tests compare both inside one process):
+//   PFP_PLAIN_LAZY_RANK   plain mode keeps no rank[] until a doubling round asks for it
+//   PFP_PLAIN_TILES       plain mode's first round regroups by the dictionary's tile scheme (heads0 / write_back0)
+//   PFP_DICT_FOLD         dictionary first round: the tile counts come from write_back0, keep0 is the first round's keep[] itself
+static bool switch_on(const char *name) { const char *e = getenv(name); return !e || atoi(e) != 0; }
 
 template <class I>
 RankViewT<I> rank_view(const SuffixOrderT<I> &so) {
@@ -1146,7 +1175,8 @@ struct DoublingOpts {
 // The sort that the regroup step finds: where its sorted keys are and what they mean.
 enum class Round {
   FirstDict,            // first round of a dictionary: packed keys in keyo (heads0 / write_back0, which also start the lazy ranks)
-  FirstPlain,           // first round of a parse or a byte text: keys in keyo, no groups before it
+  FirstPlain,           // first round of a parse or a byte text: keys in keyo, no groups before it (heads0 / write_back0 without the
+                        // dictionary's key mask, bucket table and flag bit; PFP_PLAIN_TILES=0: the list path of the later rounds)
   DictPivotGlobal,      // dictionary pivot round ordered by one device-wide sort: (group, order key) in keyo
   DictPivotGrouped,     // ... ordered inside its groups: order keys in k32o
   ParsePivot,           // parse pivot round: 64-bit keys in keyo, ordered inside its groups
@@ -1176,7 +1206,9 @@ struct Rounds {
   // among the listed suffixes, rank[] or wordrank[] and the search over skeys (rank_at) - so the words' ranks cost no pass.
   const bool range_mode;
   const int nb;                 // key of a later round = (group head << nb) | (1 + rank of the continuation)
+  const bool plain_lazy, plain_tiles, dict_fold;      // (the per-call switches above)
   bool lazy_active = false, late_rank = false;      // (see start_rounds)
+  bool plain_late = false;      // plain mode without rank[] so far: the first doubling round fills it from the slots
   I *rank_p = nullptr, *wordrank_p = nullptr;
 
   // ---- the loop's variables
@@ -1196,13 +1228,13 @@ struct Rounds {
   // ---- buffers of the first round only
   DBuf<uint64_t> &key;          // (the caller's; with keyo/valo the ping-pong pairs of every device-wide sort)
   DBuf<I> &val;
-  DBuf<I> tile_last, tile_scan;      // dictionary mode: last head per 256 slots, and its running maximum
+  DBuf<I> tile_last, tile_scan;      // first round by tiles: last head per 256 slots, and its running maximum
   // ---- every round
   DBuf<uint64_t> keyo;
   DBuf<I> valo;
   DBuf<uint8_t> hd, keep;
   // active list (slot, suffix, group) of the unresolved suffixes and per-round scratch, list_cap elements each;
-  // dictionary mode allocates them when the first round has told how many suffixes stay unresolved
+  // a first round by tiles (tiles_first) allocates them when it has told how many suffixes stay unresolved
   DBuf<I> aslot, aslot2, hv, newhead, act_i, act_grp;
   uint64_t list_cap = 0;
   DBuf<uint32_t> tile_keep, tile_heads;
@@ -1220,7 +1252,11 @@ struct Rounds {
   Rounds(pfp_ctx *c_, const SufGeom &g_, DBuf<uint64_t> &key_, DBuf<I> &val_, uint64_t h0, SuffixOrderT<I> &out_, const DoublingOpts &o_)
       : c(c_), g(g_), out(out_), o(o_), NP(g_.N), N(o_.list_len.value_or(g_.N)), lazy(o_.dict), list_mode(o_.list_len.has_value()),
         range_mode(o_.list_len.has_value() && !o_.whole_list),
-        nb(bits_for(N)), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_), val(val_) {}
+        nb(bits_for(N)), plain_lazy(!o_.dict && switch_on("PFP_PLAIN_LAZY_RANK")), plain_tiles(!o_.dict && switch_on("PFP_PLAIN_TILES")),
+        dict_fold(o_.dict && switch_on("PFP_DICT_FOLD")), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_),
+        val(val_) {}
+  // the first round regroups by tiles (slot == index, no list yet): a dictionary always, plain mode by its switch
+  bool tiles_first() const { return lazy || plain_tiles; }
 
   static uint64_t blocks(uint64_t n) { return cdiv(n, TB); }
 
@@ -1261,9 +1297,11 @@ struct Rounds {
     hd.alloc(c, N + 1); keep.alloc(c, N);
     out.grp.alloc(c, N + 8);
     if (!lazy) {
-      out.sa.alloc(c, N);
-      alloc_lists(N);
-      hipLaunchKernelGGL(iota_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, aslot.p, N);
+      if (!plain_tiles) {      // (by tiles: sa is the sorted value array, the lists come when the round has told their size)
+        out.sa.alloc(c, N);
+        alloc_lists(N);
+        hipLaunchKernelGGL(iota_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, aslot.p, N);
+      }
     } else {
       const int tb = std::min(o.key_bits, std::max(8, std::min(24, bits_for(N) - 5)));
       out.shift = o.key_bits - tb;
@@ -1282,7 +1320,10 @@ struct Rounds {
     // dictionary of word families never gets there - so it is allocated when (if) that round comes (late_rank); until then the
     // whole words, whose ranks order the dictionary, report to wordrank[d].  (PFP_DEBUG validates every rank: eager.)
     late_rank = !range_mode && lazy_active && !c->debug;
-    if (!range_mode && !late_rank) alloc_rank();
+    // Plain mode: only a doubling round reads rank[], and the parse of a collection is settled by its pivot round and the
+    // finisher; sa[] and grp[] are complete after every round there, so the round that asks fills rank[] from them in one pass
+    plain_late = !lazy && !range_mode && plain_lazy && !c->debug;
+    if (!range_mode && !late_rank && !plain_late) alloc_rank();
     if (late_rank) {
       out.wordrank.alloc(c, (uint64_t)g.wv.d + 1);
       PFP_HIP(hipMemsetAsync(out.wordrank.p, 0xff, ((uint64_t)g.wv.d + 1) * sizeof(I), c->stream));
@@ -1304,19 +1345,41 @@ struct Rounds {
     hipLaunchKernelGGL(heads32_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, gs.p, k32o.p, aslot.p, hd.p, hv.p);
   }
 
+  // tile counts of the kept slots and kept heads, written by the first round's write-back (compact() then launches no count)
+  bool counts_from_write_back() const { return lazy ? dict_fold : plain_tiles; }
+  void alloc_tile_counts() {
+    if (!tile_keep.p) { tile_keep.alloc(c, cdiv64(N, kTile) + 1); tile_heads.alloc(c, cdiv64(N, kTile) + 1);
+                        tile_off.alloc(c, cdiv64(N, kTile) + 1); tile_hoff.alloc(c, cdiv64(N, kTile) + 1); }
+  }
   void first_dict_heads_and_write_back() {
+    const bool counts = counts_from_write_back();
+    if (counts) alloc_tile_counts();
     tile_last.alloc(c, cdiv64(m, 256)); tile_scan.alloc(c, cdiv64(m, 256));
     { KScope ks(c, "pfp::heads0_kernel", m * 13);
-      hipLaunchKernelGGL(heads0_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, keyo.p, out.keymask, out.shift, out.T,
+      hipLaunchKernelGGL((heads0_kernel<I, true>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, keyo.p, out.keymask, out.shift, out.T,
                          hd.p, tile_last.p, out.tab.p); }
     inclusive_max<I>(c, out.tab.p, out.tab.p, out.T);
     inclusive_max<I>(c, tile_last.p, tile_scan.p, cdiv64(m, 256));
     { KScope ks(c, "pfp::write_back0_kernel", m * (4 + 4 + 1 + 8 + 4 + 1));
-      hipLaunchKernelGGL(write_back0_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, valo.p, tile_scan.p, hd.p, keyo.p,
-                         rank_p, out.grp.p, keep.p, (lazy_active || range_mode) ? 0 : 1); }
+      hipLaunchKernelGGL((write_back0_kernel<I, true>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, valo.p, tile_scan.p, hd.p, keyo.p,
+                         rank_p, out.grp.p, keep.p, (lazy_active || range_mode) ? 0 : 1,
+                         counts ? tile_keep.p : (uint32_t *)nullptr, counts ? tile_heads.p : (uint32_t *)nullptr); }
     if (lazy_active) active_stale = true;
     // the sorted keys and the sorted positions stay with the result; later rounds sort the (smaller) active set elsewhere
     out.skeys = std::move(keyo);
+    out.sa = std::move(valo);
+  }
+  // plain mode by tiles: the same two kernels without what belongs to the dictionary's keys; the sorted keys stay in keyo
+  void first_plain_heads_and_write_back() {
+    alloc_tile_counts();
+    tile_last.alloc(c, cdiv64(m, 256)); tile_scan.alloc(c, cdiv64(m, 256));
+    { KScope ks(c, "pfp::heads0_kernel", m * 9);
+      hipLaunchKernelGGL((heads0_kernel<I, false>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, keyo.p, ~0ull, 0, 0u, hd.p, tile_last.p,
+                         (I *)nullptr); }
+    inclusive_max<I>(c, tile_last.p, tile_scan.p, cdiv64(m, 256));
+    { KScope ks(c, "pfp::write_back0_kernel", m * (sizeof(I) + 1 + sizeof(I) + 1 + (rank_p ? sizeof(I) : 0)));
+      hipLaunchKernelGGL((write_back0_kernel<I, false>), gdim(blocks(m)), gdim(TB), 0, c->stream, m, valo.p, tile_scan.p, hd.p,
+                         (const uint64_t *)nullptr, rank_p, out.grp.p, keep.p, 0, tile_keep.p, tile_heads.p); }
     out.sa = std::move(valo);
   }
 
@@ -1332,7 +1395,10 @@ struct Rounds {
     bool pivot = false;
     switch (kind) {
       case Round::FirstDict: return first_dict_heads_and_write_back();
-      case Round::FirstPlain: heads(keyo.p, 17); break;
+      case Round::FirstPlain:
+        if (plain_tiles) return first_plain_heads_and_write_back();
+        heads(keyo.p, 17);
+        break;
       case Round::DictPivotGlobal: heads(keyo.p, 17); keys = keyo.p; pivot = true; break;
       case Round::DictPivotGrouped: heads_k32(); prevgrp = act_grp.p; pivk32 = k32o.p; pivot = true; break;
       case Round::ParsePivot: {
@@ -1371,10 +1437,9 @@ struct Rounds {
 
   // kept suffixes / kept group heads per tile -> offsets -> placement into the next active list; sets m2 and ngrp
   void compact() {
-    const bool round0 = kind == Round::FirstDict;
+    const bool round0 = kind == Round::FirstDict || (kind == Round::FirstPlain && plain_tiles);      // slot == index, no list yet
     const uint64_t ntile = cdiv64(m, kTile);
-    if (!tile_keep.p) { tile_keep.alloc(c, cdiv64(N, kTile) + 1); tile_heads.alloc(c, cdiv64(N, kTile) + 1);
-                        tile_off.alloc(c, cdiv64(N, kTile) + 1); tile_hoff.alloc(c, cdiv64(N, kTile) + 1); }
+    alloc_tile_counts();
     auto read_counts = [&]() {
       sync(c);
       I t0, t1;
@@ -1385,8 +1450,9 @@ struct Rounds {
       PFP_HIP(hipMemsetAsync(tile_keep.p + ntile, 0, 4, c->stream));
       PFP_HIP(hipMemsetAsync(tile_heads.p + ntile, 0, 4, c->stream));
       KScope ks(c, "pfp::active_place_kernel", m * 2 + 0);      // (+ active_count_kernel and the two tile scans)
-      hipLaunchKernelGGL(active_count_kernel, gdim((unsigned)cdiv64(ntile, 16)), gdim(256), 0, c->stream, keep.p, hd.p, m,
-                         tile_keep.p, tile_heads.p);
+      if (!(round0 && counts_from_write_back()))
+        hipLaunchKernelGGL(active_count_kernel, gdim((unsigned)cdiv64(ntile, 16)), gdim(256), 0, c->stream, keep.p, hd.p, m,
+                           tile_keep.p, tile_heads.p);
       exclusive_sum_u32_to<I>(c, tile_keep.p, tile_off.p, ntile + 1);
       exclusive_sum_u32_to<I>(c, tile_heads.p, tile_hoff.p, ntile + 1);
       PFP_HIP(hipMemcpyAsync(c->h_scalars, tile_off.p + ntile, sizeof(I), hipMemcpyDeviceToHost, c->stream));
@@ -1412,12 +1478,17 @@ struct Rounds {
       // whether the settled ranks get scattered after all is decided when (if) a doubling round
       // first needs them: pivot rounds read the strings, not rank[]
       lazy_pending = true;
-      keep0.alloc(c, N);
-      PFP_HIP(hipMemcpyAsync(keep0.p, keep.p, N, hipMemcpyDeviceToDevice, c->stream));
+      if (dict_fold) {      // the first round's keep[] itself; the list rounds flag list positions, m2 of them at most
+        keep0 = std::move(keep);
+        keep.alloc(c, m2);
+      } else {
+        keep0.alloc(c, N);
+        PFP_HIP(hipMemcpyAsync(keep0.p, keep.p, N, hipMemcpyDeviceToDevice, c->stream));
+      }
       out.n_refined = m2;
       if (out.paybits) {       // the merge wants to know which slots were re-ordered after this round
         out.refined.alloc(c, N + 16);
-        PFP_HIP(hipMemcpyAsync(out.refined.p, keep.p, N, hipMemcpyDeviceToDevice, c->stream));
+        PFP_HIP(hipMemcpyAsync(out.refined.p, keep0.p, N, hipMemcpyDeviceToDevice, c->stream));
         PFP_HIP(hipMemsetAsync(out.refined.p + N, 0, 16, c->stream));
       }
     }
@@ -1618,6 +1689,17 @@ struct Rounds {
     ranks_stale = false;
   }
   void prepare_ranks_for_doubling() {
+    if (plain_late && !rank_alloc) {      // plain mode's first doubling round: every suffix gets its slot's group head
+      alloc_rank();
+      KScope ks(c, "pfp::scatter_settled_kernel", N * 3 * sizeof(I));
+      hipLaunchKernelGGL(scatter_settled_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, N, out.sa.p, out.grp.p, (const uint8_t *)nullptr,
+                         (I)0, out.rank.p);
+      // (per call, like the line of the first-round keys: the tests tell the three histories apart by it - never, before any
+      //  pivot round, after one; `round` is the doubling round that asks, as the round lines count them)
+      if (getenv("PFP_TRACE_ROUNDS"))
+        fprintf(stderr, "[pfp] doubling N=%llu round=%llu: rank[] allocated late and filled from the slots\n", (unsigned long long)N,
+                (unsigned long long)out.rounds + 1);
+    }
     if (late_rank && !rank_alloc) {      // the first doubling round: rank[] is needed after all
       alloc_rank();
       ranks_stale = true;               // whatever pivot rounds settled (whole words included) is filled in from the slots
