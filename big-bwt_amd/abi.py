@@ -134,7 +134,6 @@ SIGNATURES = {
     "pfp_set_profiling": (None, [vp, i32]),
     "pfp_set_kernel_trace": (None, [vp, i32]),
     "pfp_get_kernel_trace": (i32, [vp, ptr(KernelStat), i32]),
-    "pfp_debug_msd_sort": (i32, [vp, p64, p32, u64, i32, i32]),
     "pfp_debug_lib_sort": (i32, [vp, i32, vp, vp, u64, i32, i32, p32, p32, u64]),
     "pfp_debug_scan_chain": (i32, [vp, p8, u64, i32, u64, p64, p32, u32, pp64, pp64, pp8, ptr(ScanReport)]),
     "pfp_set_max_phrase": (None, [vp, u64]),

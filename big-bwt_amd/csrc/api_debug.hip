@@ -1,5 +1,5 @@
 // api_debug.hip -- micro and diagnostic entry points: a text staged once and scanned on its own (pfp_stage_text_dev,
-// pfp_scan_staged, pfp_scan_k1_enqueue), the first-round sort and the library sorts on caller data, the fused chain's scan with a
+// pfp_scan_staged, pfp_scan_k1_enqueue), the library sorts on caller data, the fused chain's scan with a
 // report of what it did (pfp_debug_*).
 #include "api.hpp"
 
@@ -35,30 +35,6 @@ int pfp_scan_staged(pfp_ctx *c, uint64_t p, uint64_t *n_ends) {
   uint64_t k = scan_text(c, *s, s->n, s->w, p, d_ends, &used);
   sync(c);
   if (n_ends) *n_ends = k;
-  return PFP_OK;
-  PFP_CATCH(c)
-}
-
-// diagnostic: the first-round sort of radix.hip on caller data - keys (and 32-bit values, may be null) sorted in place, stable
-// on key bits [lo, hi)
-int pfp_debug_msd_sort(pfp_ctx *c, uint64_t *keys, uint32_t *vals, uint64_t n, int lo, int hi) {
-  if (!c || (!keys && n)) return PFP_EINVAL;
-  PFP_TRY_DEV(c)
-  if (!n) return PFP_OK;
-  DBuf<uint64_t> k(c, n), ka(c, n);
-  h2d(c, k.p, keys, n);
-  if (vals) {
-    DBuf<uint32_t> v(c, n), va(c, n);
-    h2d(c, v.p, vals, n);
-    msd_sort_pairs_db<uint32_t>(c, k, ka, v, va, n, lo, hi);
-    d2h(c, vals, v.p, n);
-    d2h(c, keys, k.p, n);
-    sync(c);
-  } else {
-    msd_sort_keys_db(c, k, ka, n, lo, hi);
-    d2h(c, keys, k.p, n);
-    sync(c);
-  }
   return PFP_OK;
   PFP_CATCH(c)
 }

@@ -40,6 +40,50 @@ __device__ __forceinline__ uint64_t suf_len(const SufGeom &g, uint64_t i) {
   return g.N - i;
 }
 
+// The environment switches of the sorters: diagnostics, and the paths the tests and measurements compare against.  Every entry
+// point (sort_dict_suffixes, sort_byte_suffixes, sort_int_suffixes, the two *_range) reads them once per call with
+// sorter_switches() and hands the value down; nothing else in this file looks at the environment.
+constexpr uint32_t kPivCapMax = 8192;      // widest window of a dictionary pivot round (its order key: see kPivBits)
+struct SorterSwitches {
+  bool finflag;                  // PFP_NO_FINFLAG unset.  (tests: without it, the length-gather path)
+  bool finisher;                 // PFP_NO_FINISHER unset: the comparison finisher may end the rounds
+  bool small_seg;                // PFP_NO_SMALLSEG unset: small groups are placed directly in LDS
+  bool trace_rounds;             // PFP_TRACE_ROUNDS set: a line on stderr per round and per decision of a sorter
+  uint32_t pivot_cap;            // PFP_PIVOT_CAP: bytes compared per member in a dictionary pivot round (512; below 16: no pivot rounds)
+  int keybits;                   // PFP_KEYBITS: width of the dictionary's first-round key, 8..63; 0 (unset) = the computed width
+  uint64_t parse_pivot_min;      // PFP_PARSE_PIVOT_MIN: smallest list a parse pivot round is tried on (2^16; tests run it on small inputs; 0 = never)
+  int keysonly;                  // PFP_KEYSONLY: keys-only first round of a dictionary: 1 always, 0 never, -1 (unset) = by the input
+  // 0 = the path before it, which the tests compare with byte for byte; unset or anything else = on:
+  bool plain_lazy_rank;          // PFP_PLAIN_LAZY_RANK: plain mode keeps no rank[] until a doubling round asks for it
+  bool plain_tiles;              // PFP_PLAIN_TILES: plain mode's first round regroups by the dictionary's tile scheme (heads0 / write_back0)
+  bool dict_fold;                // PFP_DICT_FOLD: dictionary first round: the tile counts come from write_back0, keep0 is the first round's keep[] itself
+  bool drop_short;               // PFP_DROP_SHORT: a minimum suffix length is honoured (0: every position is sorted)
+  bool ipivot_batch;             // PFP_IPIVOT_BATCH: the parse pivot round's key kernel issues kIntPivBatch load steps together (0: the one-step loop)
+  bool parse_keybits;            // PFP_PARSE_KEYBITS: a parse without equal neighbours gets the two-symbol key (0: the run key)
+};
+static SorterSwitches sorter_switches() {
+  auto set = [](const char *name) { return getenv(name) != nullptr; };
+  auto unless_zero = [](const char *name) { const char *e = getenv(name); return !e || atoi(e) != 0; };
+  auto number = [](const char *name, auto parse, auto unset) { const char *e = getenv(name); return e ? parse(e) : unset; };
+  SorterSwitches s;
+  s.finflag = !set("PFP_NO_FINFLAG");
+  s.finisher = !set("PFP_NO_FINISHER");
+  s.small_seg = !set("PFP_NO_SMALLSEG");
+  s.trace_rounds = set("PFP_TRACE_ROUNDS");
+  s.pivot_cap = std::min(number("PFP_PIVOT_CAP", [](const char *e) { return (uint32_t)atoll(e); }, 512u), kPivCapMax);
+  s.keybits = number("PFP_KEYBITS", [](const char *e) { return std::max(8, std::min(63, atoi(e))); }, 0);
+  s.parse_pivot_min = number("PFP_PARSE_PIVOT_MIN", [](const char *e) { const uint64_t v = strtoull(e, nullptr, 10); return v ? v : ~0ull; },
+                             (uint64_t)1 << 16);
+  s.keysonly = number("PFP_KEYSONLY", atoi, -1);
+  s.plain_lazy_rank = unless_zero("PFP_PLAIN_LAZY_RANK");
+  s.plain_tiles = unless_zero("PFP_PLAIN_TILES");
+  s.dict_fold = unless_zero("PFP_DICT_FOLD");
+  s.drop_short = unless_zero("PFP_DROP_SHORT");
+  s.ipivot_batch = unless_zero("PFP_IPIVOT_BATCH");
+  s.parse_keybits = unless_zero("PFP_PARSE_KEYBITS");
+  return s;
+}
+
 // First-round keys.  The bytes that occur in the dictionary get an order-preserving prefix-free
 // (alphabetic) code whose lengths follow their frequencies - A,C,G,T of a FASTA text cost 2-3 bits,
 // header characters and other rare bytes a dozen - and the codes of the first characters of every
@@ -93,7 +137,7 @@ static void balanced_code(const std::vector<uint64_t> &w, int lo, int hi, uint32
   balanced_code(w, lo, cut, code << 1, len + 1, codes, lens);
   balanced_code(w, cut, hi, (code << 1) | 1u, len + 1, codes, lens);
 }
-static KeyCode make_key_code(const uint64_t hist[256], double rep_hint = 0) {
+static KeyCode make_key_code(const uint64_t hist[256], double rep_hint, const SorterSwitches &sw) {
   KeyCode kc{};
   std::vector<int> sym;
   for (int b2 = 0; b2 < 256; b2++) if (hist[b2] || b2 <= 1) sym.push_back(b2);       // 0x00 / 0x01 always coded
@@ -131,7 +175,7 @@ static KeyCode make_key_code(const uint64_t hist[256], double rep_hint = 0) {
   const double need = std::log2(std::max((double)total / std::max(rep_hint, 1.0), 2.0)) + 6.0;
   kc.kbits = 63;
   for (int kb : {39, 47, 55}) if (Lm > 0 && kb * H / Lm >= need) { kc.kbits = kb; break; }
-  { const char *e = getenv("PFP_KEYBITS"); if (e) kc.kbits = std::max(8, std::min(63, atoi(e))); }
+  if (sw.keybits) kc.kbits = sw.keybits;
   kc.hmin = std::max(1, std::min(32, kc.kbits / maxlen));
   kc.maxlen = maxlen;
   return kc;
@@ -566,21 +610,10 @@ __global__ void heads32_kernel(uint64_t m, const uint8_t *__restrict__ gs, const
 // Order key, as for the dictionary's pivot rounds: smaller than the pivot: ascending offset, then symbol; the pivot's class; greater:
 // descending offset, then symbol - two 32-bit halves of a 64-bit key sorted inside every group.
 constexpr uint32_t kIntPivCap = 1024;      // symbols compared per member and round
-// smallest list such a round is tried on (PFP_PARSE_PIVOT_MIN: tests run it on small inputs; 0 = never)
-static uint64_t parse_pivot_min() {
-  const char *e = getenv("PFP_PARSE_PIVOT_MIN");
-  if (!e) return 1u << 16;
-  const uint64_t v = strtoull(e, nullptr, 10);
-  return v ? v : ~0ull;
-}
 // 16-byte load steps a member issues together in the pivot round's key kernel.  (Measured on configs[2], 15.2 M members: 4 steps
 // 0.69 ms at 54 VGPRs, 8 steps 0.80 ms at 86 VGPRs and five waves per SIMD, the one-step loop 0.85 ms)
-// PFP_IPIVOT_BATCH=0, read per call, takes the one-step loop.
+// PFP_IPIVOT_BATCH=0 takes the one-step loop.
 constexpr int kIntPivBatch = 4;
-static bool ipivot_batched() {
-  const char *e = getenv("PFP_IPIVOT_BATCH");
-  return !(e && atoi(e) == 0);
-}
 template <class I>
 __global__ void ipivot_select_kernel(uint64_t m, uint64_t N, uint64_t h, const I *__restrict__ act_i, const I *__restrict__ act_grp,
                                      const uint32_t *__restrict__ dist, unsigned long long *__restrict__ best,
@@ -902,8 +935,7 @@ __global__ void scatter_settled_kernel(uint64_t N, const I *__restrict__ sa, con
 // tie.  A member still equal to P after cap bytes joins P's class unresolved (no settled bit) and
 // vetoes the settling of that whole class (pivot_veto_kernel).  Order-key layout (kPivBits bits):
 constexpr int kPivBits = 23;
-constexpr uint32_t kPivEq = 1u << 21;
-constexpr uint32_t kPivCapMax = 8192;
+constexpr uint32_t kPivEq = 1u << 21;      // (lcp < kPivCapMax, declared with SorterSwitches at the top, sits above the byte)
 // (Tried in round 3: eight lanes per member, 128 contiguous bytes of the member's string per load instruction, the pivot's
 //  bytes coalesced, ballot for the first differing chunk.  Same lines fetched, 3x fewer address-coalescer cycles - and 17 %
 //  SLOWER (c3 6.8 -> 7.9 ms, 12.6 GB 107 -> 120 ms): the kernel is bound by the rate at which HBM serves random lines
@@ -1125,7 +1157,7 @@ __global__ void finish_write_kernel(SufGeom g, uint64_t m, const I *__restrict__
 }
 
 // after the first round, pivot rounds are tried while the groups are families (average size up to
-// kPivotAvg) and each one at least halves the unresolved set; at most kSwitch.pivot_cap bytes per comparison
+// kPivotAvg) and each one at least halves the unresolved set; at most SorterSwitches::pivot_cap bytes per comparison
 constexpr uint32_t kPivotAvg = 1024u;
 
 // the first round leaves more than N/kLazyRatio suffixes unresolved -> scatter all ranks after all
@@ -1133,27 +1165,6 @@ constexpr uint64_t kLazyRatio = 8ull;
 
 // the library's segmented sort is tried from this average group size on
 constexpr uint32_t kSegMinAvg = 24u;
-
-// the process-wide switches of the round loop, read once.  (PFP_KEYSONLY and PFP_PARSE_PIVOT_MIN are read per call: the tests
-// switch them inside one process.)
-struct SorterSwitches {
-  // the first round's sort: rocPRIM's onesweep, or (PFP_OWN_SORT=1) the hand-written MSD sort of radix.hip - bit-exact, and measured
-  // slower on every workload of round 4 (configs[2] 5.0 vs 3.8 ms, configs[1] 14.0 vs 13.4): the alphabetic code's bits carry ~0.8 bit
-  // of entropy each, so a partition by key BITS needs three passes where 16 uniform bits would do, and each pass reads its input
-  // twice
-  bool lib_sort = getenv("PFP_OWN_SORT") == nullptr;
-  bool finflag = getenv("PFP_NO_FINFLAG") == nullptr;          // (tests: without it, the length-gather path)
-  bool finisher = getenv("PFP_NO_FINISHER") == nullptr;
-  bool small_seg = getenv("PFP_NO_SMALLSEG") == nullptr;
-  bool trace_rounds = getenv("PFP_TRACE_ROUNDS") != nullptr;
-  uint32_t pivot_cap = []() { const char *e = getenv("PFP_PIVOT_CAP"); uint32_t v = e ? (uint32_t)atoll(e) : 512u; return v > kPivCapMax ? kPivCapMax : v; }();
-};
-static const SorterSwitches kSwitch;
-// ... and the ones read per call (0 = the path before it; the tests compare both inside one process):
-//   PFP_PLAIN_LAZY_RANK   plain mode keeps no rank[] until a doubling round asks for it
-//   PFP_PLAIN_TILES       plain mode's first round regroups by the dictionary's tile scheme (heads0 / write_back0)
-//   PFP_DICT_FOLD         dictionary first round: the tile counts come from write_back0, keep0 is the first round's keep[] itself
-static bool switch_on(const char *name) { const char *e = getenv(name); return !e || atoi(e) != 0; }
 
 template <class I>
 RankViewT<I> rank_view(const SuffixOrderT<I> &so) {
@@ -1164,6 +1175,8 @@ template RankViewT<uint64_t> rank_view(const SuffixOrderT<uint64_t> &);
 
 // what doubling() is asked for
 struct DoublingOpts {
+  explicit DoublingOpts(const SorterSwitches &sw_) : sw(sw_) {}
+  const SorterSwitches sw;               // the entry point's switches, for the rounds
   int key_bits = 64;                     // width of the first-round keys
   bool dict = false;                     // dictionary mode: out.lut/bytes/kbits are set by the caller, ranks are lazy
   std::optional<uint64_t> list_len;      // list mode: key/val hold this many suffixes (in position order), not all g.N - the ones of this
@@ -1206,7 +1219,7 @@ struct Rounds {
   // among the listed suffixes, rank[] or wordrank[] and the search over skeys (rank_at) - so the words' ranks cost no pass.
   const bool range_mode;
   const int nb;                 // key of a later round = (group head << nb) | (1 + rank of the continuation)
-  const bool plain_lazy, plain_tiles, dict_fold;      // (the per-call switches above)
+  const bool plain_lazy, plain_tiles, dict_fold;      // (o.sw's switches, each in the mode it belongs to)
   bool lazy_active = false, late_rank = false;      // (see start_rounds)
   bool plain_late = false;      // plain mode without rank[] so far: the first doubling round fills it from the slots
   I *rank_p = nullptr, *wordrank_p = nullptr;
@@ -1214,7 +1227,7 @@ struct Rounds {
   // ---- the loop's variables
   Round kind;                   // the sort that was just run
   uint64_t m, h, m2 = 0, ngrp = 0;      // list length and sorted prefix of that sort; what its regrouping left unresolved, in how many groups
-  uint32_t piv_cap = kSwitch.pivot_cap;      // bytes compared per member in the next pivot round
+  uint32_t piv_cap = o.sw.pivot_cap;      // bytes compared per member in the next pivot round
   bool pivot_ok = true;         // dictionary pivot rounds still halve the unresolved set
   bool ipiv_ok = true;          // parse: the pivot round (farthest rare symbol) has not given up yet
   bool small_failed = false;    // a direct-placement attempt met a group longer than its window
@@ -1252,8 +1265,8 @@ struct Rounds {
   Rounds(pfp_ctx *c_, const SufGeom &g_, DBuf<uint64_t> &key_, DBuf<I> &val_, uint64_t h0, SuffixOrderT<I> &out_, const DoublingOpts &o_)
       : c(c_), g(g_), out(out_), o(o_), NP(g_.N), N(o_.list_len.value_or(g_.N)), lazy(o_.dict), list_mode(o_.list_len.has_value()),
         range_mode(o_.list_len.has_value() && !o_.whole_list),
-        nb(bits_for(N)), plain_lazy(!o_.dict && switch_on("PFP_PLAIN_LAZY_RANK")), plain_tiles(!o_.dict && switch_on("PFP_PLAIN_TILES")),
-        dict_fold(o_.dict && switch_on("PFP_DICT_FOLD")), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_),
+        nb(bits_for(N)), plain_lazy(!o_.dict && o_.sw.plain_lazy_rank), plain_tiles(!o_.dict && o_.sw.plain_tiles),
+        dict_fold(o_.dict && o_.sw.dict_fold), kind(o_.dict ? Round::FirstDict : Round::FirstPlain), m(N), h(h0), key(key_),
         val(val_) {}
   // the first round regroups by tiles (slot == index, no list yet): a dictionary always, plain mode by its switch
   bool tiles_first() const { return lazy || plain_tiles; }
@@ -1268,13 +1281,11 @@ struct Rounds {
     if (o.idx_bits) {
       // keys-only first round: the words are (key << idx_bits | position), 16 bytes per element and pass instead of 24;
       // the sort is stable on the key bits alone, so ties stay in position order; one streaming pass splits the result
-      if (kSwitch.lib_sort) sort_keys_db(c, key, keyo, N, o.idx_bits, o.idx_bits + o.key_bits);
-      else msd_sort_keys_db(c, key, keyo, N, o.idx_bits, o.idx_bits + o.key_bits);
+      sort_keys_db(c, key, keyo, N, o.idx_bits, o.idx_bits + o.key_bits);
       KScope ks(c, "pfp::split_keys_kernel", N * (16 + sizeof(I)));
       hipLaunchKernelGGL(split_keys_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, key.p, N, o.idx_bits, keyo.p, valo.p);
     } else {
-      if (kSwitch.lib_sort) sort_pairs_db(c, key, keyo, val, valo, N, 0, o.key_bits);
-      else msd_sort_pairs_db<I>(c, key, keyo, val, valo, N, 0, o.key_bits);
+      sort_pairs_db(c, key, keyo, val, valo, N, 0, o.key_bits);
       std::swap(key, keyo); std::swap(val, valo);
     }
   }
@@ -1312,7 +1323,7 @@ struct Rounds {
     }
     // (the flag rides in the top bit of a POSITION: it needs positions below 2^31 in the 32-bit build - all NP of them, also when
     //  only a share of N < 2^31 suffixes is sorted here)
-    out.finbit = (g.mode == MODE_DICT && (kWide || NP < (1ull << 31)) && kSwitch.finflag) ? IdxTraits<I>::kTop : (I)0;
+    out.finbit = (g.mode == MODE_DICT && (kWide || NP < (1ull << 31)) && o.sw.finflag) ? IdxTraits<I>::kTop : (I)0;
     // lazy ranks are possible when pivot rounds (which never read rank[]) can follow the first round
     lazy_active = lazy && pivot_rounds_possible();
     // rank[] (one entry per dictionary position: 4 / 8 bytes each, 38 GB for a 4.8 GB dictionary in the wide build) exists
@@ -1331,7 +1342,7 @@ struct Rounds {
     }
   }
   bool pivot_rounds_possible() const {
-    return g.mode == MODE_DICT && out.finbit && kSwitch.pivot_cap >= 16 && (uint64_t)nb + kPivBits <= 64;
+    return g.mode == MODE_DICT && out.finbit && o.sw.pivot_cap >= 16 && (uint64_t)nb + kPivBits <= 64;
   }
 
   // ---- regrouping: heads of the new groups -> slots, group ids, ranks -> compaction of what stays unresolved
@@ -1492,7 +1503,7 @@ struct Rounds {
         PFP_HIP(hipMemsetAsync(out.refined.p + N, 0, 16, c->stream));
       }
     }
-    if (kSwitch.trace_rounds) {
+    if (o.sw.trace_rounds) {
       const bool grouped = kind == Round::DictPivotGrouped || kind == Round::ParsePivot || kind == Round::DoublingGrouped;
       fprintf(stderr, "[pfp] doubling N=%llu round=%llu h=%llu m=%llu -> %llu unresolved in %llu groups%s\n", (unsigned long long)N,
               (unsigned long long)out.rounds, (unsigned long long)h, (unsigned long long)m, (unsigned long long)m2,
@@ -1528,7 +1539,7 @@ struct Rounds {
 
   // the comparison finisher (see finish_rank_kernel); false: not tried, or it refused and nothing was written
   bool try_finisher() {
-    if (!(kSwitch.finisher && finisher_ok && m <= kFinishMax && out.rounds >= 1 && (g.mode == MODE_DICT || (g.mode == MODE_PLAIN && g.sym))))
+    if (!(o.sw.finisher && finisher_ok && m <= kFinishMax && out.rounds >= 1 && (g.mode == MODE_DICT || (g.mode == MODE_PLAIN && g.sym))))
       return false;
     DBuf<uint32_t> flt(c, m), feq(c, m), fgs(c, m), fov(c, 1);
     fov.zero();
@@ -1543,7 +1554,7 @@ struct Rounds {
       hipLaunchKernelGGL(finish_write_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, g, m, aslot.p, act_i.p, flt.p, feq.p, fgs.p,
                          out.finbit, out.sa.p, out.grp.p, rank_p, wordrank_p); }
     PFP_HIP(hipGetLastError());
-    if (kSwitch.trace_rounds) fprintf(stderr, "[pfp] doubling N=%llu round=%llu: the last %llu suffixes ranked by comparison\n",
+    if (o.sw.trace_rounds) fprintf(stderr, "[pfp] doubling N=%llu round=%llu: the last %llu suffixes ranked by comparison\n",
                                       (unsigned long long)N, (unsigned long long)out.rounds, (unsigned long long)m);
     out.rounds++;
     m = 0;
@@ -1561,7 +1572,7 @@ struct Rounds {
   // families of a handful of members: placed directly in LDS (after a group proved too long, only once the average is tiny)
   // (32-bit build: long families go to the side sort, so the average may be larger)
   bool small_groups() const {
-    return kSwitch.small_seg && ngrp && m / ngrp <= (kWide ? kSmallSeg / 4 : kSmallSeg / 2) && (!small_failed || m / ngrp <= 3);
+    return o.sw.small_seg && ngrp && m / ngrp <= (kWide ? kSmallSeg / 4 : kSmallSeg / 2) && (!small_failed || m / ngrp <= 3);
   }
   // large families (a collection of hundreds of copies): the library's segmented sort is worth its set-up
   // (m < 2^32 - its offsets are 32-bit - always holds in the 32-bit index build)
@@ -1644,7 +1655,7 @@ struct Rounds {
   // the parse of a collection: a pivot round with the member whose next rare symbol is farthest (see ipivot_select_kernel)
   // (a share of the parse - range mode - has no doubling rounds to fall back on: it tries whatever the list's size)
   bool parse_pivot_wanted() const {
-    return g.mode == MODE_PLAIN && g.dist && g.sym && ipiv_ok && ngrp && (range_mode || m >= parse_pivot_min()) && m < 0xFFFFFFFFull && m / ngrp >= 2;
+    return g.mode == MODE_PLAIN && g.dist && g.sym && ipiv_ok && ngrp && (range_mode || m >= o.sw.parse_pivot_min) && m < 0xFFFFFFFFull && m / ngrp >= 2;
   }
   // (32-bit index build only.)  There is no device-wide fallback: false, and no more parse pivot rounds, where neither way of
   // ordering the groups took them
@@ -1655,7 +1666,7 @@ struct Rounds {
       KScope ks(c, "pfp::ipivot_keys_kernel", m * (4 + 4 + 4 + 8 + 16 + 12 + 64));
       // the members' distances travel from one kernel to the other in hv[] (list_cap >= m entries of at least 4 bytes; nothing
       // of the list's scratch is live between next_list() and the heads of the coming sort)
-      const bool batched = ipivot_batched();
+      const bool batched = o.sw.ipivot_batch;
       uint32_t *dvs = batched ? reinterpret_cast<uint32_t *>(hv.p) : nullptr;
       hipLaunchKernelGGL(ipivot_select_kernel<I>, gdim(blocks(m)), gdim(TB), 0, c->stream, m, NP, h, act_i.p, act_grp.p, g.dist, best.p, dvs);
       if (batched)
@@ -1694,9 +1705,9 @@ struct Rounds {
       KScope ks(c, "pfp::scatter_settled_kernel", N * 3 * sizeof(I));
       hipLaunchKernelGGL(scatter_settled_kernel<I>, gdim(blocks(N)), gdim(TB), 0, c->stream, N, out.sa.p, out.grp.p, (const uint8_t *)nullptr,
                          (I)0, out.rank.p);
-      // (per call, like the line of the first-round keys: the tests tell the three histories apart by it - never, before any
-      //  pivot round, after one; `round` is the doubling round that asks, as the round lines count them)
-      if (getenv("PFP_TRACE_ROUNDS"))
+      // (the tests tell the three histories apart by this line - never, before any pivot round, after one; `round` is the
+      //  doubling round that asks, as the round lines count them)
+      if (o.sw.trace_rounds)
         fprintf(stderr, "[pfp] doubling N=%llu round=%llu: rank[] allocated late and filled from the slots\n", (unsigned long long)N,
                 (unsigned long long)out.rounds + 1);
     }
@@ -1817,7 +1828,8 @@ template void gather_ranks<uint64_t>(pfp_ctx *, const SuffixOrderT<uint64_t> &, 
 // ---- whole-array entry points: first-round keys for all N positions, then doubling()
 
 // low_counts (optional): how often the bytes 0x00 and 0x01 occur
-static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, double rep_hint = 0, uint64_t *low_counts = nullptr) {
+static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, double rep_hint, const SorterSwitches &sw,
+                             uint64_t *low_counts = nullptr) {
   DBuf<unsigned long long> hist(c, 256);
   hist.zero();
   hipLaunchKernelGGL(byte_histogram_kernel, gdim(std::min<uint64_t>(cdiv64(N, 4096), (uint64_t)c->n_cu * 8)), gdim(256), 0,
@@ -1826,21 +1838,20 @@ static KeyCode dict_key_code(pfp_ctx *c, const uint8_t *bytes, uint64_t N, doubl
   PFP_HIP(hipMemcpyAsync(hh.data(), hist.p, 2048, hipMemcpyDeviceToHost, c->stream));
   sync(c);
   if (low_counts) { low_counts[0] = hh[0]; low_counts[1] = hh[1]; }
-  return make_key_code(hh.data(), rep_hint);
+  return make_key_code(hh.data(), rep_hint, sw);
 }
 
 // keys-only first round (see sort_dict_suffixes): index bits of the combined word, 0 = sort (key, position) pairs;
 // shortens kc's key to what is left of 64 bits
 template <class I>
-static int keysonly_bits(uint64_t N, double rep_hint, KeyCode &kc) {
-  const int keysonly_env = []() { const char *e = getenv("PFP_KEYSONLY"); return e ? atoi(e) : -1; }();      // (per call: tests switch it)
-  if (!(sizeof(I) == 4 && N >= 2 && (keysonly_env == 1 || (keysonly_env != 0 && rep_hint >= 2.0 && N >= (1u << 20))))) return 0;
+static int keysonly_bits(uint64_t N, double rep_hint, const SorterSwitches &sw, KeyCode &kc) {
+  if (!(sizeof(I) == 4 && N >= 2 && (sw.keysonly == 1 || (sw.keysonly != 0 && rep_hint >= 2.0 && N >= (1u << 20))))) return 0;
   const int ib = bits_for(N - 1);
   int width = 64 - ib;                      // key bits incl. the terminator flag
   if (width > 3 * kKeysDigitBits && width % kKeysDigitBits <= 2) width -= width % kKeysDigitBits;       // a radix pass for one or two bits is a whole pass
   // (measured: 36 key bits on 129 M suffixes - first sort 7.8 -> 3.9 ms, same rounds after it; 31 key bits on 1.7 G
   //  suffixes leave three times as many unresolved after the first pivot round - the pair sort stays there)
-  if (!(width - 1 >= 35 || keysonly_env == 1)) return 0;
+  if (!(width - 1 >= 35 || sw.keysonly == 1)) return 0;
   if (kc.kbits > width - 1) { kc.kbits = std::max(8, width - 1); kc.hmin = std::max(1, std::min(32, kc.kbits / kc.maxlen)); }
   return ib;
 }
@@ -1856,24 +1867,22 @@ static uint64_t dict_keymask(const KeyCode &kc) { return kc.kbits + 1 >= 64 ? ~0
 // of the key code, then the rounds
 template <class I>
 static void dict_rounds(pfp_ctx *c, const SufGeom &g, const uint8_t *bytes, const KeyCode &kc, int idx_bits, std::optional<uint64_t> list_len,
-                        DBuf<uint64_t> &key, DBuf<I> &val, SuffixOrderT<I> &out, bool whole_list = false) {
+                        DBuf<uint64_t> &key, DBuf<I> &val, SuffixOrderT<I> &out, const SorterSwitches &sw, bool whole_list = false) {
   out.keymask = dict_keymask(kc);
   out.lut.alloc(c, 256);
   PFP_HIP(hipMemcpyAsync(out.lut.p, kc.lut, 1024, hipMemcpyHostToDevice, c->stream));
   sync(c);      // kc may be a stack object of the caller
   out.bytes = bytes; out.kbits = kc.kbits;
-  DoublingOpts o;
+  DoublingOpts o(sw);
   o.key_bits = kc.kbits + 1, o.dict = true, o.list_len = list_len, o.whole_list = whole_list, o.idx_bits = idx_bits;
   doubling<I>(c, g, key, val, (uint64_t)kc.hmin, out, o);
 }
-
-// PFP_DROP_SHORT=0: a minimum suffix length is ignored, every position is sorted (read per call: the tests compare both ways)
-static bool drop_short_enabled() { const char *e = getenv("PFP_DROP_SHORT"); return !e || atoi(e) != 0; }
 
 template <class I>
 void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const WordView &wv, SuffixOrderT<I> &out,
                         const SlotPayloadSrc *pay, int min_len) {
   require_dict_size<I>(N);
+  const SorterSwitches sw = sorter_switches();
   SufGeom g{MODE_DICT, N, wv};
   // Only the suffixes longer than min_len.  The placement of their keys (init_keys_packed_kernel) needs a dictionary in which
   // every word is longer than min_len - checked by short_words_kernel while the byte histogram is read back - and in which
@@ -1882,7 +1891,7 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
   // kept, and the final 0x00 is one more.  Anything else is sorted whole.
   const uint64_t ntile = cdiv64(N, kKeyPos);
   const uint64_t dropped = (uint64_t)wv.d * ((uint64_t)min_len + 1) + 1;
-  bool listed = min_len > 0 && wv.d >= 1 && dropped < N && drop_short_enabled();
+  bool listed = min_len > 0 && wv.d >= 1 && dropped < N && sw.drop_short;
   unsigned long long *const short_found = reinterpret_cast<unsigned long long *>(c->h_scalars + 3);
   if (listed) {
     *short_found = 0;
@@ -1890,10 +1899,10 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
     hipLaunchKernelGGL(short_words_kernel, gdim(cdiv((uint64_t)wv.d, 256)), gdim(256), 0, c->stream, wv, min_len, short_found);
   }
   uint64_t low_counts[2] = {0, 0};
-  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint, low_counts);      // (syncs)
+  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint, sw, low_counts);      // (syncs)
   if (listed && (*short_found != 0 || low_counts[0] != 1 || low_counts[1] != (uint64_t)wv.d)) {
     listed = false;
-    if (kSwitch.trace_rounds)
+    if (sw.trace_rounds)
       fprintf(stderr, "[pfp] dictionary with a word of at most %d bytes or a stray byte below 2: every position is sorted\n", min_len);
   }
   const uint64_t n = listed ? N - dropped : N;
@@ -1902,7 +1911,7 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
   // together.  Then the position fits into the same 64-bit word as a (shorter) key, the sort moves 16 bytes per
   // element and pass instead of 24 and makes 4-5 passes instead of 7, and the merge records in the key's spare bits
   // (which such an input hardly uses: most slots are re-ordered later) are given up.
-  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, kc);      // (index bits hold a POSITION: by N also where fewer are sorted)
+  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, sw, kc);      // (index bits hold a POSITION: by N also where fewer are sorted)
   DBuf<uint64_t> key(c, n);
   DBuf<I> val;
   if (!idx_bits) val.alloc(c, n);
@@ -1919,13 +1928,13 @@ void sort_dict_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, const Word
     sync(c);
     PFP_REQUIRE(c->h_scalars[0] == 0, PFP_EHIP, "bit-stream keys differ from packed_key_at at " + std::to_string(c->h_scalars[0]) + " positions");
   }
-  if (!listed) { dict_rounds<I>(c, g, bytes, kc, idx_bits, std::nullopt, key, val, out); return; }
-  dict_rounds<I>(c, g, bytes, kc, idx_bits, n, key, val, out, true);
+  if (!listed) { dict_rounds<I>(c, g, bytes, kc, idx_bits, std::nullopt, key, val, out, sw); return; }
+  dict_rounds<I>(c, g, bytes, kc, idx_bits, n, key, val, out, sw, true);
   if (out.complete) return;
   // A group was left that only a doubling round settles, and that round reads the rank of positions that may not be listed:
   // the list's result is dropped and every position sorted, once.  (Deterministic and rare: a dictionary of a parse is
   // settled by the first round and pivot rounds.  The kernel trace shows it: short_words_kernel ran, and the first round twice.)
-  if (kSwitch.trace_rounds) fprintf(stderr, "[pfp] the sort of the %llu suffixes longer than %d bytes needs a doubling round: every position is sorted\n",
+  if (sw.trace_rounds) fprintf(stderr, "[pfp] the sort of the %llu suffixes longer than %d bytes needs a doubling round: every position is sorted\n",
                                     (unsigned long long)n, min_len);
   key.release(); val.release();
   const double rep_hint = out.rep_hint;
@@ -1955,7 +1964,7 @@ void sort_byte_suffixes(pfp_ctx *c, const uint8_t *bytes, uint64_t N, SuffixOrde
   DBuf<I> val(c, N);
   { KScope ks(c, "pfp::init_keys_bytes_kernel", N * (16 + sizeof(I)));
     hipLaunchKernelGGL(init_keys_bytes_kernel<I>, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, bytes, N, key.p, val.p); }
-  doubling<I>(c, g, key, val, 8, out, DoublingOpts{});
+  doubling<I>(c, g, key, val, 8, out, DoublingOpts(sorter_switches()));
 }
 template void sort_byte_suffixes<uint32_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint32_t> &);
 template void sort_byte_suffixes<uint64_t>(pfp_ctx *, const uint8_t *, uint64_t, SuffixOrderT<uint64_t> &);
@@ -1972,10 +1981,10 @@ struct IntKeys {
 };
 // narrow_ok: the caller sorts the keys as doubling() does and reads them for order and equality only, so a string without equal
 // neighbours may get the two-symbol key of 2 sb bits (init_keys_int_run_kernel) instead of the 64-bit run key.  PFP_PARSE_KEYBITS=0
-// (read per call: tests and measurements switch it) keeps the run key.
+// (tests and measurements switch it) keeps the run key.
 static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t N, uint32_t max_sym, const uint32_t *occ, uint32_t n_sym,
                            bool want_dist, const char *dist_scope, const char *plain_scope, uint64_t plain_bytes, bool narrow_ok,
-                           IntKeys &k) {
+                           const SorterSwitches &sw, IntKeys &k) {
   // the symbol width is measured, not taken on trust (max_sym is only an upper bound for the check)
   auto need = [&](auto &b) { if (!b.p) b.alloc(c, N); };
   k.mx.alloc(c, 2);
@@ -2004,9 +2013,7 @@ static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t
   need(k.val);
   const char *layout = "plain";
   if (64 - 2 * sb >= 6) {
-    const char *e = getenv("PFP_PARSE_KEYBITS");
-    const bool narrow = narrow_ok && !has_pair && !(e && atoi(e) == 0);
-    if (narrow) {
+    if (narrow_ok && !has_pair && sw.parse_keybits) {
       // no run ends to find: no marks, no running maximum, no N-long temporaries; the same kernel under the same label
       ks.emplace(c, "pfp::init_keys_int_run_kernel", N * 16);
       hipLaunchKernelGGL(init_keys_int_run_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, (uint32_t)N, (const uint32_t *)nullptr, sb,
@@ -2026,8 +2033,8 @@ static void int_first_keys(pfp_ctx *c, SufGeom &g, const uint32_t *sym, uint64_t
     ks.emplace(c, plain_scope, plain_bytes);
     hipLaunchKernelGGL(init_keys_int_kernel, gdim(cdiv(N, 256)), gdim(256), 0, c->stream, sym, N, k.key.p, k.val.p);
   }
-  // (per call, unlike the round lines: the tests tell the layouts apart by this line inside one process)
-  if (getenv("PFP_TRACE_ROUNDS"))
+  // (the tests tell the layouts apart by this line)
+  if (sw.trace_rounds)
     fprintf(stderr, "[pfp] integer first-round keys N=%llu sb=%d: %s layout, sorted bits [0, %d)\n", (unsigned long long)N, sb, layout, k.key_bits);
 }
 
@@ -2035,11 +2042,13 @@ void sort_int_suffixes(pfp_ctx *c, const uint32_t *sym, uint64_t N, SuffixOrder 
                        uint32_t n_sym) {
   PFP_REQUIRE(N >= 1 && N < 0xFFFFFFF0ull, PFP_ELIMIT, "parse too large for 32-bit suffix indices");
   SufGeom g{MODE_PLAIN, N, WordView{}};
+  const SorterSwitches sw = sorter_switches();
   IntKeys k;
   k.key.alloc(c, N);
   k.val.alloc(c, N);
-  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, occ && n_sym && N >= parse_pivot_min(), nullptr, "pfp::init_keys_int_kernel", N * (8 + 8 + 4), true, k);
-  DoublingOpts o;
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, occ && n_sym && N >= sw.parse_pivot_min, nullptr, "pfp::init_keys_int_kernel", N * (8 + 8 + 4), true,
+                 sw, k);
+  DoublingOpts o(sw);
   o.key_bits = k.key_bits;
   doubling<uint32_t>(c, g, k.key, k.val, 2, out, o);
 }
@@ -2253,9 +2262,10 @@ void sort_dict_suffixes_range(pfp_ctx *c, const uint8_t *bytes, uint64_t N, cons
                               uint32_t parts, SuffixOrderT<I> &out, const SlotPayloadSrc *pay, const SlotPayloadSrc *count) {
   require_dict_size<I>(N);
   PFP_REQUIRE(parts >= 1 && part < parts, PFP_EINVAL, "bad key-range share");
+  const SorterSwitches sw = sorter_switches();
   SufGeom g{MODE_DICT, N, wv};
-  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint);
-  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, kc);      // (before the splitters: every rank cuts the same keys)
+  KeyCode kc = dict_key_code(c, bytes, N, out.rep_hint, sw);
+  const int idx_bits = keysonly_bits<I>(N, out.rep_hint, sw, kc);      // (before the splitters: every rank cuts the same keys)
   // splitters: every stride-th suffix's key, sorted; the same on every rank.  The share is cut by comparing every suffix with the
   // boundary SUFFIXES (range_flags_cmp4_kernel) - boundaries with distinct keys, so that they stand in the order they are used in
   // (the two earlier forms - a first-round key per position, one position per thread - went with round 4)
@@ -2297,7 +2307,7 @@ void sort_dict_suffixes_range(pfp_ctx *c, const uint8_t *bytes, uint64_t N, cons
     hipLaunchKernelGGL(init_keys_list_kernel<I>, gdim(cdiv(n, 256)), gdim(256), 0, c->stream, g.wv.bytes, n, kc, sh.idx.p, key.p, val.p, idx_bits);
   }
   sh.idx.release();
-  dict_rounds<I>(c, g, g.wv.bytes, kc, idx_bits, n, key, val, out);
+  dict_rounds<I>(c, g, g.wv.bytes, kc, idx_bits, n, key, val, out, sw);
   (void)pay;      // (no merge records in the keys of a share: its positions are a scattered list, every record would be a word lookup)
   set_share(out, sp, sh);
 }
@@ -2363,10 +2373,11 @@ void sort_int_suffixes_range(pfp_ctx *c, const uint32_t *sym, uint64_t N, uint32
                              uint32_t part, uint32_t parts, SuffixOrder &out) {
   PFP_REQUIRE(N >= 1 && N < 0xFFFFFFF0ull, PFP_ELIMIT, "parse too large for 32-bit suffix indices");
   PFP_REQUIRE(parts >= 1 && part < parts && occ && n_sym, PFP_EINVAL, "bad share of the parse's suffix array");
+  const SorterSwitches sw = sorter_switches();
   SufGeom g{MODE_PLAIN, N, WordView{}};
   IntKeys k;
   k.dist.alloc(c, N);
-  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, true, "pfp::rare_dist_kernel", "pfp::init_keys_int_run_kernel", N * 28, false, k);
+  int_first_keys(c, g, sym, N, max_sym, occ, n_sym, true, "pfp::rare_dist_kernel", "pfp::init_keys_int_run_kernel", N * 28, false, sw, k);
   // (narrow_ok false: the share keeps the 64-bit run key - its splitters and out.klo / out.khi are first-round keys that leave this
   //  function, and every rank and the caller must read them in one layout)
   k.val.release();      // unread: the list's values are gathered from the positions
@@ -2390,7 +2401,7 @@ void sort_int_suffixes_range(pfp_ctx *c, const uint32_t *sym, uint64_t N, uint32
   PFP_HIP(hipGetLastError());
   k.key.release(); sh.idx.release();
   ks_sel.reset();
-  DoublingOpts o;
+  DoublingOpts o(sw);
   o.list_len = sh.n;
   doubling<uint32_t>(c, g, lkey, lval, 2, out, o);
   set_share(out, sp, sh);

@@ -730,11 +730,6 @@ class Context(_Closing):
         """fused chain: cut the text by the cheap window hash (True, default) or by the reference's Karp-Rabin hash (False)"""
         self.lib.pfp_set_window_hash(self._h, bool(fast))
 
-    def debug_msd_sort(self, keys, vals, lo, hi):
-        """radix.hip's sort on numpy arrays (uint64 keys, optional uint32 values), in place; stable on key bits [lo, hi)"""
-        assert keys.dtype == np.uint64 and keys.flags.c_contiguous and (vals is None or (vals.dtype == np.uint32 and vals.flags.c_contiguous))
-        self._check(self.lib.pfp_debug_msd_sort(self._h, keys, vals, len(keys), lo, hi))
-
     LIB_SORT_KINDS = {"pairs_u64_u32": (0, np.uint64, np.uint32), "pairs_u64_u64": (1, np.uint64, np.uint64), "keys_db": (2, np.uint64, None),
                       "keys_raw": (3, np.uint64, None), "seg_u32_u32": (4, np.uint32, np.uint32), "seg_u32_u64": (5, np.uint32, np.uint64),
                       "seg_u64_u32": (6, np.uint64, np.uint32), "inclusive_max_u32": (7, np.uint32, None),

@@ -245,10 +245,6 @@ int pfp_get_kernel_trace(pfp_ctx *ctx, pfp_kernel_stat *out, int cap);
  * by adding a few extra trigger windows taken from inside them (default 32768; 0 = parse exactly
  * as the reference does).  The .bwt/.sa/.ssa/.esa outputs do not depend on the parse
  * (SURVEY.md 2.2-Q11); pfp_scan / pfp_parse always use the reference's trigger set. */
-/* Diagnostic (tests): the hand-written first-round sort (csrc/radix.hip: what replaces the bucket passes of gsacak.c:1395-1524
- * in the first round of the suffix sorter) on caller data: keys, and 32-bit values if vals != NULL, sorted in place, stable on
- * key bits [lo, hi). */
-int pfp_debug_msd_sort(pfp_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t n, int lo, int hi);
 /* Diagnostic (tests): the library sorts as the suffix sorter reaches them - through the wrappers of csrc/prims.hip, with their size
  * thresholds, tuned configurations and work-arounds - on caller data, in place.  kind: 0 sort_pairs_db (u64 keys, u32 vals),
  * 1 sort_pairs_db (u64, u64), 2 sort_keys_db (u64; vals unused), 3 sort_keys_raw (u64; vals unused), 4 segsort_pairs_u32 (u32 keys,

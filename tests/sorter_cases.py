@@ -7,8 +7,10 @@ As a program it runs the named cases in both index widths and prints one JSON li
     python tests/sorter_cases.py CASE [CASE ...]
     {"case": ..., "width": 32, "ok": true, "error": null, "witnesses": {"pfp::build_keys_pivot_kernel": 1, ...}}
 
-which is how the process-wide switches (PFP_NO_FINFLAG, PFP_PIVOT_CAP, ... - read once per process) get tested: a fresh child
-process per switch.  The exit status is 1 when a case differed from a reference.
+which is how the switches that force an alternative path (PFP_NO_FINFLAG, PFP_PIVOT_CAP, ...) get tested on many cases at once:
+a fresh child process per switch, with the switch in its environment from the start.  (The sorter reads every switch at each
+call, so a case can also set one around its own run: the `env` of a case.)  The exit status is 1 when a case differed from a
+reference.
 
 A gsacak collection is words of bytes >= 2, each followed by a 1, and one final 0.  "F families of V variants of L bytes with k
 substitutions" gives suffix groups of known size (V) and depth (the distance to the next substitution).
@@ -178,7 +180,7 @@ case("fam_segmented", "gsa", lambda: collection(family_block(_rng(5), 300, 40, 1
 case("fam_segmented_giant", "gsa",
      lambda: collection(family_block(_rng(6), 300, 40, 100, 2), family_block(_rng(7), 1, 40000, 40, 2, 0, 4)),
      lambda w: W([PIVOT, later_pairs(w)], [SEG32]))
-# comparison finisher: after the first pivot round (window kSwitch.pivot_cap = 512) what is left - variants that agree for more than
+# comparison finisher: after the first pivot round (window SorterSwitches::pivot_cap = 512) what is left - variants that agree for more than
 # 512 bytes - is below kFinishMax = 2^17, in groups of 4 <= kFinishGrp, with common prefixes below kFinishCmp = 8192
 case("finisher", "gsa", lambda: collection(family_block(_rng(8), 20, 4, 1500, 2)),
      lambda w: W([PIVOT, FINISH, FINISH_WRITE], [DBL, DBL32], maximum={PIVOT: 1}))
@@ -200,7 +202,7 @@ case("deep_scatter", "gsa", lambda: collection(family_block(_rng(12), 16, 8, 500
 # few enough for the lazy lookup (m <= N / kLazyRatio)
 case("deep_lazy", "gsa", lambda: collection(filler(_rng(13), 1_420_000), family_block(_rng(14), 1, 60, 3000, 2, 2900, 3000)),
      lambda w: W([PIVOT, DBL, REPAIR], [SCATTER, DBL32], maximum={PIVOT: 1}))
-# keys-only first round (PFP_KEYSONLY=1 is read per call; 32-bit build only): dictionaries below 2^20, between 2^20 and 2^22
+# keys-only first round (PFP_KEYSONLY=1; 32-bit build only): dictionaries below 2^20, between 2^20 and 2^22
 # (sort_keys_db sorts the whole word there) and above 2^22 bytes
 _ko = lambda w: W([SPLIT, KEYS0, PIVOT], [first_pairs(w)]) if w == 32 else W([PIVOT, first_pairs(w)], [SPLIT, KEYS0])      # noqa: E731
 case("keysonly_below_2^20", "gsa", lambda: collection(family_block(_rng(15), 80, 40, 150, 2)), _ko, {"PFP_KEYSONLY": "1"})
@@ -218,7 +220,7 @@ case("int_copies", "int", lambda: np.concatenate([parse_copies(300, 5000, 20, 21
      lambda w: W([INT_RUN], [IPIVOT]))
 
 # parse pivot rounds (only parse_bwt hands the sorter the counts): 2^16 phrases or more, groups of 300 -> segmented sort of
-# 64-bit keys; groups of 8 (<= kSmallSeg / 2) -> placed in LDS; a small parse with PFP_PARSE_PIVOT_MIN=64 (read per call),
+# 64-bit keys; groups of 8 (<= kSmallSeg / 2) -> placed in LDS; a small parse with PFP_PARSE_PIVOT_MIN=64,
 # and the same parse without it: no pivot round
 case("parse_segmented", "parse", lambda: parse_copies(300, 5000, 20, 21), lambda w: W([INT_RUN, IPIVOT, SEG64]))
 case("parse_small_groups", "parse", lambda: parse_copies(8, 30000, 20, 22), lambda w: W([INT_RUN, IPIVOT, SMALL], [SEG64]))

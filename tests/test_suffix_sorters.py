@@ -59,11 +59,12 @@ def test_byte_sorter(O, wctx, request, kind, n):
     run_and_check(O, wctx, request, f"bytes_{kind}_{n}")
 
 
-# ---- the process-wide switches: `static const` in sufsort.hip, read once per process, so each one gets a fresh child
+# ---- the switches that force an alternative path, each on every case below.  The sorter reads its switches at every call
+# (sorter_switches() in sufsort.hip; test_switches_are_read_per_call), so a child is not needed for them to take effect: it
+# gives each switch a process that has never run without it.
 SWITCH_CASES = ["fam_moderate", "fam_small", "finisher", "finisher_big_group", "deep_scatter", "int_runs", "parse_small_groups",
                 "bytes_fibonacci_65537", "bytes_a^n_65537"]
-SWITCHES = ["PFP_NO_FINFLAG=1", "PFP_PIVOT_CAP=0", "PFP_PIVOT_CAP=16", "PFP_NO_SMALLSEG=1", "PFP_NO_FINISHER=1", "PFP_OWN_SORT=1",
-            "PFP_KEYBITS=23", "PFP_KEYBITS=63"]
+SWITCHES = ["PFP_NO_FINFLAG=1", "PFP_PIVOT_CAP=0", "PFP_PIVOT_CAP=16", "PFP_NO_SMALLSEG=1", "PFP_NO_FINISHER=1", "PFP_KEYBITS=23", "PFP_KEYBITS=63"]
 CHILD_TIMEOUT = 300      # nine cases x two widths: a few seconds of oracle and sorting plus start-up; generous for a busy host
 _child_faulted = False
 
@@ -81,8 +82,6 @@ def switch_errors(switch, rows):
             errs.append(tag + "the finisher ran")
         if switch == "PFP_NO_SMALLSEG=1" and kind != "parse" and n(sc.SMALL):       # (the parse's pivot round places small groups regardless)
             errs.append(tag + "small groups were placed in LDS")
-        if switch == "PFP_OWN_SORT=1" and not any(k.startswith("pfp::rx_") for k in trace):
-            errs.append(tag + "no launch of the hand-written first-round sort")
         if switch in ("PFP_PIVOT_CAP=16", "PFP_KEYBITS=23", "PFP_KEYBITS=63") and kind == "gsa" and not n(sc.PIVOT):
             errs.append(tag + "no pivot round")
     return errs
@@ -116,3 +115,25 @@ def test_process_wide_switches(switch):
     assert out.returncode == 0, f"{switch}: the child ended with status {out.returncode}: {out.stderr[-2000:]}"
     errs = switch_errors(switch, rows)
     assert not errs, f"{switch}: " + "; ".join(errs)
+
+
+@pytest.mark.parametrize("switch,name,witness", [("PFP_NO_FINISHER", "finisher", sc.FINISH), ("PFP_NO_SMALLSEG", "fam_small", sc.SMALL)])
+def test_switches_are_read_per_call(O, wctx, request, switch, name, witness):
+    """the sorter reads its switches when it is called, not when the library is loaded: inside one process the same case runs
+    with the switch in the environment (right output, the witness of the switched-off path absent) and then without it (right
+    output, the witness back)"""
+    width = request.node.callspec.params["wctx"]
+    saved = os.environ.get(switch)
+    try:
+        os.environ[switch] = "1"
+        off = sc.run_case(wctx, O, name, width)
+        del os.environ[switch]
+        on = sc.run_case(wctx, O, name, width)
+    finally:
+        if saved is None:
+            os.environ.pop(switch, None)
+        else:
+            os.environ[switch] = saved
+    print(switch, name, width, json.dumps(off), json.dumps(on))
+    assert sc.row_launches(off, witness) == 0, f"{name} (idx{width}) under {switch}=1: {witness} was launched; trace: {off}"
+    assert sc.row_launches(on, witness) >= 1, f"{name} (idx{width}) without {switch}: no launch of {witness}; trace: {on}"
