@@ -201,6 +201,17 @@ SIGNATURES = {
                                   p32, p32]),
     "pfp_fm_map_long": (i32, [vp, p8, p64, u64, u64, u64, u64, u64, u64, u64, i32, p64, p8, p64, pp8, pp32, pp64, pp64, pp64, pp32, pp32,
                               pp32, pp32, pp32]),
+    "pfp_fm_fill_dev": (i32, [vp, vp, p64, u64, p32, p64, p64, p64, p64, u64, u64, p32, p64, p32]),
+    "pfp_fm_fill": (i32, [vp, p8, p64, u64, p32, p64, p64, p64, p64, u64, u64, p32, p64, pp32]),
+    "pfp_fm_chain_align_dev": (i32, [vp, vp, p64, u64, p64, p64, u64, u64, u64, u64, u64, p64, p32, p32, p32, p32, p64, p64, p32, p32, p64, p32,
+                                     p32, p64, p32, p64, p32]),
+    "pfp_fm_chain_align": (i32, [vp, p8, p64, u64, p64, p64, u64, u64, u64, u64, u64, p64, pp32, pp32, pp32, pp32, pp64, pp64, pp32, pp32, pp64,
+                                 pp32, pp32, pp64, pp32, pp64, pp32]),
+    "pfp_fm_map_long_aln_dev": (i32, [vp, vp, p64, u64, u64, u64, u64, u64, u64, u64, i32, u64, p64, p8, p64, p8, p32, p64, p64, p64, p32, p32,
+                                      p32, p32, p32, p32, p64, p32, p32, p64, p32]),
+    "pfp_fm_map_long_aln": (i32, [vp, p8, p64, u64, u64, u64, u64, u64, u64, u64, i32, u64, p64, p8, p64, pp8, pp32, pp64, pp64, pp64, pp32,
+                                  pp32, pp32, pp32, pp32, pp32, pp64, pp32, pp32, pp64, pp32]),
+    "pfp_fm_fill_stats": (i32, [vp, p64]),
     "pfp_fm_build_ms_dev": (i32, [vp, vp, u64, vp, u64, vp, u64, vp, pvp]),
     "pfp_fm_build_ms_files": (i32, [vp, cs, p8, i32, u64, u64, pvp]),
     "pfp_fm_ms_dev": (i32, [vp, vp, p64, u64, p32, p64]),

@@ -1,7 +1,7 @@
 // api_fm.hip -- searching a BWT (fmsearch.hip; the r-index of Gagie, Navarro and Prezza, PHONI for matching statistics: no
 // reference counterpart): struct pfp_fm and every pfp_fm_* call; the LCP array and thresholds (lcp.hip): pfp_lcp_*; the sequences
 // of a collection (seqmap.hip); extending seeds (fmextend.hip), aligning in a window (fmwindow.hip), edit scripts (fmcigar.hip),
-// mapping reads (fmmap.hip) and chaining anchors (fmchain.hip).
+// mapping reads (fmmap.hip), chaining anchors (fmchain.hip) and aligning chains (fmfill.hip).
 // What the calls over host arrays share is in the anonymous namespace below: one upload of the patterns (HostPatterns), one
 // budget (seq_budget) and one rule that cuts a call into groups of patterns (group_end), one way to collect a group's results
 // (HostOut::take / take_offsets, fetch_group_offsets).  align, map and map_pairs also share their beginning (seed_call_begin: the
@@ -1021,10 +1021,20 @@ int pfp_fm_map_long_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off
   });
 }
 
-int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
-                    uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
-                    uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
-                    uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match) {
+// what pfp_fm_map_long_aln returns on top of pfp_fm_map_long
+struct LongAlnHost {
+  uint64_t max_fill;
+  uint32_t **aqs;
+  uint64_t **ats;
+  uint32_t **nm, **unfilled;
+  uint64_t **cig_off;
+  uint32_t **cig;
+};
+// pfp_fm_map_long, and with aln pfp_fm_map_long_aln: one beginning, one grouping, the scripts of a group's returned chains behind its fields
+static int map_long_host(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                         uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
+                         uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
+                         uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match, const LongAlnHost *aln) {
   if (!fm || !hit_off || !strand || !seq || !off || !ts || !te || !qs || !qe || !score || !n || !match ||
       (npat && (!pat_off || !mapq || !nchains)))
     return PFP_EINVAL;
@@ -1035,11 +1045,13 @@ int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uin
   FmIndex &f = fm->f;
   fm_anchors_check(f, min_seed, max_occ, thresholds != 0);
   fm_chain_check(f, max_gap, band, min_score);
+  if (aln) fm_fill_check(f, aln->max_fill);
   SeedCall s;
   seed_call_begin(fm, pat, pat_off, npat, "read", true, min_seed, 0, thresholds != 0, s, false);
   HostOut<uint8_t> h_strand;
-  HostOut<uint32_t> h_seq, h_qs, h_qe, h_score, h_n, h_match;
-  HostOut<uint64_t> h_off, h_ts, h_te;
+  HostOut<uint32_t> h_seq, h_qs, h_qe, h_score, h_n, h_match, h_aqs, h_nm, h_unf, h_cig;
+  HostOut<uint64_t> h_off, h_ts, h_te, h_ats, h_coff;
+  if (aln) { *h_coff.grow(1) = 0; h_coff.n = 1; }
   std::vector<uint64_t> go;
   hit_off[0] = 0;
   anchor_groups(fm, s, 2, max_occ, [&](uint64_t p0, uint64_t np2, DBuf<uint64_t> &d_aoff, DBuf<uint64_t> &d_anc, uint64_t, DBuf<uint32_t> &) {
@@ -1047,6 +1059,7 @@ int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uin
     DBuf<uint64_t> d_hoff(c, np + 1), d_nc(c, np);
     DBuf<uint8_t> d_mapq(c, np);
     LongSel sel;
+    sel.keep = aln != nullptr;
     fm_map_long_select(f, d_aoff.p, d_anc.p, np, max_gap, band, min_score, max_sec, d_hoff.p, d_mapq.p, d_nc.p, sel);
     fetch_group_offsets(c, d_hoff.p, np, go, hit_off + r0);
     d2h(c, mapq + r0, d_mapq.p, np);
@@ -1062,11 +1075,210 @@ int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uin
     h_strand.take(c, d_strand.p, H); h_seq.take(c, d32.p, H); h_off.take(c, d64.p, H); h_ts.take(c, d64.p + H, H); h_te.take(c, d64.p + 2 * H, H);
     h_qs.take(c, d32.p + H, H); h_qe.take(c, d32.p + 2 * H, H); h_score.take(c, d32.p + 3 * H, H); h_n.take(c, d32.p + 4 * H, H);
     h_match.take(c, d32.p + 5 * H, H);
+    if (!aln) return;
+    DBuf<uint32_t> a32(c, 3 * H), d_cig;
+    DBuf<uint64_t> a64(c, H), d_coff(c, H + 1);
+    ChainAln st;
+    fm_map_long_align(f, s.pat, s.off + p0, np, d_aoff.p, d_anc.p, d_hoff.p, sel, aln->max_fill, AlnOut{a32.p, a64.p, a32.p + H, a32.p + 2 * H},
+                      d_coff.p, st);
+    d_cig.alloc(c, st.total);
+    fm_chain_align_write(f, st, d_coff.p, d_cig.p);
+    sync(c);
+    h_aqs.take(c, a32.p, H); h_nm.take(c, a32.p + H, H); h_unf.take(c, a32.p + 2 * H, H); h_ats.take(c, a64.p, H);
+    h_coff.take_offsets(c, d_coff.p + 1, H);
+    h_cig.take(c, d_cig.p, st.total);
   });
+  if (aln) {
+    *aln->aqs = h_aqs.release(); *aln->ats = h_ats.release(); *aln->nm = h_nm.release(); *aln->unfilled = h_unf.release();
+    *aln->cig_off = h_coff.release(); *aln->cig = h_cig.release();
+  }
   *strand = h_strand.release(); *seq = h_seq.release(); *off = h_off.release(); *ts = h_ts.release(); *te = h_te.release();
   *qs = h_qs.release(); *qe = h_qe.release(); *score = h_score.release(); *n = h_n.release(); *match = h_match.release();
   return PFP_OK;
   PFP_CATCH(c)
+}
+
+int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                    uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
+                    uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
+                    uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match) {
+  return map_long_host(fm, pat, pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec, thresholds, hit_off, mapq, nchains, strand, seq,
+                       off, ts, te, qs, qe, score, n, match, nullptr);
+}
+
+// ---------------------------------------------------------------- aligning chains (fmfill.hip)
+int pfp_fm_fill_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_seg_pat, const uint64_t *d_q0,
+                    const uint64_t *d_q1, const uint64_t *d_t0, const uint64_t *d_t1, uint64_t nseg, uint64_t max_fill, uint32_t *d_dist,
+                    uint64_t *d_cig_off, uint32_t *d_cig) {
+  if (!fm || !d_cig_off || (npat && !d_pat_off) || (nseg && (!d_seg_pat || !d_q0 || !d_q1 || !d_t0 || !d_t1 || !d_dist))) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    fm_fill(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, FillSegs{d_seg_pat, d_q0, d_q1, d_t0, d_t1}, nseg, max_fill, d_dist, d_cig_off, d_cig);
+  });
+}
+
+int pfp_fm_fill(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *seg_pat, const uint64_t *q0,
+                const uint64_t *q1, const uint64_t *t0, const uint64_t *t1, uint64_t nseg, uint64_t max_fill, uint32_t *dist, uint64_t *cig_off,
+                uint32_t **cig) {
+  if (!fm || !cig_off || !cig || (npat && !pat_off) || (nseg && (!seg_pat || !q0 || !q1 || !t0 || !t1 || !dist))) return PFP_EINVAL;
+  *cig = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_fill_check(fm->f, max_fill);
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  DBuf<uint32_t> d_sp(c, nseg), d_dist(c, nseg);
+  DBuf<uint64_t> d_seg(c, 4 * nseg), d_off(c, nseg + 1);
+  if (nseg) {
+    h2d(c, d_sp.p, seg_pat, nseg);
+    h2d(c, d_seg.p, q0, nseg); h2d(c, d_seg.p + nseg, q1, nseg); h2d(c, d_seg.p + 2 * nseg, t0, nseg); h2d(c, d_seg.p + 3 * nseg, t1, nseg);
+  }
+  const FillSegs sg{d_sp.p, d_seg.p, d_seg.p + nseg, d_seg.p + 2 * nseg, d_seg.p + 3 * nseg};
+  FillRuns runs;                                        // (every script is computed once: the runs wait in their slots for their place)
+  fm_fill_runs(fm->f, in.pat.p, in.off.p, npat, sg, nseg, max_fill, d_dist.p, d_off.p, runs);
+  DBuf<uint32_t> d_cig(c, runs.total);
+  fm_fill_write(fm->f, sg, nseg, d_dist.p, runs, d_off.p, d_cig.p);
+  if (nseg) d2h(c, dist, d_dist.p, nseg);
+  d2h(c, cig_off, d_off.p, nseg + 1);
+  sync(c);
+  HostOut<uint32_t> h_cig;
+  h_cig.take(c, d_cig.p, runs.total);
+  *cig = h_cig.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_fill_stats(pfp_fm *fm, uint64_t out[14]) {
+  if (!fm || !out) return PFP_EINVAL;
+  memcpy(out, fm->f.fill_stats, sizeof fm->f.fill_stats);
+  memset(fm->f.fill_stats, 0, sizeof fm->f.fill_stats);
+  return PFP_OK;
+}
+
+// the chains of device anchors and their scripts; what is the caller's: chain_off, out, al, cig_off; cig, mem_off and mem may be NULL
+static void chain_align_on_device(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint64_t *anc_off, const uint64_t *anc,
+                                  uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_chains, uint64_t max_fill, uint64_t *chain_off,
+                                  const ChainOut &out, const AlnOut &al, uint64_t *cig_off, uint32_t *cig, uint64_t *mem_off, uint32_t *mem) {
+  pfp_ctx *c = f.c;
+  ChainSel sel;
+  fm_chains_run(f, anc_off, anc, npat, max_gap, band, min_score, max_chains, chain_off, sel);
+  fm_chains_write(f, anc, npat, chain_off, sel, out);
+  ChainAln st;
+  fm_chain_align_runs(f, pat, pat_off, npat, anc_off, anc, chain_off, sel, nullptr, sel.total, max_fill, false, al, cig_off, st);
+  if (cig) fm_chain_align_write(f, st, cig_off, cig);
+  if (mem_off) PFP_HIP(hipMemcpyAsync(mem_off, st.mem_off.p, (st.nal + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+  if (mem && st.M) PFP_HIP(hipMemcpyAsync(mem, st.mem.p, st.M * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  sync(c);                                              // (the members, the gaps and their runs go back when this returns)
+}
+
+int pfp_fm_chain_align_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_anc_off,
+                           const uint64_t *d_anc, uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_chains, uint64_t max_fill,
+                           uint64_t *d_chain_off, uint32_t *d_score, uint32_t *d_n, uint32_t *d_qs, uint32_t *d_qe, uint64_t *d_ts, uint64_t *d_te,
+                           uint32_t *d_match, uint32_t *d_aqs, uint64_t *d_ats, uint32_t *d_nm, uint32_t *d_unfilled, uint64_t *d_cig_off,
+                           uint32_t *d_cig, uint64_t *d_mem_off, uint32_t *d_mem) {
+  if (!fm || !d_chain_off || (npat && (!d_anc_off || !d_pat_off))) return PFP_EINVAL;
+  const bool fill = d_score || d_n || d_qs || d_qe || d_ts || d_te || d_match || d_aqs || d_ats || d_nm || d_unfilled || d_cig_off || d_cig ||
+                    d_mem_off || d_mem;
+  if (fill && !(d_score && d_n && d_qs && d_qe && d_ts && d_te && d_match && d_aqs && d_ats && d_nm && d_unfilled && d_cig_off)) return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    fm_fill_check(fm->f, max_fill);
+    fm_fill_check_patterns(fm->f, d_pat_off, npat);
+    if (!fill) {
+      ChainSel sel;
+      fm_chains_run(fm->f, d_anc_off, d_anc, npat, max_gap, band, min_score, max_chains, d_chain_off, sel);
+      return;
+    }
+    chain_align_on_device(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, d_anc_off, d_anc, max_gap, band, min_score, max_chains, max_fill, d_chain_off,
+                          ChainOut{d_score, d_n, d_qs, d_qe, d_ts, d_te, d_match}, AlnOut{d_aqs, d_ats, d_nm, d_unfilled}, d_cig_off, d_cig, d_mem_off,
+                          d_mem);
+  });
+}
+
+int pfp_fm_chain_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint64_t *anc_off, const uint64_t *anc,
+                       uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_chains, uint64_t max_fill, uint64_t *chain_off,
+                       uint32_t **score, uint32_t **n, uint32_t **qs, uint32_t **qe, uint64_t **ts, uint64_t **te, uint32_t **match,
+                       uint32_t **aqs, uint64_t **ats, uint32_t **nm, uint32_t **unfilled, uint64_t **cig_off, uint32_t **cig,
+                       uint64_t **mem_off, uint32_t **mem) {
+  if (!fm || !chain_off || !score || !n || !qs || !qe || !ts || !te || !match || !aqs || !ats || !nm || !unfilled || !cig_off || !cig ||
+      (npat && (!anc_off || !pat_off)))
+    return PFP_EINVAL;
+  *score = nullptr; *n = nullptr; *qs = nullptr; *qe = nullptr; *ts = nullptr; *te = nullptr; *match = nullptr;
+  *aqs = nullptr; *ats = nullptr; *nm = nullptr; *unfilled = nullptr; *cig_off = nullptr; *cig = nullptr;
+  if (mem_off) *mem_off = nullptr;
+  if (mem) *mem = nullptr;
+  pfp_ctx *c = fm->f.c;
+  PFP_TRY_DEV(c)
+  fm_chain_check(fm->f, max_gap, band, min_score);
+  fm_fill_check(fm->f, max_fill);
+  chain_off[0] = 0;
+  HostPatterns in;
+  in.upload(c, pat, pat_off, npat);
+  for (uint64_t p = 0; p < npat; p++)
+    PFP_REQUIRE(anc_off[p] <= anc_off[p + 1], PFP_EINVAL, "anchor offsets decrease at pattern " + std::to_string(p));
+  const uint64_t A = npat ? anc_off[npat] : 0;
+  PFP_REQUIRE(anc || !A, PFP_EINVAL, "no anchors");
+  DBuf<uint64_t> d_aoff(c, npat + 1), d_anc(c, 3 * A), d_coff(c, npat + 1);
+  if (npat) h2d(c, d_aoff.p, anc_off, npat + 1);
+  if (A) h2d(c, d_anc.p, anc, 3 * A);
+  ChainSel sel;
+  fm_chains_run(fm->f, d_aoff.p, d_anc.p, npat, max_gap, band, min_score, max_chains, d_coff.p, sel);
+  const uint64_t C = sel.total;
+  DBuf<uint32_t> d32(c, 8 * C), d_cig;
+  DBuf<uint64_t> d64(c, 3 * C), d_goff(c, C + 1);
+  fm_chains_write(fm->f, d_anc.p, npat, d_coff.p, sel, ChainOut{d32.p, d32.p + C, d32.p + 2 * C, d32.p + 3 * C, d64.p, d64.p + C, d32.p + 4 * C});
+  ChainAln st;
+  fm_chain_align_runs(fm->f, in.pat.p, in.off.p, npat, d_aoff.p, d_anc.p, d_coff.p, sel, nullptr, C, max_fill, false,
+                      AlnOut{d32.p + 5 * C, d64.p + 2 * C, d32.p + 6 * C, d32.p + 7 * C}, d_goff.p, st);
+  d_cig.alloc(c, st.total);
+  fm_chain_align_write(fm->f, st, d_goff.p, d_cig.p);
+  d2h(c, chain_off, d_coff.p, npat + 1);
+  sync(c);
+  HostOut<uint32_t> h_score, h_n, h_qs, h_qe, h_match, h_aqs, h_nm, h_unf, h_cig, h_mem;
+  HostOut<uint64_t> h_ts, h_te, h_ats, h_goff, h_moff;
+  h_score.take(c, d32.p, C); h_n.take(c, d32.p + C, C); h_qs.take(c, d32.p + 2 * C, C); h_qe.take(c, d32.p + 3 * C, C);
+  h_match.take(c, d32.p + 4 * C, C); h_ts.take(c, d64.p, C); h_te.take(c, d64.p + C, C);
+  h_aqs.take(c, d32.p + 5 * C, C); h_nm.take(c, d32.p + 6 * C, C); h_unf.take(c, d32.p + 7 * C, C); h_ats.take(c, d64.p + 2 * C, C);
+  h_goff.take(c, d_goff.p, C + 1); h_cig.take(c, d_cig.p, st.total);
+  if (mem_off) h_moff.take(c, st.mem_off.p, C + 1);
+  if (mem) h_mem.take(c, st.mem.p, st.M);
+  *score = h_score.release(); *n = h_n.release(); *qs = h_qs.release(); *qe = h_qe.release(); *ts = h_ts.release(); *te = h_te.release();
+  *match = h_match.release(); *aqs = h_aqs.release(); *ats = h_ats.release(); *nm = h_nm.release(); *unfilled = h_unf.release();
+  *cig_off = h_goff.release(); *cig = h_cig.release();
+  if (mem_off) *mem_off = h_moff.release();
+  if (mem) *mem = h_mem.release();
+  return PFP_OK;
+  PFP_CATCH(c)
+}
+
+int pfp_fm_map_long_aln_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                            uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t max_fill,
+                            uint64_t *d_hit_off, uint8_t *d_mapq, uint64_t *d_nchains, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                            uint64_t *d_ts, uint64_t *d_te, uint32_t *d_qs, uint32_t *d_qe, uint32_t *d_score, uint32_t *d_n, uint32_t *d_match,
+                            uint32_t *d_aqs, uint64_t *d_ats, uint32_t *d_nm, uint32_t *d_unfilled, uint64_t *d_cig_off, uint32_t *d_cig) {
+  if (!fm || !d_hit_off || (npat && (!d_pat_off || !d_mapq || !d_nchains))) return PFP_EINVAL;
+  const bool fill = d_strand || d_seq || d_off || d_ts || d_te || d_qs || d_qe || d_score || d_n || d_match || d_aqs || d_ats || d_nm ||
+                    d_unfilled || d_cig_off || d_cig;
+  if (fill && !(d_strand && d_seq && d_off && d_ts && d_te && d_qs && d_qe && d_score && d_n && d_match && d_aqs && d_ats && d_nm && d_unfilled &&
+                d_cig_off))
+    return PFP_EINVAL;
+  return dev_call(fm, [&] {
+    fm_fill_check(fm->f, max_fill);
+    const LongOut out{d_strand, d_seq, d_off, d_ts, d_te, d_qs, d_qe, d_score, d_n, d_match};
+    const LongAln aln{max_fill, AlnOut{d_aqs, d_ats, d_nm, d_unfilled}, d_cig_off, d_cig};
+    fm_map_long(fm->f, (const uint8_t *)d_pat, d_pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec, thresholds != 0, d_hit_off,
+                d_mapq, d_nchains, fill ? &out : nullptr, fill ? &aln : nullptr);
+  });
+}
+
+int pfp_fm_map_long_aln(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                        uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t max_fill,
+                        uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts,
+                        uint64_t **te, uint32_t **qs, uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match, uint32_t **aqs,
+                        uint64_t **ats, uint32_t **nm, uint32_t **unfilled, uint64_t **cig_off, uint32_t **cig) {
+  if (!aqs || !ats || !nm || !unfilled || !cig_off || !cig) return PFP_EINVAL;
+  *aqs = nullptr; *ats = nullptr; *nm = nullptr; *unfilled = nullptr; *cig_off = nullptr; *cig = nullptr;
+  const LongAlnHost aln{max_fill, aqs, ats, nm, unfilled, cig_off, cig};
+  return map_long_host(fm, pat, pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec, thresholds, hit_off, mapq, nchains, strand, seq,
+                       off, ts, te, qs, qe, score, n, match, &aln);
 }
 
 // ---------------------------------------------------------------- sequences of a collection (seqmap.hip)

@@ -1,6 +1,7 @@
-// fmband.hpp -- the banded pass that fmextend.hip and fmwindow.hip share: m rows of Sellers' dynamic programme over a band of 16 CPL
+// fmband.hpp -- what the banded files share.  The banded pass of fmextend.hip and fmwindow.hip: m rows of Sellers' dynamic programme over a band of 16 CPL
 // diagonals, by one group of 16 lanes, forwards with a free start or backwards with a fixed end.  fmextend.hip's head states the
-// band and the layout; both files take an alignment's start from the backward form.
+// band and the layout; both files take an alignment's start from the backward form.  And the walk back along the records of a
+// pass that kept them, which fmcigar.hip and fmfill.hip share.
 #pragma once
 #include "fmdev.hpp"
 
@@ -76,6 +77,47 @@ __device__ __forceinline__ bool band_pass(const uint8_t *__restrict__ text, cons
     if (gmin16((uint64_t)low) >= (uint64_t)inf) return false;
   }
   return true;
+}
+
+// ---------------------------------------------------------------- the walk back along a pass's records (fmcigar.hip, fmfill.hip)
+// the records: 2 bits per cell, the operation rules 1-4 of "Edit scripts" choose there (0 '=', 1 'X', 2 'I', 3 'D'); word
+// (i - 1) / 16 * W + c holds row i of cell c of a band of W cells at bits 2 ((i - 1) % 16)
+constexpr uint32_t kOpI = 1, kOpD = 2, kOpEq = 7, kOpX = 8;     // the BAM codes
+
+// the uint32 words that hold the records of m rows of a band of W cells: whole blocks of 16 rows, and whole 128 bytes
+__host__ __device__ __forceinline__ uint64_t cig_words(uint64_t m, uint64_t W) { return ((m + 15) / 16 * W + 31) & ~31ull; }
+
+// one lane walks from (m, L), which is cell c of the last row, to (0, 0) along the records of a band of W cells; the runs go into
+// slot last first (at most cap of them are written) -> their number
+__device__ __forceinline__ uint32_t cig_walk(const uint32_t *ops, int W, int m, int L, int c, uint32_t *__restrict__ slot, uint32_t cap) {
+  int i = m, j = L;
+  uint32_t runs = 0, op = 0, len = 0;                   // the run that is open (op 0: none yet)
+  auto emit = [&](uint32_t o, uint32_t count) {
+    if (o == op) { len += count; return; }
+    if (len) {
+      if (runs < cap) slot[runs] = len << 4 | op;
+      runs++;
+    }
+    op = o; len = count;
+  };
+  uint64_t at = ~0ull;                                  // the word that `word` holds: '=' and 'X' stay in it for 16 rows
+  uint32_t word = 0;
+  while (i > 0 && j > 0 && (unsigned)c < (unsigned)W) {
+    const uint64_t idx = (uint64_t)((i - 1) >> 4) * W + c;
+    if (idx != at) { word = ops[idx]; at = idx; }
+    const int r = (i - 1) & 15;
+    const uint32_t top = word << (2 * (15 - r));        // row i's record in the two highest bits, the rows below it behind
+    const int eq = min(min(top ? __clz((int)top) >> 1 : 16, r + 1), j);       // the '=' from row i down, inside this word
+    if (eq) { emit(kOpEq, (uint32_t)eq); i -= eq; j -= eq; continue; }
+    const uint32_t code = top >> 30;
+    if (code <= 1) { emit(kOpX, 1); i--; j--; }
+    else if (code == 2) { emit(kOpI, 1); i--; c++; }
+    else { emit(kOpD, 1); j--; c--; }
+  }
+  if (i > 0) emit(kOpI, (uint32_t)i);
+  else if (j > 0) emit(kOpD, (uint32_t)j);
+  emit(0, 0);                                           // closes the open run
+  return runs;
 }
 
 }  // namespace

@@ -560,7 +560,9 @@ void fm_chains_run(FmIndex &f, const uint64_t *anc_off, const uint64_t *anc, uin
   }
   const uint64_t steps = chain_steps_from_env();
   DBuf<uint32_t> fs(c, A), se(c, npat), val(c, A), order(c, A);
-  DBuf<uint8_t> par(c, A), visited(c, A);
+  DBuf<uint8_t> visited(c, A);
+  DBuf<uint8_t> &par = sel.par;
+  par.alloc(c, A);
   DBuf<uint64_t> key(c, A), skey(c, A), cnt(c, npat + 1);
   sel.score.alloc(c, A); sel.n.alloc(c, A); sel.qs.alloc(c, A); sel.match.alloc(c, A); sel.ts.alloc(c, A);
   sel.order.alloc(c, A); sel.sb.alloc(c, npat);
@@ -626,7 +628,7 @@ void fm_map_long_select(FmIndex &f, const uint64_t *anc_off2, const uint64_t *an
   }
   sel.chain_off.alloc(c, 2 * npat + 1);
   {
-    ChainSel cs;
+    ChainSel gone, &cs = sel.keep ? sel.cs : gone;
     fm_chains_run(f, anc_off2, anc, 2 * npat, max_gap, band, min_score, 0, sel.chain_off.p, cs);
     const uint64_t C = cs.total;
     require_sortable(C, "chains");
@@ -662,16 +664,26 @@ void fm_map_long_fill(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, const
 
 void fm_map_long(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, uint64_t max_gap,
                  uint64_t band, uint64_t min_score, uint64_t max_sec, bool thresholds, uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains,
-                 const LongOut *out) {
+                 const LongOut *out, const LongAln *aln) {
   pfp_ctx *c = f.c;
   fm_anchors_check(f, min_seed, max_occ, thresholds);
   fm_chain_check(f, max_gap, band, min_score);
+  if (aln) fm_fill_check(f, aln->max_fill);
   LongSel sel;
+  sel.keep = aln != nullptr;
   fm_map_strands(f, pat, pat_off, npat, sel.rd, true);
   DBuf<uint64_t> anc_off(c, 2 * npat + 1), anc;
   fm_anchors(f, sel.rd.pat.p, sel.rd.off.p, 2 * npat, min_seed, max_occ, thresholds, anc_off.p, anc, nullptr);
   fm_map_long_select(f, anc_off.p, anc.p, npat, max_gap, band, min_score, max_sec, hit_off, mapq, nchains, sel);
   if (out) fm_map_long_fill(f, sel.rd.off.p, npat, hit_off, sel, *out);
+  if (aln && npat) {
+    ChainAln st;
+    fm_map_long_align(f, sel.rd.pat.p, sel.rd.off.p, npat, anc_off.p, anc.p, hit_off, sel, aln->max_fill, aln->out, aln->cig_off, st);
+    if (aln->cig) fm_chain_align_write(f, st, aln->cig_off, aln->cig);
+    sync(c);                                            // (the gaps and their runs go back when this returns)
+  } else if (aln) {
+    PFP_HIP(hipMemsetAsync(aln->cig_off, 0, sizeof(uint64_t), c->stream));
+  }
   sync(c);
 }
 

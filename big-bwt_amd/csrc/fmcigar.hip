@@ -25,6 +25,7 @@
 #include "prims.hpp"
 #include "devutil.hpp"
 #include "fmdev.hpp"
+#include "fmband.hpp"
 
 namespace pfp {
 
@@ -32,7 +33,6 @@ namespace {
 
 constexpr uint8_t kCigNone = 0xFF;
 constexpr uint64_t kCigarScratch = 1ull << 30;          // bytes of records per launch: a choice (0.8 million reads of 150 bytes at k = 8)
-constexpr uint32_t kOpI = 1, kOpD = 2, kOpEq = 7, kOpX = 8;     // the BAM codes
 
 // what an alignment is about: its pattern and its span, or ok = false (no such pattern, decreasing offsets, a pattern too long,
 // s > e, e > n, or lengths that differ by more than k)
@@ -50,9 +50,6 @@ __device__ __forceinline__ CigAln cig_aln(const uint64_t *__restrict__ off, uint
   if (L > m + (uint64_t)k || m > L + (uint64_t)k) return r;
   return CigAln{o0, s, (int)m, (int)L, true};
 }
-
-// the uint32 words that hold the records of m rows of a band of W = 16 CPL cells: whole blocks of 16 rows, and whole 128 bytes
-__host__ __device__ __forceinline__ uint64_t cig_words(uint64_t m, uint64_t W) { return ((m + 15) / 16 * W + 31) & ~31ull; }
 
 // need[ai] = the words of alignment ai's records (0: it has no script), ai < naln; need[naln] = 0
 __global__ void __launch_bounds__(kTB) cig_need_k(const uint64_t *__restrict__ off, uint64_t npat, const uint32_t *__restrict__ aln_pat,
@@ -138,39 +135,6 @@ __device__ __forceinline__ bool cig_forward(const uint8_t *__restrict__ T, const
     if (gmin16((uint64_t)low) >= (uint64_t)inf) return false;
   }
   return true;
-}
-
-// one lane walks from (m, L), which is cell c of the last row, to (0, 0) along the records of a band of W cells; the runs go into
-// slot last first (at most cap of them are written) -> their number
-__device__ __forceinline__ uint32_t cig_walk(const uint32_t *ops, int W, int m, int L, int c, uint32_t *__restrict__ slot, uint32_t cap) {
-  int i = m, j = L;
-  uint32_t runs = 0, op = 0, len = 0;                   // the run that is open (op 0: none yet)
-  auto emit = [&](uint32_t o, uint32_t count) {
-    if (o == op) { len += count; return; }
-    if (len) {
-      if (runs < cap) slot[runs] = len << 4 | op;
-      runs++;
-    }
-    op = o; len = count;
-  };
-  uint64_t at = ~0ull;                                  // the word that `word` holds: '=' and 'X' stay in it for 16 rows
-  uint32_t word = 0;
-  while (i > 0 && j > 0 && (unsigned)c < (unsigned)W) {
-    const uint64_t idx = (uint64_t)((i - 1) >> 4) * W + c;
-    if (idx != at) { word = ops[idx]; at = idx; }
-    const int r = (i - 1) & 15;
-    const uint32_t top = word << (2 * (15 - r));        // row i's record in the two highest bits, the rows below it behind
-    const int eq = min(min(top ? __clz((int)top) >> 1 : 16, r + 1), j);       // the '=' from row i down, inside this word
-    if (eq) { emit(kOpEq, (uint32_t)eq); i -= eq; j -= eq; continue; }
-    const uint32_t code = top >> 30;
-    if (code <= 1) { emit(kOpX, 1); i--; j--; }
-    else if (code == 2) { emit(kOpI, 1); i--; c++; }
-    else { emit(kOpD, 1); j--; c--; }
-  }
-  if (i > 0) emit(kOpI, (uint32_t)i);
-  else if (j > 0) emit(kOpD, (uint32_t)j);
-  emit(0, 0);                                           // closes the open run
-  return runs;
 }
 
 // one group of 16 lanes per alignment a0 <= ai < a1, 1 <= k <= PFP_FM_EXTEND_MAX_K, 16 CPL >= 2k + 1.  soff = the exclusive sums

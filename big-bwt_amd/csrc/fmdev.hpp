@@ -1,4 +1,4 @@
-// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, fmcigar.hip, fmmap.hip, lcp.hip, seqmap.hip).  Device side:
+// fmdev.hpp -- the toolkit of the files over an FmIndex (fmsearch.hip, fmapprox.hip, fmextend.hip, fmcigar.hip, fmfill.hip, fmmap.hip, lcp.hip, seqmap.hip).  Device side:
 // the index as kernel arguments, rank and select by groups of 16 lanes, the start of a group-per-pattern kernel, the steps the walks
 // share (toehold, matching-statistics start and neighbours), the 1024-byte compare, and the tiny kernels every segmented sort needs.
 // Host side: the environment's budget and stats switch, the index width as a type, the requirement checks, and the one loop that

@@ -352,6 +352,7 @@ struct FmIndex {
   DBuf<uint8_t> text;                    // the text, n1 - 1 bytes and 16 bytes of zero padding (whole 16-byte loads stay in bounds)
   DBuf<uint8_t> re_sa;                   // [runs] of I: SA value of run end i
   uint64_t ms_stats[3] = {0, 0, 0};      // fm_ms launches; with PFP_FM_MS_STATS=1 also steps that jumped and bytes their LCEs matched
+  uint64_t fill_stats[14] = {};          // with PFP_FM_MS_STATS=1 (fmfill.hip): gaps, trivial ones, then per width gaps that went through a pass and their cells
   uint64_t apx_stats[3] = {0, 0, 0};     // fm_approx launches and hits filled; with PFP_FM_MS_STATS=1 also (in [1]) LF pairs
   bool has_thr = false;                  // fm_lcp (keep) or fm_load_thresholds filled the array below
   DBuf<uint8_t> thr;                     // [runs] of I: the threshold row of run k (lcp.hip)
@@ -556,6 +557,7 @@ void fm_chain_check(const FmIndex &f, uint64_t max_gap, uint64_t band, uint64_t 
 // in the order of output inside every pattern's segment
 struct ChainSel {
   DBuf<uint32_t> score, n, qs, match, order, sb;
+  DBuf<uint8_t> par;        // how many anchors back every anchor's parent lies (fmfill.hip walks a chain's members along them)
   DBuf<uint64_t> ts;
   uint64_t total = 0;
 };
@@ -572,6 +574,8 @@ void fm_chains_write(FmIndex &f, const uint64_t *anc, uint64_t npat, const uint6
 // what fm_map_long_select leaves for fm_map_long_fill: both strands' patterns, their chains and the reads' order of them
 struct LongSel {
   MapReads rd;
+  ChainSel cs;              // keep: what the programme and the peel left stays here (fm_map_long_align reads it), else it goes at once
+  bool keep = false;
   DBuf<uint64_t> chain_off, ts, te;
   DBuf<uint32_t> score, n, qs, qe, match, order;
   uint64_t H = 0;
@@ -587,10 +591,70 @@ struct LongOut {
 void fm_map_long_select(FmIndex &f, const uint64_t *anc_off2, const uint64_t *anc, uint64_t npat, uint64_t max_gap, uint64_t band,
                         uint64_t min_score, uint64_t max_sec, uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains, LongSel &sel);
 void fm_map_long_fill(FmIndex &f, const uint64_t *pat2_off, uint64_t npat, const uint64_t *hit_off, const LongSel &sel, const LongOut &out);
-// all of it over device patterns; out == NULL: hit_off, mapq and nchains only
+struct LongAln;     // (below, with fmfill.hip's)
+// all of it over device patterns; out == NULL: hit_off, mapq and nchains only.  aln: the scripts of the returned chains as well
 void fm_map_long(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ, uint64_t max_gap,
                  uint64_t band, uint64_t min_score, uint64_t max_sec, bool thresholds, uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains,
-                 const LongOut *out);
+                 const LongOut *out, const LongAln *aln = nullptr);
+// aligning chains (fmfill.hip; pfpgpu.h, "Aligning chains", states the definitions).  Device pointers.  max_fill above
+// PFP_FM_FILL_MAX_F or an index without text -> PFP_EINVAL
+void fm_fill_check(const FmIndex &f, uint64_t max_fill);
+// device pattern offsets that decrease -> PFP_EINVAL
+void fm_fill_check_patterns(FmIndex &f, const uint64_t *pat_off, uint64_t npat);
+// segment g = (pat[g], q0[g], q1[g], t0[g], t1[g])
+struct FillSegs {
+  const uint32_t *pat;
+  const uint64_t *q0, *q1, *t0, *t1;
+};
+// what the gap passes leave for the passes that place runs: per gap its number of runs and where they wait, last first (0: none
+// are stored - a trivial gap's one run is derived); pool holds them until this goes
+struct FillRuns {
+  DBuf<uint64_t> cnt, rptr;
+  std::vector<DBuf<uint32_t>> pool;
+  uint64_t total = 0;       // the runs of all segments (fm_fill_runs)
+};
+// the gap passes alone: dist[g] (0xFFFFFFFF: no script) and out
+void fm_fill_gaps(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const FillSegs &sg, uint64_t ngap, uint64_t max_fill,
+                  uint32_t *dist, FillRuns &out);
+// pattern offsets that decrease -> PFP_EINVAL; dist and cig_off[0..nseg], the exclusive sums of the run counts
+void fm_fill_runs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const FillSegs &sg, uint64_t nseg, uint64_t max_fill,
+                  uint32_t *dist, uint64_t *cig_off, FillRuns &out);
+// the runs in order, segment g's at cig_off[g] .. cig_off[g + 1]: room for runs.total entries
+void fm_fill_write(FmIndex &f, const FillSegs &sg, uint64_t nseg, const uint32_t *dist, const FillRuns &runs, const uint64_t *cig_off, uint32_t *cig);
+// fm_fill_runs and, where cig is given, fm_fill_write
+void fm_fill(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const FillSegs &sg, uint64_t nseg, uint64_t max_fill,
+             uint32_t *dist, uint64_t *cig_off, uint32_t *cig);
+// what fm_chain_align_runs leaves for fm_chain_align_write (and for a caller that wants the members): the aligned chains' members
+// (mem_off, mem: indices inside the pattern's anchors), and per member its gap (seg_pat, seg64 = q0, q1, t0, t1, dist, runs) and
+// the bytes its trimmed anchor keeps
+struct ChainAln {
+  uint64_t nal = 0, M = 0, total = 0;      // total: the runs of all scripts, which is what the output must hold
+  DBuf<uint64_t> mem_off, seg64;
+  DBuf<uint32_t> mem, seg_pat, keep, dist;
+  FillRuns runs;
+};
+struct AlnOut {
+  uint32_t *aqs = nullptr;
+  uint64_t *ats = nullptr;
+  uint32_t *nm = nullptr, *unfilled = nullptr;
+};
+// the scripts of nal chains of those fm_chains_run left in cs (chain_off: its offsets): chain list[k] (NULL: k), k < nal.  out gets
+// nal entries each, cig_off[0..nal] the exclusive sums of the run counts.  turn: the patterns are the strands of reads
+// (fm_map_strands) and aqs of an odd pattern is turned into the read as given
+void fm_chain_align_runs(FmIndex &f, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint64_t *anc_off, const uint64_t *anc,
+                         const uint64_t *chain_off, const ChainSel &cs, const uint32_t *list, uint64_t nal, uint64_t max_fill, bool turn,
+                         const AlnOut &out, uint64_t *cig_off, ChainAln &st);
+void fm_chain_align_write(FmIndex &f, const ChainAln &st, const uint64_t *cig_off, uint32_t *cig);
+// the scripts of the sel.H chains that fm_map_long_select returns (sel.keep was set): out and cig_off as above, H entries
+void fm_map_long_align(FmIndex &f, const uint8_t *pat2, const uint64_t *pat2_off, uint64_t npat, const uint64_t *anc_off2, const uint64_t *anc,
+                       const uint64_t *hit_off, const LongSel &sel, uint64_t max_fill, const AlnOut &out, uint64_t *cig_off, ChainAln &st);
+// what pfp_fm_map_long_aln adds to fm_map_long: out and cig_off get hit_off[npat] (+ 1) entries; cig NULL: those only
+struct LongAln {
+  uint64_t max_fill;
+  AlnOut out;
+  uint64_t *cig_off;
+  uint32_t *cig;
+};
 // mapping read pairs (fmpair.hip; pfpgpu.h, "Mapping read pairs", states the definitions).  Device pointers.  fm_map_check's
 // errors; an odd number of reads, min_ins > max_ins, max_ins > PFP_FM_WINDOW_MAX_W or anchors outside 1 ..
 // PFP_FM_PAIR_MAX_ANCHORS -> PFP_EINVAL

@@ -7,7 +7,7 @@
  *   bwtsearch --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--device D] PATTERNFILE basename
  *   bwtsearch --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename
  *   bwtsearch --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] ... READS basename
- *   bwtsearch --paf [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE]
+ *   bwtsearch --paf [--cigar [--fill F]] [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE]
  *             [--seqs=FILE] [--device D] READS basename
  *
  * Patterns are the lines of PATTERNFILE, split at '\n' only, bytes kept as they are (a final '\n' ends the last line; it does
@@ -72,6 +72,12 @@
  * tags tp:A:P (the best chain) or tp:A:S (up to N further ones, --secondary, default 0, with MAPQ 0), cm:i: the chain's anchors,
  * s1:i: its score and, on a primary line with a runner-up, s2:i: the runner-up's.  With --seqs[=FILE] tname and tlen are the
  * record's; without a table tname is basename's file name and tlen the text's length.  --paf combines with no other mode.
+ * --paf --cigar aligns every printed chain base by base (include/pfpgpu.h, "Aligning chains"): the stretch between two anchors
+ * by an edit-distance alignment of at most F edits (--fill, 0..4096, default 500 = the default band, a choice; needs both).  The
+ * line's columns are then the alignment's: qs, qe and ts where the chain's first anchor begins (on strand - that moves qe), column
+ * 10 the bytes in '=' runs, column 11 the sum of all run lengths; behind the tags above come NM:i:, uf:i: (the stretches that
+ * take more than F edits and stand in the script as an insertion and a deletion; only where there are any; this program's own
+ * tag) and cg:Z: with '=', X, I, D.  Without --cigar the output is what it was.
  * Large pattern files go through in batches of at most 2^20 patterns and 64 MiB (PFP_FM_BATCH=K: at most K patterns).
  * Exit codes: 0 done, 1 a file that cannot be read, is not a BWT or lacks a sample file, a sequence table that cannot be read, is
  * malformed or does not sum to the text's length, 2 a usage error.
@@ -98,7 +104,7 @@ static void usage(const char *argv0) {
          "       %s --align K [--seed L] [--cigar] [-m MAXALN] [--thresholds] [--text FILE] [--rc] [--device D] PATTERNFILE basename\n"
          "       %s --sam K [--seed L] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] [--device D] READS basename\n"
          "       %s --sam K --paired | -2 FILE [--ins MIN:MAX] [--anchors C] [--seed L] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n"
-         "       %s --paf [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n\n"
+         "       %s --paf [--cigar [--fill F]] [--seed L] [--max-occ N] [--gap G] [--band B] [--min-score S] [--secondary N] [--thresholds] [--text FILE] [--seqs=FILE] READS basename\n\n"
          "Counts, or with -l locates, the lines of PATTERNFILE in the text whose BWT is basename.bwt, on the GPU (MI355X).\n\n"
          "  PATTERNFILE   one pattern per line (split at \\n only, bytes kept as they are)\n"
          "  basename      reads basename.bwt; with -l also basename.ssa and basename.esa (bigbwt -s -e)\n"
@@ -142,6 +148,10 @@ static void usage(const char *argv0) {
          "      --gap G     with --paf: two anchors chain when they end at most G bytes apart in the read and the text (def. 5000, a choice)\n"
          "      --band B    with --paf: ... and at most B bytes off each other's diagonal (def. 500, a choice)\n"
          "      --min-score S with --paf: a chain that scores below S is dropped (def. 40, a choice)\n"
+         "      --cigar     with --paf: align every printed chain base by base: the line's coordinates are the alignment's, columns 10\n"
+         "                  and 11 its matches and its length, and NM:i:, uf:i: (gaps left unfilled, if any) and cg:Z: (=, X, I, D) follow\n"
+         "      --fill F    with --paf --cigar: the edits the stretch between two anchors may take (0..4096, def. 500 = the default\n"
+         "                  band, a choice); a stretch that takes more stands in the script as an insertion and a deletion\n"
          "      --text FILE with --ms / --mems / --align / --sam / --paf: the text (def. inverted from basename.bwt)\n"
          "      --thresholds with --ms / --mems / --align / --sam / --paf: two passes with thresholds; reads basename.thr_pos if it exists, else computes it\n"
          "      --seqs[=FILE] load the sequence table FILE (def. basename.seqs; bigbwt -f --seqs writes it).  With -l print\n"
@@ -197,6 +207,7 @@ typedef struct {
   uint64_t min_ins, max_ins, anchors;
   uint64_t maxsec, first; char *const *qname;      /* --sam: the batch's first read, and the reads' names (NULL: their numbers) */
   uint64_t max_occ, gap, band, min_score, n; const char *tname;      /* --paf; n, tname: the text's length and name (no table) */
+  uint64_t fill;                                                     /* --paf --cigar: the edits a gap between two anchors may take */
 } batch_t;
 
 static int fail(const char *what, int rc, pfp_ctx *ctx) {
@@ -335,14 +346,21 @@ static int mode_sam(const batch_t *b) {
 }
 
 /* --paf: one line per returned chain (the definitions: include/pfpgpu.h, "Chaining anchors").  The runner-up is always asked for:
- * its score goes into the primary line */
+ * its score goes into the primary line.  --cigar: the chain's edit script ("Aligning chains") decides the line's coordinates - the
+ * read's bytes [aqs, qe) on strand +, [qs, aqs) on strand -, the text from ats - the matches and the block length, and adds NM:i:,
+ * uf:i: (the gaps left unfilled, where there are any) and cg:Z: */
 static int mode_paf(const batch_t *b) {
-  uint64_t *oo = b->oo, *nchains = b->sp, *off = NULL, *ts = NULL, *te = NULL;
+  uint64_t *oo = b->oo, *nchains = b->sp, *off = NULL, *ts = NULL, *te = NULL, *ats = NULL, *coff = NULL;
   uint8_t *strand = NULL, *mapq = malloc(b->k + 1);
-  uint32_t *seq = NULL, *qs = NULL, *qe = NULL, *score = NULL, *cn = NULL, *match = NULL;
+  uint32_t *seq = NULL, *qs = NULL, *qe = NULL, *score = NULL, *cn = NULL, *match = NULL, *aqs = NULL, *nm = NULL, *unf = NULL, *cig = NULL;
   int r = 1;
   if (!mapq) fprintf(stderr, "out of memory\n");
-  else if ((r = pfp_fm_map_long(b->fm, b->pat, b->off, b->k, b->seed, b->max_occ, b->gap, b->band, b->min_score, b->maxsec ? b->maxsec : 1,
+  else if (b->cigar) {
+    if ((r = pfp_fm_map_long_aln(b->fm, b->pat, b->off, b->k, b->seed, b->max_occ, b->gap, b->band, b->min_score, b->maxsec ? b->maxsec : 1,
+                                 b->thresholds, b->fill, oo, mapq, nchains, &strand, &seq, &off, &ts, &te, &qs, &qe, &score, &cn, &match, &aqs, &ats,
+                                 &nm, &unf, &coff, &cig)) != 0)
+      r = fail(b->base, r, b->ctx);
+  } else if ((r = pfp_fm_map_long(b->fm, b->pat, b->off, b->k, b->seed, b->max_occ, b->gap, b->band, b->min_score, b->maxsec ? b->maxsec : 1,
                                 b->thresholds, oo, mapq, nchains, &strand, &seq, &off, &ts, &te, &qs, &qe, &score, &cn, &match)) != 0)
     r = fail(b->base, r, b->ctx);
   for (uint64_t i = 0; !r && i < b->k; i++) {
@@ -353,16 +371,33 @@ static int mode_paf(const batch_t *b) {
       const int second = j > oo[i];
       const uint64_t qspan = qe[j] - qs[j], tspan = te[j] - ts[j];
       const uint64_t tlen = b->tab->nseq ? b->tab->start[seq[j] + 1] - b->tab->start[seq[j]] : b->n;
-      printf("%s\t%" PRIu64 "\t%" PRIu32 "\t%" PRIu32 "\t%c\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu32 "\t%" PRIu64 "\t%u",
-             qn, b->off[i + 1] - b->off[i], qs[j], qe[j], strand[j] ? '-' : '+', b->tab->nseq ? b->tab->name[seq[j]] : b->tname, tlen, off[j],
-             off[j] + tspan, match[j], qspan > tspan ? qspan : tspan, second ? 0u : (unsigned)mapq[i]);
+      uint64_t q0 = qs[j], q1 = qe[j], t0 = off[j], same = match[j], block = qspan > tspan ? qspan : tspan;
+      if (b->cigar) {
+        if (strand[j]) q1 = aqs[j];
+        else q0 = aqs[j];
+        t0 = off[j] + (ats[j] - ts[j]);
+        same = block = 0;
+        for (uint64_t x = coff[j]; x < coff[j + 1]; x++) {
+          block += cig[x] >> 4;
+          if ((cig[x] & 15) == 7) same += cig[x] >> 4;
+        }
+      }
+      printf("%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%c\t%s\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%u",
+             qn, b->off[i + 1] - b->off[i], q0, q1, strand[j] ? '-' : '+', b->tab->nseq ? b->tab->name[seq[j]] : b->tname, tlen, t0,
+             off[j] + tspan, same, block, second ? 0u : (unsigned)mapq[i]);
       printf("\ttp:A:%c\tcm:i:%" PRIu32 "\ts1:i:%" PRIu32, second ? 'S' : 'P', cn[j], score[j]);
       if (!second && oo[i + 1] - oo[i] > 1) printf("\ts2:i:%" PRIu32, score[j + 1]);
+      if (b->cigar) {
+        printf("\tNM:i:%" PRIu32, nm[j]);
+        if (unf[j]) printf("\tuf:i:%" PRIu32, unf[j]);
+        fputs("\tcg:Z:", stdout);
+        print_script(cig + coff[j], coff[j + 1] - coff[j]);
+      }
       putchar('\n');
     }
   }
   pfp_free(strand); pfp_free(seq); pfp_free(off); pfp_free(ts); pfp_free(te); pfp_free(qs); pfp_free(qe); pfp_free(score); pfp_free(cn);
-  pfp_free(match);
+  pfp_free(match); pfp_free(aqs); pfp_free(ats); pfp_free(nm); pfp_free(unf); pfp_free(coff); pfp_free(cig);
   free(mapq);
   return r;
 }
@@ -536,14 +571,14 @@ static int mode_count(const batch_t *b) {
 }
 
 int main(int argc, char **argv) {
-  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0, paired = 0, have_pair_opt = 0, paf = 0, have_paf_opt = 0;
+  int locate = 0, device = 0, ms = 0, mems = 0, have_m = 0, thresholds = 0, seqs = 0, docs = 0, rcomp = 0, approx = 0, kmis = 0, align = 0, kedit = 0, cigar = 0, sam = 0, have_sec = 0, paired = 0, have_pair_opt = 0, paf = 0, have_paf_opt = 0, have_fill = 0;
   const char *seqsfile = NULL, *mates2 = NULL;
   uint64_t min_ins = 0, max_ins = 1000, anchors = 8;
   pfp_seqs tab, rtab, rtab2;      /* the collection's table, and with --sam the names of a FASTA / FASTQ file's reads (-2: FILE's) */
   pfp_seqs_init(&tab);
   pfp_seqs_init(&rtab);
   pfp_seqs_init(&rtab2);
-  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0, paf_occ = 500, gap = 5000, band = 500, min_score = 40;
+  uint64_t maxocc = 0, min_len = 0, seed = 20, have_seed = 0, maxsec = 0, paf_occ = 500, gap = 5000, band = 500, min_score = 40, fill = 500;
   const char *textfile = NULL;
   static struct option lo[] = {{"device", required_argument, 0, 1001}, {"ms", no_argument, 0, 1002}, {"mems", required_argument, 0, 1003},
                                {"text", required_argument, 0, 1004}, {"thresholds", no_argument, 0, 1005}, {"help", no_argument, 0, 'h'},
@@ -553,6 +588,7 @@ int main(int argc, char **argv) {
                                {"paired", no_argument, 0, 1014}, {"ins", required_argument, 0, 1015}, {"anchors", required_argument, 0, 1016},
                                {"paf", no_argument, 0, 1017}, {"max-occ", required_argument, 0, 1018}, {"gap", required_argument, 0, 1019},
                                {"band", required_argument, 0, 1020}, {"min-score", required_argument, 0, 1021},
+                               {"fill", required_argument, 0, 1022},
                                {0, 0, 0, 0}};
   int c;
   char *end;
@@ -627,6 +663,11 @@ int main(int argc, char **argv) {
         *(c == 1018 ? &paf_occ : c == 1019 ? &gap : c == 1020 ? &band : &min_score) = v;
         have_paf_opt = 1;
       } break;
+      case 1022:
+        fill = strtoull(optarg, &end, 10);
+        if (!*optarg || *end || optarg[0] == '-' || fill > PFP_FM_FILL_MAX_F) { usage(argv[0]); return 2; }
+        have_fill = 1;
+        break;
       case 1001:
         device = (int)strtol(optarg, &end, 10);
         if (!*optarg || *end) { usage(argv[0]); return 2; }
@@ -639,12 +680,16 @@ int main(int argc, char **argv) {
     usage(argv[0]);
     return 1;
   }
-  if (paf && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp || paired || have_pair_opt)) {
+  if (paf && (locate || approx || have_m || ms || mems || docs || align || rcomp || paired || have_pair_opt)) {
     fprintf(stderr, "--paf does not combine with the other modes or with --rc (both strands are always searched)\n");
     return 2;
   }
   if (have_paf_opt && !paf) {
     fprintf(stderr, "--max-occ, --gap, --band and --min-score need --paf\n");
+    return 2;
+  }
+  if (have_fill && !(paf && cigar)) {
+    fprintf(stderr, "--fill needs --paf --cigar\n");
     return 2;
   }
   if (sam && (locate || approx || have_m || ms || mems || docs || align || cigar || rcomp)) {
@@ -665,7 +710,7 @@ int main(int argc, char **argv) {
   }
   if (optind + 2 != argc || ms + mems + locate + docs > 1 || ((ms || mems || docs) && have_m) ||
       ((textfile || thresholds) && !ms && !mems && !align && !sam && !paf) || ((ms || mems) && seqs) || (approx && (ms || mems || docs || seqs)) ||
-      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align && !sam && !paf) || (cigar && !align) ||
+      (align && (locate || approx || ms || mems || docs || seqs)) || (have_seed && !align && !sam && !paf) || (cigar && !align && !paf) ||
       (have_sec && !sam && !paf)) {
     usage(argv[0]);
     return 2;
@@ -833,7 +878,7 @@ int main(int argc, char **argv) {
       off[0] = 0; off[1] = bytes;
     }
     const batch_t b = {ctx, fm, base, &tab, pat, off, k, oo, sp, ep, maxocc, min_len, seed, thresholds, locate, kmis, kedit, cigar, min_ins, max_ins, anchors, maxsec, p0, qname,
-                       paf_occ, gap, band, min_score, info.n, tname};
+                       paf_occ, gap, band, min_score, info.n, tname, fill};
     if (mode(&b)) { rc = 1; goto done; }
     p0 += lines;
   }

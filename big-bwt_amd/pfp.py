@@ -41,6 +41,12 @@ PAIR_NAMES = ("proper", "npairs", "mapped", "rescued", "mapq", "nhits", "strand"
 FM_CHAIN_PRED = 64
 # the arrays FmIndex.map_long returns, in order: the first three per read, the others per returned chain
 LONG_NAMES = ("hit_off", "mapq", "nchains", "strand", "seq", "off", "ts", "te", "qs", "qe", "score", "n", "match")
+FM_FILL_MAX_F, FM_FILL_MAX_LEN = 4096, 65535
+# the arrays FmIndex.chain_align returns, in order: chain()'s, then per chain where its script begins, its edits, its unfilled gaps,
+# the scripts and the members
+CHAIN_ALN_NAMES = ("chain_off", "score", "n", "qs", "qe", "ts", "te", "match", "aqs", "ats", "nm", "unfilled", "cig_off", "cig", "mem_off", "mem")
+# the arrays FmIndex.map_long_aln returns, in order: map_long()'s, then per returned chain the same but the members
+LONG_ALN_NAMES = LONG_NAMES + ("aqs", "ats", "nm", "unfilled", "cig_off", "cig")
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}    # the BAM codes of the operations an edit script holds
 
 LCP_LCP, LCP_THR = 1, 2
@@ -439,6 +445,100 @@ class FmIndex(_Closing):
         self.ctx._check(self.lib.pfp_fm_map_long_dev(self._h, d_pat, d_pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec,
                                                      bool(thresholds), d_hit_off, d_mapq, d_nchains, d_strand, d_seq, d_off, d_ts, d_te, d_qs,
                                                      d_qe, d_score, d_n, d_match))
+
+    def fill(self, patterns, seg_pat, q0, q1, t0, t1, max_fill):
+        """the global alignment of stretches of patterns against stretches of the text (pfpgpu.h, "Aligning chains", 1): segment i
+        is pattern seg_pat[i]'s bytes q0[i]:q1[i] against T[t0[i]:t1[i]] -> (dist, cig_off, cig): dist[i] (uint32) edits, at most
+        max_fill (0 .. FM_FILL_MAX_F), and the runs cig[cig_off[i]:cig_off[i+1]] as cigar() gives them; 0xFFFFFFFF and no runs
+        where the segment is not one of the pattern and the text, a side is longer than FM_FILL_MAX_LEN, or the two are more than
+        max_fill edits apart"""
+        _, _, args = self._host_patterns(patterns)
+        sp = np.ascontiguousarray(seg_pat, dtype=np.uint32)
+        cols = [np.ascontiguousarray(a, dtype=np.uint64) for a in (q0, q1, t0, t1)]
+        if sp.ndim != 1 or any(a.shape != sp.shape for a in cols):
+            raise ValueError("seg_pat, q0, q1, t0 and t1: five 1-D arrays of one length")
+        ns = len(sp)
+        dist, cig_off = np.zeros(ns, dtype=np.uint32), np.zeros(ns + 1, dtype=np.uint64)
+        cig = C.POINTER(C.c_uint32)()
+        self.ctx._check(self.lib.pfp_fm_fill(self._h, *args, sp, *cols, ns, max_fill, dist, cig_off, C.byref(cig)))
+        return dist, cig_off, self._take_free(cig, cig_off[-1], np.uint32)
+
+    def fill_dev(self, d_pat, d_pat_off, npat, d_seg_pat, d_q0, d_q1, d_t0, d_t1, nseg, max_fill, d_dist, d_cig_off, d_cig=None):
+        """device pointers: pattern bytes, npat+1 uint64 offsets, nseg uint32 pattern indices and four uint64 arrays -> nseg uint32
+        d_dist and nseg+1 uint64 d_cig_off; d_cig (uint32, room for d_cig_off[nseg]) gets the runs (None: offsets only)"""
+        self.ctx._check(self.lib.pfp_fm_fill_dev(self._h, d_pat, d_pat_off, npat, d_seg_pat, d_q0, d_q1, d_t0, d_t1, nseg, max_fill, d_dist,
+                                                 d_cig_off, d_cig))
+
+    def fill_stats(self):
+        """what the gap passes counted since the last call, under PFP_FM_MS_STATS=1 only: gaps, trivial gaps, and per band width
+        (16, 32, 64, 256, 1024, 4160 cells) the gaps that went through a pass and the cells of those passes"""
+        out = np.zeros(14, dtype=np.uint64)
+        self.ctx._check(self.lib.pfp_fm_fill_stats(self._h, out))
+        return {"gaps": int(out[0]), "trivial": int(out[1]), "widths": (16, 32, 64, 256, 1024, 4160),
+                "passes": [int(v) for v in out[2:8]], "cells": [int(v) for v in out[8:14]]}
+
+    def chain_align(self, patterns, anc_off, anc, max_gap=5000, band=500, min_score=40, max_chains=0, max_fill=500):
+        """chain() and the edit script of every chain (pfpgpu.h, "Aligning chains", 2) -> the arrays CHAIN_ALN_NAMES names: chain()'s
+        eight, then per chain i aqs[i] (uint32) and ats[i] (uint64), where its first anchor begins; nm[i] edits; unfilled[i] gaps
+        that are more than max_fill edits and stand in the script as an insertion and a deletion; the runs
+        cig[cig_off[i]:cig_off[i+1]], which align P[aqs[i]:qe[i]] to T[ats[i]:te[i]]; and its anchors mem[mem_off[i]:mem_off[i+1]]
+        (uint32), in increasing order, as indices among the pattern's.  max_fill = 500 = the default band is a choice."""
+        _, _, args = self._host_patterns(patterns)
+        off = _arr(np.asarray(anc_off), np.uint64)
+        a = _arr(np.asarray(anc).reshape(-1), np.uint64)
+        npat = len(off) - 1
+        if npat != args[2] or len(a) % 3:
+            raise ValueError("anc_off: one offset more than the patterns; anc: three values per anchor")
+        chain_off = np.zeros(npat + 1, dtype=np.uint64)
+        u32, u64 = C.c_uint32, C.c_uint64
+        kinds = (u32, u32, u32, u32, u64, u64, u32, u32, u64, u32, u32, u64, u32, u64, u32)
+        ptrs = [C.POINTER(t)() for t in kinds]
+        self.ctx._check(self.lib.pfp_fm_chain_align(self._h, *args, off, a, max_gap, band, min_score, max_chains, max_fill, chain_off,
+                                                    *(C.byref(q) for q in ptrs)))
+        total = int(chain_off[-1])
+        out = [self._take_free(q, total, np.dtype(t)) for q, t in zip(ptrs[:11], kinds)]
+        cig_off = self._take_free(ptrs[11], total + 1, np.uint64)
+        cig = self._take_free(ptrs[12], cig_off[-1], np.uint32)
+        mem_off = self._take_free(ptrs[13], total + 1, np.uint64)
+        return (chain_off,) + tuple(out) + (cig_off, cig, mem_off, self._take_free(ptrs[14], mem_off[-1], np.uint32))
+
+    def chain_align_dev(self, d_pat, d_pat_off, npat, d_anc_off, d_anc, d_chain_off, d_score=None, d_n=None, d_qs=None, d_qe=None, d_ts=None,
+                        d_te=None, d_match=None, d_aqs=None, d_ats=None, d_nm=None, d_unfilled=None, d_cig_off=None, d_cig=None, d_mem_off=None,
+                        d_mem=None, max_gap=5000, band=500, min_score=40, max_chains=0, max_fill=500):
+        """device pointers: patterns, anchors as in chain_dev -> npat+1 uint64 d_chain_off; everything behind it None: offsets only;
+        else the seven fields, d_aqs, d_ats, d_nm, d_unfilled (room for d_chain_off[npat]) and d_cig_off (one more) are required,
+        d_cig (room for d_cig_off[last]), d_mem_off and d_mem may be None"""
+        self.ctx._check(self.lib.pfp_fm_chain_align_dev(self._h, d_pat, d_pat_off, npat, d_anc_off, d_anc, max_gap, band, min_score, max_chains,
+                                                        max_fill, d_chain_off, d_score, d_n, d_qs, d_qe, d_ts, d_te, d_match, d_aqs, d_ats, d_nm,
+                                                        d_unfilled, d_cig_off, d_cig, d_mem_off, d_mem))
+
+    def map_long_aln(self, patterns, min_seed, max_occ=500, max_gap=5000, band=500, min_score=40, max_sec=0, thresholds=False, max_fill=500):
+        """map_long() and the edit script of every returned chain (pfpgpu.h, "Aligning chains", 3) -> the arrays LONG_ALN_NAMES
+        names: map_long()'s thirteen, unchanged, then per returned chain i aqs[i], ats[i], nm[i], unfilled[i] and the runs
+        cig[cig_off[i]:cig_off[i+1]] as chain_align gives them for the strand's pattern: the script reads along the text.  aqs is
+        in the read as given: the script covers its bytes aqs[i]:qe[i] on strand 0 and qs[i]:aqs[i] on strand 1."""
+        npat, _, args = self._host_patterns(patterns)
+        hit_off, mapq, nchains = np.zeros(npat + 1, dtype=np.uint64), np.zeros(npat, dtype=np.uint8), np.zeros(npat, dtype=np.uint64)
+        u8, u32, u64 = C.c_uint8, C.c_uint32, C.c_uint64
+        kinds = (u8, u32, u64, u64, u64, u32, u32, u32, u32, u32, u32, u64, u32, u32, u64, u32)
+        ptrs = [C.POINTER(t)() for t in kinds]
+        self.ctx._check(self.lib.pfp_fm_map_long_aln(self._h, *args, min_seed, max_occ, max_gap, band, min_score, max_sec, bool(thresholds),
+                                                     max_fill, hit_off, mapq, nchains, *(C.byref(q) for q in ptrs)))
+        H = int(hit_off[-1])
+        out = [self._take_free(q, H, np.dtype(t)) for q, t in zip(ptrs[:14], kinds)]
+        cig_off = self._take_free(ptrs[14], H + 1, np.uint64)
+        return (hit_off, mapq, nchains) + tuple(out) + (cig_off, self._take_free(ptrs[15], cig_off[-1], np.uint32))
+
+    def map_long_aln_dev(self, d_pat, d_pat_off, npat, min_seed, d_hit_off, d_mapq, d_nchains, d_strand=None, d_seq=None, d_off=None, d_ts=None,
+                         d_te=None, d_qs=None, d_qe=None, d_score=None, d_n=None, d_match=None, d_aqs=None, d_ats=None, d_nm=None,
+                         d_unfilled=None, d_cig_off=None, d_cig=None, max_occ=500, max_gap=5000, band=500, min_score=40, max_sec=0,
+                         thresholds=False, max_fill=500):
+        """device pointers as in map_long_dev; behind its ten per-chain outputs d_aqs, d_ats, d_nm, d_unfilled (room for
+        d_hit_off[npat]) and d_cig_off (one more), required with them; d_cig (room for d_cig_off[last]) may be None"""
+        self.ctx._check(self.lib.pfp_fm_map_long_aln_dev(self._h, d_pat, d_pat_off, npat, min_seed, max_occ, max_gap, band, min_score, max_sec,
+                                                         bool(thresholds), max_fill, d_hit_off, d_mapq, d_nchains, d_strand, d_seq, d_off, d_ts,
+                                                         d_te, d_qs, d_qe, d_score, d_n, d_match, d_aqs, d_ats, d_nm, d_unfilled, d_cig_off,
+                                                         d_cig))
 
     def set_sequences(self, starts):
         """give the index the sequence table of its collection (pfpgpu.h, "Sequences of a collection"): nseq + 1 starts, the

@@ -852,7 +852,7 @@ int pfp_fm_map_pairs(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, ui
  * Chaining anchors: where a long read lies (csrc/fmchain.hip).  "Extending seeds" aligns a whole read within k <= 32 edits of one
  * seed's diagonal; a read of 10 kb carries hundreds of edits, and every one of its seeds finds the right place all the same.
  * The first step of every long-read mapper is to chain the seeds and report the chain; base-level alignment of a chain (a band in
- * the hundreds) is not done here, and a chain's span and anchors are what such an aligner takes.  The reference has no
+ * the hundreds) is "Aligning chains" below, which takes a chain's anchors.  The reference has no
  * counterpart; the method is seed chaining as in Li, "Minimap2: pairwise alignment for nucleotide sequences" (Bioinformatics
  * 2018), section 2.1, over MEM anchors instead of minimizers, in integer arithmetic.  Conventions as in "Searching a BWT" and
  * "Matching statistics".  The index is one built with text and samples (pfp_fm_build_ms_*); otherwise PFP_EINVAL, as for
@@ -960,6 +960,117 @@ int pfp_fm_map_long(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uin
                     uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t *hit_off, uint8_t *mapq,
                     uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts, uint64_t **te, uint32_t **qs,
                     uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match);
+
+/* ------------------------------------------------------------------------------------
+ * Aligning chains: how a long read aligns where its chain lies, base by base (csrc/fmfill.hip).  "Chaining anchors" says where a
+ * read lies; the anchors of a chain are exact matches already, so what is left is the stretch between two consecutive anchors: a
+ * global edit-distance alignment of up to G bytes, up to B off the diagonal - more edits than the k <= 32 of "Edit scripts", in a
+ * band that is neither symmetric nor narrow.  The reference has no counterpart; the band is Ukkonen's, the operations, the tie
+ * rules and the run format are those of "Edit scripts".  Conventions and the index as in "Chaining anchors".  Three layers, each
+ * usable on its own, each a function of its inputs alone - not of the batch, the chunks, the scratch, the slack schedule or the
+ * launch bounds.  Everything below is a choice unless it says "derived".
+ *
+ * 1. Filling one gap.  A segment is (p, q0, q1, t0, t1); the argument max_fill F is in 0 .. PFP_FM_FILL_MAX_F = 4096 (a choice:
+ * cell values stay within 16 bits and a band within one wave's registers).  It aligns P_p[q0 .. q1) against T[t0 .. t1)
+ * globally; a = q1 - q0, b = t1 - t0.
+ *   no script: dist = 0xFFFFFFFF and no runs where p >= npat, q0 > q1, q1 > m_p, t0 > t1, t1 > n, a or b above PFP_FM_FILL_MAX_LEN
+ *     = 65535, |a - b| > F (derived: the distance is at least |a - b|), or the Levenshtein distance D of the two strings (unit
+ *     costs; a pattern byte 0 equals nothing, as everywhere else) is above F.
+ *   otherwise dist = D (uint32) and the script is the one rules 1-4 of "Edit scripts" choose on the full, unbanded matrix of the
+ *     two strings, walking back from (a, b): runs of length << 4 | op with the BAM codes 7, 8, 1, 2, listed from the pattern's
+ *     first byte.  a = b = 0 gives dist = 0 and the empty script.
+ *   Derived: where both apply (q0 = 0, q1 = m_p, D <= k <= 32) the runs equal what pfp_fm_cigar gives for (p, t0, t1) at k.
+ *   F out of range or an index without text: PFP_EINVAL.  Pattern offsets that decrease: PFP_EINVAL.
+ *
+ * 2. Aligning a chain.  Inputs: patterns, anchors as pfp_fm_chain takes them (its refusals hold), G, B, S, max_chains, and F.
+ * The chains, their order and their seven fields are exactly pfp_fm_chain's.  Per chain in addition:
+ *   members: the anchors the peel's walk listed for the chain, written in increasing order c_0 .. c_{n-1}, as indices inside the
+ *     pattern's segment of anchors (uint32): mem[mem_off[c] .. mem_off[c+1]).
+ *   trimming: c_0 is kept whole.  For r >= 1 let o = max(0, qe_{r-1} - i_r, te_{r-1} - t_r); anchor r becomes (i_r + o, len_r - o,
+ *     t_r + o): it begins where the one before it has ended on both sides.  Derived: o <= len_r - 1, so every trimmed anchor
+ *     keeps at least one byte - qe_{r-1} - i_r = len_r - dq and te_{r-1} - t_r = len_r - dt, and a predecessor has dq, dt >= 1.
+ *     An anchor's ends qe_r, te_r do not move, so trimming needs no order.
+ *   gaps: gap r >= 1 is the segment P[qe_{r-1} .. i_r + o) against T[te_{r-1} .. t_r + o).  Derived: the two lengths are dq - (len_r
+ *     - o) and dt - (len_r - o), so |a - b| = |dt - dq| <= B and a, b < G.  A gap with a = b = 0 adds nothing; a gap that has a
+ *     script under layer 1 at F adds that script; any other gap is UNFILLED: it adds a I then b D (a length 0 is left out) and
+ *     counts in `unfilled`.
+ *   the script of a chain: len_0 '=', then for r = 1 .. n-1 gap r's runs and len_r - o '='; neighbouring runs of one operation are
+ *     merged.  It aligns P[aqs .. qe) to T[ats .. te) with aqs = i_0 and ats = t_0, the FIRST MEMBER'S.  These are not always the
+ *     chain's qs and ts, which are minima over the members.  In a chain that the programme walks from an anchor without a parent
+ *     they are (derived: f_j <= qe_j - i_0 along it, so a later anchor that begins before i_0 is longer than any f_j + gain and
+ *     takes no parent; the same for t): the pair (0,20,1000) (5,100,930), which would differ, does not chain - dq = 85, dt = 10,
+ *     g = 75, 20 + 10 - 19 = 11 <= 100 - and gives two chains of one anchor.  A chain that the peel cuts off at a visited anchor
+ *     can differ.  Example, G = 5000, B = 10, S = 1: anchors (0,50,1000) (60,30,1058) (60,20,1070) (55,40,1066) (95,50,1093) have f =
+ *     50, 79, 67, 81, 129 and parents -, 0, 0, 2, 1.  The peel takes 4, 1, 0 (score 129), then 3, 2 and stops at the visited 0: the
+ *     chain (60,20,1070) (55,40,1066) with score 31, qs = 55, ts = 1066, but aqs = 60, ats = 1070.  Its second anchor is trimmed by o
+ *     = max(0, 80 - 55, 1090 - 1066) = 25 to (80,15,1091); gap 1 is P[80 .. 80) against T[1090 .. 1091); the script is 20= 1D 15=,
+ *     nm = 1, and it aligns P[60 .. 95) to T[1070 .. 1106).
+ *   nm: the sum of the script's X, I and D lengths.  Derived: nm = the sum of the filled gaps' dist plus a + b of the unfilled.
+ *
+ * 3. Long reads: pfp_fm_map_long's arguments plus F; its outputs unchanged and bit-equal; per RETURNED chain (1 + max_sec per
+ * read; no other chain is aligned) aqs, ats, nm, unfilled and the script.  The script reads along the strand's pattern, that is
+ * along the text, as SAM's does.  aqs is the strand's aqs turned into the read AS GIVEN as pfp_fm_map_long turns qs: strand 0:
+ * aqs; strand 1: m - aqs.  So the script covers the read's bytes [aqs, qe) on strand 0 and [qs, aqs) on strand 1 (qs, qe: this
+ * call's outputs; on strand 1 qs = m - qe of the strand's pattern is exact and the turned value is the stretch's END).
+ *
+ * Bounds: a gap costs a rows over a band of at most F + 2 cells per round, at most five rounds (slack 8, 32, 128, 512, 2048, cut
+ * where the band proves D > F or holds the whole matrix), and a walk of at most a + b steps by one lane; gaps with a = 0, b = 0
+ * or a = b = 1 cost one lane a few loads.  The members' walk is a bounded, resumable launch under PFP_FM_CHAIN_STEPS.
+ * Device memory on top of the caller's buffers and of what pfp_fm_chain_dev / pfp_fm_map_long_dev take: 4 bytes per member and 57
+ * per gap (a member has one: its segment, its trimmed length, dist, run count, slot address, round and bucket) plus 32 per gap
+ * during a round for the plan; the runs of a band-filled gap wait in a slot of 4 min(2 min(F, |a - b| + 2e + 1) + 1, a + b)
+ * bytes; the records of a pass take a / 16 (rounded up) times the band's width (16, 32, 64, 256, 1024 or 4160 cells) times 4
+ * bytes - 68 MB for the largest legal gap - and live only during a launch: a round's gaps go through in consecutive chunks whose
+ * records fit 1 GiB (a choice, not a measurement; PFP_FM_FILL_SCRATCH=BYTES, read per call, lowers it), and one that needs more
+ * goes alone.
+ * ------------------------------------------------------------------------------------ */
+#define PFP_FM_FILL_MAX_F 4096
+#define PFP_FM_FILL_MAX_LEN 65535
+/* device pointers, patterns as in pfp_fm_count_dev; segment i is (d_seg_pat[i], d_q0[i], d_q1[i], d_t0[i], d_t1[i]).  d_dist (nseg,
+ * uint32) and d_cig_off (nseg + 1, exclusive sums of the run counts) are filled; d_cig NULL: those only, else room for
+ * d_cig_off[nseg] uint32 */
+int pfp_fm_fill_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint32_t *d_seg_pat, const uint64_t *d_q0,
+                    const uint64_t *d_q1, const uint64_t *d_t0, const uint64_t *d_t1, uint64_t nseg, uint64_t max_fill, uint32_t *d_dist,
+                    uint64_t *d_cig_off, uint32_t *d_cig);
+/* host buffers; *cig is a malloc'ed array of cig_off[nseg] entries (pfp_free; NULL when none) */
+int pfp_fm_fill(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint32_t *seg_pat, const uint64_t *q0,
+                const uint64_t *q1, const uint64_t *t0, const uint64_t *t1, uint64_t nseg, uint64_t max_fill, uint32_t *dist, uint64_t *cig_off,
+                uint32_t **cig);
+/* device pointers: patterns as in pfp_fm_count_dev; anchors, G, B, S, max_chains and the seven fields as in pfp_fm_chain_dev.  Everything behind
+ * d_chain_off NULL: the chains' offsets only.  Otherwise the seven fields, d_aqs, d_nm, d_unfilled (uint32), d_ats (uint64) and
+ * d_cig_off (d_chain_off[npat] + 1 entries) are required; d_cig NULL: no runs, else room for d_cig_off[last] uint32; d_mem_off
+ * (d_chain_off[npat] + 1) and d_mem (uint32, room for the sum of the chains' n) may each be NULL. */
+int pfp_fm_chain_align_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, const uint64_t *d_anc_off,
+                           const uint64_t *d_anc, uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_chains, uint64_t max_fill,
+                           uint64_t *d_chain_off, uint32_t *d_score, uint32_t *d_n, uint32_t *d_qs, uint32_t *d_qe, uint64_t *d_ts, uint64_t *d_te,
+                           uint32_t *d_match, uint32_t *d_aqs, uint64_t *d_ats, uint32_t *d_nm, uint32_t *d_unfilled, uint64_t *d_cig_off,
+                           uint32_t *d_cig, uint64_t *d_mem_off, uint32_t *d_mem);
+/* host buffers: chain_off (npat + 1) is filled; the arrays behind it are malloc'ed (pfp_free each; NULL when there is none):
+ * chain_off[npat] entries each, *cig_off and *mem_off one more, *cig (*cig_off)[last] and *mem (*mem_off)[last]; mem_off and mem
+ * may be NULL */
+int pfp_fm_chain_align(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, const uint64_t *anc_off, const uint64_t *anc,
+                       uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_chains, uint64_t max_fill, uint64_t *chain_off,
+                       uint32_t **score, uint32_t **n, uint32_t **qs, uint32_t **qe, uint64_t **ts, uint64_t **te, uint32_t **match,
+                       uint32_t **aqs, uint64_t **ats, uint32_t **nm, uint32_t **unfilled, uint64_t **cig_off, uint32_t **cig,
+                       uint64_t **mem_off, uint32_t **mem);
+/* pfp_fm_map_long_dev's arguments with max_fill behind thresholds, and behind its outputs: d_aqs, d_nm, d_unfilled (uint32), d_ats
+ * (uint64), d_hit_off[npat] entries each, and d_cig_off (one more); required whenever the ten are given, and NULL with them.
+ * d_cig NULL: no runs, else room for d_cig_off[last] uint32 */
+int pfp_fm_map_long_aln_dev(pfp_fm *fm, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                            uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t max_fill,
+                            uint64_t *d_hit_off, uint8_t *d_mapq, uint64_t *d_nchains, uint8_t *d_strand, uint32_t *d_seq, uint64_t *d_off,
+                            uint64_t *d_ts, uint64_t *d_te, uint32_t *d_qs, uint32_t *d_qe, uint32_t *d_score, uint32_t *d_n, uint32_t *d_match,
+                            uint32_t *d_aqs, uint64_t *d_ats, uint32_t *d_nm, uint32_t *d_unfilled, uint64_t *d_cig_off, uint32_t *d_cig);
+/* host buffers, grouped as pfp_fm_map_long groups the reads; *aqs, *ats, *nm, *unfilled: hit_off[npat] entries, *cig_off one more,
+ * *cig (*cig_off)[last] (malloc'ed; pfp_free each) */
+int pfp_fm_map_long_aln(pfp_fm *fm, const uint8_t *pat, const uint64_t *pat_off, uint64_t npat, uint64_t min_seed, uint64_t max_occ,
+                        uint64_t max_gap, uint64_t band, uint64_t min_score, uint64_t max_sec, int thresholds, uint64_t max_fill,
+                        uint64_t *hit_off, uint8_t *mapq, uint64_t *nchains, uint8_t **strand, uint32_t **seq, uint64_t **off, uint64_t **ts,
+                        uint64_t **te, uint32_t **qs, uint32_t **qe, uint32_t **score, uint32_t **n, uint32_t **match, uint32_t **aqs,
+                        uint64_t **ats, uint32_t **nm, uint32_t **unfilled, uint64_t **cig_off, uint32_t **cig);
+/* measurement (tools/fill_time.py; counted only under PFP_FM_MS_STATS=1): gaps, trivial gaps, then for each of the six band
+ * widths the gaps that went through a pass of it and the cells of those passes; the counters are reset */
+int pfp_fm_fill_stats(pfp_fm *fm, uint64_t out[14]);
 
 /* ------------------------------------------------------------------------------------
  * Matching statistics and maximal exact matches over the same index (csrc/fmsearch.hip).  The reference has no counterpart:
